@@ -70,7 +70,13 @@ def parse_args():
                          "one context's search kernel fills the CUs that the other's tail and phase-6 launches leave idle (round 6: 48.9 -> 54 M reads/s at 150 bp, pairs 50.4 -> 63.2 M, "
                          "profiles/r6/two_contexts_and_batch_size.txt); 1 = one context, its steps back to back (rounds 1-5; --streams then splits a batch)")
     ap.add_argument("--mode", choices=("se", "pe"), default="se", help="pe: 2x150 read pairs through State2::Search4 (config 3; not the headline metric)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (per-read result fields and alignment paths of a fixed, "
+                         "seeded sample of its reads) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _is_prime(n):
@@ -670,10 +676,50 @@ class Workload:
         return parity, {k: v / max(1, cnt["n_reads"]) for k, v in cnt.items()}, t_cpu
 
 
-def run_timed(wl, mappers, steps, warmup, barrier=None, alone_steps=3):
+DUMP_BYTES = 64 << 20
+DUMP_SEED = 20261015
+# result fields as a caller of the device path receives them, and the float type that holds each exactly; path_off is left out: it is
+# where the read's path landed in the shared arena (an atomic counter, so it depends on the order the waves finished in), and the
+# paths themselves are written in read order instead
+DUMP_FIELDS = {"dbpos": np.float64, "seq_index": np.float64, "coord": np.float64, "score": np.float32, "second": np.float32,
+               "mapq": np.float32, "plus": np.float32, "exit_phase": np.float32, "status": np.float32, "hit_count": np.float32,
+               "path_nops": np.float32}
+
+
+def step_outputs(wl, max_path_ops, budget=DUMP_BYTES):
+    """What the last step handed its caller, as float arrays for --dump-outputs: every result field of a fixed, seeded sample of the
+    reads (whole pairs in pe mode; which reads depends only on the batch size, never on the results) and their alignment paths
+    (run-length ops, read after read).  The sample is as large as fits `budget` when every read carries the longest path."""
+    res, ops = wl.results()
+    unit = 2 if wl.pe else 1
+    per_read = sum(np.dtype(t).itemsize for t in DUMP_FIELDS.values()) + 8 + 4 * max_path_ops  # + read_index + the longest path
+    units = len(res) // unit
+    take = min(units, (budget - (64 << 10)) // (unit * per_read))  # (64 kB for the .npy headers)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(units, size=take, replace=False)) if take < units else np.arange(units)
+    reads = (pick[:, None] * unit + np.arange(unit)[None, :]).reshape(-1)
+    sel = res[reads]
+    out = {"read_index": reads.astype(np.float64)}
+    for name, t in DUMP_FIELDS.items():
+        out[name] = sel[name].astype(t)
+    offs, nops = sel["path_off"].astype(np.int64), sel["path_nops"].astype(np.int64)
+    gather = np.repeat(offs - np.concatenate(([0], np.cumsum(nops)[:-1])), nops) + np.arange(int(nops.sum()))
+    out["path_ops"] = ops[gather].astype(np.float32)
+    return out
+
+
+def write_outputs(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+def run_timed(wl, mappers, steps, warmup, barrier=None, alone_steps=3, after_timed=None):
     """wl.timed over the contexts the run uses, and -- when batches alternate over several -- a few steps of ONE context with the device to itself afterwards
-    (outside the timed region): what each launch takes when nothing shares the device with it.  -> (seconds, kms, alone | None)"""
+    (outside the timed region): what each launch takes when nothing shares the device with it.  `after_timed` is called between the two, while the
+    output arrays still hold the last timed step.  -> (seconds, kms, alone | None)"""
     dt, kms = wl.timed(mappers, steps, warmup, barrier)
+    if after_timed:
+        after_timed()
     alone = None
     if wl.contexts > 1 and alone_steps > 0 and len(mappers) >= wl.contexts:
         keep = (wl.stage_ms.copy(), wl.round_ms, wl.p3_ms.copy(), wl.p3_stats.copy(), wl.dp_stats, wl.own_s)
@@ -1271,7 +1317,8 @@ def main():
     setup_s = time.time() - t_setup
 
     # (the one-context steps behind the timed region run on rank 0 only: they feed the line's `alone_ms` / `sequential`, nothing is gathered from them)
-    dt, kms, alone = run_timed(wl, mappers, args.steps, args.warmup, barrier=lambda: R.barrier(torch), alone_steps=5 if rank == 0 else 0)
+    dump = (lambda: write_outputs(args.dump_outputs, step_outputs(wl, api.MAX_PATH_OPS))) if args.dump_outputs and rank == 0 else None
+    dt, kms, alone = run_timed(wl, mappers, args.steps, args.warmup, barrier=lambda: R.barrier(torch), alone_steps=5 if rank == 0 else 0, after_timed=dump)
     # every rank's own numbers, for the N > 1 line: its steps between the two barriers, its set-up (genome, index placement, batches)
     per_rank = R.all_gather_floats(torch, [wl.own_s, setup_s, t_index.get("make_ufi", 0.0), t_index.get("upload", 0.0), t_index.get("broadcast_s") or 0.0])
     dt = R.max_over_ranks(torch, dt)

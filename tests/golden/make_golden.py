@@ -19,6 +19,10 @@ outputs are what the reference itself wrote:
   hitstats.json   the count lines of the reference's end-of-run report (State1::HitStats, state1.cpp:593-632) for the
                   sets above, incl. -minq 3 runs (python make_golden.py hitstats regenerates only this file)
 
+  ref_runs.json   sha256 of the .ufi / SAM files the reference wrote in the tests that run it on seeded inputs of their own
+                  (*_equals_reference_binary), keyed by test case; the tests compare against it when the binary is not built.
+                  Written by those tests: URMAP_RECORD_REF_RUNS=1 pytest tests -k equals_reference_binary
+
 Run only where /root/reference exists; the fixtures are data, the reference itself does not travel.
 """
 import gzip

@@ -285,6 +285,34 @@ def run_ref(args, cwd=None):
     return r
 
 
+REF_RUNS = os.path.join(ROOT, "tests", "golden", "ref_runs.json")
+
+
+def digest(data: bytes) -> str:
+    import hashlib
+    return hashlib.sha256(data).hexdigest()
+
+
+def reference_outputs(key, run_live):
+    """What the reference binary wrote for test case `key`: `run_live()` runs oracle/_ref/urmap and returns {name: bytes or
+    plain value}; bytes are kept as their SHA-256.  Without the binary, the values recorded from it in tests/golden/ref_runs.json
+    stand in; with it, the live run must equal that record (URMAP_RECORD_REF_RUNS=1 rewrites the record instead)."""
+    import json
+    recorded = json.load(open(REF_RUNS)) if os.path.exists(REF_RUNS) else {}
+    if not have_ref():
+        assert key in recorded, f"{key}: the reference binary is not built and {REF_RUNS} has no record of this case"
+        return recorded[key]
+    live = json.loads(json.dumps({k: digest(v) if isinstance(v, bytes) else v for k, v in run_live().items()}))
+    if os.environ.get("URMAP_RECORD_REF_RUNS"):
+        recorded[key] = live
+        with open(REF_RUNS, "w") as f:
+            json.dump(recorded, f, indent=1, sort_keys=True)
+            f.write("\n")
+    else:
+        assert recorded.get(key) == live, f"{key}: the reference binary's outputs differ from {REF_RUNS}"
+    return live
+
+
 def ufi_header(path):
     """(word_length, max_ix, seqdata_size, slot_count) from a .ufi file."""
     import struct

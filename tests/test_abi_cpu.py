@@ -210,11 +210,11 @@ def test_cli_make_ufi_is_byte_identical(gold_ufi, tmp_path):
     assert r.returncode == 1
 
 
-@pytest.mark.skipif(not ol.have_ref(), reason="reference binary oracle/_ref/urmap not built")
 @pytest.mark.parametrize("nbases", [1200, 30011, 171717, 999983])
 def test_cli_default_slot_count_equals_reference_binary(tmp_path, nbases):
     """GetPrime's ladder (prime.cpp:11-21) is regenerated, not stored: same default slot count as the reference binary
-    for FASTA files of several sizes (also with -veryfast: MaxIx 3, ufindexio.cpp:133-136)."""
+    for FASTA files of several sizes (also with -veryfast: MaxIx 3, ufindexio.cpp:133-136); the reference's .ufi files as
+    recorded in tests/golden/ref_runs.json when its binary is not built."""
     import subprocess
     from urmap_amd import synth
     exe = os.path.join(ROOT, "urmap_amd", "urmap")
@@ -223,13 +223,23 @@ def test_cli_default_slot_count_equals_reference_binary(tmp_path, nbases):
     d = str(tmp_path)
     g = synth.make_genome(nbases, [nbases - nbases // 3, nbases // 3], repeat_frac=0.2, n_families=3)
     synth.write_fasta(os.path.join(d, "x.fa"), g)
-    for extra in ([], ["-veryfast"]):
-        ol.run_ref(["-make_ufi", "x.fa", "-output", "ref.ufi"] + extra, cwd=d)
+
+    def reference():
+        out = {}
+        for tag, extra in (("", []), ("_veryfast", ["-veryfast"])):
+            ol.run_ref(["-make_ufi", "x.fa", "-output", "ref.ufi"] + extra, cwd=d)
+            out["ufi_header" + tag] = ol.ufi_header(os.path.join(d, "ref.ufi"))
+            with open(os.path.join(d, "ref.ufi"), "rb") as f:
+                out["ufi" + tag] = f.read()
+        return out
+    want = ol.reference_outputs(f"cli_default_slot_count_equals_reference_binary[{nbases}]", reference)
+    for tag, extra in (("", []), ("_veryfast", ["-veryfast"])):
         r = subprocess.run([exe, "-make_ufi", os.path.join(d, "x.fa"), "-output", os.path.join(d, "mine.ufi")] + extra,
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
         assert r.returncode == 0, r.stderr.decode()
-        assert ol.ufi_header(os.path.join(d, "mine.ufi")) == ol.ufi_header(os.path.join(d, "ref.ufi"))
-        assert filecmp.cmp(os.path.join(d, "mine.ufi"), os.path.join(d, "ref.ufi"), shallow=False)
+        assert ol.ufi_header(os.path.join(d, "mine.ufi")) == tuple(want["ufi_header" + tag])
+        with open(os.path.join(d, "mine.ufi"), "rb") as f:
+            assert ol.digest(f.read()) == want["ufi" + tag]
 
 
 def test_file_to_file_call_and_gpu_builder_fail_loudly_without_a_device(gold_ufi, tmp_path):

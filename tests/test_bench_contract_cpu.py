@@ -106,3 +106,51 @@ def test_kernel_table_lists_the_launches_of_a_single_end_step():
     kp = bench.kernel_table(FakeApi, True, 150, 1_000_000, [6.4, 47.0], c, 3.1e9, 4.6e10)
     assert [x["kernel"] for x in kp] == ["search_pe_kernel"]   # seed + probe run inside it since round 3
     assert abs(kp[0]["alg_bytes_per_read"] - (alg + 90)) < 1e-6
+
+
+def test_dump_outputs_are_a_fixed_sample_with_paths_in_read_order(tmp_path, monkeypatch):
+    """--dump-outputs: the last step's result fields and paths as float .npy files, under the byte budget, the same reads whatever
+    the results are, each read's path taken from where the arena put it (path_off) and written in read order."""
+    import numpy as np
+    from urmap_amd import api
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", str(tmp_path / "o")])
+    assert bench.parse_args().dump_outputs == str(tmp_path / "o")
+
+    class FakeWorkload:
+        def __init__(self, n, pe, seed):
+            rng = np.random.default_rng(seed)
+            self.pe = pe
+            self.res = np.zeros(n, dtype=api.RESULT_DTYPE)
+            self.res["dbpos"] = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+            self.res["score"] = rng.integers(-300, 300, n)
+            self.res["path_nops"] = rng.integers(0, 4, n)
+            perm = rng.permutation(n)  # the arena holds the paths in the order the reads finished
+            nops = self.res["path_nops"].astype(np.int64)
+            off = np.zeros(n, np.int64)
+            off[perm] = np.concatenate(([0], np.cumsum(nops[perm])[:-1]))
+            self.res["path_off"] = off
+            self.ops = np.zeros(int(nops.sum()), np.uint16)
+            for i in range(n):
+                self.ops[off[i]:off[i] + nops[i]] = (4 * (i % 1000) + np.arange(nops[i])).astype(np.uint16)
+
+        def results(self):
+            return self.res, self.ops
+
+    budget = 2 << 20
+    for pe in (False, True):
+        a = bench.step_outputs(FakeWorkload(20000, pe, 1), 96, budget=budget)
+        b = bench.step_outputs(FakeWorkload(20000, pe, 2), 96, budget=budget)
+        assert (a["read_index"] == b["read_index"]).all() and 0 < len(a["read_index"]) < 20000
+        assert sum(x.nbytes for x in a.values()) <= budget
+        assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+        if pe:
+            assert (a["read_index"][0::2] % 2 == 0).all() and (a["read_index"][1::2] == a["read_index"][0::2] + 1).all()
+        w = FakeWorkload(20000, pe, 1)
+        idx = a["read_index"].astype(np.int64)
+        assert (a["dbpos"] == w.res["dbpos"][idx]).all() and (a["score"] == w.res["score"][idx]).all()
+        want = np.concatenate([(4 * (i % 1000) + np.arange(w.res["path_nops"][i])) for i in idx])
+        assert (a["path_ops"] == want).all()
+    small = bench.step_outputs(FakeWorkload(100, False, 3), 96)
+    assert (small["read_index"] == np.arange(100)).all()
+    bench.write_outputs(str(tmp_path / "o"), small)
+    assert (np.load(str(tmp_path / "o" / "coord.npy")) == small["coord"]).all()

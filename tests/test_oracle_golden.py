@@ -66,12 +66,26 @@ def test_viterbi_known_shapes():
     assert (s, p) == (-8.0, "DDDD")
 
 
-@pytest.mark.skipif(not ol.have_ref(), reason="reference binary oracle/_ref/urmap not built")
+def _sorted_records(path):
+    return b"\n".join(sorted(read_records(path)))
+
+
+def _sorted_pairs(path):
+    body = [x for x in read_records(path) if not x.startswith(b"@")]
+    return b"\n".join(sorted(body[i] + b"|" + body[i + 1] for i in range(0, len(body), 2)))
+
+
+def _file_bytes(path):
+    with open(path, "rb") as f:
+        return f.read()
+
+
 @pytest.mark.parametrize("seed,glen,n,rl,sub,indel", [(21, 400000, 3000, 150, 0.01, 0.001),
                                                       (22, 300000, 1500, 250, 0.04, 0.01),
                                                       (23, 200000, 2000, 75, 0.02, 0.004)])
 def test_oracle_equals_reference_binary(tmp_path, seed, glen, n, rl, sub, indel):
-    """Fresh seeded genome + reads: reference -make_ufi / -map vs the oracle; .ufi bytes and SAM records."""
+    """Fresh seeded genome + reads: reference -make_ufi / -map vs the oracle; .ufi bytes and SAM records (the reference's
+    outputs as recorded in tests/golden/ref_runs.json when its binary is not built)."""
     from urmap_amd import synth
     d = str(tmp_path)
     g = synth.make_genome(seed, [glen * 6 // 10, glen * 3 // 10, glen // 10], repeat_frac=0.4, n_families=10)
@@ -82,25 +96,27 @@ def test_oracle_equals_reference_binary(tmp_path, seed, glen, n, rl, sub, indel)
         lab, s, q = reads[k]
         s = s.copy(); s[int(rng.integers(0, len(s)))] = ord("N"); reads[k] = (lab, s, q)
     synth.write_fastq(os.path.join(d, "r.fq"), reads)
-    ol.run_ref(["-make_ufi", "g.fa", "-output", "g.ufi"], cwd=d)
-    w, maxix, sds, slots = ol.ufi_header(os.path.join(d, "g.ufi"))
-    idx = ol.Index.build(os.path.join(d, "g.fa"), slots)
-    idx.save(os.path.join(d, "o.ufi"))
-    assert filecmp.cmp(os.path.join(d, "g.ufi"), os.path.join(d, "o.ufi"), shallow=False)
-    ol.run_ref(["-map", "r.fq", "-ufi", "g.ufi", "-samout", "ref.sam", "-threads", "4"], cwd=d)
-    idx.map_file_se(os.path.join(d, "r.fq"), os.path.join(d, "o.sam"), threads=4)
-    assert sorted(read_records(os.path.join(d, "ref.sam"))) == sorted(read_records(os.path.join(d, "o.sam")))
     # paired-end on the same genome
     r1, r2 = synth.make_pairs(seed + 2, g, n // 2, read_len=min(rl, 150), sub1=sub, sub2=2 * sub, ins=indel / 2, dele=indel / 2)
     synth.write_fastq(os.path.join(d, "p1.fq"), r1)
     synth.write_fastq(os.path.join(d, "p2.fq"), r2)
-    ol.run_ref(["-map2", "p1.fq", "-reverse", "p2.fq", "-ufi", "g.ufi", "-samout", "refpe.sam", "-threads", "4"], cwd=d)
-    idx.map_file_pe(os.path.join(d, "p1.fq"), os.path.join(d, "p2.fq"), os.path.join(d, "ope.sam"), threads=4)
 
-    def pairs(path):
-        body = [x for x in read_records(path) if not x.startswith(b"@")]
-        return sorted(body[i] + b"|" + body[i + 1] for i in range(0, len(body), 2))
-    assert pairs(os.path.join(d, "refpe.sam")) == pairs(os.path.join(d, "ope.sam"))
+    def reference():
+        ol.run_ref(["-make_ufi", "g.fa", "-output", "g.ufi"], cwd=d)
+        ol.run_ref(["-map", "r.fq", "-ufi", "g.ufi", "-samout", "ref.sam", "-threads", "4"], cwd=d)
+        ol.run_ref(["-map2", "p1.fq", "-reverse", "p2.fq", "-ufi", "g.ufi", "-samout", "refpe.sam", "-threads", "4"], cwd=d)
+        return {"ufi_header": ol.ufi_header(os.path.join(d, "g.ufi")), "ufi": _file_bytes(os.path.join(d, "g.ufi")),
+                "sam": _sorted_records(os.path.join(d, "ref.sam")), "pe_sam": _sorted_pairs(os.path.join(d, "refpe.sam"))}
+    want = ol.reference_outputs(f"oracle_equals_reference_binary[{seed}]", reference)
+    w, maxix, sds, slots = want["ufi_header"]
+    idx = ol.Index.build(os.path.join(d, "g.fa"), slots)
+    idx.save(os.path.join(d, "o.ufi"))
+    assert ol.ufi_header(os.path.join(d, "o.ufi")) == tuple(want["ufi_header"])
+    assert ol.digest(_file_bytes(os.path.join(d, "o.ufi"))) == want["ufi"]
+    idx.map_file_se(os.path.join(d, "r.fq"), os.path.join(d, "o.sam"), threads=4)
+    assert ol.digest(_sorted_records(os.path.join(d, "o.sam"))) == want["sam"]
+    idx.map_file_pe(os.path.join(d, "p1.fq"), os.path.join(d, "p2.fq"), os.path.join(d, "ope.sam"), threads=4)
+    assert ol.digest(_sorted_pairs(os.path.join(d, "ope.sam"))) == want["pe_sam"]
 
 
 @pytest.mark.parametrize("name,ufi_gz,with_sam", [("pe150", "g.ufi.gz", True), ("pe100_noisy", "g.ufi.gz", True),
@@ -147,52 +163,63 @@ def test_oracle_hitstats_equal_reference_report(gold_ufi, key, mode, name, minq)
     assert [int(re.match(r"\s*([\d,]+)", ln).group(1).replace(",", "")) for ln in want[:4]] == counts
 
 
-@pytest.mark.skipif(not ol.have_ref(), reason="reference binary oracle/_ref/urmap not built")
 @pytest.mark.parametrize("seed,maxix_opt", [(31, []), (32, ["-veryfast"])])
 def test_oracle_veryfast_equals_reference_binary(tmp_path, seed, maxix_opt):
     """`-veryfast`: SE method 7 (state1.cpp:166-179) and PE Search5 (search2m5.cpp:9-156, band radius 4, map2.cpp:17-21),
-    on a default index and on a `-make_ufi -veryfast` index (MaxIx 3, ufindexio.cpp:133-136): oracle vs reference SAM."""
+    on a default index and on a `-make_ufi -veryfast` index (MaxIx 3, ufindexio.cpp:133-136): oracle vs reference SAM
+    (the reference's outputs as recorded in tests/golden/ref_runs.json when its binary is not built)."""
     from urmap_amd import synth
     d = str(tmp_path)
     g = synth.make_genome(seed, [200000, 90000, 30000], repeat_frac=0.45, n_families=8, max_div=0.06)
     synth.write_fasta(os.path.join(d, "g.fa"), g, lowercase_frac=0.03)
-    ol.run_ref(["-make_ufi", "g.fa", "-output", "g.ufi"] + maxix_opt, cwd=d)
-    w, maxix, sds, slots = ol.ufi_header(os.path.join(d, "g.ufi"))
-    assert maxix == (3 if maxix_opt else 32)
-    idx = ol.Index.build(os.path.join(d, "g.fa"), slots, max_ix=maxix)
-    idx.save(os.path.join(d, "o.ufi"))
-    assert filecmp.cmp(os.path.join(d, "g.ufi"), os.path.join(d, "o.ufi"), shallow=False)
     reads = synth.make_reads(seed + 1, g, 2500, read_len=150, sub=0.03, ins=0.003, dele=0.003, random_frac=0.02)
     synth.write_fastq(os.path.join(d, "r.fq"), reads)
-    ol.run_ref(["-map", "r.fq", "-ufi", "g.ufi", "-samout", "ref.sam", "-threads", "4", "-veryfast"], cwd=d)
-    idx.map_file_se(os.path.join(d, "r.fq"), os.path.join(d, "o.sam"), method=7, threads=4)
-    assert sorted(read_records(os.path.join(d, "ref.sam"))) == sorted(read_records(os.path.join(d, "o.sam")))
     r1, r2 = synth.make_pairs(seed + 2, g, 1500, read_len=125, sub1=0.02, sub2=0.05, ins=0.002, dele=0.002)
     synth.write_fastq(os.path.join(d, "p1.fq"), r1)
     synth.write_fastq(os.path.join(d, "p2.fq"), r2)
-    ol.run_ref(["-map2", "p1.fq", "-reverse", "p2.fq", "-ufi", "g.ufi", "-samout", "refpe.sam", "-threads", "4", "-veryfast"], cwd=d)
+
+    def reference():
+        ol.run_ref(["-make_ufi", "g.fa", "-output", "g.ufi"] + maxix_opt, cwd=d)
+        ol.run_ref(["-map", "r.fq", "-ufi", "g.ufi", "-samout", "ref.sam", "-threads", "4", "-veryfast"], cwd=d)
+        ol.run_ref(["-map2", "p1.fq", "-reverse", "p2.fq", "-ufi", "g.ufi", "-samout", "refpe.sam", "-threads", "4", "-veryfast"], cwd=d)
+        return {"ufi_header": ol.ufi_header(os.path.join(d, "g.ufi")), "ufi": _file_bytes(os.path.join(d, "g.ufi")),
+                "sam": _sorted_records(os.path.join(d, "ref.sam")), "pe_sam": _sorted_pairs(os.path.join(d, "refpe.sam"))}
+    want = ol.reference_outputs(f"oracle_veryfast_equals_reference_binary[{seed}]", reference)
+    w, maxix, sds, slots = want["ufi_header"]
+    assert maxix == (3 if maxix_opt else 32)
+    idx = ol.Index.build(os.path.join(d, "g.fa"), slots, max_ix=maxix)
+    idx.save(os.path.join(d, "o.ufi"))
+    assert ol.ufi_header(os.path.join(d, "o.ufi")) == tuple(want["ufi_header"])
+    assert ol.digest(_file_bytes(os.path.join(d, "o.ufi"))) == want["ufi"]
+    idx.map_file_se(os.path.join(d, "r.fq"), os.path.join(d, "o.sam"), method=7, threads=4)
+    assert ol.digest(_sorted_records(os.path.join(d, "o.sam"))) == want["sam"]
     idx.map_file_pe(os.path.join(d, "p1.fq"), os.path.join(d, "p2.fq"), os.path.join(d, "ope.sam"), threads=4, veryfast=True)
-
-    def pairs(path):
-        body = [x for x in read_records(path) if not x.startswith(b"@")]
-        return sorted(body[i] + b"|" + body[i + 1] for i in range(0, len(body), 2))
-    assert pairs(os.path.join(d, "refpe.sam")) == pairs(os.path.join(d, "ope.sam"))
+    assert ol.digest(_sorted_pairs(os.path.join(d, "ope.sam"))) == want["pe_sam"]
 
 
-@pytest.mark.skipif(not ol.have_ref(), reason="reference binary oracle/_ref/urmap not built")
 @pytest.mark.parametrize("seed,rl,sub", [(41, 279, 0.02), (42, 250, 0.05)])
 def test_oracle_long_pairs_equal_reference_binary(tmp_path, seed, rl, sub):
     """Paired-end at the top of the reference's working range (pending seed positions are bytes, state1.h:86-87: the
-    reference binary crashes from 2x280 on): oracle vs reference SAM on 250 and 279 bp pairs."""
+    reference binary crashes from 2x280 on): oracle vs reference SAM on 250 and 279 bp pairs (the reference's outputs as
+    recorded in tests/golden/ref_runs.json when its binary is not built)."""
     from urmap_amd import synth
     d = str(tmp_path)
     g = synth.make_genome(seed, [240000, 120000, 40000], repeat_frac=0.5, n_families=10, max_div=0.05)
     synth.write_fasta(os.path.join(d, "g.fa"), g)
-    ol.run_ref(["-make_ufi", "g.fa", "-output", "g.ufi"], cwd=d)
-    idx = ol.Index.load(os.path.join(d, "g.ufi"))
     r1, r2 = synth.make_pairs(seed + 2, g, 1500, read_len=rl, sub1=sub, sub2=2 * sub, ins=0.002, dele=0.002)
     synth.write_fastq(os.path.join(d, "p1.fq"), r1)
     synth.write_fastq(os.path.join(d, "p2.fq"), r2)
-    ol.run_ref(["-map2", "p1.fq", "-reverse", "p2.fq", "-ufi", "g.ufi", "-samout", "ref.sam", "-threads", "1"], cwd=d)
+
+    def reference():
+        ol.run_ref(["-make_ufi", "g.fa", "-output", "g.ufi"], cwd=d)
+        ol.run_ref(["-map2", "p1.fq", "-reverse", "p2.fq", "-ufi", "g.ufi", "-samout", "ref.sam", "-threads", "1"], cwd=d)
+        return {"ufi_header": ol.ufi_header(os.path.join(d, "g.ufi")), "ufi": _file_bytes(os.path.join(d, "g.ufi")),
+                "sam": b"\n".join(read_records(os.path.join(d, "ref.sam")))}
+    want = ol.reference_outputs(f"oracle_long_pairs_equal_reference_binary[{seed}]", reference)
+    # the index the reference wrote, rebuilt by the oracle byte for byte (test_oracle_equals_reference_binary)
+    idx = ol.Index.build(os.path.join(d, "g.fa"), want["ufi_header"][3])
+    idx.save(os.path.join(d, "o.ufi"))
+    assert ol.digest(_file_bytes(os.path.join(d, "o.ufi"))) == want["ufi"]
+    idx = ol.Index.load(os.path.join(d, "o.ufi"))
     idx.map_file_pe(os.path.join(d, "p1.fq"), os.path.join(d, "p2.fq"), os.path.join(d, "o.sam"), threads=4)
-    assert read_records(os.path.join(d, "ref.sam")) == read_records(os.path.join(d, "o.sam"))
+    assert ol.digest(b"\n".join(read_records(os.path.join(d, "o.sam")))) == want["sam"]
