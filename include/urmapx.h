@@ -269,6 +269,58 @@ int urmapx_make_ufi_opts(int device, const char *fasta_path, const char *ufi_pat
 int urmapx_build_slots_gpu(int device, const uint8_t *seqdata, const void *d_seqdata, uint32_t seqdata_size, uint32_t word_length,
                            uint32_t max_ix, uint64_t slots, uint8_t *blob, uint32_t *truncated_out);
 
+/* ---- k-mer bit-vector read filter: -make_bitvec, -search_bitvec, -search_bitvec2 (makebitvec.cpp, searchbitvec.cpp,
+ * searchbitvec2.cpp, bitvec.{h,cpp}) ---- */
+/* A table of 4^W bits, one per W-mer, resident in the HBM of one device.  A W-mer is W letters of g_CharToLetterNucleo (ACGTU and
+ * acgtu -> 0..3, every other byte invalid), 2 bits each, the first letter most significant.  Strand 1 of a sequence is its reverse
+ * complement by characters (g_CharToCompChar: 'U' -> 'A', 'u' -> '?', which is invalid).  As in the reference's loops
+ * (makebitvec.cpp:29, searchbitvec.cpp:28), a sequence of length L contributes, on each strand, only the words that START at
+ * 0 .. L-2W+1: a sequence shorter than 2W-1 has none.  Where the reference is undefined -- a sequence or read shorter than W-1, whose
+ * unsigned loop bound wraps -- this build defines it: such a sequence contributes nothing and such a read is never found.
+ * .bv file: uint32 magic URMAPX_BV_MAGIC ("01VB" as bytes), uint32 W, 4^W/8 bytes of bits; bit n = byte[n >> 3] & (1 << (n & 7)). */
+typedef struct urmapx_bitvec urmapx_bitvec;
+#define URMAPX_BV_MAGIC 0x42563130u
+#define URMAPX_BV_MIN_W 2
+#define URMAPX_BV_MAX_W 20 /* the table alone is 128 GiB here; W outside 2..20 is URMAPX_E_UNSUPPORTED */
+/* Build on `device`: set the bit of every word of the sequences seqs[offs[i] .. offs[i+1]) (i < n), both strands; then clear that of
+ * every word of excl[excl_offs[i] .. excl_offs[i+1]) (i < n_excl; excl may be NULL with n_excl = 0).  Host arrays.  counts (may be NULL):
+ * [0] words included (the popcount after the first pass), [1] words excluded ([0] minus the popcount after the second). */
+int urmapx_bitvec_build(int device, const uint8_t *seqs, const uint64_t *offs, uint32_t n, const uint8_t *excl, const uint64_t *excl_offs,
+                        uint32_t n_excl, uint32_t word_length, urmapx_bitvec **out, uint64_t counts[2]);
+/* A .bv file straight into the HBM of `device` (page-locked pieces, no host copy of the bits).  URMAPX_E_FORMAT: bad magic or a file
+ * shorter than its header says; URMAPX_E_UNSUPPORTED: W outside 2..20. */
+int urmapx_bitvec_open(const char *bv_path, int device, urmapx_bitvec **out);
+/* Copy caller-owned host bits (4^W/8 bytes, the .bv layout) to `device`. */
+int urmapx_bitvec_wrap_host(int device, uint32_t word_length, const uint8_t *bits, urmapx_bitvec **out);
+int urmapx_bitvec_save(const urmapx_bitvec *, const char *bv_path);
+/* the 4^W/8 bytes of bits to a host array of at least that many bytes */
+int urmapx_bitvec_download(const urmapx_bitvec *, uint8_t *bits, uint64_t cap);
+uint32_t urmapx_bitvec_word_length(const urmapx_bitvec *);
+uint64_t urmapx_bitvec_bytes(const urmapx_bitvec *);
+int urmapx_bitvec_popcount(const urmapx_bitvec *, uint64_t *out);
+/* SearchBitVec1 (searchbitvec.cpp:17-55) per read: verdicts[i] = 1 if a strand-0 word of read i is set, else 2 if a strand-1 word
+ * is, else 0.  Reads of any length (concatenated bases, offs[n+1]); host arrays, synchronous. */
+int urmapx_bitvec_search(urmapx_bitvec *, const uint8_t *bases, const uint64_t *offs, uint32_t n, uint8_t *verdicts);
+/* The same over reads resident in HBM of the bit vector's device (the d_bases / d_offs convention of urmapx_map_se_device,
+ * d_offs[0] = 0), verdicts to d_verdicts[n]; asynchronous on the bit vector's stream, urmapx_bitvec_sync waits. */
+int urmapx_bitvec_search_device(urmapx_bitvec *, const void *d_bases, const void *d_offs, uint32_t n, void *d_verdicts);
+int urmapx_bitvec_sync(urmapx_bitvec *);
+/* device time (ms, HIP events) of the last build's include and exclude launches [0], [1] and of the last completed search launch [2] */
+int urmapx_bitvec_last_ms(urmapx_bitvec *, float ms[3]);
+void urmapx_bitvec_close(urmapx_bitvec *);
+/* cmd_make_bitvec (makebitvec.cpp:72-106): both FASTA files read as SeqDB::FromFasta does (case kept), the table built on `device`
+ * and written to bv_path.  excl_fa is required, as in the reference ("Missing input file name"). */
+int urmapx_make_bitvec(int device, const char *ref_fa, const char *excl_fa, uint32_t word_length, const char *bv_path, uint64_t counts[2]);
+/* cmd_search_bitvec / cmd_search_bitvec2: FASTQ (plain or .gz, the urmapx_fastq_* rules) -> the records that were found, in input
+ * order, each as FASTQSeqSource left it (a read found on strand 1 reverse-complemented with its quality string reversed).  fq2 NULL:
+ * single-end into out1.  Else pairs: a pair is written (mate 1 to out1, mate 2 to out2) when either mate is found; a mate that was not
+ * found has been through both scans, so it is written reverse-complemented.  Labels whole unless URMAPX_BV_TRUNC_LABELS (cut at the
+ * first white space).  counts (may be NULL): [0] reads (pairs) found, [1] reads (pairs) read.  URMAPX_E_FORMAT with a message in err
+ * for malformed FASTQ or mate files of unequal record counts. */
+#define URMAPX_BV_TRUNC_LABELS 1u
+int urmapx_search_bitvec_files(urmapx_bitvec *, const char *fq1, const char *fq2, const char *out1, const char *out2, unsigned flags,
+                               uint64_t counts[2], char *err, size_t errcap);
+
 /* ---- host-side text (no device involved) ---- */
 /* One SAM record of a single-end read: State1::SetSAM / SetSAM_Unmapped (setsam.cpp:12-207) with Flags = 0 as
  * State1::Output1 passes (output1.cpp:13), CIGAR per state1.cpp:707-734 + cigar.cpp.  path_ops = the batch arena.

@@ -35,7 +35,15 @@ EXPORTS = (
     "urmapx_gunzip_file", "urmapx_fastq_open", "urmapx_fastq_next", "urmapx_fastq_error", "urmapx_fastq_close",
     "urmapx_ctx_gather_microbench", "urmapx_map_files", "urmapx_host_pool_trim", "urmapx_text_create", "urmapx_text_destroy", "urmapx_text_map_se", "urmapx_text_map_pe", "urmapx_pgzip_simd", "urmapx_index_open_device", "urmapx_text_fetch_sam", "urmapx_text_set_deferred", "urmapx_text_wait", "urmapx_text_fetch_pairs", "urmapx_ctx_set_pair_info", "urmapx_ctx_get_pair_info", "urmapx_tab_pe",
     "urmapx_checksum_device", "urmapx_index_checksum", "urmapx_index_layout_checksum",
+    "urmapx_bitvec_build", "urmapx_bitvec_open", "urmapx_bitvec_wrap_host", "urmapx_bitvec_save", "urmapx_bitvec_download",
+    "urmapx_bitvec_word_length", "urmapx_bitvec_bytes", "urmapx_bitvec_popcount", "urmapx_bitvec_search", "urmapx_bitvec_search_device",
+    "urmapx_bitvec_sync", "urmapx_bitvec_last_ms", "urmapx_bitvec_close", "urmapx_make_bitvec", "urmapx_search_bitvec_files",
 )
+
+BV_MAGIC = 0x42563130
+BV_MIN_W, BV_MAX_W = 2, 20
+BV_TRUNC_LABELS = 1
+VERDICT_NONE, VERDICT_FORWARD, VERDICT_REVERSE = 0, 1, 2
 
 
 PAIR_INFO_DTYPE = np.dtype([("top_db", "<u4", 2), ("second_db", "<u4", 2), ("top_score", "<i2", 2), ("second_score", "<i2", 2),
@@ -179,6 +187,24 @@ def lib():
     L.urmapx_fastq_error.argtypes = [vp]
     L.urmapx_fastq_close.restype = None
     L.urmapx_fastq_close.argtypes = [vp]
+    L.urmapx_bitvec_build.argtypes = [i32, vp, vp, u32, vp, vp, u32, u32, C.POINTER(vp), C.POINTER(u64 * 2)]
+    L.urmapx_bitvec_open.argtypes = [cp, i32, C.POINTER(vp)]
+    L.urmapx_bitvec_wrap_host.argtypes = [i32, u32, vp, C.POINTER(vp)]
+    L.urmapx_bitvec_save.argtypes = [vp, cp]
+    L.urmapx_bitvec_download.argtypes = [vp, vp, u64]
+    L.urmapx_bitvec_word_length.restype = u32
+    L.urmapx_bitvec_word_length.argtypes = [vp]
+    L.urmapx_bitvec_bytes.restype = u64
+    L.urmapx_bitvec_bytes.argtypes = [vp]
+    L.urmapx_bitvec_popcount.argtypes = [vp, C.POINTER(u64)]
+    L.urmapx_bitvec_search.argtypes = [vp, vp, vp, u32, vp]
+    L.urmapx_bitvec_search_device.argtypes = [vp, vp, vp, u32, vp]
+    L.urmapx_bitvec_sync.argtypes = [vp]
+    L.urmapx_bitvec_last_ms.argtypes = [vp, C.POINTER(C.c_float * 3)]
+    L.urmapx_bitvec_close.argtypes = [vp]
+    L.urmapx_bitvec_close.restype = None
+    L.urmapx_make_bitvec.argtypes = [i32, cp, cp, u32, cp, C.POINTER(u64 * 2)]
+    L.urmapx_search_bitvec_files.argtypes = [vp, cp, cp, cp, cp, C.c_uint, C.POINTER(u64 * 2), cp, C.c_size_t]
     _lib = L
     return L
 
@@ -425,6 +451,121 @@ def map_files(index: "Index", fastq1, fastq2=None, samout=None, tabout=None, fir
     if rc != 0 and not (rc == E_UNSUPPORTED and allow_unsupported):
         raise UrmapxError(rc, "urmapx_map_files: " + err.value.decode("latin-1"))
     return {k: getattr(rep, k) for k, _ in MapReport._fields_}
+
+
+def _seq_arrays(seqs):
+    """list of byte strings / uint8 arrays, or (bases, offs) already concatenated -> (uint8 bases, uint64 offs)"""
+    if isinstance(seqs, tuple) and len(seqs) == 2 and isinstance(seqs[1], np.ndarray):
+        return np.ascontiguousarray(seqs[0], dtype=np.uint8), np.ascontiguousarray(seqs[1], dtype=np.uint64)
+    arrs = [np.frombuffer(bytes(x), dtype=np.uint8) if not isinstance(x, np.ndarray) else x.astype(np.uint8) for x in seqs]
+    offs = np.zeros(len(arrs) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(a) for a in arrs])
+    bases = np.concatenate(arrs) if arrs else np.zeros(0, np.uint8)
+    return np.ascontiguousarray(bases, dtype=np.uint8), offs
+
+
+class BitVec:
+    """The k-mer bit vector of -make_bitvec / -search_bitvec (4^W bits in the HBM of one device)."""
+
+    def __init__(self, handle):
+        self.h = C.c_void_p(handle)
+
+    @classmethod
+    def build(cls, device, seqs, excl=(), word_length=16):
+        """Set the words of `seqs` (both strands), then clear those of `excl`.  Each: a list of byte strings or (bases, offs).
+        -> (BitVec, (words included, words excluded))"""
+        b, o = _seq_arrays(seqs)
+        eb, eo = _seq_arrays(excl)
+        h, cnt = C.c_void_p(), (C.c_uint64 * 2)()
+        _check(lib().urmapx_bitvec_build(int(device), b.ctypes.data, o.ctypes.data, len(o) - 1, eb.ctypes.data, eo.ctypes.data, len(eo) - 1,
+                                         int(word_length), C.byref(h), C.byref(cnt)), "urmapx_bitvec_build")
+        return cls(h.value), (int(cnt[0]), int(cnt[1]))
+
+    @classmethod
+    def open(cls, path, device=0):
+        h = C.c_void_p()
+        _check(lib().urmapx_bitvec_open(os.fsencode(path), int(device), C.byref(h)), f"urmapx_bitvec_open({path})")
+        return cls(h.value)
+
+    @classmethod
+    def wrap_host(cls, word_length, bits: np.ndarray, device=0):
+        """Copy 4^W/8 bytes of bits (the .bv layout) to `device`."""
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        if len(bits) < (1 << (2 * word_length)) // 8:
+            raise ValueError("bits: fewer than 4^W/8 bytes")
+        h = C.c_void_p()
+        _check(lib().urmapx_bitvec_wrap_host(int(device), int(word_length), bits.ctypes.data, C.byref(h)), "urmapx_bitvec_wrap_host")
+        return cls(h.value)
+
+    @property
+    def word_length(self): return int(lib().urmapx_bitvec_word_length(self.h))
+
+    @property
+    def nbytes(self): return int(lib().urmapx_bitvec_bytes(self.h))
+
+    def save(self, path):
+        _check(lib().urmapx_bitvec_save(self.h, os.fsencode(path)), f"urmapx_bitvec_save({path})")
+
+    def download(self) -> np.ndarray:
+        out = np.empty(self.nbytes, dtype=np.uint8)
+        _check(lib().urmapx_bitvec_download(self.h, out.ctypes.data, len(out)), "urmapx_bitvec_download")
+        return out
+
+    def popcount(self):
+        out = C.c_uint64(0)
+        _check(lib().urmapx_bitvec_popcount(self.h, C.byref(out)), "urmapx_bitvec_popcount")
+        return int(out.value)
+
+    def search(self, bases: np.ndarray, offs: np.ndarray) -> np.ndarray:
+        """-> uint8 verdict per read: 0 not found, 1 forward, 2 reverse"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        out = np.zeros(len(offs) - 1, dtype=np.uint8)
+        _check(lib().urmapx_bitvec_search(self.h, bases.ctypes.data, offs.ctypes.data, len(out), out.ctypes.data), "urmapx_bitvec_search")
+        return out
+
+    def search_device(self, d_bases_ptr, d_offs_ptr, n, d_verdicts_ptr):
+        """asynchronous on the bit vector's stream; sync() waits"""
+        _check(lib().urmapx_bitvec_search_device(self.h, d_bases_ptr, d_offs_ptr, n, d_verdicts_ptr), "urmapx_bitvec_search_device")
+
+    def sync(self):
+        _check(lib().urmapx_bitvec_sync(self.h), "urmapx_bitvec_sync")
+
+    def last_ms(self):
+        """device ms of the last build's include and exclude launches and of the last completed search launch"""
+        ms = (C.c_float * 3)()
+        _check(lib().urmapx_bitvec_last_ms(self.h, C.byref(ms)), "urmapx_bitvec_last_ms")
+        return [float(x) for x in ms]
+
+    def search_files(self, fastq1, out1, fastq2=None, out2=None, trunc_labels=False):
+        """-search_bitvec (fastq2 None) / -search_bitvec2 file to file -> (reads or pairs found, read)"""
+        cnt = (C.c_uint64 * 2)()
+        err = C.create_string_buffer(1024)
+        enc = lambda p: os.fsencode(p) if p else None
+        rc = lib().urmapx_search_bitvec_files(self.h, enc(fastq1), enc(fastq2), enc(out1), enc(out2), BV_TRUNC_LABELS if trunc_labels else 0,
+                                              C.byref(cnt), err, len(err))
+        if rc != 0:
+            raise UrmapxError(rc, "urmapx_search_bitvec_files: " + err.value.decode("latin-1"))
+        return int(cnt[0]), int(cnt[1])
+
+    def close(self):
+        if self.h:
+            lib().urmapx_bitvec_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def make_bitvec(device, ref_fa, excl_fa, word_length, bv_path):
+    """urmap -make_bitvec ref_fa -input2 excl_fa -wordlength W -output bv_path -> (words included, words excluded)"""
+    cnt = (C.c_uint64 * 2)()
+    _check(lib().urmapx_make_bitvec(int(device), os.fsencode(ref_fa), os.fsencode(excl_fa), int(word_length), os.fsencode(bv_path), C.byref(cnt)),
+           "urmapx_make_bitvec")
+    return int(cnt[0]), int(cnt[1])
 
 
 def decode_path(ops: np.ndarray) -> str:

@@ -59,6 +59,10 @@ struct DevBuf {
 	}
 };
 
+// nbytes of the open file fd at file_off -> device array dev through page-locked buffers read by `threads` threads (urmapx.hip);
+// URMAPX_E_FORMAT if the file ends first
+int stream_to_device(int fd, uint64_t file_off, size_t nbytes, uint8_t *dev, int threads);
+
 // kernel classes of the pair kernel (pairs themselves: <= 279 bases per mate, flagged per read)
 constexpr uint32_t MAX_QL_PE = 320;
 

@@ -112,7 +112,7 @@ inline int comp_code_of(uint8_t c) {  // complement letter; lower-case 'u' has n
 	return k < 0 ? -1 : 3 - k;
 }
 
-bool load_fasta(const char *path, std::vector<std::string> &labels, std::vector<std::string> &seqs, bool trunc_labels) {
+bool load_fasta(const char *path, std::vector<std::string> &labels, std::vector<std::string> &seqs, bool trunc_labels, bool keep_case = false) {
 	FILE *f = fopen(path, "rb");
 	if (!f) return false;
 	std::vector<char> buf(1 << 22);
@@ -133,7 +133,7 @@ bool load_fasta(const char *path, std::vector<std::string> &labels, std::vector<
 		} else if (in_rec) {
 			std::string &s = seqs.back();
 			for (unsigned char c : l)
-				if (isalpha(c)) s.push_back((char)toupper(c));  // gaps, digits, blanks dropped; upper-cased
+				if (isalpha(c)) s.push_back(keep_case ? (char)c : (char)toupper(c));  // gaps, digits, blanks dropped; upper-cased for -make_ufi
 		}
 	};
 	size_t n;
@@ -151,6 +151,12 @@ bool load_fasta(const char *path, std::vector<std::string> &labels, std::vector<
 }
 
 }  // namespace
+
+// SeqDB::FromFasta (seqdbfromfasta.cpp:47-57, fastaseqsource.cpp:26-115) as -make_bitvec reads it: the same records, letters in the case
+// the file has them (the bit-vector builder tells 'u' from 'U'); bitvec.hip
+bool urx_load_fasta_keep_case(const char *path, std::vector<std::string> &labels, std::vector<std::string> &seqs) {
+	return load_fasta(path, labels, seqs, true, true);
+}
 
 // UpdateSlot for every position that is not the first indexed occurrence of its slot, in genome order (ufindex.cpp:
 // 107-148,194-322): order dependent, so one after the other.  What each insert will touch can be guessed ahead of time:

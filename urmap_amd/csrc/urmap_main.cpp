@@ -7,6 +7,10 @@
 //   urmap -map2 R1.fq -reverse R2.fq -ufi index.ufi -samout out.sam [-tabbedout out.tab]   (paired-end, map2.cpp:39-90)
 //   urmap -ufi_validate index.ufi [-gpu D]                                                   (ufistats.cpp:141-147, on the device)
 //
+//   urmap -make_bitvec ref.fa -input2 exclude.fa -wordlength W -output x.bv [-gpu D]          (makebitvec.cpp: k-mer bit vector)
+//   urmap -search_bitvec reads.fq -ref x.bv -output hits.fq [-trunclabels] [-gpu D]          (searchbitvec.cpp)
+//   urmap -search_bitvec2 R1.fq -reverse R2.fq -ref x.bv -output1 h1.fq -output2 h2.fq      (searchbitvec2.cpp; bitvec.hip)
+//
 // Pipeline of -map: one reader thread parses FASTQ into batches; batch b goes to mapping lane b mod (N*K), a host
 // thread with its own mapping context on GPU D + (b mod N) (-gpus N devices, each holding its own replica of the index,
 // -streams K contexts per device so that one lane's copies overlap another's kernels); a writer thread takes the
@@ -51,7 +55,9 @@ using namespace urx;
 
 struct Opts {
 	std::string map, map2, reverse, make_ufi, ufi, ufi_validate, samout, tabbedout, output, log;
+	std::string make_bitvec, search_bitvec, search_bitvec2, input2, ref, output1, output2;
 	bool veryfast = false, quiet = false, minq_given = false, host_build = false, notrunclabels = false;
+	bool trunclabels = false, wordlength_given = false;
 	double load_factor = 0.6;  // myopts.h: FLT_OPT(load_factor, 0.6, ...)
 	unsigned threads = 0, wordlength = 24, maxix = 0, minq = 10;
 	unsigned long long slots = 0;
@@ -78,7 +84,7 @@ static Opts parse(int argc, char **argv) {
 		else if (a == "-tabbedout") o.tabbedout = val();
 		else if (a == "-output") o.output = val();
 		else if (a == "-threads") o.threads = (unsigned)atoi(val());
-		else if (a == "-wordlength") o.wordlength = (unsigned)atoi(val());
+		else if (a == "-wordlength") { o.wordlength = (unsigned)atoi(val()); o.wordlength_given = true; }
 		else if (a == "-maxix") o.maxix = (unsigned)atoi(val());
 		else if (a == "-slots") o.slots = strtoull(val(), nullptr, 10);
 		else if (a == "-minq") { o.minq = (unsigned)atoi(val()); o.minq_given = true; }
@@ -92,7 +98,14 @@ static Opts parse(int argc, char **argv) {
 		else if (a == "-quiet") o.quiet = true;
 		else if (a == "-log") o.log = val();
 		else if (a == "-load_factor") o.load_factor = atof(val());
-		else if (a == "-trunclabels") {}  // -map: SetSAM cuts the read label at the first blank whatever this says (setsam.cpp); -make_ufi: the default
+		else if (a == "-trunclabels") o.trunclabels = true;  // -map: SetSAM cuts the read label at the first blank whatever this says (setsam.cpp); -make_ufi: the default; -search_bitvec*: cut the labels written
+		else if (a == "-make_bitvec") o.make_bitvec = val();
+		else if (a == "-search_bitvec") o.search_bitvec = val();
+		else if (a == "-search_bitvec2") o.search_bitvec2 = val();
+		else if (a == "-input2") o.input2 = val();
+		else if (a == "-ref") o.ref = val();
+		else if (a == "-output1") o.output1 = val();
+		else if (a == "-output2") o.output2 = val();
 		else if (a == "-notrunclabels") o.notrunclabels = true;
 		else die("Unknown option %s", a.c_str());
 	}
@@ -127,6 +140,20 @@ static void progress_log(bool quiet, const char *fmt, ...) {
 	va_list ap;
 	if (!quiet) { va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); }
 	if (g_log) { va_start(ap, fmt); vfprintf(g_log, fmt, ap); va_end(ap); }
+}
+
+// IntToStr (myutils.cpp:1420-1438): the unit steps
+static std::string int_to_str(unsigned long long x) {
+	char b[64];
+	const double d = (double)x;
+	if (x < 10000) snprintf(b, sizeof b, "%u", (unsigned)x);
+	else if (d < 1e6) snprintf(b, sizeof b, "%.1fk", d / 1e3);
+	else if (d < 100e6) snprintf(b, sizeof b, "%.1fM", d / 1e6);
+	else if (d < 1e9) snprintf(b, sizeof b, "%.0fM", d / 1e6);
+	else if (d < 10e9) snprintf(b, sizeof b, "%.1fG", d / 1e9);
+	else if (d < 100e9) snprintf(b, sizeof b, "%.0fG", d / 1e9);
+	else snprintf(b, sizeof b, "%.3g", d);
+	return std::string(b);
 }
 
 static void check(int rc, const char *what) {
@@ -187,23 +214,11 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 			}
 			return r;
 		};
-		auto short_int = [](unsigned long long x) {  // IntToStr (myutils.cpp:1420-1438): the unit steps
-			char b[64];
-			const double d = (double)x;
-			if (x < 10000) snprintf(b, sizeof b, "%u", (unsigned)x);
-			else if (d < 1e6) snprintf(b, sizeof b, "%.1fk", d / 1e3);
-			else if (d < 100e6) snprintf(b, sizeof b, "%.1fM", d / 1e6);
-			else if (d < 1e9) snprintf(b, sizeof b, "%.0fM", d / 1e6);
-			else if (d < 10e9) snprintf(b, sizeof b, "%.1fG", d / 1e9);
-			else if (d < 100e9) snprintf(b, sizeof b, "%.0fG", d / 1e9);
-			else snprintf(b, sizeof b, "%.3g", d);
-			return std::string(b);
-		};
 		progress_log(q, "\n%16.1f  Seconds to load index\n", load_s);
 		if (map_s < 180) progress_log(q, "%16.1f  Seconds in mapper\n", map_s);
 		else if (map_s < 2 * 60 * 60) progress_log(q, "%16.1f  Minutes in mapper\n", map_s / 60.0);
 		else progress_log(q, "%16.1f  Hours in mapper\n", map_s / 3600.0);
-		progress_log(q, "%16s  Reads (%s)\n", commas(n_reads).c_str(), short_int(n_reads).c_str());
+		progress_log(q, "%16s  Reads (%s)\n", commas(n_reads).c_str(), int_to_str(n_reads).c_str());
 		if (o.gpus == 1) progress_log(q, "%16.0f  Reads/sec. (GPU %d)\n", map_s > 0 ? (double)n_reads / map_s : 0.0, o.gpu);
 		else progress_log(q, "%16.0f  Reads/sec. (%d GPUs)\n", map_s > 0 ? (double)n_reads / map_s : 0.0, o.gpus);
 		progress_log(q, "%16s  Mapped Q>=%u (%.1f%%)\n", commas(n_accept).c_str(), minq, pct(n_accept));
@@ -317,6 +332,61 @@ static int cmd_ufi_validate(const Opts &o) {
 	return 0;
 }
 
+// ---- k-mer bit vector (bitvec.hip).  -threads is accepted and has no effect: records are written in input order ----
+static void check_bitvec_w(unsigned W) {
+	if (W < URMAPX_BV_MIN_W || W > URMAPX_BV_MAX_W)
+		die("-wordlength %u: %s (the bit vector takes word lengths %d..%d; 4^W bits)", W, urmapx_strerror(URMAPX_E_UNSUPPORTED), URMAPX_BV_MIN_W,
+		    URMAPX_BV_MAX_W);
+}
+
+// cmd_make_bitvec (makebitvec.cpp:72-106)
+static int cmd_make_bitvec(const Opts &o) {
+	if (o.input2.empty()) die("Missing input file name");
+	if (o.output.empty()) die("Missing output file name");
+	if (!o.wordlength_given) die("-wordlength option required");
+	check_bitvec_w(o.wordlength);
+	uint64_t counts[2] = {0, 0};
+	const int rc = urmapx_make_bitvec(o.gpu, o.make_bitvec.c_str(), o.input2.c_str(), o.wordlength, o.output.c_str(), counts);
+	if (rc == URMAPX_E_IO) die("Cannot read %s or write %s", (o.make_bitvec + " / " + o.input2).c_str(), o.output.c_str());
+	check(rc, "make_bitvec");
+	// the reference passes 64-bit counts to %u (their low 32 bits) and to IntToStr
+	progress_log(o.quiet, "%u words included (%s)\n", (unsigned)counts[0], int_to_str(counts[0]).c_str());
+	progress_log(o.quiet, "%u words excluded (%s)\n", (unsigned)counts[1], int_to_str(counts[1]).c_str());
+	return 0;
+}
+
+// cmd_search_bitvec / cmd_search_bitvec2 (searchbitvec.cpp:88-150, searchbitvec2.cpp:64-126)
+static int cmd_search_bitvec(const Opts &o) {
+	const bool paired = !o.search_bitvec2.empty();
+	if (paired && o.reverse.empty()) die("-reverse required");
+	if (o.ref.empty()) die("-ref option required");
+	if (paired ? (o.output1.empty() || o.output2.empty()) : o.output.empty()) die("Missing output file name");
+	{  // the header is checked before a device is opened
+		FILE *f = fopen(o.ref.c_str(), "rb");
+		if (!f) die("Cannot open %s", o.ref.c_str());
+		uint32_t hdr[2] = {0, 0};
+		const size_t got = fread(hdr, 4, 2, f);
+		fclose(f);
+		if (got < 1 || hdr[0] != URMAPX_BV_MAGIC) die("Invalid .bv file");
+		if (got < 2) die("Invalid .bv file");
+		check_bitvec_w(hdr[1]);
+	}
+	urmapx_bitvec *B = nullptr;
+	const int orc = urmapx_bitvec_open(o.ref.c_str(), o.gpu, &B);
+	if (orc == URMAPX_E_FORMAT) die("Invalid .bv file (shorter than its word length says)");
+	check(orc, ("Reading bitvec " + o.ref).c_str());
+	uint64_t counts[2] = {0, 0};
+	char err[1024];
+	const int rc = urmapx_search_bitvec_files(B, paired ? o.search_bitvec2.c_str() : o.search_bitvec.c_str(), paired ? o.reverse.c_str() : nullptr,
+	                                          paired ? o.output1.c_str() : o.output.c_str(), paired ? o.output2.c_str() : nullptr,
+	                                          o.trunclabels ? URMAPX_BV_TRUNC_LABELS : 0u, counts, err, sizeof err);
+	urmapx_bitvec_close(B);
+	if (rc != URMAPX_OK) die("%s", err[0] ? err : urmapx_strerror(rc));
+	progress_log(o.quiet, "%u / %u found (%.1f%%)\n", (unsigned)counts[0], (unsigned)counts[1],
+	             counts[1] ? 100.0 * (double)counts[0] / (double)counts[1] : 0.0);
+	return 0;
+}
+
 int main(int argc, char **argv) {
 	setenv("OMP_WAIT_POLICY", "passive", 0);  // idle pool threads sleep: three pipeline stages share the cores
 	// The HIP runtime spreads a process's streams over FOUR hardware queues unless told otherwise, and streams that share one take turns: two lanes are four
@@ -328,9 +398,14 @@ int main(int argc, char **argv) {
 	if (!o.map.empty() || !o.map2.empty()) { const int rc = cmd_map(o, argc, argv); log_close(); return rc; }
 	if (!o.make_ufi.empty()) { const int rc = cmd_make_ufi(o); log_close(); return rc; }
 	if (!o.ufi_validate.empty()) { const int rc = cmd_ufi_validate(o); log_close(); return rc; }
+	if (!o.make_bitvec.empty()) { const int rc = cmd_make_bitvec(o); log_close(); return rc; }
+	if (!o.search_bitvec.empty() || !o.search_bitvec2.empty()) { const int rc = cmd_search_bitvec(o); log_close(); return rc; }
 	fprintf(stderr, "urmap (MI355X build)\n  urmap -map reads.fq -ufi index.ufi -samout out.sam [-veryfast] [-gpu D] [-gpus N] [-streams K] [-samshards N]\n"
 	                "  urmap -map2 R1.fq -reverse R2.fq -ufi index.ufi -samout out.sam [-tabbedout out.tab] [-gpu D] [-gpus N]\n"
 	                "  urmap -make_ufi genome.fa -output index.ufi [-slots N] [-wordlength W] [-maxix M]\n"
-	                "  urmap -ufi_validate index.ufi [-gpu D]\n");
+	                "  urmap -ufi_validate index.ufi [-gpu D]\n"
+	                "  urmap -make_bitvec ref.fa -input2 exclude.fa -wordlength W -output x.bv [-gpu D]\n"
+	                "  urmap -search_bitvec reads.fq -ref x.bv -output hits.fq [-trunclabels] [-gpu D]\n"
+	                "  urmap -search_bitvec2 R1.fq -reverse R2.fq -ref x.bv -output1 h1.fq -output2 h2.fq [-trunclabels] [-gpu D]\n");
 	return 0;
 }

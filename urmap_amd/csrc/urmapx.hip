@@ -189,8 +189,9 @@ int urmapx_index_open(const char *path, urmapx_index **out) {
 static int upload_directory(urmapx_index *I);
 
 // nbytes of the file at file_off -> dev: several threads pread pieces of 128 MB into page-locked buffers, each piece goes out with
-// an asynchronous copy while the next is being read (three buffers in flight)
-static int stream_to_device(int fd, uint64_t file_off, size_t nbytes, uint8_t *dev, int threads) {
+// an asynchronous copy while the next is being read (three buffers in flight).  Also what urmapx_bitvec_open loads a .bv file with
+extern "C++" {  // (declared in internal.h, outside this extern "C" block)
+int urx::stream_to_device(int fd, uint64_t file_off, size_t nbytes, uint8_t *dev, int threads) {
 	constexpr size_t PIECE = 128u << 20;
 	constexpr int NS = 3;
 	char *stage[NS] = {nullptr, nullptr, nullptr};
@@ -235,6 +236,7 @@ static int stream_to_device(int fd, uint64_t file_off, size_t nbytes, uint8_t *d
 	if (st && hipStreamSynchronize(st) != hipSuccess && rc == URMAPX_OK) rc = URMAPX_E_NODEVICE;
 	cleanup();
 	return rc;
+}
 }
 
 // UFIndex::FromFile (ufindexio.cpp:51-115) straight into HBM.  urmapx_index_open reads the file into host arrays with one thread (27 GB at hg38
