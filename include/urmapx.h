@@ -134,6 +134,38 @@ typedef struct urmapx_validate_report {
 	double seconds;          /* the pass on the device */
 } urmapx_validate_report;
 int urmapx_index_validate(const urmapx_index *, urmapx_validate_report *out);
+/* The index statistics of -ufi_stats (UFIndex::LogStats, ufistats.cpp:5-124) as two device passes over the RESIDENT table
+ * (ufi_stats.hip).  The sequence passes look at [0, SeqDataSize - 1), as the reference's do (ufindexio.cpp:70-71).  Counters are
+ * 64 bit where the reference's are 32-bit `unsigned`: the two agree below 2^32.  Returns URMAPX_OK; URMAPX_E_ARG if the index is not
+ * resident; URMAPX_E_UNSUPPORTED for a word length over 32; URMAPX_E_FORMAT if a row is damaged (K >= 256, or a position at or past
+ * the sequence store where the reference would compare its bytes; the reference asserts), with bad_rows and first_bad_slot set and
+ * the collision count leaving those rows out.  Two byte arrays of slot_count bytes each live on the device for the call. */
+typedef struct urmapx_ufi_stats {
+	uint64_t word_length, max_ix, seqdata_size, slots;
+	uint64_t indexed;     /* complete words whose start position is in their slot's row (CountIndexedWords) */
+	uint64_t not_indexed; /* complete words whose start is not */
+	uint64_t wildcard;    /* positions where no complete word ends */
+	uint64_t indexed2;    /* sum over every slot of its row length (GetCollisionCount) */
+	uint64_t free;        /* tally classes over every slot */
+	uint64_t collision;   /* row entries k >= 1 whose W raw bytes differ from entry 0's */
+	uint64_t single_both, single_plus, end, mine, other;
+	uint64_t trunc, trunc2; /* slots whose row the MaxIx cap cut: sum of their plus counts, their number */
+	uint64_t long_mine, long_other;
+	uint64_t total;       /* sum of the (saturated) plus counts */
+	uint64_t bad_rows;    /* damaged rows (see above) */
+	uint64_t first_bad_slot; /* lowest damaged head slot; UINT64_MAX: none */
+	uint64_t count_hist[256]; /* slots whose plus count is n */
+	uint64_t trunc_hist[256]; /* truncated slots whose plus count is n */
+	double position_seconds;  /* the pass over the sequence on the device */
+	double slot_seconds;      /* the pass over the slots */
+} urmapx_ufi_stats;
+int urmapx_index_stats(const urmapx_index *, urmapx_ufi_stats *out);
+/* UFIndex::CountSlots (minus = 0; the bytes -ufi_counts writes) or CountSlots_Minus (minus != 0) of the resident table into
+ * host_out: one byte per slot, the number of words that hash there saturated at 255.  n must equal the slot count (URMAPX_E_ARG). */
+int urmapx_index_slot_counts(const urmapx_index *, int minus, uint8_t *host_out, uint64_t n);
+/* -ufi_info (ufistats.cpp:148-175): the 24-byte header of a .ufi file only, on the host.  URMAPX_E_IO if it cannot be read,
+ * URMAPX_E_FORMAT if the magic is wrong.  Any output pointer may be NULL. */
+int urmapx_ufi_info(const char *path, uint32_t *word_length, uint32_t *max_ix, uint32_t *seqdata_size, uint64_t *slot_count);
 /* Which bytes is this?  Checksum of a device-resident array: the sum, modulo 2^64, over its little-endian 64-bit words w_i
  * (i = 0, 1, ...; the last word zero-padded) of murmur64(w_i + (i + 1) * 0x9E3779B97F4A7C15) with the reference's murmur64
  * (ufindex.h:50-58).  d_ptr must be 8-byte aligned.  A sum, so the same array gives the same value on every device and in the

@@ -38,6 +38,7 @@ EXPORTS = (
     "urmapx_bitvec_build", "urmapx_bitvec_open", "urmapx_bitvec_wrap_host", "urmapx_bitvec_save", "urmapx_bitvec_download",
     "urmapx_bitvec_word_length", "urmapx_bitvec_bytes", "urmapx_bitvec_popcount", "urmapx_bitvec_search", "urmapx_bitvec_search_device",
     "urmapx_bitvec_sync", "urmapx_bitvec_last_ms", "urmapx_bitvec_close", "urmapx_make_bitvec", "urmapx_search_bitvec_files",
+    "urmapx_index_stats", "urmapx_index_slot_counts", "urmapx_ufi_info",
 )
 
 BV_MAGIC = 0x42563130
@@ -77,6 +78,16 @@ class MapReport(C.Structure):
 class ValidateReport(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("slots", "heads", "positions", "used", "reached", "bad_hash", "bad_pos", "bad_link", "bad_len",
                                           "first_bad_slot")] + [("seconds", C.c_double)]
+
+
+STATS_FIELDS = ("word_length", "max_ix", "seqdata_size", "slots", "indexed", "not_indexed", "wildcard", "indexed2", "free", "collision",
+                "single_both", "single_plus", "end", "mine", "other", "trunc", "trunc2", "long_mine", "long_other", "total", "bad_rows",
+                "first_bad_slot")
+
+
+class UfiStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in STATS_FIELDS] + [("count_hist", C.c_uint64 * 256), ("trunc_hist", C.c_uint64 * 256),
+                                                          ("position_seconds", C.c_double), ("slot_seconds", C.c_double)]
 
 
 class TextReport(C.Structure):
@@ -122,6 +133,9 @@ def lib():
         f.restype = rt
         f.argtypes = [vp]
     L.urmapx_index_validate.argtypes = [vp, C.POINTER(ValidateReport)]
+    L.urmapx_index_stats.argtypes = [vp, C.POINTER(UfiStats)]
+    L.urmapx_index_slot_counts.argtypes = [vp, i32, vp, u64]
+    L.urmapx_ufi_info.argtypes = [cp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u64)]
     L.urmapx_checksum_device.argtypes = [i32, vp, u64, C.POINTER(u64)]
     L.urmapx_index_checksum.argtypes = [vp, C.POINTER(u64)]
     L.urmapx_index_layout_checksum.argtypes = [vp, C.POINTER(u64)]
@@ -332,6 +346,23 @@ class Index:
             raise UrmapxError(rc, "urmapx_index_validate")
         return rc == 0, {n: getattr(r, n) for n, _ in ValidateReport._fields_}
 
+    def stats(self):
+        """-ufi_stats (UFIndex::LogStats, ufistats.cpp) as two device passes over the resident table -> dict of every counter, the two
+        256-bin histograms (count_hist, trunc_hist) and the passes' seconds.  A damaged row raises UrmapxError(E_FORMAT)."""
+        r = UfiStats()
+        _check(lib().urmapx_index_stats(self.h, C.byref(r)), "urmapx_index_stats")
+        d = {n: int(getattr(r, n)) for n in STATS_FIELDS}
+        d["count_hist"] = [int(x) for x in r.count_hist]
+        d["trunc_hist"] = [int(x) for x in r.trunc_hist]
+        d["position_seconds"], d["slot_seconds"] = r.position_seconds, r.slot_seconds
+        return d
+
+    def slot_counts(self, minus=False):
+        """CountSlots (the bytes -ufi_counts writes) or, minus=True, CountSlots_Minus of the resident table: uint8 per slot"""
+        out = np.empty(self.slot_count, dtype=np.uint8)
+        _check(lib().urmapx_index_slot_counts(self.h, 1 if minus else 0, out.ctypes.data, out.size), "urmapx_index_slot_counts")
+        return out
+
     def checksum(self):
         """(slot table, sequence store): urmapx_index_checksum over the resident arrays -- which table and which genome this is"""
         out = (C.c_uint64 * 2)()
@@ -427,6 +458,13 @@ class Index:
             self.close()
         except Exception:
             pass
+
+
+def ufi_info(path):
+    """-ufi_info: the header of a .ufi file (host only; the index is not loaded) -> dict"""
+    w, m, sd, sc = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+    _check(lib().urmapx_ufi_info(os.fsencode(path), C.byref(w), C.byref(m), C.byref(sd), C.byref(sc)), "urmapx_ufi_info")
+    return {"word_length": w.value, "max_ix": m.value, "seqdata_size": sd.value, "slots": sc.value}
 
 
 def gunzip_file(gz_path, out_path, threads=0):

@@ -26,27 +26,14 @@ namespace urx {
 static constexpr int CR_GROUP = 1024;
 static constexpr int CR_ROW_CAP = 32;  // UFIndex m_MaxIx of every index this build accepts
 
-// GetRow_Blob from a head slot whose tally says "mine, with a next link" -- the walk of SearchWave::walk_run, one thread per
-// chain.  out != nullptr: the positions are written; returns the row length.
+// GetRow_Blob from a head slot whose tally says "mine, with a next link" -- the walk of SearchWave::walk_run (walk_row,
+// dev_common.h), one thread per chain.  out != nullptr: the positions are written; returns the row length.
 __device__ __forceinline__ int chain_row(const uint8_t *__restrict__ blob, uint64_t N, int maxIx, uint64_t slot, uint32_t T, uint32_t pos,
                                          uint32_t *out) {
-	int K = 0;
-	for (;;) {
-		if (out) out[K] = pos;
-		++K;
-		if (K == maxIx || K >= CR_ROW_CAP) return K;
-		if (T == TALLY_PLUS1 || T == TALLY_BOTH1) return 1;
-		if (T == TALLY_END) return K;
-		if (T == TALLY_LONG_MINE || T == TALLY_LONG_OTHER) {
-			const uint64_t slotA = addmod(slot, pos & 0xFFFFu, N);
-			slot = addmod(slotA, pos >> 16, N);
-			uint32_t tA, pA;
-			load_slot(blob, slotA, tA, pA);
-			if (out) out[K - 1] = pA;
-		} else
-			slot = addmod(slot, T & TALLY_NEXT_MASK, N);
-		load_slot(blob, slot, T, pos);
-	}
+	const uint32_t cap = (uint32_t)(maxIx < CR_ROW_CAP ? maxIx : CR_ROW_CAP);  // (the layout is built only for 1 <= maxIx)
+	return (int)walk_row(blob, N, cap, slot, T, pos, [&](uint32_t k, uint32_t p) {
+		if (out) out[k] = p;
+	});
 }
 
 __device__ __forceinline__ bool heads_a_row(uint32_t T) { return (T & TALLY_MY_BIT) != 0 && T != TALLY_BOTH1 && T != TALLY_PLUS1; }

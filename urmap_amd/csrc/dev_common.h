@@ -152,6 +152,35 @@ __device__ __forceinline__ void load_slot(const uint8_t *blob, uint64_t slot, ui
 	pos = (uint32_t)(v >> 8);
 }
 
+// UFIndex::GetRow (ufindex.cpp:776-832) from a head slot {T, pos} whose tally says "mine": visit(k, position) for the row's entries
+// k = 0, 1, ... in order; returns the row length K.  At most `cap` entries (the index's MaxIx, or less).  The cap is tested before
+// a long link is resolved, so a row cut there keeps the link's step word as its last entry, as GetRow's does; otherwise the middle
+// slot's position replaces that of the slot holding the steps.  Shared by the chain-row layout (chain_rows.hip) and the index
+// statistics (ufi_stats.hip).
+template <class F>
+__device__ __forceinline__ uint32_t walk_row(const uint8_t *__restrict__ blob, uint64_t N, uint32_t cap, uint64_t slot, uint32_t T, uint32_t pos,
+                                             F &&visit) {
+	uint32_t K = 0;
+	for (;;) {
+		++K;
+		if (K >= cap || T == TALLY_PLUS1 || T == TALLY_BOTH1 || T == TALLY_END) {
+			visit(K - 1, pos);
+			return K;
+		}
+		if (T == TALLY_LONG_MINE || T == TALLY_LONG_OTHER) {
+			const uint64_t slotA = addmod(slot, pos & 0xFFFFu, N);
+			slot = addmod(slotA, pos >> 16, N);
+			uint32_t tA, pA;
+			load_slot(blob, slotA, tA, pA);
+			visit(K - 1, pA);
+		} else {
+			visit(K - 1, pos);
+			slot = addmod(slot, T & TALLY_NEXT_MASK, N);
+		}
+		load_slot(blob, slot, T, pos);
+	}
+}
+
 // PosToCoordL on the device (search_se_kernel: fill_result_core; search_pe_kernel's output): up to 64 sequences every lane tests one
 // (one round of loads instead of the binary search's five or six dependent ones); 0: the binary search always (A/B builds)
 #ifndef URX_SEQ_LANES

@@ -186,6 +186,15 @@ hipError_t build_chain_rows(const uint8_t *d_blob, uint64_t slot_count, uint32_t
 // walks, bad hashes, bad positions, bad links, bad row lengths, first bad head slot (all ones: none); ms: the pass on the device
 hipError_t validate_index(const DevIndex &X, uint64_t out[9], float *ms);
 
+// -ufi_stats (ufi_stats.hip): counters[UFI_STATS_COUNTERS] = indexed, not_indexed, wildcard (the position pass), then indexed2, free,
+// collision, single_both, single_plus, end, mine, other, trunc, trunc2, long_mine, long_other, total, bad rows (the slot pass);
+// hist[0..255] CountHist, hist[256..511] TruncHist; first_bad_slot all ones if no row is damaged; ms[2]: the two passes.  The two
+// count arrays (slot_count bytes each) live for the call only.  ufi_slot_counts_device: CountSlots (minus = 0) or CountSlots_Minus
+// into host_out (slot_count bytes).
+static constexpr int UFI_STATS_COUNTERS = 17;
+hipError_t ufi_stats_device(const DevIndex &X, uint64_t counters[UFI_STATS_COUNTERS], uint64_t hist[512], uint64_t *first_bad_slot, float ms[2]);
+hipError_t ufi_slot_counts_device(const DevIndex &X, int minus, uint8_t *host_out);
+
 // sum of murmur64(word_i + (i + 1) * golden ratio) over the array's little-endian 64-bit words (chain_rows.hip); d_ptr 8-byte aligned
 hipError_t checksum_device(const void *d_ptr, uint64_t nbytes, uint64_t *out);
 

@@ -6,6 +6,9 @@
 //
 //   urmap -map2 R1.fq -reverse R2.fq -ufi index.ufi -samout out.sam [-tabbedout out.tab]   (paired-end, map2.cpp:39-90)
 //   urmap -ufi_validate index.ufi [-gpu D]                                                   (ufistats.cpp:141-147, on the device)
+//   urmap -ufi_stats index.ufi [-log F] [-gpu D] [-quiet]                                    (ufistats.cpp:5-131; ufi_stats.hip)
+//   urmap -ufi_counts index.ufi -output F [-gpu D]                                          (ufistats.cpp:133-140, on the device)
+//   urmap -ufi_info index.ufi [-log F]                                                      (ufistats.cpp:148-175: the header only)
 //
 //   urmap -make_bitvec ref.fa -input2 exclude.fa -wordlength W -output x.bv [-gpu D]          (makebitvec.cpp: k-mer bit vector)
 //   urmap -search_bitvec reads.fq -ref x.bv -output hits.fq [-trunclabels] [-gpu D]          (searchbitvec.cpp)
@@ -54,7 +57,7 @@ using namespace urx;
 }
 
 struct Opts {
-	std::string map, map2, reverse, make_ufi, ufi, ufi_validate, samout, tabbedout, output, log;
+	std::string map, map2, reverse, make_ufi, ufi, ufi_validate, ufi_stats, ufi_counts, ufi_info, samout, tabbedout, output, log;
 	std::string make_bitvec, search_bitvec, search_bitvec2, input2, ref, output1, output2;
 	bool veryfast = false, quiet = false, minq_given = false, host_build = false, notrunclabels = false;
 	bool trunclabels = false, wordlength_given = false;
@@ -80,6 +83,9 @@ static Opts parse(int argc, char **argv) {
 		else if (a == "-make_ufi") o.make_ufi = val();
 		else if (a == "-ufi") o.ufi = val();
 		else if (a == "-ufi_validate") o.ufi_validate = val();
+		else if (a == "-ufi_stats") o.ufi_stats = val();
+		else if (a == "-ufi_counts") o.ufi_counts = val();
+		else if (a == "-ufi_info") o.ufi_info = val();
 		else if (a == "-samout") o.samout = val();
 		else if (a == "-tabbedout") o.tabbedout = val();
 		else if (a == "-output") o.output = val();
@@ -304,17 +310,24 @@ static int cmd_make_ufi(const Opts &o) {
 }
 
 // cmd_ufi_validate (ufistats.cpp:141-147): FromFile + UFIndex::Validate (ufindex.cpp:611-658), the pass itself on the device
-static int cmd_ufi_validate(const Opts &o) {
+// FromFile for the passes that read the table themselves (-ufi_validate, -ufi_stats, -ufi_counts): the file streams to the device, without
+// the derived row layouts; URMAPX_HOST_INDEX=1: through host arrays
+static urmapx_index *open_resident(const std::string &path, int gpu) {
 	urmapx_index *I = nullptr;
 	setenv("URMAPX_NO_CHAIN_ROWS", "1", 0);  // the pass reads the table itself; the derived row layout is not needed for it
 	if (getenv("URMAPX_HOST_INDEX")) {
-		check(urmapx_index_open(o.ufi_validate.c_str(), &I), ("Reading index " + o.ufi_validate).c_str());
-		check(urmapx_index_upload(I, o.gpu), "index upload");
+		check(urmapx_index_open(path.c_str(), &I), ("Reading index " + path).c_str());
+		check(urmapx_index_upload(I, gpu), "index upload");
 	} else {  // the file streams to the device (urmapx_index_open_device)
-		const int lrc = urmapx_index_open_device(o.ufi_validate.c_str(), o.gpu, &I);
+		const int lrc = urmapx_index_open_device(path.c_str(), gpu, &I);
 		if (lrc == URMAPX_E_NODEVICE || lrc == URMAPX_E_NOMEM) check(lrc, "index upload");
-		check(lrc, ("Reading index " + o.ufi_validate).c_str());
+		check(lrc, ("Reading index " + path).c_str());
 	}
+	return I;
+}
+
+static int cmd_ufi_validate(const Opts &o) {
+	urmapx_index *I = open_resident(o.ufi_validate, o.gpu);
 	urmapx_validate_report r;
 	const int rc = urmapx_index_validate(I, &r);
 	if (rc != URMAPX_OK && rc != URMAPX_E_FORMAT) check(rc, "ufi_validate");
@@ -329,6 +342,120 @@ static int cmd_ufi_validate(const Opts &o) {
 		    (unsigned long long)r.first_bad_slot, (unsigned long long)r.bad_hash, (unsigned long long)r.bad_pos, (unsigned long long)r.bad_link,
 		    (unsigned long long)r.bad_len, (unsigned long long)r.used, (unsigned long long)r.reached);
 	}
+	return 0;
+}
+
+// Int64ToStr (myutils.cpp:1440-1458): IntToStr but for its "%.1fM" step, which ends at 10M instead of 100M
+static std::string int64_to_str(unsigned long long x) {
+	char b[64];
+	const double d = (double)x;
+	if (x < 10000) snprintf(b, sizeof b, "%u", (unsigned)x);
+	else if (d < 1e6) snprintf(b, sizeof b, "%.1fk", d / 1e3);
+	else if (d < 10e6) snprintf(b, sizeof b, "%.1fM", d / 1e6);
+	else if (d < 1e9) snprintf(b, sizeof b, "%.0fM", d / 1e6);
+	else if (d < 10e9) snprintf(b, sizeof b, "%.1fG", d / 1e9);
+	else if (d < 100e9) snprintf(b, sizeof b, "%.0fG", d / 1e9);
+	else snprintf(b, sizeof b, "%.3g", d);
+	return std::string(b);
+}
+
+// MemBytesToStr (myutils.cpp:1220-1235)
+static std::string mem_bytes_to_str(double x) {
+	char b[64];
+	if (x < 1e4) snprintf(b, sizeof b, "%.1fb", x);
+	else if (x < 1e6) snprintf(b, sizeof b, "%.1fkb", x / 1e3);
+	else if (x < 10e6) snprintf(b, sizeof b, "%.1fMb", x / 1e6);
+	else if (x < 1e9) snprintf(b, sizeof b, "%.0fMb", x / 1e6);
+	else if (x < 100e9) snprintf(b, sizeof b, "%.1fGb", x / 1e9);
+	else snprintf(b, sizeof b, "%.0fGb", x / 1e9);
+	return std::string(b);
+}
+
+static double get_pct(uint64_t x, uint64_t y) { return y ? 100.0 * (double)x / (double)y : 0.0; }  // GetPct (myutils.h:344-345)
+
+// UFIndex::LogStats's report (ufistats.cpp:62-123), the counters printed as the 64-bit values they are
+static std::string stats_report(const urmapx_ufi_stats &r) {
+	std::string out;
+	char b[256];
+	auto put = [&](const char *fmt, auto... a) { snprintf(b, sizeof b, fmt, a...); out += b; };
+	unsigned maxi = 0;
+	for (unsigned i = 0; i < 256; ++i)
+		if (r.count_hist[i]) maxi = i;
+	if (maxi > 4) maxi = 4;
+	for (unsigned i = 0; i <= maxi; ++i) {
+		const unsigned long long ch = r.count_hist[i], th = r.trunc_hist[i];
+		put("[%3u]  %10llu", i, ch);
+		if (i == 0) put("  %7.7s ", "");
+		else put("  %7.2f%%", get_pct(ch, r.total));
+		if ((i > 1 && i <= r.max_ix) || th != 0) {
+			put("  %10llu  ", th);
+			put("  %7.2f%%", get_pct(th, ch));
+			if (i == 1 && th > 0) put(" <<< TRUNCATED SINGLES");
+			if (th > 0 && i > r.max_ix) put(" <<< GT MaxIx %u", (unsigned)r.max_ix);
+		}
+		out += "\n";
+	}
+	out += "\n";
+	put("%10llu  Word length\n", (unsigned long long)r.word_length);
+	put("%10llu  MaxIx\n", (unsigned long long)r.max_ix);
+	put("%10llu  Sequence data (%s)\n", (unsigned long long)r.seqdata_size, int_to_str(r.seqdata_size).c_str());
+	put("%10llu  Slots (%s)\n", (unsigned long long)r.slots, int64_to_str(r.slots).c_str());
+	const std::pair<const char *, uint64_t> rows[] = {
+	    {"Indexed", r.indexed}, {"Indexed2", r.indexed2}, {"NotIndexed", r.not_indexed}, {"Wildcard", r.wildcard}, {"Free", r.free},
+	    {"Collision", r.collision}, {"SingleBoth", r.single_both}, {"SinglePlus", r.single_plus}, {"End", r.end}, {"Mine", r.mine},
+	    {"Other", r.other}, {"Trunc", r.trunc}, {"Trunc2", r.trunc2}, {"LongMine", r.long_mine}, {"LongOther", r.long_other},
+	    {"Total", r.total}};
+	for (const auto &x : rows) put("%10llu  %s\n", (unsigned long long)x.second, x.first);
+	out += "\n";
+	return out;
+}
+
+// cmd_ufi_stats (ufistats.cpp:126-131): the report goes to the log (Log), and to stderr unless -quiet
+static int cmd_ufi_stats(const Opts &o) {
+	urmapx_index *I = open_resident(o.ufi_stats, o.gpu);
+	urmapx_ufi_stats r;
+	const int rc = urmapx_index_stats(I, &r);
+	urmapx_index_close(I);
+	if (rc == URMAPX_E_FORMAT)
+		die("ufi_stats: damaged row at slot 0x%llx (%llu rows with a position past the sequence store or 256 entries or more)",
+		    (unsigned long long)r.first_bad_slot, (unsigned long long)r.bad_rows);
+	check(rc, "ufi_stats");
+	const std::string rep = stats_report(r);
+	if (g_log) fputs(rep.c_str(), g_log);
+	if (!o.quiet) {
+		fputs(rep.c_str(), stderr);
+		fprintf(stderr, "position pass %.3f s, slot pass %.3f s (GPU %d)\n", r.position_seconds, r.slot_seconds, o.gpu);
+	}
+	return 0;
+}
+
+// cmd_ufi_counts (ufistats.cpp:133-140): CountSlots, one byte per slot
+static int cmd_ufi_counts(const Opts &o) {
+	if (o.output.empty()) die("Missing output file name");
+	urmapx_index *I = open_resident(o.ufi_counts, o.gpu);
+	const uint64_t n = urmapx_index_slot_count(I);
+	std::vector<uint8_t> counts(n);
+	const int rc = urmapx_index_slot_counts(I, 0, counts.data(), n);
+	urmapx_index_close(I);
+	check(rc, "ufi_counts");
+	FILE *f = fopen(o.output.c_str(), "wb");
+	if (!f) die("Cannot create %s", o.output.c_str());
+	if (fwrite(counts.data(), 1, n, f) != n || fclose(f) != 0) die("Write error %s", o.output.c_str());
+	return 0;
+}
+
+// cmd_ufi_info (ufistats.cpp:148-175): the header, without loading the index
+static int cmd_ufi_info(const Opts &o) {
+	uint32_t w = 0, m = 0, sd = 0;
+	uint64_t sc = 0;
+	const int rc = urmapx_ufi_info(o.ufi_info.c_str(), &w, &m, &sd, &sc);
+	if (rc == URMAPX_E_IO) die("Cannot read %s", o.ufi_info.c_str());
+	if (rc == URMAPX_E_FORMAT) die("%s: not a .ufi file (bad magic)", o.ufi_info.c_str());
+	check(rc, "ufi_info");
+	progress_log(o.quiet, " Word length  %u\n", w);
+	progress_log(o.quiet, "       MaxIx  %u\n", m);
+	progress_log(o.quiet, "     SeqData  %u (%s)\n", sd, mem_bytes_to_str((double)sd).c_str());
+	progress_log(o.quiet, "       Slots  %llu (%s)\n", (unsigned long long)sc, mem_bytes_to_str((double)sc).c_str());
 	return 0;
 }
 
@@ -398,12 +525,18 @@ int main(int argc, char **argv) {
 	if (!o.map.empty() || !o.map2.empty()) { const int rc = cmd_map(o, argc, argv); log_close(); return rc; }
 	if (!o.make_ufi.empty()) { const int rc = cmd_make_ufi(o); log_close(); return rc; }
 	if (!o.ufi_validate.empty()) { const int rc = cmd_ufi_validate(o); log_close(); return rc; }
+	if (!o.ufi_stats.empty()) { const int rc = cmd_ufi_stats(o); log_close(); return rc; }
+	if (!o.ufi_counts.empty()) { const int rc = cmd_ufi_counts(o); log_close(); return rc; }
+	if (!o.ufi_info.empty()) { const int rc = cmd_ufi_info(o); log_close(); return rc; }
 	if (!o.make_bitvec.empty()) { const int rc = cmd_make_bitvec(o); log_close(); return rc; }
 	if (!o.search_bitvec.empty() || !o.search_bitvec2.empty()) { const int rc = cmd_search_bitvec(o); log_close(); return rc; }
 	fprintf(stderr, "urmap (MI355X build)\n  urmap -map reads.fq -ufi index.ufi -samout out.sam [-veryfast] [-gpu D] [-gpus N] [-streams K] [-samshards N]\n"
 	                "  urmap -map2 R1.fq -reverse R2.fq -ufi index.ufi -samout out.sam [-tabbedout out.tab] [-gpu D] [-gpus N]\n"
 	                "  urmap -make_ufi genome.fa -output index.ufi [-slots N] [-wordlength W] [-maxix M]\n"
 	                "  urmap -ufi_validate index.ufi [-gpu D]\n"
+	                "  urmap -ufi_stats index.ufi [-log F] [-gpu D] [-quiet]\n"
+	                "  urmap -ufi_counts index.ufi -output F [-gpu D]\n"
+	                "  urmap -ufi_info index.ufi [-log F]\n"
 	                "  urmap -make_bitvec ref.fa -input2 exclude.fa -wordlength W -output x.bv [-gpu D]\n"
 	                "  urmap -search_bitvec reads.fq -ref x.bv -output hits.fq [-trunclabels] [-gpu D]\n"
 	                "  urmap -search_bitvec2 R1.fq -reverse R2.fq -ref x.bv -output1 h1.fq -output2 h2.fq [-trunclabels] [-gpu D]\n");

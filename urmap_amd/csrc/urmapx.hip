@@ -472,6 +472,51 @@ int urmapx_index_validate(const urmapx_index *I, urmapx_validate_report *out) {
 	const bool ok = !v[4] && !v[5] && !v[6] && !v[7] && v[2] == v[3];
 	return ok ? URMAPX_OK : URMAPX_E_FORMAT;
 }
+int urmapx_index_stats(const urmapx_index *I, urmapx_ufi_stats *out) {
+	if (!I || !out) return URMAPX_E_ARG;
+	memset(out, 0, sizeof *out);
+	out->first_bad_slot = ~0ull;
+	if (!I->d_blob || !I->d_seq || I->device < 0) return URMAPX_E_ARG;  // urmapx_index_upload first
+	if (I->W < 1 || I->W > 32) return URMAPX_E_UNSUPPORTED;
+	HIP_TRY(hipSetDevice(I->device));
+	uint64_t c[UFI_STATS_COUNTERS], hist[512], first_bad = ~0ull;
+	float ms[2] = {0.f, 0.f};
+	HIP_TRY(ufi_stats_device(I->view(), c, hist, &first_bad, ms));
+	out->word_length = I->W; out->max_ix = I->maxIx; out->seqdata_size = I->seqDataSize; out->slots = I->slotCount;
+	out->indexed = c[0]; out->not_indexed = c[1]; out->wildcard = c[2];
+	out->indexed2 = c[3]; out->free = c[4]; out->collision = c[5]; out->single_both = c[6]; out->single_plus = c[7]; out->end = c[8];
+	out->mine = c[9]; out->other = c[10]; out->trunc = c[11]; out->trunc2 = c[12]; out->long_mine = c[13]; out->long_other = c[14];
+	out->total = c[15]; out->bad_rows = c[16]; out->first_bad_slot = first_bad;
+	memcpy(out->count_hist, hist, sizeof out->count_hist);
+	memcpy(out->trunc_hist, hist + 256, sizeof out->trunc_hist);
+	out->position_seconds = ms[0] * 1e-3;
+	out->slot_seconds = ms[1] * 1e-3;
+	return out->bad_rows ? URMAPX_E_FORMAT : URMAPX_OK;
+}
+int urmapx_index_slot_counts(const urmapx_index *I, int minus, uint8_t *host_out, uint64_t n) {
+	if (!I || !host_out || n != I->slotCount) return URMAPX_E_ARG;
+	if (!I->d_blob || !I->d_seq || I->device < 0) return URMAPX_E_ARG;
+	if (I->W < 1 || I->W > 32) return URMAPX_E_UNSUPPORTED;
+	HIP_TRY(hipSetDevice(I->device));
+	HIP_TRY(ufi_slot_counts_device(I->view(), minus, host_out));
+	return URMAPX_OK;
+}
+int urmapx_ufi_info(const char *path, uint32_t *word_length, uint32_t *max_ix, uint32_t *seqdata_size, uint64_t *slot_count) {
+	if (!path) return URMAPX_E_ARG;
+	FILE *f = fopen(path, "rb");
+	if (!f) return URMAPX_E_IO;
+	uint32_t u = 0, w = 0, m = 0, sd = 0;
+	uint64_t sc = 0;
+	const bool got = rd(f, &u, 4) && (u != MAGIC1 || (rd(f, &w, 4) && rd(f, &m, 4) && rd(f, &sd, 4) && rd(f, &sc, 8)));
+	fclose(f);
+	if (!got) return URMAPX_E_IO;
+	if (u != MAGIC1) return URMAPX_E_FORMAT;
+	if (word_length) *word_length = w;
+	if (max_ix) *max_ix = m;
+	if (seqdata_size) *seqdata_size = sd;
+	if (slot_count) *slot_count = sc;
+	return URMAPX_OK;
+}
 int urmapx_checksum_device(int device, const void *d_ptr, uint64_t nbytes, uint64_t *out) {
 	if (!d_ptr || !out || ((uintptr_t)d_ptr & 7)) return URMAPX_E_ARG;
 	HIP_TRY(hipSetDevice(device));
