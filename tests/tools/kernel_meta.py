@@ -3,6 +3,7 @@
 The library's .hip_fatbin section holds one clang offload bundle per translation unit; each bundle's gfx950 entry is an ELF
 code object whose NT_AMDGPU_METADATA note lists, per kernel, what the compiler allocated.  Nothing is compiled here: the
 numbers are those of the binary that runs."""
+import hashlib
 import os
 import re
 import struct
@@ -10,6 +11,7 @@ import subprocess
 import tempfile
 
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+OBJCOPY = "/opt/rocm/lib/llvm/bin/llvm-objcopy"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 FIELDS = {"vgpr": ".vgpr_count", "agpr": ".agpr_count", "sgpr": ".sgpr_count", "vgpr_spill": ".vgpr_spill_count", "sgpr_spill": ".sgpr_spill_count",
           "scratch": ".private_segment_fixed_size", "lds": ".group_segment_fixed_size", "max_threads": ".max_flat_workgroup_size"}
@@ -48,25 +50,26 @@ def waves_per_simd(vgpr, agpr=0):
     return max(1, min(8, 512 // tot))
 
 
-def kernel_table(so_path):
-    """{demangled kernel name without its argument list: {vgpr, agpr, sgpr, vgpr_spill, sgpr_spill, scratch, lds, max_threads, waves_per_simd}}"""
+def _rows(elf_path):
+    """{mangled kernel name: resource row} of one code object on disk"""
     table = {}
-    for co in code_objects(so_path):
-        with tempfile.NamedTemporaryFile(suffix=".elf") as f:
-            f.write(co)
-            f.flush()
-            txt = subprocess.run([READELF, "--notes", f.name], capture_output=True, text=True, check=True).stdout
-        for blk in re.split(r"\n  - \.agpr_count:", "\n" + txt)[1:]:
-            blk = "    .agpr_count:" + blk
-            m = re.search(r"\.name:\s+(\S+)", blk)
-            if not m:
-                continue
-            row = {}
-            for k, f_ in FIELDS.items():
-                mm = re.search(re.escape(f_) + r":\s+(\d+)", blk)
-                row[k] = int(mm.group(1)) if mm else 0
-            row["waves_per_simd"] = waves_per_simd(row["vgpr"], row["agpr"])
-            table[m.group(1)] = row
+    txt = subprocess.run([READELF, "--notes", elf_path], capture_output=True, text=True, check=True).stdout
+    for blk in re.split(r"\n  - \.agpr_count:", "\n" + txt)[1:]:
+        blk = "    .agpr_count:" + blk
+        m = re.search(r"\.name:\s+(\S+)", blk)
+        if not m:
+            continue
+        row = {}
+        for k, f_ in FIELDS.items():
+            mm = re.search(re.escape(f_) + r":\s+(\d+)", blk)
+            row[k] = int(mm.group(1)) if mm else 0
+        row["waves_per_simd"] = waves_per_simd(row["vgpr"], row["agpr"])
+        table[m.group(1)] = row
+    return table
+
+
+def _nice(table):
+    """the same table keyed by the demangled kernel name without its argument list"""
     names = list(table)
     out = {}
     for mangled, nice in zip(names, demangle(names)):
@@ -86,14 +89,57 @@ def kernel_table(so_path):
     return out
 
 
-if __name__ == "__main__":
-    import sys
-    here = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    so = sys.argv[1] if len(sys.argv) > 1 else os.path.join(here, "urmap_amd", "liburmapx.so")
-    pat = sys.argv[2] if len(sys.argv) > 2 else ""
-    t = kernel_table(so)
+def kernel_table(so_path):
+    """{demangled kernel name without its argument list: {vgpr, agpr, sgpr, vgpr_spill, sgpr_spill, scratch, lds, max_threads, waves_per_simd}}"""
+    table = {}
+    for co in code_objects(so_path):
+        with tempfile.NamedTemporaryFile(suffix=".elf") as f:
+            f.write(co)
+            f.flush()
+            table.update(_rows(f.name))
+    return _nice(table)
+
+
+def code_digests(so_path):
+    """One entry per code object (= translation unit with kernels), ordered by its kernel names: {kernels: the sorted names, text / rodata: sha256 of
+    the section's bytes, rows: {name: resource row}}.  Two builds run the same device code iff these agree: the whole code object does not compare
+    (its symbol table carries an id derived from the source text), the instructions and constants do."""
+    out = []
+    for co in code_objects(so_path):
+        with tempfile.TemporaryDirectory() as d:
+            elf = os.path.join(d, "co.elf")
+            with open(elf, "wb") as f:
+                f.write(co)
+            rows = _nice(_rows(elf))
+            if not rows:
+                continue
+            sha = {}
+            for sec in (".text", ".rodata"):
+                binp = os.path.join(d, "sec.bin")
+                subprocess.run([OBJCOPY, "-O", "binary", "--only-section=" + sec, elf, binp], check=True)
+                with open(binp, "rb") as f:
+                    sha[sec] = hashlib.sha256(f.read()).hexdigest()
+            out.append({"kernels": sorted(rows), "text": sha[".text"], "rodata": sha[".rodata"], "rows": rows})
+    return sorted(out, key=lambda e: e["kernels"])
+
+
+def _print_rows(t, pat=""):
     print(f"{'kernel':64s} {'vgpr':>5s} {'sgpr':>5s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s} {'lds':>6s} {'waves':>5s}")
     for k in sorted(t):
         if pat in k:
             r = t[k]
             print(f"{k:64s} {r['vgpr']:5d} {r['sgpr']:5d} {r['vgpr_spill']:6d} {r['sgpr_spill']:6d} {r['scratch']:7d} {r['lds']:6d} {r['waves_per_simd']:5d}")
+
+
+if __name__ == "__main__":
+    import sys
+    here = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    args = [a for a in sys.argv[1:] if a != "--digests"]
+    so = args[0] if len(args) > 0 else os.path.join(here, "urmap_amd", "liburmapx.so")
+    if "--digests" in sys.argv[1:]:  # kernel_meta.py --digests [library]: what has to agree between two builds of the same device code
+        for n, e in enumerate(code_digests(so)):
+            print(f"code object {n}: {len(e['kernels'])} kernels\n  .text   sha256 {e['text']}\n  .rodata sha256 {e['rodata']}")
+            _print_rows(e["rows"])
+            print()
+    else:
+        _print_rows(kernel_table(so), args[1] if len(args) > 1 else "")

@@ -43,22 +43,19 @@ __device__ __forceinline__ float dpp_f(float v, float fill) {
 // compiler's form costs five instructions per step (constant fill, nop, v_mov_dpp, a canonicalising max, the max):
 // with dst = src1 = the value itself a lane whose DPP source does not exist is simply not written (bound_ctrl:0) and
 // keeps its value.  s_nop 1 = the two wait states a DPP read needs after the VALU write of the same register.
-#ifndef URX_DPP_NOP
-#define URX_DPP_NOP "s_nop 1\n\t"  // build-time knob (debugging): the wait between the steps
-#endif
 __device__ __forceinline__ float wave_prefix_max(float v) {
 	asm volatile(
-	    URX_DPP_NOP
+	    "s_nop 1\n\t"
 	    "v_max_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-	    URX_DPP_NOP
+	    "s_nop 1\n\t"
 	    "v_max_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-	    URX_DPP_NOP
+	    "s_nop 1\n\t"
 	    "v_max_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-	    URX_DPP_NOP
+	    "s_nop 1\n\t"
 	    "v_max_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-	    URX_DPP_NOP
+	    "s_nop 1\n\t"
 	    "v_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-	    URX_DPP_NOP
+	    "s_nop 1\n\t"
 	    "v_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
 	    "s_nop 1"
 	    : "+v"(v));
@@ -74,9 +71,6 @@ __device__ __forceinline__ uint32_t letter_of(uint32_t c) {
 // Reads are upper-case ACGT almost always, and for those four bytes (c >> 1) & 3 is 0 / 1 / 3 / 2 (A / C / G / T): membership, complement (alpha.cpp:3005) and
 // the 4-bit code (seq_code below: A 0, C 1, G 2, T 3) are one byte picked out of a constant -- four instructions where the general functions take a dozen to forty.
 // The search kernels test a read once (one ballot) and take these when every byte passes; any other read (N, lower case, IUPAC) takes the general functions.
-#ifndef URX_ACGT_FAST
-#define URX_ACGT_FAST 1  // 0: the general functions always (A/B builds)
-#endif
 __device__ __forceinline__ uint32_t acgt_pick(uint32_t table, uint32_t c) { return (table >> (((c >> 1) & 3u) << 3)) & 0xFFu; }
 __device__ __forceinline__ bool is_upper_acgt(uint32_t c) { return c == acgt_pick(0x47544341u, c); }
 __device__ __forceinline__ uint32_t comp_char_acgt(uint32_t c) { return acgt_pick(0x43414754u, c); }
@@ -182,10 +176,7 @@ __device__ __forceinline__ uint32_t walk_row(const uint8_t *__restrict__ blob, u
 }
 
 // PosToCoordL on the device (search_se_kernel: fill_result_core; search_pe_kernel's output): up to 64 sequences every lane tests one
-// (one round of loads instead of the binary search's five or six dependent ones); 0: the binary search always (A/B builds)
-#ifndef URX_SEQ_LANES
-#define URX_SEQ_LANES 1
-#endif
+// (one round of loads instead of the binary search's five or six dependent ones)
 
 // wave-uniform bit vector of 64*N bits kept in registers
 template <int N>
@@ -242,9 +233,6 @@ struct BitVec {
 // return the full walk's result and the caller compares their penalty with the cap in order.
 // The walk visits mismatches only.  The loop over the N words is wave-uniform and unrolled; inside a word the set
 // bits are consumed one by one (x &= x - 1), so an iteration is ~20 VALU instructions with no word selection.
-#ifndef URX_WALK_IN_TEST
-#define URX_WALK_IN_TEST 0  // 1: the forward walk tests every mismatch position against the read's length (rounds 2-5)
-#endif
 template <int N>
 __device__ __forceinline__ void xdrop_walk_lane(const uint64_t (&w)[N], int qpos, int W, int QL, int mis, int xdrop, int cap,
                                                 int &bst_out, int &startpos_out, int &endpos_out, int &pen_out) {
@@ -263,19 +251,6 @@ __device__ __forceinline__ void xdrop_walk_lane(const uint64_t (&w)[N], int qpos
 		while (x) {
 			const int m = 64 * c + __builtin_ctzll(x);
 			x &= x - 1;
-#if URX_WALK_IN_TEST
-			const bool in = m < QL;  // padding bits past the read end the word; the tail run below ends the walk
-			const int s1 = score + (m - cur);
-			const bool nb = in && m > cur && s1 > bst;
-			bst = nb ? s1 : bst;
-			endpos = nb ? m - 1 : endpos;
-			score = in ? s1 + mis : score;
-			pen = in ? pen - mis : pen;
-			cur = in ? m + 1 : cur;
-			const bool stop = in && (bst - score > xdrop || pen > cap);
-			alive = alive && !stop;
-			x = (stop || !in) ? 0ull : x;
-#else
 			// (no bit at or beyond QL is ever set: lane_mismatch_planes and lane_mismatch_mask clear them -- the test for them cost six of the loop's 22 instructions)
 			const int s1 = score + (m - cur);
 			const bool nb = m > cur && s1 > bst;
@@ -287,7 +262,6 @@ __device__ __forceinline__ void xdrop_walk_lane(const uint64_t (&w)[N], int qpos
 			const bool stop = bst - score > xdrop || pen > cap;
 			alive = alive && !stop;
 			x = stop ? 0ull : x;
-#endif
 		}
 	}
 	{  // no mismatch left: the run to the end of the read
@@ -334,12 +308,8 @@ __device__ __forceinline__ void xdrop_walk_lane(const uint64_t (&w)[N], int qpos
 // Mismatches outside the seed window [qpos, qpos + W) of a lane's bit vector.  ExtendPen never looks inside the seed
 // (extendpen.cpp:24-27), so this is the most its walks can meet: a full-length hit costs exactly -mis times this, and no
 // score along the walks exceeds QL minus this.
-#ifndef URX_SEED_FUNNEL
-#define URX_SEED_FUNNEL 1  // 0: the round-2 form (per word: two 64-bit masks from the seed's bounds, 24 instructions a word)
-#endif
 template <int N>
 __device__ __forceinline__ int mismatches_outside_seed(const uint64_t (&w)[N], int qpos, int W) {
-#if URX_SEED_FUNNEL
 	// all mismatches, minus those among the W <= 32 seed bits: the two dwords that hold bits qpos .. qpos + 31 picked out of the vector, one funnel shift
 	int pc = 0;
 #pragma unroll
@@ -355,17 +325,6 @@ __device__ __forceinline__ int mismatches_outside_seed(const uint64_t (&w)[N], i
 	const uint32_t x = __builtin_amdgcn_alignbit(b, a, (uint32_t)qpos & 31u);
 	const uint32_t m = W >= 32 ? 0xFFFFFFFFu : ((1u << W) - 1u);
 	return pc - __builtin_popcount(x & m);
-#else
-	int pc = 0;
-#pragma unroll
-	for (int c = 0; c < N; ++c) {
-		const int lo = qpos - 64 * c, hi = lo + W;  // seed bits of this word: [lo, hi) cut to [0, 64)
-		const uint64_t below_hi = hi >= 64 ? ~0ull : (hi <= 0 ? 0ull : ((1ull << hi) - 1ull));
-		const uint64_t below_lo = lo >= 64 ? ~0ull : (lo <= 0 ? 0ull : ((1ull << lo) - 1ull));
-		pc += __builtin_popcountll(w[c] & ~(below_hi & ~below_lo));
-	}
-	return pc;
-#endif
 }
 
 // inclusive prefix sum of a non-negative int over the 64 lanes (DPP, same ladder as wave_prefix_max)
@@ -504,16 +463,6 @@ __device__ __forceinline__ void glds_dword(const void *gsrc, uint32_t lds_dst) {
 	             : "v"(gsrc), "s"(lds_dst)
 	             : "memory");
 }
-// L2 prefetch (round 6): the 64-byte sectors of [p, p + nbytes) are asked for by LDS-DMA dword loads whose data lands in a sink that
-// nobody reads -- no register is named, so nothing of the wave waits for them or can be overwritten by them.  The search kernels
-// issue these for the NEXT batch of candidate windows before they walk the current one: the real gather of that batch, one
-// batch-time later, finds its sectors in L2 instead of paying an HBM round trip in front of every dependent step.  (Loads return
-// in order: a touch must be issued BEHIND the loads the wave is about to wait for, never in front of them.)
-__device__ __forceinline__ void glds_touch(const uint8_t *p, int nbytes, uint32_t lds_sink) {  // nbytes wave-uniform, a multiple of 4
-	lds_sink = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_sink);  // M0 takes a scalar
-	for (int o = 0; o < nbytes; o += 64) glds_dword(p + o, lds_sink);
-	glds_dword(p + nbytes - 4, lds_sink);
-}
 __device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 template <class T>
@@ -552,28 +501,20 @@ __device__ __forceinline__ void lds_sync() {
 	__builtin_amdgcn_s_barrier();
 	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
-// The search kernels' blocks are one wavefront.  URX_LDS_SYNC (build flag, measurement only) makes every barrier of theirs
-// LDS-only; the default keeps __syncthreads() wherever lanes exchange data through global scratch.
-#ifdef URX_LDS_SYNC
-#define URX_SYNC() lds_sync()
-#else
+// The search kernels' blocks are one wavefront; their barriers stay __syncthreads() because lanes also exchange data through
+// global scratch.
 #define URX_SYNC() __syncthreads()
-#endif
 
 // The slots of the k-mers that start in one 64-position chunk of a read, both strands (State1::SetSlotsVec,
 // state1.cpp:396-438, with murmur64 / WordToSlot, ufindex.h:50-65): lane l cuts the W letters of the k-mer starting at
 // position 64c + l out of the read's ballot planes (bit p of lo / hi = letter bits of base p, inv / invm = base p cannot
 // be part of a plus- / minus-strand k-mer), c0 = the chunk's words, c1 = the next chunk's.  sp = plus-strand slot at that
 // position; sm = slot of the reverse-complement k-mer over the same bases (minus-strand position nwords-1-p).
-#ifndef URX_KMER_STREAM
-#define URX_KMER_STREAM 1  // 0: the round-1 form below (each lane spreads its own planes: four bit interleaves of 15 instructions per k-mer pair)
-#endif
 __device__ __forceinline__ void kmer_slots(const DevIndex &X, uint64_t lo0, uint64_t hi0, uint64_t inv0, uint64_t invm0, uint64_t lo1,
                                            uint64_t hi1, uint64_t inv1, uint64_t invm1, int lane, uint32_t p, uint32_t nwords,
                                            uint64_t &sp, uint64_t &sm, bool &vp, bool &vm) {
 	const uint32_t W = X.W;
 	const uint64_t wmask = (W >= 32) ? 0xFFFFFFFFull : ((1ull << W) - 1ull);
-#if URX_KMER_STREAM
 	// Round 6: the bit interleave of the two letter planes is the same for every lane -- it is done ONCE, on the wave-uniform ballot words (scalar
 	// instructions), for the 96 bases a chunk's k-mers can cover: stream S has bit 2i = low letter bit of base i, bit 2i + 1 = high bit; stream T the two
 	// swapped.  A lane's words are 2W bits cut out of the streams at bit 2 * lane: the minus-strand word is the complement of S's piece (letters
@@ -602,23 +543,6 @@ __device__ __forceinline__ void kmer_slots(const DevIndex &X, uint64_t lo0, uint
 	const uint64_t m2 = (W >= 32) ? ~0ull : ((1ull << (2u * W)) - 1ull);
 	const uint64_t wp = __brevll(segT & m2) >> (64u - 2u * W);
 	const uint64_t wm = ~segS & m2;
-#else
-	uint64_t flo = lo0 >> lane, fhi = hi0 >> lane, finv = inv0 >> lane, finvm = invm0 >> lane;
-	if (lane) {
-		flo |= lo1 << (64 - lane);
-		fhi |= hi1 << (64 - lane);
-		finv |= inv1 << (64 - lane);
-		finvm |= invm1 << (64 - lane);
-	}
-	flo &= wmask; fhi &= wmask; finv &= wmask; finvm &= wmask;
-	vp = p < nwords && finv == 0;
-	vm = p < nwords && finvm == 0;
-	// plus strand word at query position p: first base is the most significant letter
-	const uint64_t rlo = __brevll(flo) >> (64 - W), rhi = __brevll(fhi) >> (64 - W);
-	const uint64_t wp = spread32(rlo) | (spread32(rhi) << 1);
-	// reverse-complement word covering the same bases: letters complemented, order already reversed
-	const uint64_t wm = spread32(~flo & wmask) | (spread32(~fhi & wmask) << 1);
-#endif
 	sp = mod_slots(murmur64(wp & X.shiftMask), X.slotCount, X.slotMagic);
 	sm = mod_slots(murmur64(wm & X.shiftMask), X.slotCount, X.slotMagic);
 }

@@ -167,27 +167,16 @@ __global__ __launch_bounds__(64) void viterbi_batch_pair_kernel(urmapx_params P,
 // ------------------------------------------------------------------------------------------------
 // HSP record word: startq | len << 10 | score << 20 | aligned << 30 | plus << 31 (each field <= 1023)
 static constexpr uint32_t PK_MASK = 1023u, PK_LEN_SH = 10, PK_SCORE_SH = 20, PK_ALIGNED = 1u << 30, PK_PLUS_SH = 31;
-// Round 6: the windows of the next candidate batch (and a read's long rows) are touched into L2 ahead of their gathers (dev_common.h:
-// glds_touch).  The sink of those loads is 256 bytes of LDS; the HSP list in LDS gives them up (192 entries instead of 256: a read
-// with more keeps the rest in its block's global scratch, as before) so that the block stays under the 10 240 bytes that let 16 of
-// them share a CU.  URX_PREFETCH=0: the round-5 kernel (A/B builds).
-#ifndef URX_PREFETCH
-#define URX_PREFETCH 0  // bit 0: the next batch's windows, bit 1: a read's long rows
-#endif
-// (The scan of the next batch issued beside the current batch's window gather -- URX_SCAN_AHEAD, commit f9ec288 -- was bit-identical and 5-17 % slower:
-// profiles/r6/ab_scan_ahead.txt.)
-#ifndef URX_HSP_CAP
-#define URX_HSP_CAP (URX_PREFETCH ? 192 : 256)  // build-time experiment (profiles/r5/ab_waves5.txt): 64 frees 1.5 KB of LDS per block
-#endif
-static constexpr int HSP_CAP = URX_HSP_CAP;        // HSPs of a read held in LDS
+// The first 256 HSPs of a read are held in LDS; a read with more keeps the rest in its block's global scratch.  Nothing is prefetched:
+// every candidate window is fetched by the gather that uses it.  (Touching the next batch's windows into L2 ahead of their gathers,
+// and scanning the next batch beside the current batch's gather, were both measured in round 6 and did not ship: DESIGN.md,
+// "Retired switches".)
+static constexpr int HSP_CAP = 256;             // HSPs of a read held in LDS
 static constexpr int SEARCH_OVF_BLOCKS = 2048;  // grid of the second pass (reads whose HSP list outgrew LDS): these are the
                                                 // costliest reads of a batch (hundreds of AlignHSP calls each), so they get most of the chip
 static constexpr int HSP_TOTAL_CAP = 8192;  // beyond that: in the block's global scratch (the reference's list is unbounded;
                                             // 8192 > 2 strands x 127 k-mers x MaxIx 32 candidate diagonals of a 150 bp read)
-#ifndef URX_TICKET_CHUNK
-#define URX_TICKET_CHUNK 4
-#endif
-static constexpr int TICKET_CHUNK = URX_TICKET_CHUNK;
+static constexpr int TICKET_CHUNK = 4;
 static constexpr int ROW_CAP = 32;  // UFIndex m_MaxIx of every index this build accepts
 
 // per-block global scratch of the search kernel: chain rows, the wide-band DP's rows and trace, the banded DP's trace cells
@@ -227,13 +216,10 @@ __device__ __noinline__ int hsp_overflow_add(uint2 *ovf, int n, int cap, uint32_
 	return 1;
 }
 
-#ifndef URX_SE_HITW1
-#define URX_SE_HITW1 1
-#endif
 // hit-list words (64 hits each) of the first pass.  5 of 1 M reads of a repeat-rich genome end with more than 64 hits and
 // are mapped again by a launch of their own (0.9 ms); with two words they stay in the first pass, which then runs 1.6 ms
 // longer (such a read is its tail): one word it stays.  The pair kernel keeps two (kernels_pe.hip: -1.5 ms).
-static constexpr int SE_HITW1 = URX_SE_HITW1;
+static constexpr int SE_HITW1 = 1;
 // LAYOUT 1 (round 5): the slot entries in LDS come out of DevIndex::slot16 -- pr_lo = the slot's position, pr_hi = tally | row length
 // << 8, pr_sl = the row's second position (rows of two) or its index in DevIndex::rows -- instead of the two dwords around the
 // 5-byte slot and the slot number's low half
@@ -538,16 +524,12 @@ struct SearchWave {
 			uint32_t sdb, pk;
 			const bool want = hsp_wants_dp(base + lane, sdb, pk);
 			njobs += __builtin_popcountll(__ballot(want));
-			// a right flank window that the end of the sequence store cuts short (alignhsp.cpp:143-145) makes a band wider than
-			// a wavefront: dp_kernel runs its DPs two to a wavefront in packed int16 and has no wide path -- such a read (it lies
-			// within a read length of the end of the last sequence) keeps its phase 6 in this kernel
+			// a right flank window that the end of the sequence store cuts short (alignhsp.cpp:143-145) makes a band wider than a wavefront
 			clipped |= want && (uint64_t)(sdb - (pk & PK_MASK)) + (uint64_t)QL + 2ull * P.band_radius >= (uint64_t)X.seqDataSize;
 		}
-#ifdef URX_DP_PAIR
-		if (__ballot(clipped) != 0) return -1;
-#else
+		// Not acted on: dp_kernel has a wide path for such a band.  The computation stays for now: without it (and the `reserved` word below)
+		// the compiler allocates and schedules the search kernels differently (profiles/r7/code_identity.txt): it goes with a change that is measured.
 		(void)clipped;
-#endif
 		if (njobs == 0) return 0;
 		if (P3 && (hspCount > hsp_lds || hspCount > P3_HSP)) return -1;
 		uint32_t jb = 0, slot = 0;
@@ -729,7 +711,7 @@ struct SearchWave {
 		if (haveTop) {
 			uint32_t lo = 0, hi = X.seqCount - 1;
 			uint32_t found = 0xFFFFFFFFu, coord = 0xFFFFFFFFu, tl = 0;
-			if (URX_SEQ_LANES && X.seqCount <= 64u) {
+			if (X.seqCount <= 64u) {
 				// up to 64 sequences (a human genome's chromosomes): every lane tests one -- one round of loads where the search below makes
 				// five or six dependent ones; the sequences do not overlap, so at most one lane holds the position
 				const int lane = fresh_lane(this->lane);
@@ -785,7 +767,7 @@ struct SearchWave {
 	// A position without a k-mer gathered zeros: tally 0 = TALLY_FREE.
 	uint32_t *pr_lo, *pr_hi, *pr_sl;
 	uint64_t *pr_hb;
-	uint32_t pf_sink = 0;  // LDS address of the L2 touches' sink (dev_common.h: glds_touch); 0: no touches
+	uint32_t reserved = 0;  // padding (once the LDS address of a prefetch sink): kept with park_for_dp's `clipped` so that the compiled kernels stay what was measured
 	__device__ __forceinline__ void probe_get(int s, int q, uint32_t &tally, uint32_t &pos) const {
 		const int e = s * KCH * 64 + (s ? nwords - 1 - q : q);
 		if constexpr (LAYOUT == 1) {
@@ -967,22 +949,6 @@ struct SearchWave {
 					rowstore[(size_t)(NSEG + g) * 64 + lane] = ps[g];
 				}
 			}
-#if (URX_PREFETCH & 2)
-			// round 6: the rows of three and more (phase 5 reads their entries 1.. out of DevIndex::rows, one dependent round trip in front
-			// of every batch's window gather) are touched into L2 now, behind the next read's probe gathers: phase 4 runs in between
-			if (pf_sink) {
-				const uint32_t sink = (uint32_t)__builtin_amdgcn_readfirstlane((int)pf_sink);
-#pragma unroll
-				for (int g = 0; g < NSEG; ++g)
-					if (rl[g] > 2) {
-						const uint8_t *rp = reinterpret_cast<const uint8_t *>(X.rows + (size_t)(uint32_t)(sl[g] >> 32) + 1);
-						const int nb = 4 * (rl[g] - 1);
-						glds_dword(rp, sink);
-						glds_dword(rp + nb - 4, sink);
-						if (nb > 64) glds_dword(rp + 64, sink);
-					}
-			}
-#endif
 			return;
 		}
 		uint2 info[NSEG];
@@ -1024,31 +990,11 @@ struct SearchWave {
 		return X.rows[(size_t)rowstore[(size_t)seg * 64 + l] + (uint32_t)k];
 	}
 
-	// exclusive prefix over the first `used` of NS segments of per-lane counts -> pre[]; returns the total.  (Round 6: two segments per prefix sum -- a
-	// lane's count is at most ROW_CAP = 32, a segment's total at most 2 048, so two of them ride in the halves of one word and no carry crosses --, and the
-	// segments a step does not use are not summed: phases 1-2 fill a quarter of the list's segments.  URX_SCAN_PACK=0: one sum per segment, all of them.)
-#ifndef URX_SCAN_PACK
-#define URX_SCAN_PACK 0  // measured: -0.8 % on the 250-base search, +0.7 % on the 150-base one (18 more spilled registers in the two-chunk instance): off (profiles/r6/ab_instruction_trims.txt)
-#endif
+	// exclusive prefix over the NS segments of per-lane counts -> pre[]; returns the total: one prefix sum per segment, all of them.  (Two segments per
+	// sum, skipping those a step does not use, measured -0.8 % on the 250-base search and +0.7 % on the 150-base one: profiles/r6/ab_instruction_trims.txt.)
 	template <int NS>
-	__device__ __forceinline__ int scan_counts(const int (&cnt)[NS], int used) {
-		static_assert(NS % 2 == 0, "segments are summed two at a time");
+	__device__ __forceinline__ int scan_counts(const int (&cnt)[NS]) {
 		int carry = 0;
-#if URX_SCAN_PACK
-#pragma unroll
-		for (int sgm = 0; sgm < NS; sgm += 2) {
-			if (sgm < used) {  // wave-uniform
-				const int inc = wave_prefix_sum(cnt[sgm] | (cnt[sgm + 1] << 16));
-				const uint32_t tot = (uint32_t)rdlane(inc, 63);
-				const int t0 = (int)(tot & 0xFFFFu), t1 = (int)(tot >> 16);
-				pre[sgm * 64 + lane] = (uint16_t)(carry + (inc & 0xFFFF) - cnt[sgm]);
-				pre[(sgm + 1) * 64 + lane] = (uint16_t)(carry + t0 + (int)((uint32_t)inc >> 16) - cnt[sgm + 1]);
-				carry += t0 + t1;
-			}
-		}
-		if (lane == 0) pre[used * 64] = (uint16_t)carry;
-#else
-		used = NS;
 #pragma unroll
 		for (int sgm = 0; sgm < NS; ++sgm) {
 			int inc = wave_prefix_sum(cnt[sgm]);
@@ -1056,7 +1002,6 @@ struct SearchWave {
 			carry += rdlane(inc, 63);
 		}
 		if (lane == 0) pre[NS * 64] = (uint16_t)carry;
-#endif
 		if (carry > 0xFFFF) status |= URMAPX_ST_HSP_OVERFLOW;  // only a 1024-base read whose every k-mer owns a full chain gets here
 		URX_SYNC();
 		return carry;
@@ -1079,13 +1024,7 @@ struct SearchWave {
 // cold paths; LDS per block is kept under 10 KB for the same 16 blocks per CU) -- measured 10 % faster than 3 waves
 // with no spills.  Reads <= 320: 2 (the five-word bit vectors and the window loads in flight do not fit fewer
 // registers without hundreds of spills).
-#ifndef SEARCH_WAVES_NCH3
-#define SEARCH_WAVES_NCH3 4
-#endif
-#ifndef SEARCH_WAVES_NCH4
-#define SEARCH_WAVES_NCH4 3
-#endif
-#define SEARCH_WAVES_PER_EU(NCH) ((NCH) <= 3 ? SEARCH_WAVES_NCH3 : (NCH) == 4 ? SEARCH_WAVES_NCH4 : (NCH) == 5 ? 2 : 1)
+#define SEARCH_WAVES_PER_EU(NCH) ((NCH) <= 3 ? 4 : (NCH) == 4 ? 3 : (NCH) == 5 ? 2 : 1)
 // The kernel is a software pipeline over the reads a block takes from the ticket counter.  While read i is searched,
 //   * the bytes of read i+1 arrive in LDS (one LDS-DMA load issued right after read i's own bytes were taken out), and
 //   * between phases 3 and 4 -- when the chain heads of read i are in registers and its slot entries are dead -- the
@@ -1140,8 +1079,6 @@ __global__ __launch_bounds__(64, SEARCH_WAVES_PER_EU(NCH)) void search_se_kernel
 	// candidate queue (ring): reference position, query position | plus << 14 | second phase << 15
 	__shared__ __attribute__((aligned(8))) uint32_t cq_db[128];
 	__shared__ uint16_t cq_qp[128];
-	constexpr bool PF = (URX_PREFETCH & 1) != 0;
-	__shared__ uint32_t pf_sink[URX_PREFETCH ? 64 : 1];  // where the L2 touches land (glds_touch); never read
 	constexpr bool RS_LDS = KCH < NCH || (NCH == 2 && ROWS == 2 && PART == 0 && !OVF && !DBG);
 	__shared__ uint32_t rs_lds[RS_LDS ? 2 * SW::NSEG * 64 : 1];  // the row store (rows_fetch, row_entry)
 	// between two gather steps both are idle: the next read's slot numbers are staged there on their way to the pr_* arrays
@@ -1160,7 +1097,6 @@ __global__ __launch_bounds__(64, SEARCH_WAVES_PER_EU(NCH)) void search_se_kernel
 	S.ropsL = ropsL; S.ropsR = ropsR; S.cand = cand; S.top = top; S.pre = pre;
 	S.hsp_db = hsp_db; S.hsp_pk = hsp_pk;
 	S.pr_lo = pr_lo; S.pr_hi = pr_hi; S.pr_sl = pr_sl; S.pr_hb = pr_hb;
-	if constexpr ((URX_PREFETCH & 2) != 0) S.pf_sink = lds_addr(pf_sink);
 	{
 		uint8_t *sc = scratch + (size_t)blockIdx.x * scratch_stride;
 		if constexpr (RS_LDS) S.rowstore = rs_lds;
@@ -1273,7 +1209,7 @@ __global__ __launch_bounds__(64, SEARCH_WAVES_PER_EU(NCH)) void search_se_kernel
 			wait_vm0();
 			URX_SYNC();
 			const int mis = (int)(reinterpret_cast<uintptr_t>(bases + off) & 3);
-			// (dev_common.h: URX_ACGT_FAST) a read of upper-case ACGT only -- nearly every read -- takes the four-instruction complement and code
+			// (dev_common.h: acgt_pick) a read of upper-case ACGT only -- nearly every read -- takes the four-instruction complement and code
 			uint32_t chv[NCH];
 			bool plain = true;
 #pragma unroll
@@ -1282,7 +1218,7 @@ __global__ __launch_bounds__(64, SEARCH_WAVES_PER_EU(NCH)) void search_se_kernel
 				chv[c] = p < QL ? (uint32_t)nextQ[mis + p] : (uint32_t)'A';
 				plain = plain && is_upper_acgt(chv[c]);
 			}
-			const bool acgt = URX_ACGT_FAST && __ballot(!plain) == 0;  // wave-uniform
+			const bool acgt = __ballot(!plain) == 0;  // wave-uniform
 #pragma unroll
 			for (int c = 0; c < NCH; ++c) {
 				const int p = 64 * c + lane;
@@ -1462,8 +1398,8 @@ __global__ __launch_bounds__(64, SEARCH_WAVES_PER_EU(NCH)) void search_se_kernel
 					cnt[SW::NSEG + g] = rl[g] > 2 ? rl[g] : 0;
 				}
 			}
-			const int used = URX_SCAN_PACK ? (step == 1 ? 2 * KCH : 2 * SW::NSEG) : 2 * SW::NSEG;  // segments of this step's list: phases 1-2 fill the first 2 KCH
-			const int total = S.template scan_counts<2 * SW::NSEG>(cnt, used);
+			const int used = 2 * SW::NSEG;  // segments of the list
+			const int total = S.template scan_counts<2 * SW::NSEG>(cnt);
 			const int totalFirst = (int)S.pre[(step == 1 ? KCH : SW::NSEG) * 64];  // candidates of the first of the two phases
 			bool crossed = false;
 			// The candidate stream is first filtered -- a candidate on the 64-base diagonal block of a hit already found
@@ -1481,8 +1417,7 @@ __global__ __launch_bounds__(64, SEARCH_WAVES_PER_EU(NCH)) void search_se_kernel
 					if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(stats) + 1 + slot, (unsigned long long)(now - tsub));
 					tsub = now;
 				};
-				// (PF: the scan runs one step ahead -- up to 128 queued -- so that the batch after this one is known when its windows are touched)
-				while (qcount < (PF ? 65 : 64) && scanned < total) {
+				while (qcount < 64 && scanned < total) {
 					const int g = scanned + lane;
 					uint32_t s_qpos = 0, s_db = 0;
 					bool s_plus = true, ok = false;
@@ -1534,12 +1469,6 @@ __global__ __launch_bounds__(64, SEARCH_WAVES_PER_EU(NCH)) void search_se_kernel
 				qhead = (qhead + nb) & 127; qcount -= nb;
 				URX_SYNC();
 				bool c_live = c_ok;
-				if constexpr (PF) {
-					// scanned a step earlier than it is gathered: a candidate on the diagonal block of a hit found meanwhile returns at once
-					// in the reference (extendpen.cpp:15-17) -- it is dropped here as the scan would have dropped it
-					c_live = c_ok && !S.overlaps_any_hit(c_db - c_qpos);
-					if (__ballot(c_live) == 0) { laps(8); continue; }
-				}
 				laps(8);
 				uint64_t mm[NCH];
 #pragma unroll
@@ -1548,14 +1477,6 @@ __global__ __launch_bounds__(64, SEARCH_WAVES_PER_EU(NCH)) void search_se_kernel
 					if (c_live) lane_mismatch_mask<NCH>(g_seq, c_db - c_qpos, sQ2 + (c_plus ? 0 : SW::QMAX), QL, mm);
 				} else {
 					if (c_live) lane_mismatch_planes<NCH>(g_seqp, c_db - c_qpos, qpl + (c_plus ? 0 : 2 * NCH), QL, mm);
-				}
-				if constexpr (PF) {
-					// the windows of the batch AFTER this one (already in the queue) on their way into L2 while this one is walked and consumed
-					if (!q_other && lane < qcount) {
-						const int pos = (qhead + lane) & 127;
-						const uint32_t ndblo = cq_db[pos] - (uint32_t)(cq_qp[pos] & 0x3FFFu);
-						glds_touch(reinterpret_cast<const uint8_t *>(g_seqp + (ndblo >> 5)), 16 * ((QL - 1) / 32 + 2), lds_addr(pf_sink));
-					}
 				}
 				laps(9);
 				// ExtendPen's two x-drop walks (extendpen.cpp:25-78), every lane on its own bit vector.  The accumulated
@@ -1702,236 +1623,13 @@ __global__ __launch_bounds__(256) void dp_round_lists_kernel(DpWork dp, DpBounds
 // admits the HSP when its turn comes -- is left to finalize_se_kernel.  One conservative shortcut: if the penalty
 // after the left flank already exceeds the cap the job was made under, the right flank is not run (the cap only
 // falls, so the ordered replay returns at that same test).
-#ifndef URX_DP_WAVES
-#define URX_DP_WAVES 0  // build-time knob: register budget of dp_kernel as waves per SIMD (0 = the compiler's choice, 5)
-#endif
-#if URX_DP_WAVES
-#define URX_DP_ATTR __attribute__((amdgpu_waves_per_eu(URX_DP_WAVES, URX_DP_WAVES)))
-#else
-#define URX_DP_ATTR
-#endif
-// URX_DP_PAIR (build-time, off): the round-3 prototype that runs the jobs two to a wavefront with every row >= 1 of
-// both in packed int16 (viterbi_dev.h: VFlank, viterbi_pair_rows).  Bit-identical to the fp32 kernel on every parity test
-// and bench check -- and slower: 6.8 instead of 4.1 ms per 1 M 150-base reads, 77 instead of 37 ms per 1 M 250-base reads
-// (DESIGN.md section 3.4 has the instruction counts).  Kept for the A/B; tests/test_gpu_parity.py runs the packed rows
-// through viterbi_batch_pair_kernel either way.
-#ifdef URX_DP_PAIR
+// The trace cells of the narrow band live in the block's global scratch, not in LDS.  They were what held this kernel to 5.75 waves
+// per SIMD for 150-base reads and to 4.25 for 250-base reads (9.2 KB of LDS per block); the stores are one dword per lane per eight
+// rows and the traceback reads a few dozen cells.  250 bases: 31.5 -> 27.7 ms per 1 M reads, 150: 3.06 -> 2.94.
+// (Two jobs to a wavefront in packed int16 -- viterbi_dev.h: VFlank, viterbi_pair_rows -- is bit-identical and slower, 6.8 instead of
+// 4.1 ms per 1 M 150-base reads: DESIGN.md section 3.4.  tests/test_gpu_parity.py runs the packed rows through viterbi_batch_pair_kernel.)
 template <int NCH>
-__global__ __launch_bounds__(64) URX_DP_ATTR void dp_kernel(DevIndex X, urmapx_params P, const uint8_t *__restrict__ bases,
-                                                const uint64_t *__restrict__ offs, DpWork dp, uint8_t *scratch,
-                                                size_t scratch_stride, const uint8_t *__restrict__ g_seq, uint32_t klo, uint32_t khi,
-                                                uint32_t *ticket, const uint32_t *__restrict__ list, const uint32_t *list_count) {
-	constexpr int QMAX = 64 * NCH;
-	constexpr int TB_ROWS8 = (QMAX - 24) / 8 + 2;
-	// two jobs at a time (viterbi_dev.h: VFlank, viterbi_pair_rows): each has its query strand, target window, trace buffer
-	// and run buffers; the windows sit behind the queries so that the bytes read around a window are LDS
-	__shared__ __attribute__((aligned(16))) uint8_t sQ[2][QMAX];
-	__shared__ uint8_t sT[2][QMAX + 64 + 32];
-	__shared__ uint32_t tb[2][TB_ROWS8 * 64];
-	__shared__ uint16_t ropsL[2][OPS_CAP], ropsR[2][OPS_CAP], cand[URMAPX_MAX_PATH_OPS];
-	const int lane = threadIdx.x;
-	WideScratch ws;
-	ws.carve(scratch + (size_t)blockIdx.x * scratch_stride, QMAX, QMAX + 64);
-	const VPar VP(P);
-	const int BR = 2 * (int)P.band_radius;
-	const uint32_t made = dp.counters[0];
-	const uint32_t njobs = made < dp.jobs_cap ? made : dp.jobs_cap;
-	auto load_window = [&](uint8_t *dst, uint32_t tlo, int tl) {  // true: the window holds a '-' pad byte
-		bool gap = false;
-		for (int i = lane; i < tl; i += 64) {
-			const uint8_t c = g_seq[tlo + i];
-			dst[i] = c;
-			gap |= (c == '-');
-		}
-		URX_SYNC();
-		return __ballot(gap) != 0;
-	};
-	uint32_t n_gated = 0;  // statistics
-	// this round's jobs: those with klo <= k < khi.  Blocks take tiles of DP_TILE consecutive jobs from the round's work
-	// counter (a read in a repeat family owns hundreds of consecutive jobs of the last round and none of the first: a
-	// fixed tile-to-block map left blocks idle while others still had a dozen DPs to run); the k of a tile's jobs comes in
-	// with one load and the block runs those of this round two at a time.
-#ifndef URX_DP_TILE
-#define URX_DP_TILE 32  // 8: 8.6 ms, 16: 5.7, 32: 5.3, 48: 5.6, 64: 5.9 per 1 M 150-base reads (the counter is one address for all blocks)
-#endif
-	constexpr uint32_t DP_TILE = URX_DP_TILE;
-	for (;;) {
-	uint32_t tile = 0;
-	if (lane == 0) tile = atomicAdd(ticket, DP_TILE);
-	tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile);
-	if (tile >= njobs) break;
-	uint32_t kk = 0xFFFFu;  // 0xFFFF: slot not in use
-	if (lane < (int)DP_TILE && tile + lane < njobs) kk = dp.kidx[tile + lane];
-	uint64_t todo = __ballot(kk >= klo && kk < khi && kk != 0xFFFFu);
-	while (todo) {
-		// ---- up to two jobs that pass AlignHSP's first test under the cap the replay has reached so far ----
-		struct JobState {
-			uint32_t j, startdb, pk, flags, vst_l, vst_r, combinedTLo;
-			int maxpen, QL, startq, len, leftScore, rightScore, rtrim, totalPen, nL, nR;
-			bool plus;
-		} js[2];
-		// (every index into js / F below is a compile-time constant after unrolling: a run-time index would put both
-		// problems' state into scratch memory -- the first version of this loop ran five times slower for it)
-		auto take_job = [&](JobState &S, uint8_t *sq) -> bool {
-			while (todo) {
-				const uint32_t j = tile + (uint32_t)__builtin_ctzll(todo);
-				todo &= todo - 1;
-				const DpJob J = dp.jobs[j];
-				if (J.read == 0xFFFFFFFFu) continue;
-				const int glen = (int)((J.pk >> PK_LEN_SH) & PK_MASK), gscore = (int)((J.pk >> PK_SCORE_SH) & PK_MASK);
-				if (glen - gscore > J.maxpen) {  // the cap only falls
-					if (lane == 0) dp.jobs[j].flags = DPJ_GATED;
-					++n_gated;
-					continue;
-				}
-				S.j = j; S.startdb = J.startdb; S.pk = J.pk; S.maxpen = J.maxpen;
-				const uint64_t off = offs[J.read];
-				S.QL = (int)(offs[J.read + 1] - off);
-				S.startq = (int)(J.pk & PK_MASK); S.len = glen;
-				S.plus = (J.pk >> PK_PLUS_SH) & 1u;
-				S.flags = 0; S.vst_l = 0; S.vst_r = 0; S.combinedTLo = J.startdb;
-				S.leftScore = 0; S.rightScore = 0; S.rtrim = 0; S.totalPen = glen - gscore; S.nL = 0; S.nR = 0;
-				URX_SYNC();
-				const uint8_t *q = bases + off;
-#pragma unroll
-				for (int c = 0; c < NCH; ++c) {
-					const int p = 64 * c + lane;
-					if (p < S.QL) sq[p] = S.plus ? q[p] : (uint8_t)comp_char(q[S.QL - 1 - p]);
-				}
-				return true;
-			}
-			return false;
-		};
-		bool have[2];
-		have[0] = take_job(js[0], sQ[0]);
-		have[1] = have[0] && take_job(js[1], sQ[1]);
-		if (!have[0]) break;
-		URX_SYNC();
-		// ---- the left flanks of both jobs, then the right flanks (the right one's budget depends on the left one's outcome) ----
-#pragma unroll 1
-		for (int side = 0; side < 2; ++side) {
-			const bool left = side == 0;
-			VFlank F[2];
-			bool run[2] = {false, false}, narrow[2] = {false, false};
-			int fql[2] = {0, 0}, allGap[2] = {0, 0}, need[2] = {0, 0};
-			uint32_t tlo[2] = {0, 0}, tl[2] = {0, 0};
-#pragma unroll
-			for (int h = 0; h < 2; ++h) {
-				F[h].active = false;
-				if (!have[h]) continue;
-				JobState &S = js[h];
-				if (left) {
-					if (S.startq <= 0) continue;
-					fql[h] = S.startq;
-					const uint32_t leftTHi = S.startdb - 1;
-					tl[h] = (uint32_t)(fql[h] + BR);
-					if (S.startdb < (uint32_t)S.startq || tl[h] >= leftTHi) { S.flags |= DPJ_LEFT_FAIL; continue; }
-					tlo[h] = leftTHi - tl[h] + 1;
-				} else {
-					const int rightQLo = S.startq + S.len;
-					if ((S.flags & DPJ_LEFT_FAIL) || rightQLo >= S.QL) continue;
-					if (S.totalPen > S.maxpen) { S.flags |= DPJ_RIGHT_SKIPPED; continue; }
-					fql[h] = S.QL - rightQLo;
-					tlo[h] = S.startdb + (uint32_t)S.len;
-					uint32_t thi = tlo[h] + (uint32_t)fql[h] + (uint32_t)BR;
-					if (thi >= X.seqDataSize) thi = X.seqDataSize - 1;
-					tl[h] = thi - tlo[h] + 1;
-				}
-				if (load_window(sT[h] + 32, tlo[h], (int)tl[h])) { S.flags |= left ? DPJ_LEFT_FAIL : DPJ_RIGHT_FAIL; continue; }
-				// a flank score below `need` puts the penalty over the cap the job was made under (unless the all-gap floor
-				// rescues it): the DP may stop as soon as that is certain
-				allGap[h] = P.gap_open_score + (fql[h] - 1) * P.gap_ext_score;
-				need[h] = fql[h] - (S.maxpen - S.totalPen);
-				run[h] = true;
-				narrow[h] = F[h].setup(VP, left ? sQ[h] : sQ[h] + (S.startq + S.len), fql[h], sT[h] + 32, (int)tl[h], left, !left, tb[h], TB_ROWS8,
-				                       (float)need[h], allGap[h] < need[h]);
-				if (!narrow[h]) F[h].active = false;
-			}
-			viterbi_pair_rows(F[0], F[1]);
-#pragma unroll
-			for (int h = 0; h < 2; ++h) {
-				if (!run[h]) continue;
-				JobState &S = js[h];
-				RevOps R;
-				R.ops = left ? ropsL[h] : ropsR[h];
-				uint32_t vst = 0;
-				int score;
-				bool aborted = false;
-				if (narrow[h]) {
-					score = (int)F[h].finish(R, vst);
-					aborted = F[h].aborted;
-				} else {  // cannot happen: the search kernel keeps reads with a clipped flank window to itself (park_for_dp)
-					score = 0; R.begin(); vst = URMAPX_ST_BAND_TOO_WIDE;
-				}
-				if (aborted) { score = need[h] - 1; R.begin(); vst = 0; if (!left) S.flags |= DPJ_RIGHT_ABORTED; }
-				if (left) {
-					S.vst_l = vst;
-					S.nL = R.n;
-					// TrimLeftIs (pathinfo.cpp:153-171): the leading I run is the last run in traceback order
-					int nTrimI = 0;
-					if (S.nL > 0) {
-						const uint32_t lastop = ropsL[h][S.nL - 1];
-						if ((lastop & 3u) == OP_I) { nTrimI = (int)(lastop >> 2); --S.nL; }
-					}
-					S.combinedTLo = tlo[h] + (uint32_t)nTrimI;
-					if (allGap[h] > score) score = allGap[h];
-					S.leftScore = score;
-					S.totalPen += fql[h] - score;
-				} else {
-					S.vst_r = vst;
-					S.nR = R.n;
-					// TrimRightIs (pathinfo.cpp:173-190): trailing I run = first run in traceback order, never the whole path
-					if (S.nR > 1 && (ropsR[h][0] & 3u) == OP_I) S.rtrim = 1;
-					if (allGap[h] > score) score = allGap[h];
-					S.rightScore = score;
-				}
-			}
-		}
-		// ---- per job: path = Left || M x len || Right, run-length merged (uniform; lane 0 stores into LDS, then one coalesced copy) ----
-#pragma unroll
-		for (int h = 0; h < 2; ++h) {
-			if (!have[h]) continue;
-			JobState &S = js[h];
-			int nc = 0;
-			if (!(S.flags & (DPJ_LEFT_FAIL | DPJ_RIGHT_FAIL | DPJ_RIGHT_SKIPPED | DPJ_RIGHT_ABORTED))) {
-				int cop = -1, clen = 0;
-				bool ovf = false;
-				auto put = [&](int op, int l) {
-					if (l <= 0) return;
-					if (op == cop) { clen += l; return; }
-					if (clen) { if (nc < URMAPX_MAX_PATH_OPS) { if (lane == 0) cand[nc] = (uint16_t)((clen << 2) | cop); ++nc; } else ovf = true; }
-					cop = op; clen = l;
-				};
-				for (int t = S.nL - 1; t >= 0; --t) { const uint32_t o = ropsL[h][t]; put((int)(o & 3u), (int)(o >> 2)); }
-				put(OP_M, S.len);
-				for (int t = S.nR - 1; t >= S.rtrim; --t) { const uint32_t o = ropsR[h][t]; put((int)(o & 3u), (int)(o >> 2)); }
-				put(-2, 1);  // flush
-				if (ovf) { S.flags |= DPJ_PATH_LONG; nc = 0; }
-				URX_SYNC();
-				uint16_t *out = dp.ops + (size_t)S.j * DP_JOB_OPS;
-				for (int t = lane; t < nc; t += 64) out[t] = cand[t];
-				URX_SYNC();
-			}
-			if (lane == 0) {
-				DpJob *o = dp.jobs + S.j;
-				o->combined_tlo = S.combinedTLo;
-				o->left_score = (int16_t)S.leftScore; o->right_score = (int16_t)S.rightScore;
-				o->nops = (uint8_t)nc; o->flags = (uint8_t)S.flags; o->vst_l = (uint8_t)S.vst_l; o->vst_r = (uint8_t)S.vst_r;
-			}
-		}
-	}
-	}
-	if (lane == 0 && n_gated) atomicAdd(dp.counters + 3, n_gated);
-}
-#else
-// URX_DP_TB_GLOBAL (default 1): the trace cells of the narrow band live in the block's global scratch, not in LDS.  They were what held
-// this kernel to 5.75 waves per SIMD for 150-base reads and to 4.25 for 250-base reads (9.2 KB of LDS per block); the stores are one
-// dword per lane per eight rows and the traceback reads a few dozen cells.  250 bases: 31.5 -> 27.7 ms per 1 M reads, 150: 3.06 -> 2.94.
-#ifndef URX_DP_TB_GLOBAL
-#define URX_DP_TB_GLOBAL 1
-#endif
-template <int NCH>
-__global__ __launch_bounds__(64) URX_DP_ATTR void dp_kernel(DevIndex X, urmapx_params P, const uint8_t *__restrict__ bases,
+__global__ __launch_bounds__(64) void dp_kernel(DevIndex X, urmapx_params P, const uint8_t *__restrict__ bases,
                                                 const uint64_t *__restrict__ offs, DpWork dp, uint8_t *scratch,
                                                 size_t scratch_stride, const uint8_t *__restrict__ g_seq, uint32_t klo, uint32_t khi,
                                                 uint32_t *ticket, const uint32_t *__restrict__ list, const uint32_t *list_count) {
@@ -1945,23 +1643,10 @@ __global__ __launch_bounds__(64) URX_DP_ATTR void dp_kernel(DevIndex X, urmapx_p
 	__shared__ __attribute__((aligned(16))) uint8_t sQT[QMAX + QMAX + 64];
 	uint8_t *const sQ = sQT, *const sT = sQT + QMAX;
 	static_assert(QMAX >= 64, "the window lies band_radius + 1 bytes or more inside sQT (viterbi_dev.h: B_LDS)");
-#if URX_DP_TB_GLOBAL  // the trace cells in the block's global scratch: LDS per block 7 -> 1.2 KB (+ the wide path's rows)
+	// the trace cells in the block's global scratch: LDS per block 7 -> 1.2 KB (+ the wide path's rows)
 	uint32_t *const tb = reinterpret_cast<uint32_t *>(scratch + (size_t)blockIdx.x * scratch_stride +
 	                                                  ((WideScratch::bytes(QMAX, QMAX + 64) + 255) & ~(size_t)255));
-#ifdef URX_DP_NO_WLDS  // debugging aid: the wide path's rows in the global trace buffer too (what search_se_kernel's inline DP does)
-#define URX_DP_WLDS
-#else
 	__shared__ uint32_t wlds[3 * QMAX];  // the wide path's three per-row arrays (it used the idle trace buffer when that was LDS)
-#define URX_DP_WLDS , wlds, 3 * QMAX
-#endif
-#elif defined(URX_DP_WLDS_TEST)  // debugging aid: the trace buffer in LDS as shipped, the wide path's rows in an array of their own
-	__shared__ uint32_t tb[TB_ROWS8 * 64];
-	__shared__ uint32_t wlds[URX_DP_WLDS_TEST * QMAX];
-#define URX_DP_WLDS , wlds, URX_DP_WLDS_TEST * QMAX
-#else
-	__shared__ uint32_t tb[TB_ROWS8 * 64];
-#define URX_DP_WLDS
-#endif
 	__shared__ uint16_t ropsL[OPS_CAP], ropsR[OPS_CAP], cand[URMAPX_MAX_PATH_OPS];
 	const int lane = threadIdx.x;
 	WideScratch ws;
@@ -1992,16 +1677,7 @@ __global__ __launch_bounds__(64) URX_DP_ATTR void dp_kernel(DevIndex X, urmapx_p
 	// every round paid one ticket per 32 jobs MADE, and tickets are atomics on one address, which retire at 88 M/s on this
 	// device whatever else the machine does -- 0.41 M tickets = 4.7 ms per round for 1 M 250-base reads, of which the first
 	// two rounds had 7 % and 30 % of the jobs to run (7.5 ms each).
-#ifndef URX_DP_TILE
-#define URX_DP_TILE 16
-#endif
-#ifndef URX_DP_TB_GLOBAL
-#define URX_DP_TB_GLOBAL 1
-#endif
-#ifndef URX_DP_EDGE2
-#define URX_DP_EDGE2 false  // viterbi_dev.h: edge rows with the tests of their edge only -- bit-identical, 10 % fewer instructions per edge row and no faster: off
-#endif
-	constexpr uint32_t DP_TILE = URX_DP_TILE;
+	constexpr uint32_t DP_TILE = 16;
 	(void)klo; (void)khi; (void)njobs;
 	const uint32_t nlist = *list_count < dp.jobs_cap ? *list_count : dp.jobs_cap;
 	// A block's first tile is its own (tile blockIdx.x), the ticket counter deals the tiles behind the grid's first sweep: a
@@ -2058,10 +1734,6 @@ __global__ __launch_bounds__(64) URX_DP_ATTR void dp_kernel(DevIndex X, urmapx_p
 		RevOps RL, RR;
 		RL.ops = ropsL; RR.ops = ropsR;
 		RL.begin(); RR.begin();
-#if defined(URX_DP_WLDS_TEST) && defined(URX_DP_WLDS_FILL)
-		for (int t = lane; t < URX_DP_WLDS_TEST * QMAX; t += 64) wlds[t] = URX_DP_WLDS_FILL;
-		URX_SYNC();
-#endif
 		if (startq > 0) {
 			const int leftQL = startq;
 			const uint32_t leftTHi = startdb - 1;
@@ -2076,8 +1748,8 @@ __global__ __launch_bounds__(64) URX_DP_ATTR void dp_kernel(DevIndex X, urmapx_p
 					const int allGap = P.gap_open_score + (leftQL - 1) * P.gap_ext_score;
 					const int need = leftQL - (J.maxpen - totalPen);
 					bool aborted = false;
-					leftScore = (int)viterbi_wave<true, URX_DP_EDGE2>(VP, sQ, leftQL, sT, (int)leftTL, true, false, tb, TB_ROWS8, ws, RL, vst_l, lane,
-					                                    (float)need, allGap < need ? &aborted : nullptr URX_DP_WLDS);
+					leftScore = (int)viterbi_wave<true>(VP, sQ, leftQL, sT, (int)leftTL, true, false, tb, TB_ROWS8, ws, RL, vst_l, lane,
+					                                    (float)need, allGap < need ? &aborted : nullptr, wlds, 3 * QMAX);
 					if (aborted) { leftScore = need - 1; RL.begin(); vst_l = 0; }
 					// TrimLeftIs (pathinfo.cpp:153-171): the leading I run is the last run in traceback order
 					int nTrimI = 0;
@@ -2105,8 +1777,8 @@ __global__ __launch_bounds__(64) URX_DP_ATTR void dp_kernel(DevIndex X, urmapx_p
 					const int allGap = P.gap_open_score + (rightQL - 1) * P.gap_ext_score;
 					const int need = rightQL - (J.maxpen - totalPen);
 					bool aborted = false;
-					rightScore = (int)viterbi_wave<true, URX_DP_EDGE2>(VP, sQ + rightQLo, rightQL, sT, (int)rightTL, false, true, tb, TB_ROWS8, ws, RR, vst_r, lane,
-					                                     (float)need, allGap < need ? &aborted : nullptr URX_DP_WLDS);
+					rightScore = (int)viterbi_wave<true>(VP, sQ + rightQLo, rightQL, sT, (int)rightTL, false, true, tb, TB_ROWS8, ws, RR, vst_r, lane,
+					                                     (float)need, allGap < need ? &aborted : nullptr, wlds, 3 * QMAX);
 					if (aborted) { rightScore = need - 1; RR.begin(); vst_r = 0; flags |= DPJ_RIGHT_ABORTED; }
 					// TrimRightIs (pathinfo.cpp:173-190): trailing I run = first run in traceback order, never the whole path
 					if (RR.n > 1 && (ropsR[0] & 3u) == OP_I) rtrim = 1;
@@ -2144,22 +1816,14 @@ __global__ __launch_bounds__(64) URX_DP_ATTR void dp_kernel(DevIndex X, urmapx_p
 	}
 	if (lane == 0 && n_gated) atomicAdd(dp.counters + 3, n_gated);
 }
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // kernel D: phase 6's ordered part for the parked reads -- the jobs of a read in HSP order through AlignHSP's tests
 // and AddHitX, then CalcMAPQ6 / SetMappedPos and the result record.  One wavefront per read.
 // ------------------------------------------------------------------------------------------------
-#ifndef URX_FIN_WAVES
-#define URX_FIN_WAVES 8  // register budget of finalize_se_kernel as waves per SIMD: 51 VGPRs, no spill; the kernel waits on memory and wants waves (0 = the compiler's choice: 85 VGPRs, 5 waves)
-#endif
-#if URX_FIN_WAVES
-#define URX_FIN_ATTR __attribute__((amdgpu_waves_per_eu(URX_FIN_WAVES, URX_FIN_WAVES)))
-#else
-#define URX_FIN_ATTR
-#endif
+// register budget of finalize_se_kernel: 8 waves per SIMD (51 VGPRs, no spill; the kernel waits on memory and wants waves -- the compiler's own choice is 85 VGPRs, 5 waves)
 template <int NCH, bool OVF>
-__global__ __launch_bounds__(64) URX_FIN_ATTR void finalize_se_kernel(DevIndex X, urmapx_params P, const uint64_t *__restrict__ offs, DpWork dp,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void finalize_se_kernel(DevIndex X, urmapx_params P, const uint64_t *__restrict__ offs, DpWork dp,
                                                          urmapx_result *__restrict__ results, urmapx_path_op *__restrict__ path_ops,
                                                          uint32_t *path_used, int hsp_lds_cap, uint32_t *ovf_list, uint32_t klo,
                                                          uint32_t khi) {
@@ -2315,7 +1979,7 @@ size_t p3_state_words(uint32_t max_read_len) {
 }
 size_t dp_scratch_stride(uint32_t max_read_len) {
 	const int qmax = 64 * (max_read_len <= 128 ? 2 : max_read_len <= 192 ? 3 : max_read_len <= 256 ? 4 : max_read_len <= 320 ? 5 : max_read_len <= 512 ? 8 : 16);
-	// the wide-band rows and trace bytes, then room for the narrow band's trace cells (URX_DP_TB_GLOBAL: dp_kernel keeps them here
+	// the wide-band rows and trace bytes, then room for the narrow band's trace cells (dp_kernel keeps them here
 	// instead of in LDS)
 	return ((WideScratch::bytes(qmax, qmax + 64) + 255) & ~(size_t)255) + (size_t)((qmax - 24) / 8 + 2) * 256;
 }

@@ -19,30 +19,15 @@
 
 namespace urx {
 
-// URX_PE_DIET (round 6): the first pass's block at 10 240 bytes of LDS, so that FOUR of them fit a SIMD's share of a CU
-// (with 128 VGPRs; the round-5 kernel: 12 864 B, 168 VGPRs, three waves).  Where the bytes come from:
-//   1  one word of hits per mate in LDS (hits 65..128 of a mate in the block's global scratch, URX_PE_TAIL; without the tail such a pair
-//      goes to the second pass), 64 HSPs of a mate in LDS instead of 128 (the list goes on in global scratch, as before), 136 seeds per mate
-//      instead of QMAX (a pair with more: second pass)
-//   2  (ships) both words of hits in LDS: 64 HSPs, 104 seeds per mate, a hit's run count in the upper bits of its score word, pending lists
-//      of QMAX - 16 positions, the pending stage's prefix array inside seed_area
-//   0  the round-5 kernel
-// Measured (profiles/r6/ab_pe_waves4.txt, ab_pe_tail.txt), ms per 1 M reads on one box: 0: 21.60, 1: 20.35-20.48, 2: 19.59-19.63.
-#ifndef URX_PE_DIET
-#define URX_PE_DIET 2
-#endif
+// The first pass's block is 10 216 bytes of LDS, so that FOUR of them fit a SIMD's share of a CU (with 128 VGPRs; the round-5 kernel: 12 864 B,
+// 168 VGPRs, three waves).  Where the bytes come from: 64 HSPs of a mate in LDS instead of 128 (the list goes on in global scratch), 104 seeds
+// per mate instead of QMAX (a pair with more: second pass), a hit's run count in the upper bits of its score word (reads of up to 192 bases:
+// score < 256), pending lists of QMAX - 16 positions, the pending stage's prefix array inside seed_area.  Both words of hits stay in LDS.
+// Measured against the round-5 layout and against one hit word in LDS with the second in global scratch (profiles/r6/ab_pe_waves4.txt,
+// ab_pe_tail.txt), ms per 1 M reads on one box: 21.60, 20.35-20.48, this one 19.59-19.63.
 static constexpr int PE_HIT_CAP = 64;
-#ifndef URX_PE_TAIL
-#define URX_PE_TAIL 1  // diet 1: hits 65..128 of a mate in global scratch (0: such a pair goes to the second pass)
-#endif
-// URX_PE_DIET 2: BOTH hit words stay in LDS and the bytes come from elsewhere -- 104 seeds per mate, a hit's run count in the upper bits of
-// its score word (reads of up to 192 bases: score < 256), pending lists of QMAX - 16 positions, no tail pointer: 10 216 B
-#define URX_PE_PACK (URX_PE_DIET == 2)
-static constexpr int PE_HITW1 = (URX_PE_DIET == 1 && !URX_PE_TAIL) ? 1 : 2;     // hit-list words (64 hits each) of the first pass: 19 of 1 M reads end with 65..83 hits, none with more than 128
-// ... of which in LDS.  On the diet the second word lives in the block's global scratch (hit_tail): the 19-in-a-million pairs that reach it are
-// also the costliest of a batch, and as the second pass's whole work list they kept a launch of their own going for 1.8 ms (profiles/r6/ab_pe_waves4.txt)
-static constexpr int PE_HITW1_LDS = URX_PE_DIET == 1 ? 1 : 2;
-static constexpr int PE_HSP_CAP = URX_PE_DIET ? 64 : 128;       // HSPs of a mate held in LDS
+static constexpr int PE_HITW1 = 2;      // hit-list words (64 hits each) of the first pass: 19 of 1 M reads end with 65..83 hits, none with more than 128
+static constexpr int PE_HSP_CAP = 64;   // HSPs of a mate held in LDS
 static constexpr int PE_HSP_OVF_CAP = 8064;  // per mate, in global scratch
 static constexpr int PE_OVF_BLOCKS = 1024;   // grid of the second pass (the costliest pairs of a batch)
 static constexpr int PE_T2_BLOCKS = 64;      // grid of the third pass (pairs with more than 256 hits on a mate)
@@ -59,31 +44,12 @@ __host__ __device__ inline size_t pe_rowstore_offset(int qmax) {
 }
 
 __host__ __device__ inline size_t pe_tb_offset(int qmax);
-__host__ __device__ inline size_t pe_tail_offset(int qmax);
 
 // TIER: 0 = first pass (hit lists of PE_HITW1 x 64 per mate), 1 = second pass over the pairs that outgrew a list (4 x 64
 // hits, HSP lists continued in global memory), 2 = third pass over the pairs that outgrew those (PE_HITW2 x 64 = 1024
 // hits per mate: the reference's list has no bound, state1.cpp:193-228; this pass exists so that a pair in a satellite
 // is mapped, not flagged -- it runs a handful of pairs per run and is not tuned)
 static constexpr int PE_HITW2 = 16;
-// The first pass's hits beyond its LDS word (diet): kept out of line, as search_se_kernel's hsp_overflow_add, so that the registers of a
-// path 19 pairs in a million take do not count against the loops every pair runs.  tail: [k] position, [64 + k] score << 1 | plus, [128 + k] runs.
-__device__ __noinline__ bool pe_tail_overlaps_any(const uint32_t *tail, int nt, uint32_t db) {  // wave-uniform db: one hit per lane
-	const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-	return __ballot(lane < nt && (tail[lane] >> 6) == (db >> 6)) != 0;
-}
-__device__ __noinline__ bool pe_tail_overlaps_each(const uint32_t *tail, int nt, uint32_t db) {  // a db per lane
-	bool ov = false;
-	for (int k = 0; k < nt; ++k) ov |= (tail[k] >> 6) == (db >> 6);
-	return ov;
-}
-__device__ __noinline__ uint32_t pe_tail_get(const uint32_t *tail, int at) { return tail[at]; }
-__device__ __noinline__ void pe_tail_put(uint32_t *tail, int k, uint32_t db, uint32_t sp, uint32_t nops) {
-	const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-	if (lane == 0) { tail[k] = db; tail[64 + k] = sp; tail[128 + k] = nops; }
-	__threadfence_block();
-}
-
 // The wave-uniform state of a mate that changes as the pair is searched.  It lives in LDS, not in the Mate object: the Mate
 // objects are in private memory (the pairing loop picks a mate at run time), where every access is a scratch load or
 // store -- a memory round trip for a counter.  Through `hot` it is a ds_read / ds_write (all lanes, same address).
@@ -99,15 +65,12 @@ struct MateHot {
 	bool q_other;  // the read holds a byte outside the code list: its windows are compared as ASCII
 	uint2 *hsp_ovf;             // this mate's HSP list beyond LDS, global
 	urmapx_path_op *hit_paths;  // its hits' paths, global
-#if !URX_PE_PACK
-	uint32_t *hit_tail;         // first pass on the diet: hits beyond the LDS word -- [k] position, [64 + k] score << 1 | plus, [128 + k] runs of the path; global
-#endif
 };
 // Everything a mate owns, as ONE LDS object per mate.  Round 4: a Mate is now a handful of pointers held in registers -- the
 // pointer to this object is the only thing that differs between the two mates, so `the mate picked at run time` is an address
 // computation, not an array of objects in private memory (where every member access was a scratch load: 331 scratch
 // instructions per pair in round 3).  The hit list lives here too (it was four per-lane words per mate in private memory).
-static constexpr int pe_hitw(int tier) { return tier == 0 ? PE_HITW1_LDS : tier == 1 ? 4 : PE_HITW2; }
+static constexpr int pe_hitw(int tier) { return tier == 0 ? PE_HITW1 : tier == 1 ? 4 : PE_HITW2; }
 template <int NCH, int TIER>
 struct MateLds {
 	static constexpr int QMAX = 64 * NCH;
@@ -117,7 +80,7 @@ struct MateLds {
 	__attribute__((aligned(16))) uint8_t sQ[2][QMAX];     // [0] read as given, [1] reverse complement
 	uint32_t hit_db[HITS];
 	uint16_t hit_sp[HITS];   // score << 1 | plus
-	static constexpr bool PACK = URX_PE_PACK && TIER == 0 && NCH <= 3;  // the run count rides in hit_sp (bits 9..15)
+	static constexpr bool PACK = TIER == 0 && NCH <= 3;  // the run count rides in hit_sp (bits 9..15)
 	uint8_t hit_nops[PACK ? 4 : HITS];  // runs of a hit's path (<= URMAPX_MAX_PATH_OPS = 96)
 	uint32_t hsp_db[PE_HSP_CAP], hsp_ql[PE_HSP_CAP];
 	uint16_t hsp_sf[PE_HSP_CAP];
@@ -149,11 +112,6 @@ struct Mate {
 #define q_other (hot->q_other)
 #define hsp_ovf (hot->hsp_ovf)
 #define hit_paths (hot->hit_paths)
-#if URX_PE_PACK
-#define hit_tail ((uint32_t *)nullptr)
-#else
-#define hit_tail (hot->hit_tail)
-#endif
 #define QL (hot->QL)
 #define nwords (hot->nwords)
 #define pendCount (hot->pendCount)
@@ -186,17 +144,15 @@ struct Mate {
 	// aid that lowers the first pass's caps makes it HITW x 16 in the second pass, so that a fixture with a few dozen hits
 	// per mate reaches the third)
 	__device__ __forceinline__ int hits_room() const { return OVF ? HITW << hit_wsh : hit_cap; }
-	static constexpr int HITS_LDS = MateLds<NCH, TIER>::HITS;
-	static constexpr bool TAIL = TIER == 0 && PE_HITW1_LDS < PE_HITW1;  // hits beyond HITS_LDS exist and live in hit_tail
-	__device__ __forceinline__ uint32_t hdb(int i) const { return (TAIL && i >= HITS_LDS) ? pe_tail_get(hit_tail, i - HITS_LDS) : hit_db[i]; }      // i wave-uniform
+	__device__ __forceinline__ uint32_t hdb(int i) const { return hit_db[i]; }      // i wave-uniform
 	static constexpr bool PACK = MateLds<NCH, TIER>::PACK;
 	__device__ __forceinline__ uint32_t hsp_of(int i) const {
 		if constexpr (PACK) return (uint32_t)hit_sp[i] & 0x1FFu;
-		return (TAIL && i >= HITS_LDS) ? pe_tail_get(hit_tail, 64 + i - HITS_LDS) : (uint32_t)hit_sp[i];
+		return (uint32_t)hit_sp[i];
 	}
 	__device__ __forceinline__ int hnops(int i) const {
 		if constexpr (PACK) return (int)(hit_sp[i] >> 9);
-		return (TAIL && i >= HITS_LDS) ? (int)pe_tail_get(hit_tail, 128 + i - HITS_LDS) : (int)hit_nops[i];
+		return (int)hit_nops[i];
 	}
 	// HSPs: LDS [PE_HSP_CAP] (hsp_db, hsp_ql, hsp_sf); beyond hsp_lds in global scratch as {db, startq | len << 9 | sf << 18}
 	// dbg_cut (MateHot): diagnostic only (URMAPX_DEBUG_STOP_PE 41 / 42 / 43): leave search_pending after that part
@@ -213,11 +169,6 @@ struct Mate {
 	__device__ __forceinline__ bool overlaps_hit(uint32_t db) const {
 		bool eq = false;
 		const int n = hitCount;
-		if constexpr (TAIL) {
-			eq = lane < n && (hit_db[lane] >> 6) == (db >> 6);  // (HITS_LDS == 64)
-			if (__ballot(eq) != 0) return true;
-			return n > HITS_LDS && pe_tail_overlaps_any(hit_tail, n - HITS_LDS, db);
-		}
 		for (int b = 0; b < n; b += 64) eq |= b + lane < n && (hit_db[b + lane] >> 6) == (db >> 6);
 		return __ballot(eq) != 0;
 	}
@@ -226,8 +177,7 @@ struct Mate {
 	__device__ __forceinline__ bool overlaps_any_hit(uint32_t db) const {
 		bool ov = false;
 		const int n = hitCount;
-		for (int k = 0; k < (TAIL && n > HITS_LDS ? HITS_LDS : n); ++k) ov |= (hit_db[k] >> 6) == (db >> 6);  // one address for all lanes: an LDS broadcast
-		if (TAIL && n > HITS_LDS) ov |= pe_tail_overlaps_each(hit_tail, n - HITS_LDS, db);
+		for (int k = 0; k < n; ++k) ov |= (hit_db[k] >> 6) == (db >> 6);  // one address for all lanes: an LDS broadcast
 		return ov;
 	}
 
@@ -247,8 +197,7 @@ struct Mate {
 		}
 		if (!keep) return -1;
 		if (hitCount >= hits_room()) { status |= URMAPX_ST_HIT_OVERFLOW; if (topHit == idx) topHit = -1; return -1; }
-		if (TAIL && idx >= HITS_LDS) pe_tail_put(hit_tail, idx - HITS_LDS, db, ((uint32_t)score << 1) | (plus ? 1u : 0u), (uint32_t)cand_nops);
-		else if (lane == 0) {
+		if (lane == 0) {
 			hit_db[idx] = db;
 			if constexpr (PACK) hit_sp[idx] = (uint16_t)(((uint32_t)score << 1) | (plus ? 1u : 0u) | ((uint32_t)cand_nops << 9));
 			else { hit_sp[idx] = (uint16_t)(((uint32_t)score << 1) | (plus ? 1u : 0u)); hit_nops[idx] = (uint8_t)cand_nops; }
@@ -963,7 +912,6 @@ struct Mate {
 #undef q_other
 #undef hsp_ovf
 #undef hit_paths
-#undef hit_tail
 #undef hot
 #undef sQ
 #undef qpl
@@ -978,13 +926,10 @@ struct Mate {
 // Waves per SIMD the register allocation aims at.  The pair kernel waits on memory 70 % of its wave cycles and issues
 // instructions in 40 % of its SIMD cycles at two waves per SIMD (profiles/r3/pmc_sq_pe.json): it is bound by latency, and
 // a third wave hides more of it than the extra spills cost -- 2 waves (228 VGPRs): 40.4 ms per 1 M reads, 3 waves (168
-// VGPRs): 34.6 ms; asking for 4 (128 VGPRs) the compiler settles at 194 = 2 waves again.  LDS allows 12 blocks per CU
-// for reads <= 192 (13.2 KB each: the DP trace lives in global scratch, the seed-stage arrays share one area by lifetime).
-#ifndef URX_PE_WAVES
-#define URX_PE_WAVES(NCH) ((NCH) <= 3 ? (URX_PE_DIET ? 4 : 3) : 2)
-#endif
+// VGPRs): 34.6 ms.  Since round 6 the first pass's block is small enough for FOUR (10 216 B of LDS, 128 VGPRs: the top of this
+// file); the second pass of the same read lengths is asked for four as well and settles at two.
 template <int NCH, int TIER>
-__global__ __launch_bounds__(64, TIER == 2 ? 1 : URX_PE_WAVES(NCH)) void search_pe_kernel(DevIndex X, urmapx_params P, const uint8_t *__restrict__ bases,
+__global__ __launch_bounds__(64, TIER == 2 ? 1 : NCH <= 3 ? 4 : 2) void search_pe_kernel(DevIndex X, urmapx_params P, const uint8_t *__restrict__ bases,
                                                        const uint64_t *__restrict__ offs, uint32_t npairs,
                                                        urmapx_result *__restrict__ results,
                                                        urmapx_path_op *__restrict__ path_ops, uint32_t *path_used,
@@ -1003,12 +948,11 @@ __global__ __launch_bounds__(64, TIER == 2 ? 1 : URX_PE_WAVES(NCH)) void search_
 	//   the pending stage's candidate queue                                 on  seed_db
 	__shared__ MateLds<NCH, TIER> ml[2];
 	static_assert(URMAPX_MAX_PATH_OPS <= 127, "hit_nops is a byte (seven bits when it rides in hit_sp)");
-	static_assert(!M::TAIL || M::HITS_LDS == 64, "the tail begins at hit 64");
 	// Both1 seed lists of the two mates in enumeration order: qpos | plus << 15, db position
 	// later passes: 2 * (QMAX - 20) >= 2 * (QMAX - W + 1) for the word lengths in use (W >= 21).  First pass: QMAX -- a mate returns a
 	// seed only where the diagonal changes (getseed.cpp:60-66), a handful per read; a pair with more goes to the second pass
 	// (LDS per block decides how many pairs a CU keeps in flight)
-	constexpr int SEED_CAP = TIER == 0 ? (URX_PE_DIET && NCH <= 3 ? (URX_PE_PACK ? 104 : 136) : QMAX) : 2 * (QMAX - 20);
+	constexpr int SEED_CAP = TIER == 0 ? (NCH <= 3 ? 104 : QMAX) : 2 * (QMAX - 20);
 	__shared__ __attribute__((aligned(16))) uint16_t seed_q[2][SEED_CAP];
 	__shared__ __attribute__((aligned(16))) uint32_t seed_db[2][SEED_CAP];
 	// cached ExtendPen outcome of every seed (see extend_pen_cached); bit 15 of seed_pen = "already extended once"
@@ -1029,8 +973,8 @@ __global__ __launch_bounds__(64, TIER == 2 ? 1 : URX_PE_WAVES(NCH)) void search_
 	static_assert((2 * OPS_CAP + URMAPX_MAX_PATH_OPS) * 2 >= 64, "AlignHSP's window lies band_radius + 1 bytes or more inside seed_area (viterbi_dev.h: B_LDS)");
 	uint32_t *const wide_lds = seed_area + ALIGN_BYTES / 4;
 	constexpr int WIDE_LDS_DWORDS = (int)(sizeof(seed_area) - ALIGN_BYTES) / 4;
-	// (diet 2: the prefix array lies at the start of seed_area instead -- the pending stage's chain rows run while AlignHSP's buffers there are idle)
-	constexpr bool PRE_IN_AREA = URX_PE_PACK && TIER == 0 && NCH <= 3;
+	// (first pass, reads of up to 192 bases: the prefix array lies at the start of seed_area instead -- the pending stage's chain rows run while AlignHSP's buffers there are idle)
+	constexpr bool PRE_IN_AREA = TIER == 0 && NCH <= 3;
 	static_assert(2 * QMAX + (PRE_IN_AREA ? 0 : 66 * 2) <= sizeof(seed_q), "alias");
 	uint8_t *const rowlen = reinterpret_cast<uint8_t *>(&seed_q[0][0]);  // shared by the two mates: SearchPE_Pending runs on one mate at a time
 	uint16_t *const pre = PRE_IN_AREA ? reinterpret_cast<uint16_t *>(seed_area) : reinterpret_cast<uint16_t *>(rowlen + 2 * QMAX);
@@ -1063,9 +1007,6 @@ __global__ __launch_bounds__(64, TIER == 2 ? 1 : URX_PE_WAVES(NCH)) void search_
 		                           (TIER == 2 ? (size_t)PE_OVF_BLOCKS * 2 * PE_HIT_CAP * 4 * URMAPX_MAX_PATH_OPS : (size_t)0) +
 		                           ((size_t)blockIdx.x * 2 + a) * PE_HIT_CAP * M::HITW * URMAPX_MAX_PATH_OPS
 		                     : reinterpret_cast<urmapx_path_op *>(sc) + (size_t)a * PE_HIT_CAP * PE_HITW1 * URMAPX_MAX_PATH_OPS;
-#if !URX_PE_PACK
-		hot(a).hit_tail = reinterpret_cast<uint32_t *>(sc + pe_tail_offset(QMAX)) + a * 192;
-#endif
 		hot(a).hit_cap = (hsp_lds_cap >= 64 && hsp_lds_cap <= PE_HSP_CAP) ? (hsp_lds_cap & ~63) / 4 : PE_HIT_CAP * PE_HITW1;
 		hot(a).hit_wsh = (hsp_lds_cap >= 64 && hsp_lds_cap <= PE_HSP_CAP) ? 4 : 6;
 		hot(a).hsp_lds = (hsp_lds_cap >= 64 && hsp_lds_cap <= PE_HSP_CAP) ? (hsp_lds_cap & ~63) : PE_HSP_CAP;
@@ -1096,7 +1037,7 @@ __global__ __launch_bounds__(64, TIER == 2 ? 1 : URX_PE_WAVES(NCH)) void search_
 			res[a].score = 0; res[a].second = 0; res[a].mapq = 0; res[a].plus = 0; res[a].exit_phase = 0; res[a].status = 0;
 			res[a].hit_count = 0; res[a].path_nops = 0; res[a].path_off = 0;
 			if (QL < W || QL > QMAX || W > 32 || X.maxIx > 32 || QL - (W - 1) > 256) bad = true;  // pending positions are bytes
-			// (diet 2: this pass's pending lists hold QMAX - 16 positions -- enough for every W >= 17; an index with shorter words sends such a pair to the general kernel)
+			// (first pass, reads of up to 192 bases: this pass's pending lists hold QMAX - 16 positions -- enough for every W >= 17; an index with shorter words sends such a pair to the general kernel)
 			if (MateLds<NCH, TIER>::PACK && QL - (W - 1) > QMAX - 16) bad = true;
 			hot(a).QL = QL; hot(a).nwords = QL - (W - 1);
 		}
@@ -1120,7 +1061,7 @@ __global__ __launch_bounds__(64, TIER == 2 ? 1 : URX_PE_WAVES(NCH)) void search_
 		for (int a = 0; a < 2; ++a) {
 			const uint8_t *q = bases + offs[2 * pr + a];
 			const int QL = hot(a).QL;
-			// (dev_common.h: URX_ACGT_FAST) a mate of upper-case ACGT only takes the four-instruction complement and code
+			// (dev_common.h: acgt_pick) a mate of upper-case ACGT only takes the four-instruction complement and code
 			bool plain = true;
 #pragma unroll
 			for (int c = 0; c < NCH; ++c) {
@@ -1130,7 +1071,7 @@ __global__ __launch_bounds__(64, TIER == 2 ? 1 : URX_PE_WAVES(NCH)) void search_
 				plain = plain && (p >= QL || is_upper_acgt(cp));
 				qch[a][0][c] = cp; qch[a][1][c] = cmr;
 			}
-			acgt[a] = URX_ACGT_FAST && __ballot(!plain) == 0;  // wave-uniform
+			acgt[a] = __ballot(!plain) == 0;  // wave-uniform
 #pragma unroll
 			for (int c = 0; c < NCH; ++c) {
 				const int p = 64 * c + lane;
@@ -1499,7 +1440,7 @@ __global__ __launch_bounds__(64, TIER == 2 ? 1 : URX_PE_WAVES(NCH)) void search_
 				R.score = (int16_t)(sp >> 1);
 				uint32_t lo = 0, hi = X.seqCount - 1;
 				uint32_t found = 0xFFFFFFFFu, coord = 0xFFFFFFFFu, tl = 0;
-				if (URX_SEQ_LANES && X.seqCount <= 64u) {  // every lane tests one sequence: one round of loads (search_se_kernel: fill_result_core)
+				if (X.seqCount <= 64u) {  // every lane tests one sequence: one round of loads (search_se_kernel: fill_result_core)
 					const bool mine = (uint32_t)lane < X.seqCount;
 					const uint32_t o = mine ? X.seqOffsets[lane] : 0u, sl = mine ? X.seqLengths[lane] : 0u;
 					const uint64_t m = __ballot(mine && db >= o && db < o + sl);
@@ -1552,13 +1493,10 @@ static int pe_nch_for(uint32_t max_read_len) {
 __host__ __device__ inline size_t pe_tb_offset(int qmax) {
 	return (pe_rowstore_offset(qmax) + (size_t)2 * (qmax / 64) * PE_ROW_CAP * 64 * 4 + 255) & ~(size_t)255;
 }
-// behind the trace cells: the first pass's hits 65..128 of both mates (3 x 64 words each)
-__host__ __device__ inline size_t pe_tail_offset(int qmax) {
-	return (pe_tb_offset(qmax) + (size_t)(qmax / 8 + 2) * 64 * 4 + 255) & ~(size_t)255;
-}
 size_t search_pe_scratch_stride(uint32_t max_read_len) {
 	const int qmax = 64 * pe_nch_for(max_read_len);
-	size_t b = pe_tail_offset(qmax) + (size_t)2 * 192 * 4;
+	size_t b = (pe_tb_offset(qmax) + (size_t)(qmax / 8 + 2) * 64 * 4 + 255) & ~(size_t)255;  // the end of the trace cells
+	b += (size_t)2 * 192 * 4;  // padding (once two hit tails): the stride decides every block's scratch base and stays what it was measured with
 	return (b + 255) & ~(size_t)255;
 }
 

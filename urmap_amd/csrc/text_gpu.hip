@@ -678,9 +678,6 @@ __global__ __launch_bounds__(SAM_WAVES * 64) void sam_kernel(SamArgs A) {
 			}
 			if ((t_fl & 2u) || t_hl != t_want) {  // never: the two kernels count the same bytes
 				if (lane == 0) atomicOr(&A.hdr->flags, 32u);
-#ifdef URX_DEBUG_TEXT
-				if (lane == 0) printf("sam_kernel mismatch: rec %u qn %u hl %u want %u QL %u fl %u direct %d\n", rec_i, t_qn, t_hl, t_want, t_QL, t_fl, (int)direct);
-#endif
 				continue;
 			}
 			const uint8_t *label = raw + t_s1 + 1u;
