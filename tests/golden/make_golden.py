@@ -11,6 +11,9 @@ outputs are what the reference itself wrote:
   reference `urmap -map X.fq -ufi g.ufi -samout X.sam -threads 1`; the @PG line is dropped.
   pe150_1/2.fq, pe100_noisy_1/2.fq + .sam + .tab   300 pairs each, reference `urmap -map2 A_1.fq -reverse A_2.fq ...
                                                    -samout A.sam -tabbedout A.tab`
+  se_alpha.fq/.sam, pe_alpha_1/2.fq + .sam + .tab, each .gz   560 reads / 300 pairs of 150 bp in the letter classes of tests/alphabet_lib.py (N at
+                  the ends and in runs, lower case, IUPAC, U / u, letters without a complement, reads that keep the store's N), the
+                  classes of the two mates drawn independently; python make_golden.py alpha regenerates only these
   r.fa, r.ufi.gz, pe120_rep_*               repeat-rich second genome: pairs with a second-best pair (see make_repeat_set)
 
   ufi_opts.json   sha256 / slot count / labels of the reference's .ufi for -make_ufi option sets (-load_factor, -veryfast,
@@ -78,6 +81,38 @@ def make_repeat_set(tmp):
     ol.run_ref(["-map2", name + "_1.fq", "-reverse", name + "_2.fq", "-ufi", "r.ufi", "-tabbedout", name + "_nosam.tab",
                 "-threads", "1"], cwd=tmp)
     shutil.copy(os.path.join(tmp, name + "_nosam.tab"), os.path.join(HERE, name + "_nosam.tab"))
+
+
+def _gz(src, dst, data=None):
+    """fixture kept gzip-compressed (mtime 0: the same bytes every time); the tests unpack it"""
+    if data is None:
+        with open(src, "rb") as f:
+            data = f.read()
+    with open(dst, "wb") as raw, gzip.GzipFile(filename="", fileobj=raw, mode="wb", mtime=0) as z:
+        z.write(data)
+
+
+def make_alpha(tmp):
+    """se_alpha / pe_alpha: the letter classes of tests/alphabet_lib.py against the existing g.ufi, `-threads 1`; every file .gz"""
+    import alphabet_lib as al
+    with gzip.open(os.path.join(HERE, "g.ufi.gz"), "rb") as z, open(os.path.join(tmp, "g.ufi"), "wb") as f:
+        f.write(z.read())
+    store = al.Store(ol.Index.load(os.path.join(tmp, "g.ufi")), os.path.join(HERE, "g.fa"))
+    reads, _ = al.make_reads(31, store, 560, read_len=150)
+    synth.write_fastq(os.path.join(tmp, "se_alpha.fq"), reads)
+    _gz(os.path.join(tmp, "se_alpha.fq"), os.path.join(HERE, "se_alpha.fq.gz"))
+    ol.run_ref(["-map", "se_alpha.fq", "-ufi", "g.ufi", "-samout", "se_alpha.sam", "-threads", "1"], cwd=tmp)
+    _gz(None, os.path.join(HERE, "se_alpha.sam.gz"), b"\n".join(ol.sam_records(os.path.join(tmp, "se_alpha.sam"))) + b"\n")
+    r1, r2, _, _ = al.make_pairs(32, store, 300, read_len=150)
+    name = "pe_alpha"
+    synth.write_fastq(os.path.join(tmp, name + "_1.fq"), r1)
+    synth.write_fastq(os.path.join(tmp, name + "_2.fq"), r2)
+    for suf in ("_1.fq", "_2.fq"):
+        _gz(os.path.join(tmp, name + suf), os.path.join(HERE, name + suf + ".gz"))
+    ol.run_ref(["-map2", name + "_1.fq", "-reverse", name + "_2.fq", "-ufi", "g.ufi", "-samout", name + ".sam",
+                "-tabbedout", name + ".tab", "-threads", "1"], cwd=tmp)
+    _gz(None, os.path.join(HERE, name + ".sam.gz"), b"\n".join(ol.sam_records(os.path.join(tmp, name + ".sam"))) + b"\n")
+    _gz(os.path.join(tmp, name + ".tab"), os.path.join(HERE, name + ".tab.gz"))
 
 
 HITSTATS_CASES = [  # (key, mode, read set, index, extra options)
@@ -190,6 +225,7 @@ def main():
         with open(os.path.join(HERE, name + ".sam"), "wb") as f:
             f.write(b"\n".join(ol.sam_records(os.path.join(tmp, name + ".sam"))) + b"\n")
         shutil.copy(os.path.join(tmp, name + ".tab"), os.path.join(HERE, name + ".tab"))
+    make_alpha(tmp)
     make_repeat_set(tmp)
     make_hitstats(tmp)
     make_ufi_opts(tmp)
@@ -202,6 +238,11 @@ if __name__ == "__main__":
         _tmp = os.path.join(HERE, "_tmp")
         os.makedirs(_tmp, exist_ok=True)
         make_hitstats(_tmp)
+        shutil.rmtree(_tmp)
+    elif sys.argv[1:] == ["alpha"]:
+        _tmp = os.path.join(HERE, "_tmp")
+        os.makedirs(_tmp, exist_ok=True)
+        make_alpha(_tmp)
         shutil.rmtree(_tmp)
     elif sys.argv[1:] == ["ufiopts"]:
         _tmp = os.path.join(HERE, "_tmp")

@@ -223,3 +223,133 @@ def test_oracle_long_pairs_equal_reference_binary(tmp_path, seed, rl, sub):
     idx = ol.Index.load(os.path.join(d, "o.ufi"))
     idx.map_file_pe(os.path.join(d, "p1.fq"), os.path.join(d, "p2.fq"), os.path.join(d, "o.sam"), threads=4)
     assert ol.digest(b"\n".join(read_records(os.path.join(d, "o.sam")))) == want["sam"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# letter classes (tests/alphabet_lib.py): N at the ends and in runs, lower case, IUPAC, U / u, letters without a complement,
+# reads that keep the store's N -- in single reads and, independently, in both mates of a pair
+# ---------------------------------------------------------------------------------------------------------------------------
+def _alpha_golden_sets(gold_ufi):
+    """the generator's output for the golden sets again (it is a pure function of the seed), with the tags"""
+    import alphabet_lib as al
+    store = al.Store(ol.Index.load(gold_ufi), os.path.join(GOLD, "g.fa"))
+    reads, tags = al.make_reads(31, store, 560, read_len=150)
+    r1, r2, t1, t2 = al.make_pairs(32, store, 300, read_len=150)
+    return reads, tags, r1, r2, t1, t2
+
+
+def _alpha(name, tmp_path=None):
+    """an alpha fixture (kept .gz): its bytes, or -- with tmp_path -- the path of an unpacked copy"""
+    with gzip.open(os.path.join(GOLD, name + ".gz"), "rb") as z:
+        data = z.read()
+    if tmp_path is None:
+        return data
+    p = os.path.join(tmp_path, name)
+    with open(p, "wb") as f:
+        f.write(data)
+    return p
+
+
+def _fastq_bytes(reads):
+    return b"".join(b"@" + lab.encode() + b"\n" + s.tobytes() + b"\n+\n" + q.tobytes() + b"\n" for lab, s, q in reads)
+
+
+def test_oracle_alpha_sam_equals_reference_golden(gold_ufi, tmp_path):
+    """se_alpha: 560 reads, 40 of each letter class.  The oracle's SAM is the reference's, byte for byte; every class that can map
+    has at least 20 mapped reads in the oracle's results (the oracle reaches: see the assertion message of check_classes)."""
+    import alphabet_lib as al
+    from conftest import reads_to_arrays
+    reads, tags = _alpha_golden_sets(gold_ufi)[:2]
+    assert _fastq_bytes(reads) == _alpha("se_alpha.fq")  # the tags belong to the file's reads
+    idx = ol.Index.load(gold_ufi)
+    out = os.path.join(tmp_path, "o.sam")
+    idx.map_file_se(_alpha("se_alpha.fq", tmp_path), out, threads=2)
+    assert read_records(out) == [l for l in _alpha("se_alpha.sam").split(b"\n") if l]
+    bases, offs = reads_to_arrays(reads)
+    ores, _, _ = idx.map_se(bases, offs)
+    cc = al.check_classes(tags, ores, np.diff(offs.astype(np.int64)), min_exact=1)  # 40 case_kept reads on a 40 kbp genome
+    print("se_alpha (reads, mapped) per class:", cc)
+    assert {t["kind"] for t in tags} == set(al.KINDS)
+
+
+def test_oracle_alpha_pairs_equal_reference_golden(gold_ufi, tmp_path):
+    """pe_alpha: 300 pairs, the class of each mate drawn on its own.  SAM and -tabbedout lines of the oracle are the reference's,
+    byte for byte; all nine (plain, four-plane, other)^2 mate combinations occur at least 10 times and at least 30 proper pairs have
+    a mate 2 that is not plain."""
+    import alphabet_lib as al
+    from conftest import reads_to_arrays
+    _, _, r1, r2, t1, t2 = _alpha_golden_sets(gold_ufi)
+    assert _fastq_bytes(r1) == _alpha("pe_alpha_1.fq")
+    assert _fastq_bytes(r2) == _alpha("pe_alpha_2.fq")
+    idx = ol.Index.load(gold_ufi)
+    sam, tab = os.path.join(tmp_path, "o.sam"), os.path.join(tmp_path, "o.tab")
+    idx.map_file_pe_tab(_alpha("pe_alpha_1.fq", tmp_path), _alpha("pe_alpha_2.fq", tmp_path), sam, tab, threads=2)
+    assert _file_bytes(tab) == _alpha("pe_alpha.tab")
+    assert ol.sam_records(sam) == [l for l in _alpha("pe_alpha.sam").split(b"\n") if l]
+    combos, proper = al.check_pair_kinds(t1, t2, _alpha("pe_alpha.sam"))
+    bases, offs = reads_to_arrays([x for ab in zip(r1, r2) for x in ab])
+    ores, _, _ = idx.map_pe(bases, offs)
+    cc = al.check_classes([x for ab in zip(t1, t2) for x in ab], ores, np.diff(offs.astype(np.int64)), min_exact=1)
+    print("pe_alpha pairs per (kind of mate 1, kind of mate 2):", combos, "proper pairs with a non-plain mate 2:", proper)
+    print("pe_alpha (mates, mapped) per class:", cc)
+
+
+@pytest.mark.parametrize("veryfast", [False, True])
+def test_oracle_alphabet_equals_reference_binary(tmp_path, veryfast):
+    """A fresh genome with soft-masked stretches and N runs, 2 800 single reads and 1 500 pairs in the letter classes, default and
+    -veryfast (on a MaxIx 3 index): oracle vs reference SAM (the reference's outputs as recorded in tests/golden/ref_runs.json
+    when its binary is not built).  Then the same index with the FASTA's case put back into its sequence store
+    (alphabet_lib.soft_masked_index), where reads that keep the store's case have to match lower case against lower case: the
+    reference binary takes that .ufi as it is."""
+    import alphabet_lib as al
+    from urmap_amd import synth
+    d = str(tmp_path)
+    g = synth.make_genome(51, [200000, 90000, 30000], repeat_frac=0.4, n_families=10, n_run_frac=0.02)
+    fa = os.path.join(d, "g.fa")
+    synth.write_fasta(fa, g, lowercase_frac=0.06, seed=5)
+    vf = ["-veryfast"] if veryfast else []
+    slots = 524309
+    idx = ol.Index.build(fa, slots, max_ix=3 if veryfast else 32)
+    idx.save(os.path.join(d, "o.ufi"))
+    soft = al.soft_masked_index(idx, fa)
+    soft.save(os.path.join(d, "soft.ufi"))
+    inputs = {}
+    for name, oi in (("hard", idx), ("soft", soft)):
+        store = al.Store(oi, fa)
+        reads, tags = al.make_reads(52, store, 2800, read_len=150, sub=0.02, indel=0.002)
+        r1, r2, t1, t2 = al.make_pairs(53, store, 1500, read_len=125, sub1=0.02, sub2=0.04, indel=0.002)
+        synth.write_fastq(os.path.join(d, name + "_r.fq"), reads)
+        synth.write_fastq(os.path.join(d, name + "_1.fq"), r1)
+        synth.write_fastq(os.path.join(d, name + "_2.fq"), r2)
+        inputs[name] = (reads, tags, r1, r2, t1, t2)
+
+    def reference():
+        ol.run_ref(["-make_ufi", "g.fa", "-output", "g.ufi", "-slots", str(slots)] + vf, cwd=d)
+        out = {"ufi": _file_bytes(os.path.join(d, "g.ufi"))}
+        for name, ufi in (("hard", "g.ufi"), ("soft", "soft.ufi")):
+            ol.run_ref(["-map", name + "_r.fq", "-ufi", ufi, "-samout", name + ".sam", "-threads", "1"] + vf, cwd=d)
+            ol.run_ref(["-map2", name + "_1.fq", "-reverse", name + "_2.fq", "-ufi", ufi, "-samout", name + "_pe.sam", "-tabbedout",
+                        name + "_pe.tab", "-threads", "1"] + vf, cwd=d)
+            out[name + "_sam"] = b"\n".join(read_records(os.path.join(d, name + ".sam")))
+            out[name + "_pe_sam"] = b"\n".join(read_records(os.path.join(d, name + "_pe.sam")))
+            out[name + "_pe_tab"] = _file_bytes(os.path.join(d, name + "_pe.tab"))
+        return out
+    want = ol.reference_outputs(f"oracle_alphabet_equals_reference_binary[{'veryfast' if veryfast else 'default'}]", reference)
+    assert ol.digest(_file_bytes(os.path.join(d, "o.ufi"))) == want["ufi"]
+    from conftest import reads_to_arrays
+    for name, oi in (("hard", idx), ("soft", soft)):
+        reads, tags, r1, r2, t1, t2 = inputs[name]
+        osam, opsam, otab = (os.path.join(d, name + x) for x in ("_o.sam", "_ope.sam", "_ope.tab"))
+        oi.map_file_se(os.path.join(d, name + "_r.fq"), osam, method=7 if veryfast else 6, threads=4)
+        assert ol.digest(b"\n".join(read_records(osam))) == want[name + "_sam"], name
+        oi.map_file_pe_tab(os.path.join(d, name + "_1.fq"), os.path.join(d, name + "_2.fq"), opsam, otab, threads=4, veryfast=veryfast)
+        assert ol.digest(b"\n".join(read_records(opsam))) == want[name + "_pe_sam"], name
+        assert ol.digest(_file_bytes(otab)) == want[name + "_pe_tab"], name
+        bases, offs = reads_to_arrays(reads)
+        ores, _, _ = oi.map_se(bases, offs, method=7 if veryfast else 6, threads=4)
+        cc = al.check_classes(tags, ores, np.diff(offs.astype(np.int64)))
+        combos, proper = al.check_pair_kinds(t1, t2, _file_bytes(opsam))
+        print(name, "veryfast" if veryfast else "default", "(reads, mapped) per class:", cc, "pairs per kind combination:", combos,
+              "proper pairs with a non-plain mate 2:", proper)
+        if name == "soft":  # lower case has to match lower case here
+            assert sum(1 for t in tags if t["cls"] == "case_kept" and t["lower"] and t["kind"] == "four") >= 20

@@ -627,7 +627,7 @@ __device__ __forceinline__ void viterbi_pair_rows(VFlank &a, VFlank &b) {
 			if (k < n) {  // wave-uniform
 				// rows a problem does not have any more (or that lie behind its abort) change nothing in its half
 				const uint32_t rowm = ((liveA && i0 + k < LAa) ? 0x0000FFFFu : 0u) | ((liveB && i0 + k < LAb) ? 0xFFFF0000u : 0u);
-				const vshort2 jv = pk_s2(j0 + (uint32_t)k * 0x00010001u);
+				const vshort2 jv = pk_s2(j0) + (vshort2)((short)k);  // per half: a 32-bit add carries into the other problem's column when the low half's goes from -1 to 0
 				const uint32_t ge0 = ~pk_ltm(jv, (vshort2)((short)0));
 				const uint32_t actm = realm & ge0 & pk_ltm(jv, LB2) & rowm;
 				const uint32_t semim = semil & pk_zerom(pk_u(jv) ^ pk_u(LB2)) & rowm;
