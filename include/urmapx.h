@@ -405,6 +405,12 @@ typedef struct urmapx_map_options {
 	                     * run removes the shard files it wrote */
 	int discard_sam;    /* measurement: the SAM text is made and copied to the host, then dropped instead of written (report.medium
 	                     * "discarded"): what the device lanes sustain when the output medium is not in the way */
+	int bgzf;           /* -bgzf: samout is a BGZF file (see "BGZF output" below): the header and every chunk's text as gzip members of their
+	                     * own, deflated on the device for the chunks the device formats and by urmapx_bgzf_compress_host for the others, the
+	                     * end-of-file member last.  With sam_shards every shard is such a file.  0: plain text, whatever samout is called.
+	                     * Text from the device is cut every 65 280 bytes within a chunk.  Text the host formats (-host, chunks handed back)
+	                     * is compressed per host thread, each thread's share of a batch as members of its own: valid BGZF that inflates to
+	                     * the same text, but there the members' cuts, the file's bytes and its size depend on host_threads */
 } urmapx_map_options;
 typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:593-632) and where the time went */
 	uint64_t reads, mapped_q, mapped_lowq, unmapped, unsupported;
@@ -431,6 +437,7 @@ typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:59
 	double alloc_dev_s, alloc_pinned_s;              /* seconds all threads of the call spent in hipMalloc / hipFree of the lanes' device arrays, and in
 	                                                  * hipHostMalloc / hipHostFree of page-locked chunk buffers (kept for the next call: 0 calls when warm) */
 	uint32_t alloc_dev_calls, alloc_pinned_calls;
+	uint64_t sam_text_bytes, sam_file_bytes;         /* SAM text made (header included), bytes written to samout: equal unless bgzf */
 } urmapx_map_report;
 /* fastq2 NULL: single-end (-map); else the mates' file (-map2 ... -reverse).  samout / tabout may be NULL.  The index
  * needs its host arrays, or to be resident on first_gpu already (the other devices' replicas are then copied from there).  Batch b is mapped on device
@@ -474,6 +481,7 @@ typedef struct urmapx_text_report {
 	float ms_h2d, ms_parse, ms_map, ms_format, ms_d2h;     /* the chunk on its stream, by events: copy in, parse, map, SAM text, copy out */
 	float ms_map_search, ms_map_dp;                        /* of ms_map (single-end): the search launch; phase 6's dp + finalize launches */
 	float ms_map_enqueue;                                  /* host time spent enqueueing the mapping launches (no wait inside: all of it is the calling thread) */
+	uint64_t sam_text_bytes;                               /* bytes of SAM text made; differs from sam_bytes only under urmapx_text_set_bgzf */
 } urmapx_text_report;
 /* One per mapping context; calls on it run on the context's stream (one thread at a time per context). */
 int urmapx_text_create(urmapx_ctx *, urmapx_text **out);
@@ -495,6 +503,15 @@ int urmapx_text_map_pe(urmapx_text *, const char *fastq1, size_t fastq1_bytes, c
  * Round 5: a lane of urmapx_map_files runs this way (the reference has no counterpart: its threads write records as they finish). */
 int urmapx_text_set_deferred(urmapx_text *, int on);
 int urmapx_text_wait(urmapx_text *, urmapx_text_report *report);
+/* on != 0: the chunk's text is deflated on the device (urmapx_bgzf_compress_device on the context's stream, behind the kernel that
+ * writes the text) and `sam` receives whole BGZF members, no end-of-file member: a chunk is not the end of a file.  report.sam_bytes
+ * is then the compressed size, report.sam_text_bytes the text's, ms_format includes the compressor.  `sam` must hold
+ * urmapx_bgzf_bound(text bytes) - 28: a smaller one gives URMAPX_TEXT_SAM_CAP with that number in sam_bytes, as for plain text.
+ * Where the wait sits: the compressed size exists only once the compressor has run, so urmapx_text_map_se / _pe / _fetch_sam wait on the
+ * context's stream for it (one 8-byte copy behind the compress launch) and only then enqueue the copy of exactly that many bytes -- on
+ * the second stream when deferred, so the PCIe transfer still overlaps the next chunk; what no longer overlaps it is the text kernel and
+ * the compressor of this chunk.  URMAPX_E_ARG while a chunk is in flight or waiting to be fetched. */
+int urmapx_text_set_bgzf(urmapx_text *, int on);
 /* After URMAPX_TEXT_SAM_CAP: the text of the chunk just mapped into a buffer of at least report.sam_bytes (the search is
  * not run again).  URMAPX_E_ARG if no such chunk is waiting. */
 int urmapx_text_fetch_sam(urmapx_text *, char *sam, size_t sam_cap, urmapx_text_report *report);
@@ -532,6 +549,28 @@ int urmapx_gunzip_file(const char *gz_path, const char *out_path, int threads, u
 /* Which of the reader's vector paths this host runs: bit 0 = symbols to bytes 32 at a time (AVX2), bit 1 = CRC-32 by carry-less
  * multiplication (PCLMULQDQ; set only after the routine has reproduced zlib's crc32 on its self-test).  URMAPX_PGZIP_NO_SIMD=1: neither. */
 int urmapx_pgzip_simd(void);
+
+/* ---- BGZF output (-bgzf): gzip members of at most 65 280 bytes of text, each with the 'BC' extra field that holds its size ----
+ * What bgzip / htslib write and `gzip -dc`, Python's gzip, samtools and bgzip -d read.  The input is cut every 65 280 bytes wherever
+ * that falls; every piece becomes one member (18 bytes of header, one deflate block, CRC-32, ISIZE); with_eof appends htslib's 28-byte
+ * empty member.  A piece that would not shrink is a stored block, so a member is at most its text + 31 bytes.
+ * urmapx_bgzf_bound(n): the most n bytes can become, end-of-file member included. */
+size_t urmapx_bgzf_bound(size_t n);
+/* zlib's deflate (level 1) inside that framing, on the calling thread, no device.  URMAPX_E_ARG: cap < urmapx_bgzf_bound(n). */
+int urmapx_bgzf_compress_host(const void *in, size_t n, void *out, size_t cap, size_t *used, int with_eof);
+/* The device compressor (bgzf_gpu.hip): LZ77 matches within the piece (hash of 4 bytes, greedy), per-piece dynamic Huffman codes,
+ * CRC-32 on the device; one workgroup per piece.  The same input gives the same bytes on every run.  Host arrays, synchronous.
+ * URMAPX_E_NODEVICE without a usable device.  _timed: *ms = the compress launches alone, by events. */
+int urmapx_bgzf_compress(int device, const void *in, size_t n, void *out, size_t cap, size_t *used, int with_eof);
+int urmapx_bgzf_compress_timed(int device, const void *in, size_t n, void *out, size_t cap, size_t *used, int with_eof, float *ms);
+/* The same with everything resident in the HBM of `device`, asynchronous on the stream the compressor was created with (a hipStream_t;
+ * NULL: the default stream): d_in[n] -> d_out[out_cap >= urmapx_bgzf_bound(n)], the size to *d_used (device memory).  The compressor
+ * object owns the launch's scratch (a staging slot per piece, 1024 token arenas of 255 KiB): one per stream, one call at a time. */
+typedef struct urmapx_bgzf urmapx_bgzf;
+int urmapx_bgzf_create(int device, void *stream, urmapx_bgzf **out);
+void urmapx_bgzf_destroy(urmapx_bgzf *);
+int urmapx_bgzf_compress_device(int device, const void *d_in, size_t n, void *d_out, size_t out_cap, uint64_t *d_used, int with_eof,
+                                urmapx_bgzf *);
 
 const char *urmapx_strerror(int code);
 /* "gfx950" etc. of the ctx's device; NULL without a device */

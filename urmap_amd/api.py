@@ -39,6 +39,8 @@ EXPORTS = (
     "urmapx_bitvec_word_length", "urmapx_bitvec_bytes", "urmapx_bitvec_popcount", "urmapx_bitvec_search", "urmapx_bitvec_search_device",
     "urmapx_bitvec_sync", "urmapx_bitvec_last_ms", "urmapx_bitvec_close", "urmapx_make_bitvec", "urmapx_search_bitvec_files",
     "urmapx_index_stats", "urmapx_index_slot_counts", "urmapx_ufi_info",
+    "urmapx_bgzf_bound", "urmapx_bgzf_compress_host", "urmapx_bgzf_compress", "urmapx_bgzf_compress_timed", "urmapx_bgzf_create",
+    "urmapx_bgzf_destroy", "urmapx_bgzf_compress_device", "urmapx_text_set_bgzf",
 )
 
 BV_MAGIC = 0x42563130
@@ -61,7 +63,7 @@ class Params(C.Structure):
 
 class MapOptions(C.Structure):
     _fields_ = [("first_gpu", C.c_int), ("gpus", C.c_int), ("streams", C.c_int), ("host_threads", C.c_int), ("batch", C.c_uint32),
-                ("veryfast", C.c_int), ("minq", C.c_uint), ("cmdline", C.c_char_p), ("sam_shards", C.c_int), ("discard_sam", C.c_int)]
+                ("veryfast", C.c_int), ("minq", C.c_uint), ("cmdline", C.c_char_p), ("sam_shards", C.c_int), ("discard_sam", C.c_int), ("bgzf", C.c_int)]
 
 
 class MapReport(C.Structure):
@@ -72,7 +74,8 @@ class MapReport(C.Structure):
                 ("dev_h2d_s", C.c_double), ("dev_parse_s", C.c_double), ("dev_map_s", C.c_double), ("dev_format_s", C.c_double),
                 ("dev_d2h_s", C.c_double), ("shards", C.c_int), ("placement", C.c_char * 256), ("shard_scan_s", C.c_double),
                 ("dev_map_search_s", C.c_double), ("dev_map_dp_s", C.c_double), ("map_enqueue_s", C.c_double),
-                ("alloc_dev_s", C.c_double), ("alloc_pinned_s", C.c_double), ("alloc_dev_calls", C.c_uint32), ("alloc_pinned_calls", C.c_uint32)]
+                ("alloc_dev_s", C.c_double), ("alloc_pinned_s", C.c_double), ("alloc_dev_calls", C.c_uint32), ("alloc_pinned_calls", C.c_uint32),
+                ("sam_text_bytes", C.c_uint64), ("sam_file_bytes", C.c_uint64)]
 
 
 class ValidateReport(C.Structure):
@@ -94,7 +97,7 @@ class TextReport(C.Structure):
     _fields_ = [("records", C.c_uint32), ("reason", C.c_uint32), ("sam_bytes", C.c_uint64), ("mapped_q", C.c_uint64),
                 ("mapped_lowq", C.c_uint64), ("unmapped", C.c_uint64), ("unsupported", C.c_uint64),
                 ("ms_h2d", C.c_float), ("ms_parse", C.c_float), ("ms_map", C.c_float), ("ms_format", C.c_float), ("ms_d2h", C.c_float),
-                ("ms_map_search", C.c_float), ("ms_map_dp", C.c_float), ("ms_map_enqueue", C.c_float)]
+                ("ms_map_search", C.c_float), ("ms_map_dp", C.c_float), ("ms_map_enqueue", C.c_float), ("sam_text_bytes", C.c_uint64)]
 
 
 TEXT_OK, TEXT_CR, TEXT_RAGGED, TEXT_BAD_RECORD, TEXT_LONG_NAME, TEXT_SAM_CAP, TEXT_TOO_LARGE, TEXT_UNEQUAL, TEXT_INTERNAL, TEXT_DEFERRED = range(10)
@@ -477,11 +480,11 @@ def gunzip_file(gz_path, out_path, threads=0):
 
 
 def map_files(index: "Index", fastq1, fastq2=None, samout=None, tabout=None, first_gpu=0, gpus=1, streams=2, host_threads=0,
-              batch=0, veryfast=False, minq=10, cmdline=None, allow_unsupported=False, sam_shards=0, discard_sam=False):
+              batch=0, veryfast=False, minq=10, cmdline=None, allow_unsupported=False, sam_shards=0, discard_sam=False, bgzf=False):
     """urmap -map / -map2 file to file (cmd_map / cmd_map2) on an index that has its host arrays or is resident on
-    first_gpu.  -> dict of State1::HitStats' counters and stage times."""
+    first_gpu.  bgzf: samout is a BGZF file (-bgzf).  -> dict of State1::HitStats' counters and stage times."""
     o = MapOptions(first_gpu, gpus, streams, host_threads, batch, int(veryfast), minq, cmdline.encode() if cmdline else None,
-                   int(sam_shards), int(discard_sam))
+                   int(sam_shards), int(discard_sam), int(bgzf))
     rep = MapReport()
     err = C.create_string_buffer(1024)
     enc = lambda p: os.fsencode(p) if p else None
@@ -489,6 +492,46 @@ def map_files(index: "Index", fastq1, fastq2=None, samout=None, tabout=None, fir
     if rc != 0 and not (rc == E_UNSUPPORTED and allow_unsupported):
         raise UrmapxError(rc, "urmapx_map_files: " + err.value.decode("latin-1"))
     return {k: getattr(rep, k) for k, _ in MapReport._fields_}
+
+
+BGZF_PIECE = 65280
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def bgzf_bound(n):
+    """the most n bytes of text can become as BGZF, end-of-file member included"""
+    L = lib()
+    L.urmapx_bgzf_bound.restype = C.c_size_t
+    L.urmapx_bgzf_bound.argtypes = [C.c_size_t]
+    return int(L.urmapx_bgzf_bound(int(n)))
+
+
+def _bgzf(fn_name, head, data, eof, cap, tail=()):
+    src = np.frombuffer(bytes(data), dtype=np.uint8)
+    cap = bgzf_bound(len(src)) if cap is None else int(cap)
+    out = np.empty(max(1, cap), dtype=np.uint8)
+    used = C.c_size_t()
+    fn = getattr(lib(), fn_name)
+    fn.argtypes = [C.c_int] * len(head) + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int] + [C.c_void_p] * len(tail)
+    _check(fn(*head, src.ctypes.data if len(src) else None, len(src), out.ctypes.data, cap, C.byref(used), int(bool(eof)), *tail), fn_name)
+    return out[: used.value].tobytes()
+
+
+def bgzf_compress_host(data, eof=True, cap=None):
+    """bytes -> BGZF (zlib inside the framing, on the host, no device)"""
+    return _bgzf("urmapx_bgzf_compress_host", (), data, eof, cap)
+
+
+def bgzf_compress(data, device=0, eof=True, cap=None):
+    """bytes -> BGZF, deflated on the device (bgzf_gpu.hip)"""
+    return _bgzf("urmapx_bgzf_compress", (int(device),), data, eof, cap)
+
+
+def bgzf_compress_timed(data, device=0, eof=True):
+    """-> (BGZF bytes, ms of the compress launches alone, by events)"""
+    ms = C.c_float()
+    out = _bgzf("urmapx_bgzf_compress_timed", (int(device),), data, eof, None, (C.cast(C.byref(ms), C.c_void_p),))
+    return out, float(ms.value)
 
 
 def _seq_arrays(seqs):
@@ -782,6 +825,17 @@ class Mapper:
                                           nops.ctypes.data), "urmapx_viterbi_batch")
         paths = [decode_path(ops[i * MAX_PATH_OPS: i * MAX_PATH_OPS + int(nops[i])]) for i in range(n)]
         return scores, status, paths
+
+    def set_bgzf(self, on=True):
+        """The text stage of this mapper delivers each chunk's SAM text as BGZF members (urmapx_text_set_bgzf): report['sam_bytes'] is
+        the compressed size, report['sam_text_bytes'] the text's."""
+        if self._text is None:
+            t = C.c_void_p()
+            _check(lib().urmapx_text_create(self.h, C.byref(t)), "urmapx_text_create")
+            self._text = t
+        L = lib()
+        L.urmapx_text_set_bgzf.argtypes = [C.c_void_p, C.c_int]
+        _check(L.urmapx_text_set_bgzf(self._text, int(bool(on))), "urmapx_text_set_bgzf")
 
     def map_text_se(self, fastq: bytes, minq=10, sam_cap=None):
         """A chunk of FASTQ text (cut after a record's last newline) -> (the SAM text of its records | None, report dict).

@@ -935,3 +935,51 @@ extern "C" int urmapx_pgzip_simd(void) {
 	(void)urx::crc32_of((const uint8_t *)"", 0);  // (runs the self-check)
 	return (urx::cpu_has("avx2") && !getenv("URMAPX_PGZIP_NO_SIMD") ? 1 : 0) | (urx::g_crc_pclmul == 1 ? 2 : 0);
 }
+
+// ---- BGZF output on the host (include/urmapx.h): the framing of bgzf_gpu.hip with zlib's deflate inside ----
+namespace {
+constexpr size_t kBgzfPiece = 65280;
+const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+void put_le(uint8_t *p, uint32_t v, int bytes) {
+	for (int k = 0; k < bytes; ++k) p[k] = (uint8_t)(v >> (8 * k));
+}
+}  // namespace
+
+extern "C" size_t urmapx_bgzf_bound(size_t n) { return n + 31 * ((n + kBgzfPiece - 1) / kBgzfPiece) + 28; }
+
+extern "C" int urmapx_bgzf_compress_host(const void *in, size_t n, void *out, size_t cap, size_t *used, int with_eof) {
+	if (!out || !used || (n && !in)) return URMAPX_E_ARG;
+	if (cap < urmapx_bgzf_bound(n)) return URMAPX_E_ARG;
+	const uint8_t *src = (const uint8_t *)in;
+	uint8_t *dst = (uint8_t *)out;
+	size_t at = 0;
+	z_stream z;
+	memset(&z, 0, sizeof z);
+	if (n && deflateInit2(&z, 1, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return URMAPX_E_NOMEM;
+	for (size_t off = 0; off < n; off += kBgzfPiece) {
+		const uint32_t k = (uint32_t)std::min(kBgzfPiece, n - off);
+		uint8_t *m = dst + at;
+		const uint8_t head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+		memcpy(m, head, 16);
+		// a deflate stream that is not shorter than a stored block (5 bytes + the text) is replaced by one
+		deflateReset(&z);
+		z.next_in = const_cast<Bytef *>(src + off); z.avail_in = k;
+		z.next_out = m + 18; z.avail_out = k + 4;
+		size_t body;
+		if (deflate(&z, Z_FINISH) == Z_STREAM_END) body = (size_t)(k + 4) - z.avail_out;
+		else {
+			m[18] = 1;
+			put_le(m + 19, k, 2); put_le(m + 21, ~k, 2);
+			memcpy(m + 23, src + off, k);
+			body = (size_t)k + 5;
+		}
+		put_le(m + 18 + body, urx::crc32_of(src + off, k), 4);
+		put_le(m + 22 + body, k, 4);
+		put_le(m + 16, (uint32_t)(26 + body - 1), 2);
+		at += 26 + body;
+	}
+	if (n) deflateEnd(&z);
+	if (with_eof) { memcpy(dst + at, kBgzfEof, 28); at += 28; }
+	*used = at;
+	return URMAPX_OK;
+}

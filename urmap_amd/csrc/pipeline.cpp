@@ -275,6 +275,18 @@ private:
 	std::atomic<uint64_t> size_{0};
 };
 
+// -bgzf: text replaced by its BGZF members (urmapx_bgzf_compress_host), for what the host formats: the header, the chunks the device
+// parser hands back, the whole -host road
+bool bgzf_members(std::string &text, int with_eof = 0) {
+	std::string z;
+	z.resize(urmapx_bgzf_bound(text.size()));
+	size_t used = 0;
+	if (urmapx_bgzf_compress_host(text.data(), text.size(), &z[0], z.size(), &used, with_eof) != URMAPX_OK) return false;
+	z.resize(used);
+	text.swap(z);
+	return true;
+}
+
 // Page-locked host buffers are kept for the next call of this process (pinning and unpinning a few hundred MB costs tens
 // of milliseconds each way, as much as mapping the chunk that travels in them); urmapx_host_pool_trim() lets go of them.
 class HostPool {
@@ -889,6 +901,8 @@ int map_files_impl(urmapx_index *I, const urmapx_map_options *opt, const InputRa
 	std::string medium_name = "file";
 	const bool have_sam = samout != nullptr;
 	uint64_t sam_off = 0;
+	const bool bgzf = opt->bgzf != 0 && have_sam;
+	std::atomic<uint64_t> sam_text_bytes{0};  // text made; sam_off counts what goes to the file
 	Failure fail;
 	if (samout) {
 		if (opt->discard_sam) sink.open_discard();
@@ -896,6 +910,8 @@ int map_files_impl(urmapx_index *I, const urmapx_map_options *opt, const InputRa
 		if (range.header) {
 			std::string hdr;
 			append_sam_header_text(hdr, I, opt->cmdline);
+			sam_text_bytes += hdr.size();
+			if (bgzf && !bgzf_members(hdr)) { say("out of memory"); release(); return URMAPX_E_NOMEM; }  // (members of its own: the chunks' come from the device)
 			if (!sink.write_at(hdr.data(), hdr.size(), 0, 1)) { say(std::string("Cannot write ") + samout); release(); return URMAPX_E_IO; }
 			sam_off = hdr.size();
 		}
@@ -1320,6 +1336,7 @@ int map_files_impl(urmapx_index *I, const urmapx_map_options *opt, const InputRa
 						if (!sink.write_at(j->out, (size_t)j->rep.sam_bytes, at, write_threads))
 							fail.raise(URMAPX_E_IO, std::string("Error writing ") + samout);
 						sam_off += j->rep.sam_bytes;
+						sam_text_bytes += j->rep.sam_text_bytes;
 						if (ftab && !j->tab.empty() && fwrite(j->tab.data(), 1, j->tab.size(), ftab) != j->tab.size())
 							fail.raise(URMAPX_E_IO, std::string("Error writing ") + tabout);
 						t_write += secs(tw0, now());
@@ -1353,6 +1370,11 @@ int map_files_impl(urmapx_index *I, const urmapx_map_options *opt, const InputRa
 					// The copy back is a stage of its own (urmapx_text_set_deferred): chunk i's text crosses PCIe while the lane's stream takes
 					// chunk i + 1 in and maps it; the lane waits for chunk i's copy when chunk i + 1 has been enqueued to its end.
 					// URMAPX_NO_DEFERRED_COPY=1 (measurement): every chunk is waited for before the next is taken.
+					if (T) {
+						const int brc = urmapx_text_set_bgzf(T, bgzf ? 1 : 0);  // (a lane from the pool keeps what its last run set)
+						if (brc == URMAPX_E_NOMEM) { text_nomem.store(true); T = nullptr; }
+						else if (brc) fail.raise(brc, std::string("urmapx_text_set_bgzf: ") + urmapx_strerror(brc));
+					}
 					const bool defer = T && !getenv("URMAPX_NO_DEFERRED_COPY") && urmapx_text_set_deferred(T, 1) == URMAPX_OK;
 					auto ok_so_far = [](const TextJob &q) { return !q.rc && (q.rep.reason == 0 || q.rep.reason == URMAPX_TEXT_DEFERRED); };
 					auto hand_on = [&](std::unique_ptr<TextJob> &q) {
@@ -1384,7 +1406,8 @@ int map_files_impl(urmapx_index *I, const urmapx_map_options *opt, const InputRa
 								if (!TextJob::grow(j->out, j->out_cap, (size_t)j->rep.sam_bytes + j->rep.sam_bytes / 16 + (1u << 20))) j->rc = URMAPX_E_NOMEM;
 								else j->rc = urmapx_text_fetch_sam(T, j->out, j->out_cap, &j->rep);
 							}
-							if (ok_so_far(*j) && fq_bytes && j->rep.records) sam_per_fastq = (double)j->rep.sam_bytes / (double)fq_bytes;
+							// (under bgzf the buffer takes the worst case of the text, a 2100th more than the text itself)
+							if (ok_so_far(*j) && fq_bytes && j->rep.records) sam_per_fastq = (double)j->rep.sam_text_bytes / (double)fq_bytes * (bgzf ? 1.001 : 1.0);
 							j->tab.clear();
 							if (ok_so_far(*j) && ftab && j->rep.records) {
 								const uint32_t np = j->rep.records / 2;
@@ -1588,6 +1611,8 @@ int map_files_impl(urmapx_index *I, const urmapx_map_options *opt, const InputRa
 					else if (r.mapq >= minq) ++c.accept;
 					else ++c.reject;
 				}
+				sam_text_bytes += out.size();
+				if (bgzf && !bgzf_members(out)) fail.raise(URMAPX_E_NOMEM, "out of memory");
 			}
 			for (const Cnt &c : cnt) { n_accept += c.accept; n_reject += c.reject; n_nohit += c.nohit; n_unsupported += c.unsupported; }
 			n_reads += n;
@@ -1674,6 +1699,12 @@ int map_files_impl(urmapx_index *I, const urmapx_map_options *opt, const InputRa
 		while (recycled.try_pop(j)) j.reset();
 	}
 	}  // host phase
+	if (bgzf && !fail.set.load()) {  // htslib's empty member: the file is complete
+		std::string eof;
+		(void)bgzf_members(eof, 1);
+		if (!sink.write_at(eof.data(), eof.size(), sam_off, 1)) fail.raise(URMAPX_E_IO, std::string("Error writing ") + samout);
+		sam_off += eof.size();
+	}
 	if (have_sam && !sink.finish(sam_off)) fail.raise(URMAPX_E_IO, std::string("Error writing ") + samout);
 	if (ftab) fclose(ftab);
 	const auto t2 = std::chrono::steady_clock::now();
@@ -1693,6 +1724,7 @@ int map_files_impl(urmapx_index *I, const urmapx_map_options *opt, const InputRa
 		report->dev_format_s = dev_ms[3] * 1e-3; report->dev_d2h_s = dev_ms[4] * 1e-3;
 		report->dev_map_search_s = dev_ms[5] * 1e-3; report->dev_map_dp_s = dev_ms[6] * 1e-3; report->map_enqueue_s = dev_ms[7] * 1e-3;
 		report->shards = 1;
+		report->sam_text_bytes = sam_text_bytes.load(); report->sam_file_bytes = have_sam ? sam_off : 0;
 		snprintf(report->placement, sizeof report->placement, "%s", placement.c_str());
 	}
 	if (fail.set.load()) { say(fail.msg); return fail.code; }
@@ -1792,11 +1824,18 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
 	if (fd1 >= 0) close(fd1);
 	if (fd2 >= 0) close(fd2);
 	const double scan_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_scan0).count();
+	// a shard without records: an empty file, under -bgzf the end-of-file member alone (every shard is a complete BGZF file)
+	auto empty_sam = [&](const std::string &path) {
+		FILE *f = fopen(path.c_str(), "wb");
+		if (!f) return;
+		std::string eof;
+		if (opt->bgzf && bgzf_members(eof, 1)) (void)fwrite(eof.data(), 1, eof.size(), f);
+		fclose(f);
+	};
 	auto empty_shards_from = [&](int s0) {
 		for (int s = s0; s < shards; ++s) {
-			FILE *f = fopen((std::string(samout) + "." + std::to_string(s)).c_str(), "wb");
-			if (f) fclose(f);
-			if (tabout) { f = fopen((std::string(tabout) + "." + std::to_string(s)).c_str(), "wb"); if (f) fclose(f); }
+			empty_sam(std::string(samout) + "." + std::to_string(s));
+			if (tabout) { FILE *f = fopen((std::string(tabout) + "." + std::to_string(s)).c_str(), "wb"); if (f) fclose(f); }
 		}
 	};
 	if (!cut) {
@@ -1845,9 +1884,8 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
 			memset(&reps[(size_t)s], 0, sizeof reps[(size_t)s]);
 			const InputRange &r = ranges[(size_t)s];
 			if (r.lo[0] >= r.hi[0]) {  // nothing left for this shard (fewer records than shards)
-				FILE *f = fopen(sam.c_str(), "wb");
-				if (f) fclose(f);
-				if (tabout) { f = fopen(tab.c_str(), "wb"); if (f) fclose(f); }
+				empty_sam(sam);
+				if (tabout) { FILE *f = fopen(tab.c_str(), "wb"); if (f) fclose(f); }
 				return;
 			}
 			rcs[(size_t)s] = map_files_impl(replicas[(size_t)g0], &o, r, fastq1, fastq2, sam.c_str(), tabout ? tab.c_str() : nullptr, &reps[(size_t)s], e, sizeof e);
@@ -1876,6 +1914,7 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
 		for (const urmapx_map_report &r : reps) {
 			report->reads += r.reads; report->mapped_q += r.mapped_q; report->mapped_lowq += r.mapped_lowq; report->unmapped += r.unmapped;
 			report->unsupported += r.unsupported; report->parse_s += r.parse_s; report->gpu_s += r.gpu_s; report->format_s += r.format_s;
+			report->sam_text_bytes += r.sam_text_bytes; report->sam_file_bytes += r.sam_file_bytes;
 			report->write_s += r.write_s; report->lanes += r.lanes; report->host_threads += r.host_threads; report->input_bytes += r.input_bytes;
 			report->dev_h2d_s += r.dev_h2d_s; report->dev_parse_s += r.dev_parse_s; report->dev_map_s += r.dev_map_s;
 			report->dev_format_s += r.dev_format_s; report->dev_d2h_s += r.dev_d2h_s;

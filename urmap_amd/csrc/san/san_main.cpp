@@ -1,7 +1,7 @@
 // san_main.cpp -- driver of the sanitizer builds (make san): the host side of the drop-in path run from the command line, with the
 // device side replaced by san/stub_device.cpp.  tests/test_sanitizers_cpu.py runs it on well-formed and on damaged input; a
 // sanitizer report ends the process with exit code 99 (ASAN_OPTIONS / UBSAN_OPTIONS / TSAN_OPTIONS exitcode, set by the tests).
-//   urmap_san map <fastq1> [-2 fastq2] -o out.sam [-tab out.tab] [-batch N] [-streams K] [-gpus N] [-shards N] [-threads T] [-null]
+//   urmap_san map <fastq1> [-2 fastq2] -o out.sam [-tab out.tab] [-batch N] [-streams K] [-gpus N] [-shards N] [-threads T] [-null] [-bgzf]
 //   urmap_san gunzip <in.gz> <out> [threads]
 //   urmap_san fastq <file> <batch>
 //   urmap_san makeufi <fasta> <out.ufi> <slots>
@@ -32,6 +32,7 @@ static int cmd_map(int argc, char **argv) {
 		else if (a == "-shards") o.sam_shards = atoi(val());
 		else if (a == "-threads") o.host_threads = atoi(val());
 		else if (a == "-null") o.discard_sam = 1;
+		else if (a == "-bgzf") o.bgzf = 1;
 		else return 2;
 	}
 	static const uint32_t lengths[3] = {1000000u, 250000u, 4000000000u};

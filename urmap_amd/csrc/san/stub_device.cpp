@@ -34,7 +34,7 @@ struct urmapx_ctx {
 };
 struct urmapx_text {
 	urmapx_ctx *C = nullptr;
-	bool deferred = false;
+	bool deferred = false, bgzf = false;
 	struct Chunk { std::string text; char *dst; urmapx_text_report rep; };
 	std::deque<Chunk> flying;   // deferred: text made, "copy" not done until urmapx_text_wait
 	std::string waiting;        // after URMAPX_TEXT_SAM_CAP
@@ -210,6 +210,15 @@ void count(urmapx_text_report *rep, const urmapx_result &r, unsigned minq) {
 }
 // hands the text over as the device stage does: at once, later (deferred), or not yet (the caller's buffer is too small)
 int deliver(urmapx_text *T, std::string &&text, char *sam, size_t cap, urmapx_text_report *rep) {
+	rep->sam_text_bytes = text.size();
+	if (T->bgzf) {  // the device compressor's stand-in: the same framing from the host compressor
+		std::string z(urmapx_bgzf_bound(text.size()), 0);
+		size_t used = 0;
+		const int rc = urmapx_bgzf_compress_host(text.data(), text.size(), &z[0], z.size(), &used, 0);
+		if (rc) return rc;
+		z.resize(used);
+		text.swap(z);
+	}
 	rep->sam_bytes = text.size();
 	++T->chunk_nr;
 	const char *force = getenv("URX_STUB_FORCE_SAM_CAP");  // every N-th chunk pretends the buffer was too small
@@ -277,6 +286,11 @@ int urmapx_text_map_pe(urmapx_text *T, const char *fq1, size_t n1, const char *f
 int urmapx_text_set_deferred(urmapx_text *T, int on) {
 	if (!T->flying.empty()) return URMAPX_E_ARG;
 	T->deferred = on != 0;
+	return URMAPX_OK;
+}
+int urmapx_text_set_bgzf(urmapx_text *T, int on) {
+	if (!T->flying.empty() || T->have_waiting) return URMAPX_E_ARG;
+	T->bgzf = on != 0;
 	return URMAPX_OK;
 }
 int urmapx_text_wait(urmapx_text *T, urmapx_text_report *rep) {

@@ -734,6 +734,12 @@ struct urmapx_text {
 	bool pending = false;
 	SamArgs pending_args;
 	urmapx_text_report pending_rep;
+	// urmapx_text_set_bgzf: the text is deflated into zout behind sam_kernel and zout is what crosses PCIe
+	bool bgzf = false;
+	urmapx_bgzf *Z = nullptr;
+	DevBuf<uint8_t> zout;
+	DevBuf<uint64_t> zused;
+	uint64_t *h_zused = nullptr;  // page-locked
 };
 
 namespace {
@@ -793,10 +799,19 @@ int finish_tail(urmapx_text *T, int set, urmapx_text_report *rep) {
 
 int fetch_sam(urmapx_text *T, char *sam, size_t sam_cap, urmapx_text_report *rep) {
 	*rep = T->pending_rep;
+	const uint64_t text_bytes = rep->sam_bytes;
+	rep->sam_text_bytes = text_bytes;
+	const size_t zcap = T->bgzf ? urmapx_bgzf_bound((size_t)text_bytes) - 28 : 0;  // (no end-of-file member behind a chunk)
+	if (T->bgzf) rep->sam_bytes = zcap;
 	if (!sam || rep->sam_bytes > sam_cap) { rep->reason = URMAPX_TEXT_SAM_CAP; rep->records = 0; return URMAPX_OK; }
+	rep->sam_bytes = text_bytes;
 	hipStream_t st = ctx_stream(T->C);
 	int rc;
 	const int set = (int)(T->chunk_no & 1u);
+	if (T->bgzf) {
+		if (T->zout.cap < zcap + 64 && T->waiting) HIP_TRY(hipStreamSynchronize(T->copy_st));
+		if ((rc = T->zout.ensure(zcap + 64))) return rc;
+	}
 	if (T->sam.cap < (size_t)rep->sam_bytes + 64 && T->waiting) HIP_TRY(hipStreamSynchronize(T->copy_st));  // (the array is about to be replaced under a copy)
 	if ((rc = T->sam.ensure((size_t)rep->sam_bytes + 64))) return rc;
 	SamArgs A = T->pending_args;
@@ -806,13 +821,23 @@ int fetch_sam(urmapx_text *T, char *sam, size_t sam_cap, urmapx_text_report *rep
 	hipLaunchKernelGGL(sam_kernel, dim3(GRID), dim3(SAM_WAVES * 64), 0, st, A);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(T->h_hdr + 2 + set, T->hdr.p, sizeof(TextHdr), hipMemcpyDeviceToHost, st));  // (on the main stream: the next chunk clears the header there)
-	if (T->tail_ok) HIP_TRY(hipEventRecord(T->tail_ev[set][1], st));
+	const uint8_t *d_src = T->sam.p;
+	if (T->bgzf) {
+		// the number of bytes to copy back exists only behind the compressor: this is the one place the calling thread waits for it
+		if ((rc = urmapx_bgzf_compress_device(ctx_device(T->C), T->sam.p, (size_t)text_bytes, T->zout.p, T->zout.cap, T->zused.p, 0, T->Z))) return rc;
+		HIP_TRY(hipMemcpyAsync(T->h_zused, T->zused.p, 8, hipMemcpyDeviceToHost, st));
+		if (T->tail_ok) HIP_TRY(hipEventRecord(T->tail_ev[set][1], st));
+		HIP_TRY(hipStreamSynchronize(st));
+		rep->sam_bytes = *T->h_zused;
+		if (rep->sam_bytes > zcap) return URMAPX_E_NODEVICE;  // (never expected: the bound is the compressor's own)
+		d_src = T->zout.p;
+	} else if (T->tail_ok) HIP_TRY(hipEventRecord(T->tail_ev[set][1], st));
 	hipStream_t cs = T->deferred ? T->copy_st : st;
 	if (T->deferred) {
 		if (T->tail_ok) HIP_TRY(hipStreamWaitEvent(cs, T->tail_ev[set][1], 0));
 		else HIP_TRY(hipStreamSynchronize(st));
 	}
-	HIP_TRY(hipMemcpyAsync(sam, T->sam.p, rep->sam_bytes, hipMemcpyDeviceToHost, cs));
+	HIP_TRY(hipMemcpyAsync(sam, d_src, rep->sam_bytes, hipMemcpyDeviceToHost, cs));
 	if (T->tail_ok) HIP_TRY(hipEventRecord(T->tail_ev[set][2], cs));
 	T->tail_rep[set] = *rep;
 	T->pending = false;
@@ -972,6 +997,9 @@ void urmapx_text_destroy(urmapx_text *T) {
 		for (hipEvent_t x : set)
 			if (x) (void)hipEventDestroy(x);
 	for (int k = 0; k < 2; ++k) { T->raw[k].release(); T->tile_counts[k].release(); T->ends[k].release(); T->blen[k].release(); }
+	if (T->Z) urmapx_bgzf_destroy(T->Z);
+	T->zout.release(); T->zused.release();
+	if (T->h_zused) (void)hipHostFree(T->h_zused);
 	T->bases.release(); T->sam.release(); T->comp.release();
 	T->sums.release(); T->lens.release(); T->qn.release(); T->rec_offs.release();
 	T->used.release(); T->tname_offs.release(); T->offs.release(); T->tnames.release(); T->results.release(); T->pathops.release();
@@ -997,6 +1025,19 @@ int urmapx_text_set_deferred(urmapx_text *T, int on) {
 	if (!T || T->waiting || T->pending) return URMAPX_E_ARG;
 	if (on && !T->tail_ok) return URMAPX_E_NODEVICE;  // the second stream is ordered behind the first by events: none, no deferred copies (the caller keeps the plain mode)
 	T->deferred = on != 0;
+	return URMAPX_OK;
+}
+
+int urmapx_text_set_bgzf(urmapx_text *T, int on) {
+	if (!T || T->waiting || T->pending) return URMAPX_E_ARG;
+	if (on && !T->Z) {
+		HIP_TRY(hipSetDevice(ctx_device(T->C)));
+		int rc = T->zused.ensure(1);
+		if (rc) return rc;
+		if (!T->h_zused) HIP_TRY(hipHostMalloc((void **)&T->h_zused, 8, hipHostMallocDefault));
+		if ((rc = urmapx_bgzf_create(ctx_device(T->C), (void *)ctx_stream(T->C), &T->Z))) return rc;
+	}
+	T->bgzf = on != 0;
 	return URMAPX_OK;
 }
 

@@ -59,6 +59,7 @@ using namespace urx;
 struct Opts {
 	std::string map, map2, reverse, make_ufi, ufi, ufi_validate, ufi_stats, ufi_counts, ufi_info, samout, tabbedout, output, log;
 	std::string make_bitvec, search_bitvec, search_bitvec2, input2, ref, output1, output2;
+	bool bgzf = false;  // -bgzf: -samout is a BGZF file, deflated on the device
 	bool veryfast = false, quiet = false, minq_given = false, host_build = false, notrunclabels = false;
 	bool trunclabels = false, wordlength_given = false;
 	double load_factor = 0.6;  // myopts.h: FLT_OPT(load_factor, 0.6, ...)
@@ -100,6 +101,7 @@ static Opts parse(int argc, char **argv) {
 		else if (a == "-samshards") o.samshards = atoi(val());
 		else if (a == "-batch") o.batch = (unsigned)atoi(val());
 		else if (a == "-veryfast") o.veryfast = true;
+		else if (a == "-bgzf") o.bgzf = true;
 		else if (a == "-host") o.host_build = true;
 		else if (a == "-quiet") o.quiet = true;
 		else if (a == "-log") o.log = val();
@@ -192,6 +194,7 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 	mo.sam_shards = o.samshards;  // -samout out.sam -samshards N: out.sam.0 .. out.sam.N-1, `cat` of them = the one file
 	mo.first_gpu = o.gpu; mo.gpus = o.gpus; mo.streams = o.streams; mo.host_threads = (int)o.threads; mo.batch = o.batch;
 	mo.veryfast = o.veryfast ? 1 : 0; mo.minq = o.minq; mo.cmdline = cl.c_str();
+	mo.bgzf = o.bgzf ? 1 : 0;
 	urmapx_map_report rep;
 	memset(&rep, 0, sizeof rep);
 	char err[1024];
@@ -230,6 +233,9 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 		progress_log(q, "%16s  Mapped Q>=%u (%.1f%%)\n", commas(n_accept).c_str(), minq, pct(n_accept));
 		progress_log(q, "%16s  Mapped Q< %u (%.1f%%)\n", commas(n_reject).c_str(), minq, pct(n_reject));
 		progress_log(q, "%16s  Unmapped (%.1f%%)\n\n", commas(n_nohit).c_str(), pct(n_nohit));
+		if (o.bgzf && !o.samout.empty())
+			progress_log(q, "%16s  Bytes of SAM text, %s written as BGZF (%.3f)\n\n", commas(rep.sam_text_bytes).c_str(), commas(rep.sam_file_bytes).c_str(),
+			             rep.sam_text_bytes ? (double)rep.sam_file_bytes / (double)rep.sam_text_bytes : 0.0);
 		if (o.minq_given && !paired) progress_log(q, "\nWARNING: Option -minq not used\n\n");
 	}
 	urmapx_index_close(I);
@@ -530,8 +536,9 @@ int main(int argc, char **argv) {
 	if (!o.ufi_info.empty()) { const int rc = cmd_ufi_info(o); log_close(); return rc; }
 	if (!o.make_bitvec.empty()) { const int rc = cmd_make_bitvec(o); log_close(); return rc; }
 	if (!o.search_bitvec.empty() || !o.search_bitvec2.empty()) { const int rc = cmd_search_bitvec(o); log_close(); return rc; }
-	fprintf(stderr, "urmap (MI355X build)\n  urmap -map reads.fq -ufi index.ufi -samout out.sam [-veryfast] [-gpu D] [-gpus N] [-streams K] [-samshards N]\n"
-	                "  urmap -map2 R1.fq -reverse R2.fq -ufi index.ufi -samout out.sam [-tabbedout out.tab] [-gpu D] [-gpus N]\n"
+	fprintf(stderr, "urmap (MI355X build)\n  urmap -map reads.fq -ufi index.ufi -samout out.sam [-veryfast] [-gpu D] [-gpus N] [-streams K] [-samshards N] [-bgzf]\n"
+	                "  urmap -map2 R1.fq -reverse R2.fq -ufi index.ufi -samout out.sam [-tabbedout out.tab] [-gpu D] [-gpus N] [-bgzf]\n"
+	                "      -bgzf: the file named by -samout is BGZF (gzip members of 64 KB of text, deflated on the GPU); `gzip -dc` gives the SAM text\n"
 	                "  urmap -make_ufi genome.fa -output index.ufi [-slots N] [-wordlength W] [-maxix M]\n"
 	                "  urmap -ufi_validate index.ufi [-gpu D]\n"
 	                "  urmap -ufi_stats index.ufi [-log F] [-gpu D] [-quiet]\n"
