@@ -411,6 +411,11 @@ typedef struct urmapx_map_options {
 	                     * Text from the device is cut every 65 280 bytes within a chunk.  Text the host formats (-host, chunks handed back)
 	                     * is compressed per host thread, each thread's share of a batch as members of its own: valid BGZF that inflates to
 	                     * the same text, but there the members' cuts, the file's bytes and its size depend on host_threads */
+	int bam;            /* -bamout: samout is a BAM file (see "BAM output" below): the header block and every chunk's alignment records inside
+	                     * BGZF members framed as under bgzf (which is implied; setting both is URMAPX_E_ARG), the records encoded on the
+	                     * device for the chunks the device formats and by urmapx_bam_se / _pe for the others.  With sam_shards every shard is
+	                     * a complete BAM file with the header.  A QNAME over 254 bytes does not fit a BAM record: URMAPX_E_FORMAT, the read
+	                     * named in err.  0: SAM */
 } urmapx_map_options;
 typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:593-632) and where the time went */
 	uint64_t reads, mapped_q, mapped_lowq, unmapped, unsupported;
@@ -437,7 +442,7 @@ typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:59
 	double alloc_dev_s, alloc_pinned_s;              /* seconds all threads of the call spent in hipMalloc / hipFree of the lanes' device arrays, and in
 	                                                  * hipHostMalloc / hipHostFree of page-locked chunk buffers (kept for the next call: 0 calls when warm) */
 	uint32_t alloc_dev_calls, alloc_pinned_calls;
-	uint64_t sam_text_bytes, sam_file_bytes;         /* SAM text made (header included), bytes written to samout: equal unless bgzf */
+	uint64_t sam_text_bytes, sam_file_bytes;         /* SAM text (bam: header block and records) made, bytes written to samout: equal unless bgzf / bam */
 } urmapx_map_report;
 /* fastq2 NULL: single-end (-map); else the mates' file (-map2 ... -reverse).  samout / tabout may be NULL.  The index
  * needs its host arrays, or to be resident on first_gpu already (the other devices' replicas are then copied from there).  Batch b is mapped on device
@@ -481,7 +486,8 @@ typedef struct urmapx_text_report {
 	float ms_h2d, ms_parse, ms_map, ms_format, ms_d2h;     /* the chunk on its stream, by events: copy in, parse, map, SAM text, copy out */
 	float ms_map_search, ms_map_dp;                        /* of ms_map (single-end): the search launch; phase 6's dp + finalize launches */
 	float ms_map_enqueue;                                  /* host time spent enqueueing the mapping launches (no wait inside: all of it is the calling thread) */
-	uint64_t sam_text_bytes;                               /* bytes of SAM text made; differs from sam_bytes only under urmapx_text_set_bgzf */
+	uint64_t sam_text_bytes;                               /* bytes of SAM text (urmapx_text_set_bam: of BAM records) made; differs from sam_bytes only
+	                                                        * under urmapx_text_set_bgzf */
 } urmapx_text_report;
 /* One per mapping context; calls on it run on the context's stream (one thread at a time per context). */
 int urmapx_text_create(urmapx_ctx *, urmapx_text **out);
@@ -512,6 +518,12 @@ int urmapx_text_wait(urmapx_text *, urmapx_text_report *report);
  * the second stream when deferred, so the PCIe transfer still overlaps the next chunk; what no longer overlaps it is the text kernel and
  * the compressor of this chunk.  URMAPX_E_ARG while a chunk is in flight or waiting to be fetched. */
 int urmapx_text_set_bgzf(urmapx_text *, int on);
+/* on != 0: the chunk's output is its BAM alignment records (bam_kernel in text_gpu.hip; the layout under "BAM output" below) instead
+ * of SAM text: no header block, records in input order, back to back.  With urmapx_text_set_bgzf off `sam` receives the raw records,
+ * with it on BGZF members of them (a record may span members); report.sam_text_bytes is the uncompressed record bytes either way.
+ * Deferred mode, URMAPX_TEXT_SAM_CAP and urmapx_text_fetch_sam as for text.  A chunk with a QNAME over 254 bytes is handed back
+ * (URMAPX_TEXT_LONG_NAME).  URMAPX_E_ARG while a chunk is in flight or waiting to be fetched. */
+int urmapx_text_set_bam(urmapx_text *, int on);
 /* After URMAPX_TEXT_SAM_CAP: the text of the chunk just mapped into a buffer of at least report.sam_bytes (the search is
  * not run again).  URMAPX_E_ARG if no such chunk is waiting. */
 int urmapx_text_fetch_sam(urmapx_text *, char *sam, size_t sam_cap, urmapx_text_report *report);
@@ -571,6 +583,26 @@ int urmapx_bgzf_create(int device, void *stream, urmapx_bgzf **out);
 void urmapx_bgzf_destroy(urmapx_bgzf *);
 int urmapx_bgzf_compress_device(int device, const void *d_in, size_t n, void *d_out, size_t out_cap, uint64_t *d_used, int with_eof,
                                 urmapx_bgzf *);
+
+/* ---- BAM output (-bamout): SAM/BAM specification v1, section 4 ----
+ * The file is BGZF (above); inside it the header block -- magic "BAM\1", l_text, the header text append_sam_header writes (@SQ lines,
+ * the @PG line), n_ref, (l_name, name\0, l_ref) per sequence of the index in index order -- then one record per read, in input order.
+ * A record carries exactly what the SAM record of the same read carries, field for field: refID / pos (-1 / -1 where the text has
+ * '*' / 0), l_read_name = QNAME + NUL, mapq, bin = reg2bin(pos, pos + the reference bases the CIGAR spans, or pos + 1), the CIGAR runs
+ * after the dangling-M polish as len << 4 | op, flag, l_seq, next_refID / next_pos from RNEXT ('=' is refID) / PNEXT, tlen, SEQ as
+ * printed (reverse-complemented for a minus-strand hit) 4 bits a base through "=ACMGRSVTWYHKDBN" (either case; any other letter 15),
+ * QUAL - 33 (0xFF throughout where the text has '*').  No optional fields: the SAM output has none.
+ * urmapx_bam_header: the uncompressed header block; returns its size and writes it if it fits cap (buf may be NULL to ask). */
+size_t urmapx_bam_header(const urmapx_index *, const char *cmdline, void *buf, size_t cap);
+/* The host encoders, arguments as urmapx_sam_se / _pe: one record, the two records of a pair.  Return the bytes written, 0 if they do
+ * not fit cap, URMAPX_BAM_LONG_NAME if a QNAME is over 254 bytes (l_read_name is one byte; nothing is truncated).  The device encoder
+ * (urmapx_text_set_bam) writes the same bytes for the same read. */
+#define URMAPX_BAM_LONG_NAME ((size_t)-1)
+size_t urmapx_bam_se(const urmapx_index *, const urmapx_result *r, const urmapx_path_op *path_ops, const char *label,
+                     const uint8_t *seq, const uint8_t *qual, uint32_t read_len, char *buf, size_t cap);
+size_t urmapx_bam_pe(const urmapx_index *, const urmapx_result *r1, const urmapx_result *r2, const urmapx_path_op *path_ops,
+                     const char *label1, const uint8_t *seq1, const uint8_t *qual1, uint32_t len1, const char *label2,
+                     const uint8_t *seq2, const uint8_t *qual2, uint32_t len2, char *buf, size_t cap);
 
 const char *urmapx_strerror(int code);
 /* "gfx950" etc. of the ctx's device; NULL without a device */

@@ -41,6 +41,7 @@ EXPORTS = (
     "urmapx_index_stats", "urmapx_index_slot_counts", "urmapx_ufi_info",
     "urmapx_bgzf_bound", "urmapx_bgzf_compress_host", "urmapx_bgzf_compress", "urmapx_bgzf_compress_timed", "urmapx_bgzf_create",
     "urmapx_bgzf_destroy", "urmapx_bgzf_compress_device", "urmapx_text_set_bgzf",
+    "urmapx_text_set_bam", "urmapx_bam_header", "urmapx_bam_se", "urmapx_bam_pe",
 )
 
 BV_MAGIC = 0x42563130
@@ -63,7 +64,8 @@ class Params(C.Structure):
 
 class MapOptions(C.Structure):
     _fields_ = [("first_gpu", C.c_int), ("gpus", C.c_int), ("streams", C.c_int), ("host_threads", C.c_int), ("batch", C.c_uint32),
-                ("veryfast", C.c_int), ("minq", C.c_uint), ("cmdline", C.c_char_p), ("sam_shards", C.c_int), ("discard_sam", C.c_int), ("bgzf", C.c_int)]
+                ("veryfast", C.c_int), ("minq", C.c_uint), ("cmdline", C.c_char_p), ("sam_shards", C.c_int), ("discard_sam", C.c_int), ("bgzf", C.c_int),
+                ("bam", C.c_int)]
 
 
 class MapReport(C.Structure):
@@ -416,6 +418,71 @@ class Index:
             out.append(buf.raw[:n])
         return b"".join(out)
 
+    def bam_header(self, cmdline=None) -> bytes:
+        """The uncompressed header block of a BAM file over this index (urmapx_bam_header): magic, the SAM header text, the references."""
+        L = lib()
+        L.urmapx_bam_header.restype = C.c_size_t
+        L.urmapx_bam_header.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]
+        cl = cmdline.encode() if isinstance(cmdline, str) else cmdline
+        n = L.urmapx_bam_header(self.h, cl, None, 0)
+        buf = C.create_string_buffer(max(1, n))
+        assert L.urmapx_bam_header(self.h, cl, buf, n) == n
+        return buf.raw[:n]
+
+    def _bam_call(self, fn_name, *args):
+        fn = getattr(lib(), fn_name)
+        fn.restype = C.c_size_t
+        cap = 1 << 16
+        while True:
+            buf = C.create_string_buffer(cap)
+            n = fn(*args, buf, C.c_size_t(cap))
+            if n == C.c_size_t(-1).value:
+                raise UrmapxError(-2, f"{fn_name}: a QNAME over 254 bytes does not fit a BAM record")
+            if n:
+                return buf.raw[:n]
+            cap *= 4
+            if cap > 1 << 28:
+                raise UrmapxError(-5, f"{fn_name}: record does not fit")
+
+    def bam_se(self, results: np.ndarray, ops: np.ndarray, labels, bases: np.ndarray, offs: np.ndarray,
+               quals: np.ndarray) -> bytes:
+        """BAM records (urmapx_bam_se) of a mapped batch, in input order: what sam_se prints, in the binary layout.  Host side only.
+        UrmapxError naming the read for a QNAME over 254 bytes."""
+        results = np.ascontiguousarray(results)
+        ops = np.ascontiguousarray(ops, dtype=np.uint16)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        out = []
+        ops_ptr = C.c_void_p(ops.ctypes.data if len(ops) else None)
+        for i in range(len(results)):
+            o, e = int(offs[i]), int(offs[i + 1])
+            try:
+                out.append(self._bam_call("urmapx_bam_se", self.h, C.c_void_p(results[i:i + 1].ctypes.data), ops_ptr, labels[i].encode("latin-1"),
+                                          C.c_void_p(bases[o:e].ctypes.data), C.c_void_p(quals[o:e].ctypes.data), C.c_uint32(e - o)))
+            except UrmapxError as x:
+                raise UrmapxError(x.code, f"{x}: read {labels[i][:60]}...") if x.code == -2 else x
+        return b"".join(out)
+
+    def bam_pe(self, results: np.ndarray, ops: np.ndarray, labels, bases: np.ndarray, offs: np.ndarray,
+               quals: np.ndarray) -> bytes:
+        """BAM records of mapped PAIRS (reads 2i, 2i+1 = mates of pair i; urmapx_bam_pe): what sam_pe prints, in the binary layout."""
+        results = np.ascontiguousarray(results)
+        ops = np.ascontiguousarray(ops, dtype=np.uint16)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        out = []
+        ops_ptr = C.c_void_p(ops.ctypes.data if len(ops) else None)
+        for i in range(0, len(results), 2):
+            o1, e1, e2 = int(offs[i]), int(offs[i + 1]), int(offs[i + 2])
+            try:
+                out.append(self._bam_call("urmapx_bam_pe", self.h, C.c_void_p(results[i:i + 1].ctypes.data), C.c_void_p(results[i + 1:i + 2].ctypes.data),
+                                          ops_ptr, labels[i].encode("latin-1"), C.c_void_p(bases[o1:e1].ctypes.data), C.c_void_p(quals[o1:e1].ctypes.data),
+                                          C.c_uint32(e1 - o1), labels[i + 1].encode("latin-1"), C.c_void_p(bases[e1:e2].ctypes.data),
+                                          C.c_void_p(quals[e1:e2].ctypes.data), C.c_uint32(e2 - e1)))
+            except UrmapxError as x:
+                raise UrmapxError(x.code, f"{x}: pair {labels[i][:60]}...") if x.code == -2 else x
+        return b"".join(out)
+
     def tab_pe(self, res, info, labels, offs, sam_on=True):
         """-tabbedout lines (State2::OutputTab2) for pairs interleaved as in map_pe; labels = per read."""
         L = lib()
@@ -480,11 +547,11 @@ def gunzip_file(gz_path, out_path, threads=0):
 
 
 def map_files(index: "Index", fastq1, fastq2=None, samout=None, tabout=None, first_gpu=0, gpus=1, streams=2, host_threads=0,
-              batch=0, veryfast=False, minq=10, cmdline=None, allow_unsupported=False, sam_shards=0, discard_sam=False, bgzf=False):
+              batch=0, veryfast=False, minq=10, cmdline=None, allow_unsupported=False, sam_shards=0, discard_sam=False, bgzf=False, bam=False):
     """urmap -map / -map2 file to file (cmd_map / cmd_map2) on an index that has its host arrays or is resident on
-    first_gpu.  bgzf: samout is a BGZF file (-bgzf).  -> dict of State1::HitStats' counters and stage times."""
+    first_gpu.  bgzf: samout is a BGZF file (-bgzf).  bam: samout is a BAM file (-bamout).  -> dict of State1::HitStats' counters and stage times."""
     o = MapOptions(first_gpu, gpus, streams, host_threads, batch, int(veryfast), minq, cmdline.encode() if cmdline else None,
-                   int(sam_shards), int(discard_sam), int(bgzf))
+                   int(sam_shards), int(discard_sam), int(bgzf), int(bam))
     rep = MapReport()
     err = C.create_string_buffer(1024)
     enc = lambda p: os.fsencode(p) if p else None
@@ -836,6 +903,17 @@ class Mapper:
         L = lib()
         L.urmapx_text_set_bgzf.argtypes = [C.c_void_p, C.c_int]
         _check(L.urmapx_text_set_bgzf(self._text, int(bool(on))), "urmapx_text_set_bgzf")
+
+    def set_bam(self, on=True):
+        """The text stage of this mapper delivers each chunk's BAM alignment records instead of SAM text (urmapx_text_set_bam): raw
+        records, or BGZF members of them after set_bgzf; report['sam_text_bytes'] is the uncompressed record bytes either way."""
+        if self._text is None:
+            t = C.c_void_p()
+            _check(lib().urmapx_text_create(self.h, C.byref(t)), "urmapx_text_create")
+            self._text = t
+        L = lib()
+        L.urmapx_text_set_bam.argtypes = [C.c_void_p, C.c_int]
+        _check(L.urmapx_text_set_bam(self._text, int(bool(on))), "urmapx_text_set_bam")
 
     def map_text_se(self, fastq: bytes, minq=10, sam_cap=None):
         """A chunk of FASTQ text (cut after a record's last newline) -> (the SAM text of its records | None, report dict).

@@ -277,6 +277,11 @@ private:
 
 // -bgzf: text replaced by its BGZF members (urmapx_bgzf_compress_host), for what the host formats: the header, the chunks the device
 // parser hands back, the whole -host road
+// -bamout: a QNAME that l_read_name cannot hold ends the run (nothing is truncated)
+std::string bam_long_name(const char *label) {
+	return std::string("QNAME longer than 254 bytes does not fit a BAM record, read ") + label;
+}
+
 bool bgzf_members(std::string &text, int with_eof = 0) {
 	std::string z;
 	z.resize(urmapx_bgzf_bound(text.size()));
@@ -901,15 +906,17 @@ int map_files_impl(urmapx_index *I, const urmapx_map_options *opt, const InputRa
 	std::string medium_name = "file";
 	const bool have_sam = samout != nullptr;
 	uint64_t sam_off = 0;
-	const bool bgzf = opt->bgzf != 0 && have_sam;
+	const bool bam = opt->bam != 0 && have_sam;  // -bamout: BAM records where the SAM text was, always inside BGZF members
+	const bool bgzf = (opt->bgzf != 0 || bam) && have_sam;
 	std::atomic<uint64_t> sam_text_bytes{0};  // text made; sam_off counts what goes to the file
 	Failure fail;
 	if (samout) {
 		if (opt->discard_sam) sink.open_discard();
 		else if (!sink.open(samout)) { say(std::string("Cannot create ") + samout); release(); return URMAPX_E_IO; }
-		if (range.header) {
+		if (range.header || bam) {  // (every shard of a BAM run is a BAM file: each has the header block)
 			std::string hdr;
-			append_sam_header_text(hdr, I, opt->cmdline);
+			if (bam) append_bam_header(hdr, I, opt->cmdline);
+			else append_sam_header_text(hdr, I, opt->cmdline);
 			sam_text_bytes += hdr.size();
 			if (bgzf && !bgzf_members(hdr)) { say("out of memory"); release(); return URMAPX_E_NOMEM; }  // (members of its own: the chunks' come from the device)
 			if (!sink.write_at(hdr.data(), hdr.size(), 0, 1)) { say(std::string("Cannot write ") + samout); release(); return URMAPX_E_IO; }
@@ -1372,8 +1379,10 @@ int map_files_impl(urmapx_index *I, const urmapx_map_options *opt, const InputRa
 					// URMAPX_NO_DEFERRED_COPY=1 (measurement): every chunk is waited for before the next is taken.
 					if (T) {
 						const int brc = urmapx_text_set_bgzf(T, bgzf ? 1 : 0);  // (a lane from the pool keeps what its last run set)
+						int brc2 = 0;
 						if (brc == URMAPX_E_NOMEM) { text_nomem.store(true); T = nullptr; }
 						else if (brc) fail.raise(brc, std::string("urmapx_text_set_bgzf: ") + urmapx_strerror(brc));
+						else if ((brc2 = urmapx_text_set_bam(T, bam ? 1 : 0))) fail.raise(brc2, std::string("urmapx_text_set_bam: ") + urmapx_strerror(brc2));
 					}
 					const bool defer = T && !getenv("URMAPX_NO_DEFERRED_COPY") && urmapx_text_set_deferred(T, 1) == URMAPX_OK;
 					auto ok_so_far = [](const TextJob &q) { return !q.rc && (q.rep.reason == 0 || q.rep.reason == URMAPX_TEXT_DEFERRED); };
@@ -1592,10 +1601,27 @@ int map_files_impl(urmapx_index *I, const urmapx_map_options *opt, const InputRa
 					const urmapx_result &r = j->results[i];
 					const uint64_t off = j->reads.offs[i];
 					const unsigned L = (unsigned)(j->reads.offs[i + 1] - off);
-					if (have_sam && !paired)
+					if (bam) {  // the host encoders (sam.cpp): the bytes the device writes for the same read
+						if (!paired) {
+							if (!append_bam_record(out, I, r, j->ops.data(), 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, j->reads.label(i),
+							                       j->reads.bases.data() + off, j->reads.quals.data() + off, L))
+								fail.raise(URMAPX_E_FORMAT, bam_long_name(j->reads.label(i)));
+						} else if ((i & 1) == 0) {
+							const uint64_t off2 = j->reads.offs[i + 1];
+							const unsigned L2 = (unsigned)(j->reads.offs[i + 2] - off2);
+							pbuf.resize(strlen(j->reads.label(i)) + strlen(j->reads.label(i + 1)) + 2 * (size_t)(L + L2) + 4 * ((size_t)r.path_nops + j->results[i + 1].path_nops) + 2048);
+							const size_t k = urmapx_bam_pe(I, &j->results[i], &j->results[i + 1], j->ops.data(), j->reads.label(i),
+							                               j->reads.bases.data() + off, j->reads.quals.data() + off, L,
+							                               j->reads.label(i + 1), j->reads.bases.data() + off2,
+							                               j->reads.quals.data() + off2, L2, pbuf.data(), pbuf.size());
+							if (k == URMAPX_BAM_LONG_NAME) fail.raise(URMAPX_E_FORMAT, bam_long_name(strlen(j->reads.label(i)) >= strlen(j->reads.label(i + 1)) ? j->reads.label(i) : j->reads.label(i + 1)));
+							else out.append(pbuf.data(), k);
+						}
+					}
+					if (have_sam && !bam && !paired)
 						append_sam_record(out, I, r, j->ops.data(), 0, "*", 0xFFFFFFFFu, 0, j->reads.label(i),
 						                  j->reads.bases.data() + off, j->reads.quals.data() + off, L);
-					if (have_sam && paired && (i & 1) == 0) {
+					if (have_sam && !bam && paired && (i & 1) == 0) {
 						const uint64_t off2 = j->reads.offs[i + 1];
 						const unsigned L2 = (unsigned)(j->reads.offs[i + 2] - off2);
 						pbuf.resize(strlen(j->reads.label(i)) + strlen(j->reads.label(i + 1)) + 3 * (size_t)(L + L2) + 2048);
@@ -1754,6 +1780,10 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
                            const char *samout, const char *tabout, urmapx_map_report *report, char *err, size_t errcap) {
 	if (err && errcap) err[0] = 0;
 	if (!I || !opt || !fastq1) return URMAPX_E_ARG;
+	if (opt->bam && opt->bgzf) {
+		if (err && errcap) snprintf(err, errcap, "bam and bgzf together: a BAM file is always BGZF");
+		return URMAPX_E_ARG;
+	}
 	const int shards = opt->sam_shards > 1 ? opt->sam_shards : 1;
 	if (shards == 1) return map_files_impl(I, opt, InputRange(), fastq1, fastq2, samout, tabout, report, err, errcap);
 	auto say = [&](const std::string &s) {
@@ -1824,12 +1854,14 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
 	if (fd1 >= 0) close(fd1);
 	if (fd2 >= 0) close(fd2);
 	const double scan_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_scan0).count();
-	// a shard without records: an empty file, under -bgzf the end-of-file member alone (every shard is a complete BGZF file)
+	// a shard without records: an empty file, under -bgzf the end-of-file member alone (every shard is a complete BGZF file), under
+	// -bamout the header block in a member of its own in front of that (every shard is a complete BAM file)
 	auto empty_sam = [&](const std::string &path) {
 		FILE *f = fopen(path.c_str(), "wb");
 		if (!f) return;
 		std::string eof;
-		if (opt->bgzf && bgzf_members(eof, 1)) (void)fwrite(eof.data(), 1, eof.size(), f);
+		if (opt->bam) append_bam_header(eof, I, opt->cmdline);
+		if ((opt->bgzf || opt->bam) && bgzf_members(eof, 1)) (void)fwrite(eof.data(), 1, eof.size(), f);
 		fclose(f);
 	};
 	auto empty_shards_from = [&](int s0) {

@@ -401,8 +401,11 @@ static inline size_t cigar_max_chars(unsigned nops) { return 11 * ((size_t)nops 
 
 // Any number of runs (the general kernels' paths are as long as the read): the runs are merged as they come (path D, query
 // only, is CIGAR I and vice versa); the dangling-M rule needs the first three and the last three merged runs only.
-static char *put_cigar(char *p, const urmapx_path_op *ops, unsigned nops, unsigned QL) {
-	if (nops == 0) { p = put_uint(p, QL); *p++ = 'M'; return p; }
+// The op walk of both record writers: emit(len, op) for every run the CIGAR has, in order -- put_cigar prints them, bam_record
+// packs them.
+template <class Emit>
+static void for_each_cigar_run(const urmapx_path_op *ops, unsigned nops, unsigned QL, Emit emit) {
+	if (nops == 0) { emit(QL, 'M'); return; }
 	char op_fixed[URMAPX_MAX_PATH_OPS + 1];
 	unsigned len_fixed[URMAPX_MAX_PATH_OPS + 1];
 	std::vector<char> op_big;
@@ -433,7 +436,11 @@ static char *put_cigar(char *p, const urmapx_path_op *ops, unsigned nops, unsign
 			--N;
 		}
 	}
-	for (unsigned i = first; i < N; ++i) { p = put_uint(p, len[i]); *p++ = op[i]; }
+	for (unsigned i = first; i < N; ++i) emit(len[i], op[i]);
+}
+
+static char *put_cigar(char *p, const urmapx_path_op *ops, unsigned nops, unsigned QL) {
+	for_each_cigar_run(ops, nops, QL, [&](unsigned len, char op) { p = put_uint(p, len); *p++ = op; });
 	return p;
 }
 
@@ -541,6 +548,118 @@ void append_sam_header_text(std::string &out, const urmapx_index *I, const char 
 	out += "@PG\tID:urmap\tPN:urmap\tVN:1.0.mi355x\tCL:";
 	if (cmdline) out += cmdline;
 	out.push_back('\n');
+}
+
+
+// ---------------- BAM records (SAM/BAM specification v1, section 4.2) ----------------
+// What append_sam_record prints, field for field, in the binary layout: the same flags, the same CIGAR runs (for_each_cigar_run),
+// the same SEQ and QUAL bytes (reverse-complemented / reversed for a minus-strand hit) packed.
+static unsigned char g_nib[256];
+static struct NibInit {
+	NibInit() {  // "=ACMGRSVTWYHKDBN" -> 0..15, either case; every other byte is N (htslib's seq_nt16_table)
+		memset(g_nib, 15, sizeof g_nib);
+		const char *t = "=ACMGRSVTWYHKDBN";
+		for (int i = 0; t[i]; ++i) { g_nib[(unsigned char)t[i]] = (unsigned char)i; g_nib[(unsigned char)tolower(t[i])] = (unsigned char)i; }
+	}
+} g_nib_init;
+
+static inline void put_le32(char *p, uint32_t v) { p[0] = (char)v; p[1] = (char)(v >> 8); p[2] = (char)(v >> 16); p[3] = (char)(v >> 24); }
+
+static uint32_t bam_reg2bin(int64_t beg, int64_t end) {  // section 5.3
+	--end;
+	if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
+	if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
+	if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
+	if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
+	if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
+	return 0;
+}
+
+bool append_bam_record(std::string &out, const urmapx_index *I, const urmapx_result &r, const urmapx_path_op *ops, uint32_t aflags,
+                       uint32_t mate_seq_index, uint32_t mate_pos, int tlen, const char *label, const uint8_t *seq, const uint8_t *qual,
+                       unsigned QL) {
+	const size_t ql = qname_len(label);
+	if (ql > 254) return false;  // l_read_name is one byte and counts the NUL
+	const bool mapped = r.dbpos != 0xFFFFFFFFu;
+	uint32_t flags = aflags;
+	if (!mapped) {  // SetSAM_Unmapped keeps these bits (append_unmapped)
+		flags = 0x04;
+		if (aflags & 0x01) flags |= 0x01;
+		if (aflags & 0x40) flags |= 0x40;
+		else if (aflags & 0x80) flags |= 0x80;
+		if (aflags & 0x08) flags |= 0x08;
+		else if (aflags & 0x20) flags |= 0x20;
+	}
+	const size_t at = out.size();
+	out.resize(at + 36 + ql + 1);
+	memcpy(&out[at + 36], label, ql);
+	out[at + 36 + ql] = 0;
+	uint32_t n_cigar = 0;
+	uint64_t ref_span = 0;
+	if (mapped)
+		for_each_cigar_run(r.path_nops ? ops + r.path_off : nullptr, r.path_nops, QL, [&](unsigned len, char op) {
+			char w[4];
+			put_le32(w, (uint32_t)len << 4 | (op == 'M' ? 0u : op == 'I' ? 1u : 2u));
+			out.append(w, 4);
+			++n_cigar;
+			if (op != 'I') ref_span += len;
+		});
+	if (n_cigar > 0xFFFFu) { out.resize(at); return false; }  // (n_cigar_op is 16 bit; no read this build maps comes near)
+	int32_t ref_id = -1, pos = -1, next_id = -1, next_pos = -1;
+	if (mapped) {
+		ref_id = (int32_t)r.seq_index;
+		pos = (int32_t)r.coord;
+		// RNEXT / PNEXT as append_sam_record prints them: '*' without a mate label, '=' for the same label, 0 for no position
+		const char *tlabel = urmapx_index_label(I, r.seq_index);
+		const char *mlabel = mate_seq_index == 0xFFFFFFFFu ? "" : urmapx_index_label(I, mate_seq_index);
+		if (mlabel[0] == 0 || (mlabel[0] == '*' && mlabel[1] == 0)) next_id = -1;
+		else if (strcmp(mlabel, tlabel) == 0) next_id = ref_id;
+		else next_id = (int32_t)mate_seq_index;
+		next_pos = mate_pos == 0 || mate_pos == 0xFFFFFFFFu ? -1 : (int32_t)mate_pos;
+	}
+	const uint32_t bin = bam_reg2bin(pos, (int64_t)pos + (int64_t)(ref_span ? ref_span : 1));
+	const size_t seq_at = out.size();
+	out.resize(seq_at + (QL + 1) / 2 + QL);
+	unsigned char *ps = (unsigned char *)&out[seq_at], *pq = ps + (QL + 1) / 2;
+	const bool fwd = !mapped || r.plus;
+	for (unsigned i = 0; i < QL; i += 2) {
+		const unsigned hi = fwd ? g_nib[seq[i]] : g_nib[g_comp[seq[QL - 1 - i]]];
+		const unsigned lo = i + 1 < QL ? (fwd ? g_nib[seq[i + 1]] : g_nib[g_comp[seq[QL - 2 - i]]]) : 0u;
+		ps[i / 2] = (unsigned char)(hi << 4 | lo);
+	}
+	// QUAL '*' (none given, or that one character for one base) is 0xFF throughout
+	if (!qual || (QL == 1 && qual[0] == '*')) memset(pq, 0xFF, QL);
+	else
+		for (unsigned i = 0; i < QL; ++i) pq[i] = (unsigned char)((fwd ? qual[i] : qual[QL - 1 - i]) - 33);
+	char *c = &out[at];
+	put_le32(c, (uint32_t)(out.size() - at - 4));
+	put_le32(c + 4, (uint32_t)ref_id);
+	put_le32(c + 8, (uint32_t)pos);
+	put_le32(c + 12, (uint32_t)(ql + 1) | (mapped ? (uint32_t)r.mapq : 0u) << 8 | bin << 16);
+	put_le32(c + 16, n_cigar | flags << 16);
+	put_le32(c + 20, QL);
+	put_le32(c + 24, (uint32_t)next_id);
+	put_le32(c + 28, (uint32_t)next_pos);
+	put_le32(c + 32, (uint32_t)(mapped ? tlen : 0));
+	return true;
+}
+
+void append_bam_header(std::string &out, const urmapx_index *I, const char *cmdline) {
+	std::string text;
+	append_sam_header_text(text, I, cmdline);
+	char w[4];
+	out.append("BAM\1", 4);
+	put_le32(w, (uint32_t)text.size()); out.append(w, 4);
+	out += text;
+	const uint32_t n = urmapx_index_seq_count(I);
+	put_le32(w, n); out.append(w, 4);
+	for (uint32_t i = 0; i < n; ++i) {
+		const char *name = urmapx_index_label(I, i);
+		const size_t l = strlen(name) + 1;
+		put_le32(w, (uint32_t)l); out.append(w, 4);
+		out.append(name, l);
+		put_le32(w, urmapx_index_seq_length(I, i)); out.append(w, 4);
+	}
 }
 
 }  // namespace urx
@@ -716,11 +835,10 @@ static uint32_t paired_flags(bool first, bool revcomp, bool mate_revcomp, bool m
 	return f;
 }
 
-extern "C" size_t urmapx_sam_pe(const urmapx_index *I, const urmapx_result *r1, const urmapx_result *r2,
-                                const urmapx_path_op *path_ops, const char *label1, const uint8_t *seq1,
-                                const uint8_t *qual1, uint32_t len1, const char *label2, const uint8_t *seq2,
-                                const uint8_t *qual2, uint32_t len2, char *buf, size_t cap) {
-	// SetSAM2, output2.cpp:61-128 (positions compared are coordinates inside the sequences, as the reference does)
+// SetSAM2, output2.cpp:61-128 (positions compared are coordinates inside the sequences, as the reference does): what both mates'
+// records take from the pair
+struct PairFields { bool m1, m2; uint32_t f1, f2; int tlen1, tlen2; };
+static PairFields pair_fields(const urmapx_result *r1, const urmapx_result *r2, uint32_t len1, uint32_t len2) {
 	const bool m1 = r1->dbpos != 0xFFFFFFFFu, m2 = r2->dbpos != 0xFFFFFFFFu;
 	const bool plus1 = m1 && r1->plus, plus2 = m2 && r2->plus;
 	const bool consistent = m1 && m2 && (plus1 != plus2);
@@ -742,11 +860,50 @@ extern "C" size_t urmapx_sam_pe(const urmapx_index *I, const urmapx_result *r1, 
 	const bool rc1 = m1 && !r1->plus, rc2 = m2 && !r2->plus;
 	uint32_t f1 = paired_flags(true, rc1, rc2, !m2), f2 = paired_flags(false, rc2, rc1, !m1);
 	if (proper) { f1 |= 2u; f2 |= 2u; }
-	const char *l1 = m1 ? urmapx_index_label(I, r1->seq_index) : "";
-	const char *l2 = m2 ? urmapx_index_label(I, r2->seq_index) : "";
+	return PairFields{m1, m2, f1, f2, tlen1, tlen2};
+}
+
+extern "C" size_t urmapx_sam_pe(const urmapx_index *I, const urmapx_result *r1, const urmapx_result *r2,
+                                const urmapx_path_op *path_ops, const char *label1, const uint8_t *seq1,
+                                const uint8_t *qual1, uint32_t len1, const char *label2, const uint8_t *seq2,
+                                const uint8_t *qual2, uint32_t len2, char *buf, size_t cap) {
+	const PairFields P = pair_fields(r1, r2, len1, len2);
+	const char *l1 = P.m1 ? urmapx_index_label(I, r1->seq_index) : "";
+	const char *l2 = P.m2 ? urmapx_index_label(I, r2->seq_index) : "";
 	std::string out;
-	urx::append_sam_record(out, I, *r1, path_ops, f1, l2, m2 ? r2->coord : 0xFFFFFFFFu, tlen1, label1, seq1, qual1, len1);
-	urx::append_sam_record(out, I, *r2, path_ops, f2, l1, m1 ? r1->coord : 0xFFFFFFFFu, tlen2, label2, seq2, qual2, len2);
+	urx::append_sam_record(out, I, *r1, path_ops, P.f1, l2, P.m2 ? r2->coord : 0xFFFFFFFFu, P.tlen1, label1, seq1, qual1, len1);
+	urx::append_sam_record(out, I, *r2, path_ops, P.f2, l1, P.m1 ? r1->coord : 0xFFFFFFFFu, P.tlen2, label2, seq2, qual2, len2);
+	if (out.size() > cap) return 0;
+	memcpy(buf, out.data(), out.size());
+	return out.size();
+}
+
+// ---------------- BAM: the C entry points (argument lists of urmapx_sam_se / _pe) ----------------
+extern "C" size_t urmapx_bam_header(const urmapx_index *I, const char *cmdline, void *buf, size_t cap) {
+	if (!I) return 0;
+	std::string out;
+	urx::append_bam_header(out, I, cmdline);
+	if (buf && out.size() <= cap) memcpy(buf, out.data(), out.size());
+	return out.size();
+}
+
+extern "C" size_t urmapx_bam_se(const urmapx_index *I, const urmapx_result *r, const urmapx_path_op *path_ops, const char *label,
+                                const uint8_t *seq, const uint8_t *qual, uint32_t read_len, char *buf, size_t cap) {
+	std::string out;
+	if (!urx::append_bam_record(out, I, *r, path_ops, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, label, seq, qual, read_len)) return URMAPX_BAM_LONG_NAME;
+	if (out.size() > cap) return 0;
+	memcpy(buf, out.data(), out.size());
+	return out.size();
+}
+
+extern "C" size_t urmapx_bam_pe(const urmapx_index *I, const urmapx_result *r1, const urmapx_result *r2, const urmapx_path_op *path_ops,
+                                const char *label1, const uint8_t *seq1, const uint8_t *qual1, uint32_t len1, const char *label2,
+                                const uint8_t *seq2, const uint8_t *qual2, uint32_t len2, char *buf, size_t cap) {
+	PairFields P = pair_fields(r1, r2, len1, len2);
+	std::string out;
+	if (!urx::append_bam_record(out, I, *r1, path_ops, P.f1, P.m2 ? r2->seq_index : 0xFFFFFFFFu, P.m2 ? r2->coord : 0xFFFFFFFFu, P.tlen1, label1, seq1, qual1, len1) ||
+	    !urx::append_bam_record(out, I, *r2, path_ops, P.f2, P.m1 ? r1->seq_index : 0xFFFFFFFFu, P.m1 ? r1->coord : 0xFFFFFFFFu, P.tlen2, label2, seq2, qual2, len2))
+		return URMAPX_BAM_LONG_NAME;
 	if (out.size() > cap) return 0;
 	memcpy(buf, out.data(), out.size());
 	return out.size();

@@ -124,6 +124,14 @@ void append_sam_record(std::string &out, const urmapx_index *I, const urmapx_res
 void append_tab_pe(std::string &out, const urmapx_index *I, const urmapx_result *r1, const urmapx_result *r2, const urmapx_pair_info *info,
                    const char *label1, size_t n, uint32_t len1, uint32_t len2, int sam_on);
 
+// One BAM record (include/urmapx.h, "BAM output"): append_sam_record's fields in the binary layout.  mate_seq_index UINT32_MAX: no mate
+// (RNEXT '*').  false, nothing appended: the QNAME is over 254 bytes.
+bool append_bam_record(std::string &out, const urmapx_index *I, const urmapx_result &r, const urmapx_path_op *ops, uint32_t flags,
+                       uint32_t mate_seq_index, uint32_t mate_pos, int tlen, const char *label, const uint8_t *seq, const uint8_t *qual,
+                       unsigned QL);
+// magic, l_text, append_sam_header_text's text, n_ref, the reference list
+void append_bam_header(std::string &out, const urmapx_index *I, const char *cmdline);
+
 // 256-entry complement table of alpha.cpp:3005 (IUPAC, case preserving, 'u' and non-letters -> '?')
 const unsigned char *complement_table();
 

@@ -1,7 +1,8 @@
 // san_main.cpp -- driver of the sanitizer builds (make san): the host side of the drop-in path run from the command line, with the
 // device side replaced by san/stub_device.cpp.  tests/test_sanitizers_cpu.py runs it on well-formed and on damaged input; a
 // sanitizer report ends the process with exit code 99 (ASAN_OPTIONS / UBSAN_OPTIONS / TSAN_OPTIONS exitcode, set by the tests).
-//   urmap_san map <fastq1> [-2 fastq2] -o out.sam [-tab out.tab] [-batch N] [-streams K] [-gpus N] [-shards N] [-threads T] [-null] [-bgzf]
+//   urmap_san map <fastq1> [-2 fastq2] -o out.sam [-tab out.tab] [-batch N] [-streams K] [-gpus N] [-shards N] [-threads T] [-null] [-bgzf] [-bam] [-biglen N]
+//       (-biglen: bases of the stand-in index's third sequence, 4 000 000 000 unless given; a BAM position holds 2^31 - 1)
 //   urmap_san gunzip <in.gz> <out> [threads]
 //   urmap_san fastq <file> <batch>
 //   urmap_san makeufi <fasta> <out.ufi> <slots>
@@ -20,6 +21,7 @@ static int cmd_map(int argc, char **argv) {
 	urmapx_map_options o;
 	memset(&o, 0, sizeof o);
 	o.gpus = 1; o.streams = 2; o.minq = 10; o.cmdline = "urmap_san";
+	uint32_t biglen = 4000000000u;
 	for (int i = 1; i < argc; ++i) {
 		const std::string a = argv[i];
 		auto val = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -33,9 +35,11 @@ static int cmd_map(int argc, char **argv) {
 		else if (a == "-threads") o.host_threads = atoi(val());
 		else if (a == "-null") o.discard_sam = 1;
 		else if (a == "-bgzf") o.bgzf = 1;
+		else if (a == "-bam") o.bam = 1;
+		else if (a == "-biglen") biglen = (uint32_t)strtoul(val(), nullptr, 10);
 		else return 2;
 	}
-	static const uint32_t lengths[3] = {1000000u, 250000u, 4000000000u};
+	const uint32_t lengths[3] = {1000000u, 250000u, biglen};
 	static const char *const labels[3] = {"chrA", "chrB a label with spaces", "chrBig"};
 	urmapx_index *I = urx_stub_index(3, lengths, labels);
 	urmapx_map_report rep;

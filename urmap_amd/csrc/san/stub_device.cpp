@@ -34,7 +34,7 @@ struct urmapx_ctx {
 };
 struct urmapx_text {
 	urmapx_ctx *C = nullptr;
-	bool deferred = false, bgzf = false;
+	bool deferred = false, bgzf = false, bam = false;
 	struct Chunk { std::string text; char *dst; urmapx_text_report rep; };
 	std::deque<Chunk> flying;   // deferred: text made, "copy" not done until urmapx_text_wait
 	std::string waiting;        // after URMAPX_TEXT_SAM_CAP
@@ -249,7 +249,12 @@ int urmapx_text_map_se(urmapx_text *T, const char *fastq, size_t n, unsigned min
 		stub_search(T->C->I, q.seq, q.L, &r);
 		count(rep, r, minq);
 		label.assign(q.label, q.label_n);
-		urx::append_sam_record(text, T->C->I, r, nullptr, 0, "*", 0xFFFFFFFFu, 0, label.c_str(), q.seq, q.qual, q.L);
+		if (!T->bam) urx::append_sam_record(text, T->C->I, r, nullptr, 0, "*", 0xFFFFFFFFu, 0, label.c_str(), q.seq, q.qual, q.L);
+		else if (!urx::append_bam_record(text, T->C->I, r, nullptr, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, label.c_str(), q.seq, q.qual, q.L)) {
+			memset(rep, 0, sizeof *rep);
+			rep->reason = URMAPX_TEXT_LONG_NAME;  // (the device encoder hands such a chunk back)
+			return URMAPX_OK;
+		}
 	}
 	rep->records = (uint32_t)recs.size();
 	return deliver(T, std::move(text), sam, cap, rep);
@@ -274,8 +279,13 @@ int urmapx_text_map_pe(urmapx_text *T, const char *fq1, size_t n1, const char *f
 		stub_pair_info(r, &T->C->info[i]);
 		l1.assign(a[i].label, a[i].label_n); l2.assign(b[i].label, b[i].label_n);
 		buf.resize(l1.size() + l2.size() + 3 * (size_t)(a[i].L + b[i].L) + 2048);
-		const size_t k = urmapx_sam_pe(T->C->I, &r[0], &r[1], nullptr, l1.c_str(), a[i].seq, a[i].qual, a[i].L, l2.c_str(), b[i].seq, b[i].qual, b[i].L,
-		                               buf.data(), buf.size());
+		const size_t k = (T->bam ? urmapx_bam_pe : urmapx_sam_pe)(T->C->I, &r[0], &r[1], nullptr, l1.c_str(), a[i].seq, a[i].qual, a[i].L, l2.c_str(), b[i].seq,
+		                                                          b[i].qual, b[i].L, buf.data(), buf.size());
+		if (k == URMAPX_BAM_LONG_NAME) {
+			memset(rep, 0, sizeof *rep);
+			rep->reason = URMAPX_TEXT_LONG_NAME;
+			return URMAPX_OK;
+		}
 		text.append(buf.data(), k);
 		for (int q = 0; q < 4; ++q) T->line_ends1.push_back(a[i].ends[q]);
 		T->lens2.push_back(b[i].L);
@@ -291,6 +301,11 @@ int urmapx_text_set_deferred(urmapx_text *T, int on) {
 int urmapx_text_set_bgzf(urmapx_text *T, int on) {
 	if (!T->flying.empty() || T->have_waiting) return URMAPX_E_ARG;
 	T->bgzf = on != 0;
+	return URMAPX_OK;
+}
+int urmapx_text_set_bam(urmapx_text *T, int on) {
+	if (!T->flying.empty() || T->have_waiting) return URMAPX_E_ARG;
+	T->bam = on != 0;
 	return URMAPX_OK;
 }
 int urmapx_text_wait(urmapx_text *T, urmapx_text_report *rep) {

@@ -9,6 +9,7 @@
 //   raw bytes --nl_count / nl_emit--> line ends --record_kernel--> read lengths --scan--> offs
 //             --copy_bases_kernel--> bases   --urmapx_map_se_device--> results, paths
 //             --sam_len_kernel--> record lengths --scan--> record offsets --sam_kernel--> SAM text
+//   (urmapx_text_set_bam: bam_len_kernel and bam_kernel of bam_gpu.hip in the last line's two places, BAM records for SAM text)
 //
 // Paired-end (urmapx_text_map_pe): one chunk of each mate file with the same number of records; both are parsed as above,
 // the mates' bases are interleaved (reads 2i, 2i+1 = pair i, map2.cpp:27-32), State2::Search runs
@@ -25,6 +26,7 @@
 
 #include "internal.h"
 #include "sam.h"
+#include "text_dev.h"
 
 using namespace urx;
 
@@ -32,18 +34,9 @@ namespace {
 
 constexpr int NL_TILE = 16384, NL_THREADS = 256;  // 64 bytes per thread
 constexpr int SC_THREADS = 256, SC_ITEMS = 8, SC_TILE = SC_THREADS * SC_ITEMS;
-constexpr int SAM_WAVES = 4;        // wavefronts per block of the record kernels
-// an LDS array named by an LDS pointer (32 bit, ds_* instructions), as in dev_common.h
-template <class T> using lds_ptr = __attribute__((address_space(3))) T *;
-template <class T> __device__ __forceinline__ lds_ptr<T> to_lds(T *p) { return (lds_ptr<T>)p; }
 constexpr int HEAD_CAP = 1600;      // bytes of one record between QNAME and SEQ held in LDS (12 * 97 CIGAR + fields)
 constexpr int TNAME_MAX = 160;      // longest target label the device formatter takes
 
-struct TextHdr {  // device; [0] and [1]: the chunk of each file (n_lines, n_records, flags, max_len); [0] also the call's totals
-	uint32_t n_lines, n_records, flags, max_len;
-	uint32_t total_bases, sam_total, n_reads, pad1;  // n_reads: records of the batch (single-end: n_records; pairs: twice that)
-	unsigned long long cnt[4];  // accept, reject, nohit, unsupported
-};
 
 __device__ __forceinline__ uint32_t eq_mask(uint32_t w, uint32_t byte_x4) {  // bit 7 of every byte of w equal to the byte
 	const uint32_t x = w ^ byte_x4;
@@ -173,7 +166,6 @@ __global__ __launch_bounds__(NL_THREADS) void nl_emit_kernel(const uint4 *raw, u
 }
 
 // ---- records ----
-__device__ __forceinline__ uint32_t line_start(const uint32_t *ends, uint32_t k) { return k ? ends[k - 1] + 1u : 0u; }
 
 // read lengths; structure of every record ('@' first, a label line that is not empty, as many quality bytes as bases)
 __global__ __launch_bounds__(256) void record_kernel(const uint8_t *raw, const uint32_t *ends, TextHdr *hdr, uint32_t *blen) {
@@ -277,23 +269,6 @@ __global__ __launch_bounds__(256) void interleave_lens_kernel(TextHdr *hdr, cons
 }
 
 // ---- SAM ----
-struct SamArgs {
-	const uint8_t *raw[2];       // the chunk of each file (single-end: [0] only)
-	const uint32_t *ends[2];
-	uint32_t paired;             // records 2i, 2i+1 = the mates of pair i, from raw[0] and raw[1]
-	const urmapx_result *results;
-	const urmapx_path_op *ops;
-	const char *tnames;          // target labels back to back
-	const uint32_t *tname_offs;  // seqCount + 1
-	const uint8_t *comp;         // 256-byte complement table (alpha.cpp:3005)
-	uint32_t seq_count;
-	uint32_t minq;
-	TextHdr *hdr;
-	uint32_t *lens;              // PASS 0 out
-	uint32_t *qn;                // PASS 0 out: QNAME bytes of every record (PASS 1 does not scan the labels again)
-	const uint32_t *rec_offs;    // PASS 1 in
-	char *sam;                   // PASS 1 out
-};
 
 // Where the head of a record is written: LDS (HeadLds) or, for a head longer than the LDS buffer, straight into the output
 // (HeadGlobal).  Two types, two instantiations of build_head: a generic pointer that is LDS on one path and global on the
@@ -322,90 +297,9 @@ __device__ __forceinline__ void dev_put_int(W &w, int v) {
 	dev_put_uint(w, (uint32_t)v);
 }
 
-// SetSAM's arguments (setsam.cpp:73-74): single-end passes 0, "*", UINT32_MAX, 0 (output1.cpp:13); pairs what SetSAM2
-// works out (output2.cpp:61-128)
-struct MateFields {
-	uint32_t flags;
-	bool mate_mapped;
-	uint32_t mate_seq_index, mate_coord;
-	int tlen;
-};
-
-__device__ __forceinline__ uint32_t paired_flags(bool first, bool revcomp, bool mate_revcomp, bool mate_unmapped) {  // output2.cpp:18-36
-	uint32_t f = first ? 0x41u : 0x81u;
-	if (revcomp) f |= 0x10u;
-	if (mate_unmapped) f |= 0x08u;
-	else if (mate_revcomp) f |= 0x20u;
-	return f;
-}
-
-// SetSAM2 (output2.cpp:61-128) for mate `second` of a pair with results r1, r2 and read lengths len1, len2
-__device__ MateFields pair_fields(const urmapx_result &r1, const urmapx_result &r2, uint32_t len1, uint32_t len2, bool second) {
-	const bool m1 = r1.dbpos != 0xFFFFFFFFu, m2 = r2.dbpos != 0xFFFFFFFFu;
-	const bool plus1 = m1 && r1.plus, plus2 = m2 && r2.plus;
-	const bool consistent = m1 && m2 && (plus1 != plus2);
-	int tlen1 = 0, tlen2 = 0;
-	bool proper = false;
-	if (m1 && m2) {
-		if (r1.coord <= r2.coord) {
-			tlen1 = (int)(r2.coord + len2) - (int)r1.coord;
-			if (tlen1 > 0 && tlen1 < 1000 && consistent) proper = true;
-			if (tlen1 > 1000) tlen1 = 0;
-			tlen2 = -tlen1;
-		} else {
-			tlen2 = (int)(r1.coord + len1) - (int)r2.coord;
-			if (tlen2 > 0 && tlen2 < 1000 && consistent) proper = true;
-			if (tlen2 > 1000) tlen2 = 0;
-			tlen1 = -tlen2;
-		}
-	}
-	const bool rc1 = m1 && !r1.plus, rc2 = m2 && !r2.plus;
-	MateFields F;
-	F.flags = second ? paired_flags(false, rc2, rc1, !m1) : paired_flags(true, rc1, rc2, !m2);
-	if (proper) F.flags |= 2u;
-	F.mate_mapped = second ? m1 : m2;
-	F.mate_seq_index = second ? r1.seq_index : r2.seq_index;
-	F.mate_coord = second ? r1.coord : r2.coord;
-	F.tlen = second ? tlen2 : tlen1;
-	return F;
-}
 
 // Lane 0 writes the fields between QNAME and SEQ of a mapped or unmapped record (SetSAM / SetSAM_Unmapped,
 // setsam.cpp:12-207) to `head`; returns the length, or 0 if it does not fit the device formatter.
-// The merged CIGAR runs of a path, seen from both ends: N of them, the first three (fo / fl) and the last three (lo / ll, [2] = the
-// last), and the characters they print as.
-struct CigarEnds {
-	uint32_t N, chars;
-	char fo[3], lo[3];
-	uint32_t fl[3], ll[3];
-};
-__device__ __forceinline__ uint32_t dev_digits(uint32_t v) {
-	return v < 10u ? 1u : v < 100u ? 2u : v < 1000u ? 3u : v < 10000u ? 4u : v < 100000u ? 5u : v < 1000000u ? 6u : v < 10000000u ? 7u
-	     : v < 100000000u ? 8u : v < 1000000000u ? 9u : 10u;
-}
-__device__ void cigar_ends(const urmapx_path_op *ops, uint32_t nops, CigarEnds &E) {
-	E.N = 0; E.chars = 0;
-	for (int t = 0; t < 3; ++t) { E.fo[t] = 0; E.lo[t] = 0; E.fl[t] = 0; E.ll[t] = 0; }
-	char cur = 0;
-	uint32_t curlen = 0;
-	bool have = false;
-	auto close_run = [&]() {
-		if (E.N < 3) { E.fo[E.N] = cur; E.fl[E.N] = curlen; }
-		E.lo[0] = E.lo[1]; E.ll[0] = E.ll[1]; E.lo[1] = E.lo[2]; E.ll[1] = E.ll[2]; E.lo[2] = cur; E.ll[2] = curlen;
-		E.chars += dev_digits(curlen) + 1u;
-		++E.N;
-	};
-	for (uint32_t i = 0; i < nops; ++i) {
-		const uint32_t code = ops[i] & 3u, len = ops[i] >> 2;
-		const char c = code == 0 ? 'M' : code == 1 ? 'I' : 'D';
-		if (have && cur == c) curlen += len;
-		else {
-			if (have) close_run();
-			cur = c; curlen = len; have = true;
-		}
-	}
-	if (have) close_run();
-}
 
 template <class W>
 __device__ uint32_t build_head(const SamArgs &A, const urmapx_result &r, const MateFields &F, uint32_t QL, W &w) {
@@ -438,35 +332,11 @@ __device__ uint32_t build_head(const SamArgs &A, const urmapx_result &r, const M
 	if (nops == 0) { dev_put_uint(w, QL); w.put('M'); }
 	else {
 		// Any number of runs (the general kernels' paths are as long as the read): the runs are merged as they stream by, twice --
-		// once for what CIGAROpsFixDanglingMs (cigar.cpp:141-199) needs to know (how many merged runs, the first three, the last
-		// three: head rule XOR tail rule, as in sam.cpp), once to write them.
+		// once for what CIGAROpsFixDanglingMs (cigar.cpp:141-199) needs to know (cigar_ends), once to write them (walk_cigar_runs).
 		const urmapx_path_op *ops = A.ops + r.path_off;
 		CigarEnds E;
 		cigar_ends(ops, nops, E);
-		const bool head_rule = E.N >= 3 && E.fo[0] == 'M' && E.fl[0] <= 2 && E.fl[1] > 4 && E.fo[2] == 'M';
-		const bool tail_rule = !head_rule && E.N >= 3 && E.lo[2] == 'M' && E.ll[2] <= 2 && E.ll[1] > 4 && E.lo[0] == 'M';
-		uint32_t k = 0;  // index of the merged run being closed
-		char cur = 0;
-		uint32_t curlen = 0;
-		bool have = false;
-		auto close_run = [&]() {
-			uint32_t len = curlen;
-			bool skip = false;
-			if (head_rule) { if (k == 0) skip = true; else if (k == 2) len += E.fl[0]; }
-			if (tail_rule) { if (k == E.N - 1) skip = true; else if (k == E.N - 3) len += E.ll[2]; }
-			if (!skip) { dev_put_uint(w, len); w.put(cur); }
-			++k;
-		};
-		for (uint32_t i = 0; i < nops; ++i) {
-			const uint32_t code = ops[i] & 3u, len = ops[i] >> 2;
-			const char c = code == 0 ? 'M' : code == 1 ? 'I' : 'D';  // path D (query only) is CIGAR I and vice versa (cigar.cpp:22-25)
-			if (have && cur == c) curlen += len;
-			else {
-				if (have) close_run();
-				cur = c; curlen = len; have = true;
-			}
-		}
-		close_run();
+		walk_cigar_runs(ops, nops, E, [&](uint32_t len, char op) { dev_put_uint(w, len); w.put(op); });
 	}
 	w.put('\t');
 	// RNEXT: '*' without a mapped mate, '=' if the mate's target has the same label, else that label (setsam.cpp:150-166)
@@ -547,31 +417,6 @@ __device__ uint32_t head_length(const SamArgs &A, const urmapx_result &r, const 
 	return n;
 }
 
-// what a record has besides its result: where its lines are, QNAME length ("/1" "/2" dropped, cut at the first blank:
-// setsam.cpp:36-46), SetSAM's mate arguments
-struct RecView {
-	const uint8_t *raw;
-	uint32_t s1, e1, e3, QL;
-	MateFields F;
-};
-__device__ __forceinline__ RecView record_view(const SamArgs &A, uint32_t i, const urmapx_result &r) {
-	RecView V;
-	const uint32_t side = A.paired ? (i & 1u) : 0u, rec = A.paired ? (i >> 1) : i;
-	V.raw = A.raw[side];
-	const uint32_t *ends = A.ends[side];
-	V.s1 = line_start(ends, 4 * rec); V.e1 = ends[4 * rec];
-	const uint32_t e2 = ends[4 * rec + 1];
-	V.e3 = ends[4 * rec + 2];
-	V.QL = e2 - (V.e1 + 1u);
-	V.F.flags = 0; V.F.mate_mapped = false; V.F.mate_seq_index = 0; V.F.mate_coord = 0xFFFFFFFFu; V.F.tlen = 0;
-	if (A.paired) {
-		const urmapx_result rm = A.results[i ^ 1u];
-		const uint32_t *oe = A.ends[side ^ 1u];
-		const uint32_t QLm = oe[4 * rec + 1] - (oe[4 * rec] + 1u);
-		V.F = side ? pair_fields(rm, r, QLm, V.QL, true) : pair_fields(r, rm, V.QL, QLm, false);
-	}
-	return V;
-}
 
 // Record lengths and the HitStats counters (output1.cpp:20-30), one THREAD per record: nothing is written but a number,
 // so the serial part of a record (the head between QNAME and SEQ) runs for 64 records at a time.
@@ -624,7 +469,6 @@ __global__ __launch_bounds__(256) void sam_len_kernel(SamArgs A) {
 // wavefront's large LDS buffer, or, longer than that, straight into the output.  A record's length must be the one sam_len_kernel
 // reserved; if not, the chunk is flagged and handed back (flag 32).
 constexpr int HEAD_SMALL = 96;
-__device__ __forceinline__ uint32_t bcast(uint32_t v, int t) { return (uint32_t)__builtin_amdgcn_readlane((int)v, t); }
 
 __global__ __launch_bounds__(SAM_WAVES * 64) void sam_kernel(SamArgs A) {
 	__shared__ char s_heads[SAM_WAVES][64 * HEAD_SMALL];
@@ -740,6 +584,8 @@ struct urmapx_text {
 	DevBuf<uint8_t> zout;
 	DevBuf<uint64_t> zused;
 	uint64_t *h_zused = nullptr;  // page-locked
+	// urmapx_text_set_bam: bam_gpu.hip's two kernels stand where sam_len_kernel and sam_kernel stand, `sam` holds BAM records
+	bool bam = false;
 };
 
 namespace {
@@ -818,7 +664,8 @@ int fetch_sam(urmapx_text *T, char *sam, size_t sam_cap, urmapx_text_report *rep
 	A.sam = (char *)T->sam.p;
 	// the text of the chunk before may still be on its way out of T->sam
 	if (T->deferred && T->waiting && T->tail_ok) HIP_TRY(hipStreamWaitEvent(st, T->tail_ev[set ^ 1][2], 0));
-	hipLaunchKernelGGL(sam_kernel, dim3(GRID), dim3(SAM_WAVES * 64), 0, st, A);
+	if (T->bam) bam_launch(A, st);
+	else hipLaunchKernelGGL(sam_kernel, dim3(GRID), dim3(SAM_WAVES * 64), 0, st, A);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(T->h_hdr + 2 + set, T->hdr.p, sizeof(TextHdr), hipMemcpyDeviceToHost, st));  // (on the main stream: the next chunk clears the header there)
 	const uint8_t *d_src = T->sam.p;
@@ -917,7 +764,8 @@ int map_text(urmapx_text *T, const char *fastq1, size_t nbytes1, const char *fas
 	A.results = T->results.p; A.ops = T->pathops.p; A.tnames = T->tnames.p;
 	A.tname_offs = T->tname_offs.p; A.comp = T->comp.p; A.seq_count = T->seq_count; A.minq = minq; A.hdr = hdr;
 	A.lens = T->lens.p; A.qn = T->qn.p; A.rec_offs = T->rec_offs.p; A.sam = nullptr;
-	hipLaunchKernelGGL(sam_len_kernel, dim3(GRID), dim3(256), 0, st, A);
+	if (T->bam) bam_len_launch(A, st);
+	else hipLaunchKernelGGL(sam_len_kernel, dim3(GRID), dim3(256), 0, st, A);
 	hipLaunchKernelGGL(scan_sums_kernel, dim3(GRID), dim3(SC_THREADS), 0, st, T->lens.p, &hdr->n_reads, T->sums.p);
 	hipLaunchKernelGGL(scan_small_kernel, dim3(1), dim3(1024), 0, st, T->sums.p, &hdr->n_reads, (uint32_t)SC_TILE, 0u, &hdr->sam_total, &hdr->flags);
 	hipLaunchKernelGGL(scan_apply_kernel<uint32_t>, dim3(GRID), dim3(SC_THREADS), 0, st, T->lens.p, &hdr->n_reads, T->sums.p, T->rec_offs.p);
@@ -1038,6 +886,12 @@ int urmapx_text_set_bgzf(urmapx_text *T, int on) {
 		if ((rc = urmapx_bgzf_create(ctx_device(T->C), (void *)ctx_stream(T->C), &T->Z))) return rc;
 	}
 	T->bgzf = on != 0;
+	return URMAPX_OK;
+}
+
+int urmapx_text_set_bam(urmapx_text *T, int on) {
+	if (!T || T->waiting || T->pending) return URMAPX_E_ARG;
+	T->bam = on != 0;
 	return URMAPX_OK;
 }
 

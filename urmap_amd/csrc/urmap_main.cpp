@@ -60,6 +60,7 @@ struct Opts {
 	std::string map, map2, reverse, make_ufi, ufi, ufi_validate, ufi_stats, ufi_counts, ufi_info, samout, tabbedout, output, log;
 	std::string make_bitvec, search_bitvec, search_bitvec2, input2, ref, output1, output2;
 	bool bgzf = false;  // -bgzf: -samout is a BGZF file, deflated on the device
+	std::string bamout; // -bamout: a BAM file in -samout's place, records encoded and deflated on the device
 	bool veryfast = false, quiet = false, minq_given = false, host_build = false, notrunclabels = false;
 	bool trunclabels = false, wordlength_given = false;
 	double load_factor = 0.6;  // myopts.h: FLT_OPT(load_factor, 0.6, ...)
@@ -102,6 +103,7 @@ static Opts parse(int argc, char **argv) {
 		else if (a == "-batch") o.batch = (unsigned)atoi(val());
 		else if (a == "-veryfast") o.veryfast = true;
 		else if (a == "-bgzf") o.bgzf = true;
+		else if (a == "-bamout") o.bamout = val();
 		else if (a == "-host") o.host_build = true;
 		else if (a == "-quiet") o.quiet = true;
 		else if (a == "-log") o.log = val();
@@ -176,6 +178,10 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 	if (o.gpus < 1 || o.gpus > 64) die("-gpus must be 1..64");
 	if (o.streams < 1 || o.streams > 8) die("-streams must be 1..8");
 	if (o.samshards < 0 || o.samshards > 64) die("-samshards must be 0..64");
+	const bool bam = !o.bamout.empty();
+	if (bam && !o.samout.empty()) die("-bamout replaces -samout: give one of the two");
+	if (bam && o.bgzf) die("-bgzf goes with -samout: a -bamout file is always BGZF");
+	const std::string &samout = bam ? o.bamout : o.samout;
 	const auto t0 = std::chrono::steady_clock::now();
 	urmapx_index *I = nullptr;
 	// the file streams to the first device (urmapx_index_open_device); URMAPX_HOST_INDEX=1: through host arrays as before (measurement)
@@ -195,11 +201,12 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 	mo.first_gpu = o.gpu; mo.gpus = o.gpus; mo.streams = o.streams; mo.host_threads = (int)o.threads; mo.batch = o.batch;
 	mo.veryfast = o.veryfast ? 1 : 0; mo.minq = o.minq; mo.cmdline = cl.c_str();
 	mo.bgzf = o.bgzf ? 1 : 0;
+	mo.bam = bam ? 1 : 0;
 	urmapx_map_report rep;
 	memset(&rep, 0, sizeof rep);
 	char err[1024];
 	const int rc = urmapx_map_files(I, &mo, paired ? o.map2.c_str() : o.map.c_str(), paired ? o.reverse.c_str() : nullptr,
-	                                o.samout.empty() ? nullptr : o.samout.c_str(), o.tabbedout.empty() ? nullptr : o.tabbedout.c_str(),
+	                                samout.empty() ? nullptr : samout.c_str(), o.tabbedout.empty() ? nullptr : o.tabbedout.c_str(),
 	                                &rep, err, sizeof err);
 	if (rc != URMAPX_OK && rc != URMAPX_E_UNSUPPORTED) die("%s", err[0] ? err : urmapx_strerror(rc));
 	const unsigned long long n_reads = rep.reads, n_accept = rep.mapped_q, n_reject = rep.mapped_lowq, n_nohit = rep.unmapped;
@@ -233,8 +240,8 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 		progress_log(q, "%16s  Mapped Q>=%u (%.1f%%)\n", commas(n_accept).c_str(), minq, pct(n_accept));
 		progress_log(q, "%16s  Mapped Q< %u (%.1f%%)\n", commas(n_reject).c_str(), minq, pct(n_reject));
 		progress_log(q, "%16s  Unmapped (%.1f%%)\n\n", commas(n_nohit).c_str(), pct(n_nohit));
-		if (o.bgzf && !o.samout.empty())
-			progress_log(q, "%16s  Bytes of SAM text, %s written as BGZF (%.3f)\n\n", commas(rep.sam_text_bytes).c_str(), commas(rep.sam_file_bytes).c_str(),
+		if ((o.bgzf && !o.samout.empty()) || bam)
+			progress_log(q, bam ? "%16s  Bytes of BAM records, %s written as BGZF (%.3f)\n\n" : "%16s  Bytes of SAM text, %s written as BGZF (%.3f)\n\n", commas(rep.sam_text_bytes).c_str(), commas(rep.sam_file_bytes).c_str(),
 			             rep.sam_text_bytes ? (double)rep.sam_file_bytes / (double)rep.sam_text_bytes : 0.0);
 		if (o.minq_given && !paired) progress_log(q, "\nWARNING: Option -minq not used\n\n");
 	}
@@ -539,6 +546,8 @@ int main(int argc, char **argv) {
 	fprintf(stderr, "urmap (MI355X build)\n  urmap -map reads.fq -ufi index.ufi -samout out.sam [-veryfast] [-gpu D] [-gpus N] [-streams K] [-samshards N] [-bgzf]\n"
 	                "  urmap -map2 R1.fq -reverse R2.fq -ufi index.ufi -samout out.sam [-tabbedout out.tab] [-gpu D] [-gpus N] [-bgzf]\n"
 	                "      -bgzf: the file named by -samout is BGZF (gzip members of 64 KB of text, deflated on the GPU); `gzip -dc` gives the SAM text\n"
+	                "      -bamout out.bam: in place of -samout, a BAM file (records encoded and deflated on the GPU, unsorted, no optional fields);\n"
+	                "               with -samshards N every out.bam.0 .. out.bam.N-1 is a complete BAM file\n"
 	                "  urmap -make_ufi genome.fa -output index.ufi [-slots N] [-wordlength W] [-maxix M]\n"
 	                "  urmap -ufi_validate index.ufi [-gpu D]\n"
 	                "  urmap -ufi_stats index.ufi [-log F] [-gpu D] [-quiet]\n"
