@@ -165,6 +165,52 @@ def test_shards_pairs_tab_and_compressed_input(san, reads, which):
     assert outs["text"][0].count(b"\n") == 2 * len(recs2) + 4 and outs["text"][1].count(b"\n") == len(recs2)
 
 
+@pytest.fixture(scope="module")
+def long_mates(tmp_path_factory):
+    """20 000 pairs whose mate labels carry a 1 000-byte comment (5 MB against 25 MB), and the host road's SAM and tab for them"""
+    d = str(tmp_path_factory.mktemp("long_mates"))
+    fq, fq2 = os.path.join(d, "a.fq"), os.path.join(d, "b.fq")
+    open(fq, "wb").write(fastq_text(make_reads(20000, 31)))
+    open(fq2, "wb").write(fastq_text([(l[:-1] + b"2 " + b"c" * 1000, s, q) for l, s, q in make_reads(20000, 32)]))
+    for p in (fq, fq2):
+        with open(p, "rb") as f:
+            open(p + ".gz", "wb").write(gzip.compress(f.read(), 1))
+    return {"dir": d, "fq": fq, "fq2": fq2, "want": {}}
+
+
+@pytest.mark.parametrize("which", ["asan", "tsan"])
+@pytest.mark.parametrize("form", ["plain", "gz", "fifo"])
+@pytest.mark.parametrize("batch", [20000, 80000])
+def test_pairs_whose_mate_records_are_much_longer(san, long_mates, which, form, batch):
+    """the mate chunk outgrows the job's buffer (more than 1.25 x the first file's chunk + 4 MiB): in the middle of the file (-batch 20000) and
+    on the last chunk (-batch 80000), cut from a plain file, from the inflated stream and from a FIFO -- the bytes of the host road"""
+    exe, d, fq, fq2 = san[which], long_mates["dir"], long_mates["fq"], long_mates["fq2"]
+
+    def mapped(name, m1, m2, env):
+        sam, tab = os.path.join(d, name + ".sam"), os.path.join(d, name + ".tab")
+        rc, out = run(exe, ["map", m1, "-2", m2, "-o", sam, "-tab", tab, "-batch", batch], dict(env, URX_STUB_MAP="1"))
+        assert rc == 0 and "reads=40000 " in out, out
+        # every byte of both files went to the device stand-in (a regrow that gave up would leave its chunk to the host reader), or none did
+        assert f" input_bytes={0 if env.get('URMAPX_HOST_TEXT') else os.path.getsize(fq) + os.path.getsize(fq2)} " in out, out
+        return open(sam, "rb").read(), open(tab, "rb").read()
+
+    if (which, batch) not in long_mates["want"]:
+        long_mates["want"][which, batch] = mapped(f"{which}_{batch}_host", fq, fq2, {"URMAPX_HOST_TEXT": "1"})
+    name = f"{which}_{batch}_{form}"
+    if form == "fifo":
+        fifo = os.path.join(d, name + ".fifo")
+        os.mkfifo(fifo)
+        feeder = subprocess.Popen(["sh", "-c", 'cat "$0" > "$1"', fq2, fifo])
+        try:
+            got = mapped(name, fq, fifo, {})
+        finally:
+            feeder.kill()
+            feeder.wait()
+    else:
+        got = mapped(name, fq + ".gz" if form == "gz" else fq, fq2 + ".gz" if form == "gz" else fq2, {"URMAPX_PGZIP_SEGMENT": "65536"} if form == "gz" else {})
+    assert got == long_mates["want"][which, batch]
+
+
 def test_odd_but_legal_fastq_takes_the_host_reader(san, reads):
     """'\\r\\n' line ends, no final newline, blank lines at the end: the device parser hands such a chunk back and the host reader
     continues at its first byte (pipeline.cpp's resume) -- same records as the clean file"""

@@ -9,12 +9,16 @@
 // (map.cpp:58-61, seqsource.cpp:30-66) but writes in completion order; here records are written in input
 // order.  No data moves between devices.  The batch arrays that cross PCIe are page-locked once they have their size.
 //
-// Single-end input from a plain file takes the shorter road first (text phase): the reader cuts the file into chunks at
+// Input from files, .gz files and pipes takes the shorter road first (text phase): the reader cuts the input into chunks at
 // record starts and reads them into page-locked buffers, a lane hands the chunk's BYTES to the device and gets the bytes
 // of its SAM records back (text_gpu.hip: line ends, record checks, search, SAM text all on the GPU), and the writer
 // copies them into the output file.  The host then only moves bytes.  A chunk the device parser does not take as it is
 // ends the text phase; the host reader continues at that chunk's first byte with the line count kept, so '\r', blank
 // lines and malformed records get the reference's handling and messages.
+//
+// map_files_impl is open -> text phase -> host phase (if the text phase left work) -> finish.  Run holds what the stages share and
+// lets go of it in close(); TextPhase (stream or plain-file reader, lanes, writer) and HostPhase (reader, mate reader, lanes, formatter,
+// flusher) hold their channels; each member a thread writes while the others run names that thread.
 #include <fcntl.h>
 #include <sched.h>
 #include <functional>
@@ -89,6 +93,38 @@ struct Job {
 	Pin<urmapx_path_op> pin_ops;
 };
 
+using Clock = std::chrono::steady_clock;
+inline Clock::time_point now() { return Clock::now(); }
+inline double secs(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+// thread t's share of n units split over a team of T: [part(n, t, T), part(n, t + 1, T))
+inline size_t part(size_t n, int t, int T) { return (size_t)((uint64_t)n * (uint64_t)t / (uint64_t)T); }
+
+// n bytes of fd at `off` into dst; false: an error, or the file ends first
+inline bool pread_all(int fd, char *dst, size_t n, uint64_t off) {
+	for (size_t got = 0; got < n;) {
+		const ssize_t k = pread(fd, dst + got, n - got, (off_t)(off + got));
+		if (k <= 0) return false;
+		got += (size_t)k;
+	}
+	return true;
+}
+// [off, off + n) of a file into dst, by several threads
+inline bool read_range(int fd, char *dst, uint64_t off, size_t n, int threads) {
+	std::atomic<bool> ok{true};
+#pragma omp parallel for schedule(static, 1) num_threads(threads)
+	for (int t = 0; t < threads; ++t) {
+		const size_t lo = part(n, t, threads), hi = part(n, t + 1, threads);
+		if (!pread_all(fd, dst + lo, hi - lo, off + lo)) ok.store(false);
+	}
+	return ok.load();
+}
+// number of '\n' in [c, e)
+inline size_t count_nl(const char *c, const char *e) {
+	size_t n = 0;
+	for (const char *nl; c < e && (nl = (const char *)memchr(c, '\n', (size_t)(e - c))); c = nl + 1) ++n;
+	return n;
+}
+
 template <class T>
 class Channel {  // bounded queue
 public:
@@ -102,19 +138,11 @@ public:
 	bool pop(T &v) {
 		std::unique_lock<std::mutex> l(m_);
 		cv_.wait(l, [&] { return !q_.empty() || closed_; });
-		if (q_.empty()) return false;
-		v = std::move(q_.front());
-		q_.pop_front();
-		cv_.notify_all();
-		return true;
+		return take(v);
 	}
 	bool try_pop(T &v) {
 		std::lock_guard<std::mutex> l(m_);
-		if (q_.empty()) return false;
-		v = std::move(q_.front());
-		q_.pop_front();
-		cv_.notify_all();
-		return true;
+		return take(v);
 	}
 	void close() {
 		std::lock_guard<std::mutex> l(m_);
@@ -123,6 +151,13 @@ public:
 	}
 
 private:
+	bool take(T &v) {  // under m_
+		if (q_.empty()) return false;
+		v = std::move(q_.front());
+		q_.pop_front();
+		cv_.notify_all();
+		return true;
+	}
 	std::mutex m_;
 	std::condition_variable cv_;
 	std::deque<T> q_;
@@ -134,15 +169,13 @@ private:
 struct Trace {
 	bool on = getenv("URMAPX_PIPE_TRACE") != nullptr;
 	std::mutex m;
-	std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+	Clock::time_point t0 = now();
 	struct Ev { const char *what; int lane; size_t job; double a, b; };
 	std::vector<Ev> evs;
-	double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-	void add(const char *what, int lane, size_t job, double a) {
+	void add(const char *what, int lane, size_t job, Clock::time_point since) {
 		if (!on) return;
-		const double b = ms();
 		std::lock_guard<std::mutex> l(m);
-		evs.push_back(Ev{what, lane, job, a, b});
+		evs.push_back(Ev{what, lane, job, 1e3 * secs(t0, since), 1e3 * secs(t0, now())});
 	}
 	void dump() {
 		if (!on) return;
@@ -191,19 +224,19 @@ public:
 		if (discard_) return 1;
 		if (const char *e = getenv("URMAPX_WRITE_THREADS")) return std::max(1, atoi(e));
 		if (sequential_ || fd_ < 0) return 1;
-		struct statfs fs;
-		if (fstatfs(fd_, &fs) != 0) return 1;
-		const long t = (long)fs.f_type;
-		if (t == 0x01021994L /* tmpfs */ || t == (long)0x858458f6L /* ramfs */) return 1;
-		return std::max(1, std::min(4, host_threads));
+		return in_memory() != 0 ? 1 : std::max(1, std::min(4, host_threads));
 	}
 	const char *medium() const {
 		if (discard_) return "discarded";
 		if (sequential_) return "pipe";
+		const int m = fd_ < 0 ? -1 : in_memory();
+		return m < 0 ? "file" : m ? "tmpfs" : "disk file system";
+	}
+	// 1: the file lives on tmpfs or ramfs, 0: on another file system, -1: not known
+	int in_memory() const {
 		struct statfs fs;
-		if (fd_ < 0 || fstatfs(fd_, &fs) != 0) return "file";
-		const long t = (long)fs.f_type;
-		return (t == 0x01021994L || t == (long)0x858458f6L) ? "tmpfs" : "disk file system";
+		if (fstatfs(fd_, &fs) != 0) return -1;
+		return fs.f_type == 0x01021994L /* tmpfs */ || (long)fs.f_type == (long)0x858458f6L /* ramfs */;
 	}
 	// makes the file at least `end` bytes long (pieces below `end` can then be written from several threads at once)
 	bool reserve(uint64_t end) {
@@ -238,7 +271,7 @@ public:
 					char *dst = m + (off - a);
 #pragma omp parallel for schedule(static, 1) num_threads(threads)
 					for (int t = 0; t < threads; ++t) {
-						const size_t lo = n * (size_t)t / (size_t)threads, hi = n * (size_t)(t + 1) / (size_t)threads;
+						const size_t lo = part(n, t, threads), hi = part(n, t + 1, threads);
 						memcpy(dst + lo, p + lo, hi - lo);
 					}
 					munmap(m, len);
@@ -249,7 +282,7 @@ public:
 		std::atomic<bool> ok{true};
 #pragma omp parallel for schedule(static, 1) num_threads(threads)
 		for (int t = 0; t < threads; ++t) {
-			const size_t lo = n * (size_t)t / (size_t)threads, hi = n * (size_t)(t + 1) / (size_t)threads;
+			const size_t lo = part(n, t, threads), hi = part(n, t + 1, threads);
 			size_t done = lo;
 			while (done < hi) {
 				ssize_t w = pwrite(fd_, p + done, hi - done, (off_t)(off + done));
@@ -457,12 +490,7 @@ uint64_t find_record_start(int fd, uint64_t from, uint64_t fsize) {
 	for (size_t win = 1u << 16; win <= (8u << 20); win *= 4) {
 		const size_t len = (size_t)std::min<uint64_t>(win, fsize - from);
 		w.resize(len);
-		size_t got = 0;
-		while (got < len) {
-			ssize_t k = pread(fd, w.data() + got, len - got, (off_t)(from + got));
-			if (k <= 0) return 0;
-			got += (size_t)k;
-		}
+		if (!pread_all(fd, w.data(), len, from)) return 0;
 		const char *b = w.data(), *e = b + len;
 		for (const char *nl = (const char *)memchr(b, '\n', len); nl && nl + 1 < e; nl = (const char *)memchr(nl + 1, '\n', (size_t)(e - nl - 1))) {
 			if (nl[1] != '@') continue;
@@ -529,19 +557,7 @@ public:
 		if (!gz_) {
 			const size_t n = (size_t)std::min<uint64_t>(cap, csize_ - cpos_);
 			if (n == 0) { eof_ = true; return 0; }
-			std::atomic<bool> ok{true};
-			if (threads < 1) threads = 1;
-#pragma omp parallel for schedule(static, 1) num_threads(threads)
-			for (int t = 0; t < threads; ++t) {
-				const size_t lo = n * (size_t)t / (size_t)threads, hi = n * (size_t)(t + 1) / (size_t)threads;
-				size_t done = lo;
-				while (done < hi) {
-					const ssize_t k = pread(fd_, dst + done, hi - done, (off_t)(cpos_ + done));
-					if (k <= 0) { ok.store(false); break; }
-					done += (size_t)k;
-				}
-			}
-			if (!ok) { bad_ = true; return 0; }
+			if (!read_range(fd_, dst, cpos_, n, std::max(1, threads))) { bad_ = true; return 0; }
 			cpos_ += n;
 			return n;
 		}
@@ -693,14 +709,7 @@ uint64_t count_newlines(int fd, uint64_t from, uint64_t to, int threads, std::ve
 			if (r <= 0) break;
 			have += (size_t)r;
 		}
-		const char *c = buf.data(), *e = c + have;
-		uint64_t n = 0;
-		while (c < e) {
-			const char *nl = (const char *)memchr(c, '\n', (size_t)(e - c));
-			if (!nl) break;
-			++n;
-			c = nl + 1;
-		}
+		const uint64_t n = count_nl(buf.data(), buf.data() + have);
 		total += n;
 		if (per_piece) (*per_piece)[(size_t)k] = n;
 	}
@@ -815,52 +824,164 @@ bool pin_to(const DevicePlace &P) { return P.ok && sched_setaffinity(0, sizeof P
 // A pipeline thread that pinned itself hands its OpenMP workers back unpinned: the workers of its team inherited its
 // narrowed mask when they were made, libomp returns them to a pool the CALLER's later parallel regions draw from, and those would
 // then run on one socket.  Run by the pinned thread as its last act: every thread of its team takes the mask the caller had.
-void unpin_team(bool was_pinned, const cpu_set_t &caller_mask, int team) {
-	if (!was_pinned) return;
+struct Unpin {
+	bool was_pinned;
+	const cpu_set_t &caller_mask;
+	int team;
+	~Unpin() {
+		if (!was_pinned) return;
 #pragma omp parallel num_threads(team > 0 ? team : 1)
-	(void)sched_setaffinity(0, sizeof caller_mask, &caller_mask);
+		(void)sched_setaffinity(0, sizeof caller_mask, &caller_mask);
+	}
+};
+void omp_team(int n) { omp_workers_sleep_when_idle(); omp_set_num_threads(n); }
+void say(char *err, size_t errcap, const std::string &s) {
+	if (err && errcap) snprintf(err, errcap, "%s", s.c_str());
 }
-
-int map_files_impl(urmapx_index *I, const urmapx_map_options *opt, const InputRange &range, const char *fastq1, const char *fastq2,
-                   const char *samout, const char *tabout, urmapx_map_report *report, char *err, size_t errcap) {
-	auto say = [&](const std::string &s) {
-		if (err && errcap) snprintf(err, errcap, "%s", s.c_str());
-	};
-	if (err && errcap) err[0] = 0;
-	if (!I || !opt || !fastq1) return URMAPX_E_ARG;
-	const bool paired = fastq2 != nullptr;
-	const int gpus = opt->gpus > 0 ? opt->gpus : 1, streams = opt->streams > 0 ? opt->streams : 2;
-	if (gpus > 64 || streams > 8) { say("gpus must be 1..64, streams 1..8"); return URMAPX_E_ARG; }
-	const uint32_t batch = opt->batch ? opt->batch : (1u << 18);
-	const unsigned minq = paired ? opt->minq : 10;  // only cmd_map2 reads -minq (map2.cpp:76); -map keeps State1::m_Minq = 10
-	// URMAPX_FORCE_DEVICE=d (test aid): every lane runs on physical device d, so that the N-device code path can be
-	// exercised on a machine with one GPU
+// host threads for FASTQ parsing and SAM formatting (the mapping itself runs on the GPU)
+int host_threads_of(const urmapx_map_options &o) {
+	return o.host_threads > 0 ? o.host_threads : std::min(16, std::max(1, (int)std::thread::hardware_concurrency()));
+}
+// URMAPX_FORCE_DEVICE=d (test aid): every lane runs on physical device d, so that the N-device code path can be
+// exercised on a machine with one GPU
+int phys_device(const urmapx_map_options &o, int g) {
 	const char *forced = getenv("URMAPX_FORCE_DEVICE");
-	auto phys = [&](int g) { return forced ? atoi(forced) : opt->first_gpu + g; };
-	urmapx_params P;
-	int rc = urmapx_params_for_method((opt->veryfast && !paired) ? 7 : 6, &P);  // -map2 always uses method 6 (map2.cpp:15-16)
-	if (rc) return rc;
-	// one replica of the index per device (uploaded concurrently), K mapping contexts on each
-	const int n_lanes = gpus * streams;
-	std::vector<urmapx_index *> replicas((size_t)gpus, nullptr);
-	std::vector<urmapx_ctx *> ctxs((size_t)n_lanes, nullptr);
-	std::vector<urmapx_text *> texts((size_t)n_lanes, nullptr);  // a lane's text stage: from the pool, or made by the lane's thread
-	const bool pool_lanes = LanePool::enabled();
-	const bool lane_veryfast = paired && opt->veryfast, lane_pair_info = paired && tabout != nullptr;
-	bool run_ok = false;  // set at the end of a run without failure: only then are the lanes worth keeping
-	auto release = [&]() {
-		for (int l = 0; l < n_lanes; ++l) {
-			urmapx_ctx *C = ctxs[(size_t)l];
-			urmapx_text *T = texts[(size_t)l];
-			// (a lane of the caller's own index only: the other devices' replicas are closed below.  set_deferred refuses while a text is on its way)
-			if (C && pool_lanes && run_ok && l % gpus == 0 && replicas[0] == I && (!T || urmapx_text_set_deferred(T, 0) == URMAPX_OK))
-				LanePool::get().give(PooledLane{I, phys(0), P, lane_veryfast, lane_pair_info, C, T, env_knobs()});
-			else LanePool::destroy(PooledLane{I, 0, P, false, false, C, T, 0});
-			ctxs[(size_t)l] = nullptr; texts[(size_t)l] = nullptr;
+	return forced ? atoi(forced) : o.first_gpu + g;
+}
+std::string shard_name(const char *path, int s) { return std::string(path) + "." + std::to_string(s); }
+void create_empty(const std::string &path) { if (FILE *f = fopen(path.c_str(), "wb")) fclose(f); }
+bool is_gz_name(const char *path) { const size_t l = strlen(path); return l > 3 && !strcmp(path + l - 3, ".gz"); }
+// a non-empty regular file that is neither .gz nor standard input: its descriptor and size, else -1
+int open_plain(const char *path, uint64_t &size) {
+	if (is_gz_name(path) || !strcmp(path, "-")) return -1;
+	const int fd = open(path, O_RDONLY);
+	struct stat st;
+	if (fd >= 0 && (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size == 0)) { close(fd); return -1; }
+	if (fd >= 0) size = (uint64_t)st.st_size;
+	return fd;
+}
+// '\n' count of each of `threads` slices of p[0, n), and their sum
+size_t count_lines(const char *p, size_t n, int threads, std::vector<size_t> &per) {
+	per.assign((size_t)threads, 0);
+#pragma omp parallel for schedule(static, 1) num_threads(threads)
+	for (int t = 0; t < threads; ++t) per[(size_t)t] = count_nl(p + part(n, t, threads), p + part(n, t + 1, threads));
+	size_t lines = 0;
+	for (size_t k : per) lines += k;
+	return lines;
+}
+// offset behind the `lines`-th '\n' of p[0, n), given count_lines' counts of its slices; 0: p holds fewer (or none is asked for)
+size_t nth_line_end(const char *p, size_t n, const std::vector<size_t> &per, size_t lines) {
+	const int T = (int)per.size();
+	size_t cum = 0;
+	for (int t = 0; t < T && lines > 0; ++t) {
+		if (cum + per[(size_t)t] >= lines) {  // the chunk ends in this slice: walk to its last '\n'
+			const char *c = p + part(n, t, T), *e = p + part(n, t + 1, T);
+			for (size_t need = lines - cum; need; --need) c = (const char *)memchr(c, '\n', (size_t)(e - c)) + 1;
+			return (size_t)(c - p);
 		}
-		for (int g = 1; g < gpus; ++g) urmapx_index_close(replicas[(size_t)g]);
-	};
-	{
+		cum += per[(size_t)t];
+	}
+	return 0;
+}
+// a larger page-locked buffer for the job's input, holding the first `keep` bytes and the `keep2` bytes at `at2` of the old one
+bool regrow(TextJob &j, size_t want, size_t keep, size_t at2 = 0, size_t keep2 = 0) {
+	size_t ncap = 0;
+	char *nb = HostPool::get().acquire(want, ncap);
+	if (!nb) return false;
+	if (keep) memcpy(nb, j.in, keep);
+	if (keep2) memcpy(nb + at2, j.in + at2, keep2);
+	HostPool::get().release(j.in, j.in_cap);
+	j.in = nb; j.in_cap = ncap;
+	return true;
+}
+// The mate file's chunk of a text job as the reader cuts it: it lies in the job's buffer behind the first file's `keep` bytes, from
+// `pad` on (a multiple of 4096)
+struct MateChunk {
+	TextJob &j;
+	size_t keep, pad;
+	size_t have = 0, n2 = 0;  // mate bytes read into the buffer; of them the chunk's: as many lines as the first file's chunk holds
+	bool found = false, give_up = false;
+	char *dst() const { return j.in + pad; }
+	// the mate chunk outgrew the buffer (its records are longer than the first file's were so far): a larger one, with what has been read
+	bool grow(size_t room) { return regrow(j, pad + room, keep, pad, have); }
+	void end_at(size_t n) { n2 = n; found = true; }
+	// the cut stands: the job gets the chunk, and the next buffer is sized by the ratio seen
+	void hand_to_job(double &bytes2_per_byte1) {
+		j.in2 = dst(); j.nbytes2 = n2;
+		if (keep && n2) bytes2_per_byte1 = (double)n2 / (double)keep;
+	}
+};
+// the fields of a report that add up over the shards of a sharded run
+using Rep = urmapx_map_report;
+constexpr uint64_t Rep::*kReportCounts[] = {&Rep::reads, &Rep::mapped_q, &Rep::mapped_lowq, &Rep::unmapped, &Rep::unsupported, &Rep::input_bytes, &Rep::sam_text_bytes, &Rep::sam_file_bytes};
+constexpr double Rep::*kReportTimes[] = {&Rep::parse_s, &Rep::gpu_s, &Rep::format_s, &Rep::write_s, &Rep::dev_h2d_s, &Rep::dev_parse_s, &Rep::dev_map_s, &Rep::dev_format_s,
+	&Rep::dev_d2h_s, &Rep::dev_map_search_s, &Rep::dev_map_dp_s, &Rep::map_enqueue_s};
+
+// One run of one pipeline (urmapx_map_files, or one shard of it): what its stages share.  open() fills it, the text phase and the host phase
+// run on it one after the other, finish() ends the files and reports.  While a phase's threads run, a member without a note is only read.
+struct Run {
+	urmapx_index *const I;
+	const urmapx_map_options &opt;
+	const InputRange &range;
+	const char *const fastq1, *const fastq2, *const samout, *const tabout;
+	// constants derived from the options
+	const bool paired = fastq2 != nullptr;
+	const int gpus = opt.gpus > 0 ? opt.gpus : 1, streams = opt.streams > 0 ? opt.streams : 2, n_lanes = gpus * streams;
+	const int host_threads = host_threads_of(opt);
+	const uint32_t batch = opt.batch ? opt.batch : (1u << 18);
+	const unsigned minq = paired ? opt.minq : 10;  // only cmd_map2 reads -minq (map2.cpp:76); -map keeps State1::m_Minq = 10
+	const bool have_sam = samout != nullptr;
+	const bool bam = opt.bam != 0 && have_sam;  // -bamout: BAM records where the SAM text was, always inside BGZF members
+	const bool bgzf = (opt.bgzf != 0 || bam) && have_sam;
+	const bool pool_lanes = LanePool::enabled(), lane_veryfast = paired && opt.veryfast, lane_pair_info = paired && tabout != nullptr;
+	urmapx_params P;
+	// one replica of the index per device (uploaded concurrently), K mapping contexts on each
+	std::vector<urmapx_index *> replicas;
+	std::vector<urmapx_ctx *> ctxs;
+	std::vector<urmapx_text *> texts;  // a lane's text stage: from the pool, or made by the lane's thread -- [l] is written by text lane l
+	bool run_ok = false;  // set at the end of a run without failure: only then are the lanes worth keeping
+	// where each device hangs (NUMA node of its PCI function): lane threads run there; a pipeline whose devices share one node -- every
+	// shard of a sharded run on a two-socket node -- has its reader and writer there too
+	std::vector<DevicePlace> places;
+	bool one_node = false;
+	cpu_set_t caller_mask;
+	// this is a library call: the caller's OpenMP setting comes back at the end
+	// (the calling thread's block time comes back too -- kmp_set_blocktime(0) applies to the teams THIS thread starts later)
+	const int omp_threads_before = omp_get_max_threads(), omp_blocktime_before = omp_idle_blocktime();
+	FileSink sink;
+	std::unique_ptr<FILE, int (*)(FILE *)> ftab{nullptr, fclose};  // -tabbedout (outfiles.cpp:7-12): State2::OutputTab2's line per pair; only -map2 writes it
+	FastqReader rd, rd2;  // the host reader's and the mate reader's (host phase)
+	Failure fail;
+	Trace trace;
+	Clock::time_point t1;
+	// The running totals, as they are reported.  Written while threads run by:
+	//   reads .. unsupported, input_bytes, sam_text_bytes, dev_*_s, map_enqueue_s   the text writer; the host formatter
+	//   sam_file_bytes   the same two: it is the offset in samout at which the next piece goes (the header's size before the first)
+	//   parse_s          the text reader; the host reader
+	//   write_s          the text writer; the flusher
+	//   gpu_s            every lane, under lane_time_lock
+	//   format_s         the text lanes (tab lines), under lane_time_lock; the host formatter
+	urmapx_map_report rep{};
+	std::mutex lane_time_lock;
+	~Run() {
+		close();
+		omp_set_num_threads(omp_threads_before);
+		omp_set_idle_blocktime(omp_blocktime_before);
+	}
+	int phys(int g) const { return phys_device(opt, g); }
+	int failed(int rc, std::string &msg, const std::string &why) const { msg = why; return rc; }
+	void add_lane_time(double Rep::*stage, Clock::time_point since) {
+		std::lock_guard<std::mutex> g(lane_time_lock);
+		rep.*stage += secs(since, now());
+	}
+	void cannot_write_sam() { fail.raise(URMAPX_E_IO, std::string("Error writing ") + samout); }
+	int open(std::string &msg) {
+		if (gpus > 64 || streams > 8) return failed(URMAPX_E_ARG, msg, "gpus must be 1..64, streams 1..8");
+		int rc = urmapx_params_for_method((opt.veryfast && !paired) ? 7 : 6, &P);  // -map2 always uses method 6 (map2.cpp:15-16)
+		if (rc) return rc;
+		replicas.assign((size_t)gpus, nullptr);
+		ctxs.assign((size_t)n_lanes, nullptr);
+		texts.assign((size_t)n_lanes, nullptr);
 		std::vector<int> rcs((size_t)gpus, 0);
 		std::vector<std::thread> up;
 		for (int g = 0; g < gpus; ++g)
@@ -870,891 +991,802 @@ int map_files_impl(urmapx_index *I, const urmapx_map_options *opt, const InputRa
 			});
 		for (auto &t : up) t.join();
 		for (int g = 0; g < gpus; ++g)
-			if (rcs[(size_t)g]) { say(std::string("Uploading index to the GPU: ") + urmapx_strerror(rcs[(size_t)g])); release(); return rcs[(size_t)g]; }
-	}
-	for (int l = 0; l < n_lanes; ++l) {
-		if (pool_lanes && l % gpus == 0 && LanePool::get().take(I, phys(0), P, lane_veryfast, lane_pair_info, ctxs[(size_t)l], texts[(size_t)l])) continue;
-		rc = urmapx_ctx_create(replicas[(size_t)(l % gpus)], phys(l % gpus), &P, &ctxs[(size_t)l]);
-		if (!rc && paired && opt->veryfast) rc = urmapx_ctx_set_pe_veryfast(ctxs[(size_t)l], 1);
-		if (!rc && paired && tabout) rc = urmapx_ctx_set_pair_info(ctxs[(size_t)l], 1);
-		if (rc) { say(std::string("Creating mapping context: ") + urmapx_strerror(rc)); release(); return rc; }
-	}
-	// where each device hangs (NUMA node of its PCI function): lane threads run there; a pipeline whose devices share one node -- every
-	// shard of a sharded run on a two-socket node -- has its reader and writer there too
-	std::vector<DevicePlace> places((size_t)gpus);
-	for (int g = 0; g < gpus; ++g) places[(size_t)g] = place_of_device(phys(g));
-	bool one_node = places[0].ok;
-	for (int g = 1; g < gpus; ++g) one_node = one_node && places[(size_t)g].ok && places[(size_t)g].node == places[0].node;
-	std::string placement;
-	for (int g = 0; g < gpus; ++g)
-		placement += (g ? " gpu" : "gpu") + std::to_string(phys(g)) + (places[(size_t)g].ok ? "@node" + std::to_string(places[(size_t)g].node) : std::string("@any"));
-	placement += one_node ? "; reader+writer@node" + std::to_string(places[0].node) : std::string("; reader+writer@any");
-	// host threads for FASTQ parsing and SAM formatting (the mapping itself runs on the GPU)
-	const int host_threads = opt->host_threads > 0 ? opt->host_threads : std::min(16, std::max(1, (int)std::thread::hardware_concurrency()));
-	const int omp_threads_before = omp_get_max_threads();  // this is a library call: the caller's OpenMP setting comes back at the end
-	// (the calling thread's block time comes back too -- kmp_set_blocktime(0) below applies to the teams THIS thread starts later)
-	struct OmpRestore { int n, blocktime; ~OmpRestore() { omp_set_num_threads(n); omp_set_idle_blocktime(blocktime); } } omp_restore{omp_threads_before, omp_idle_blocktime()};
-	omp_workers_sleep_when_idle();
-	omp_set_num_threads(host_threads);
-	cpu_set_t caller_mask;
-	CPU_ZERO(&caller_mask);
-	(void)sched_getaffinity(0, sizeof caller_mask, &caller_mask);
-	FileSink sink;
-	int write_threads_used = 1;
-	bool text_on_device = false;
-	uint64_t input_bytes = 0;  // uncompressed FASTQ bytes the text phase handed to the device
-	std::string medium_name = "file";
-	const bool have_sam = samout != nullptr;
-	uint64_t sam_off = 0;
-	const bool bam = opt->bam != 0 && have_sam;  // -bamout: BAM records where the SAM text was, always inside BGZF members
-	const bool bgzf = (opt->bgzf != 0 || bam) && have_sam;
-	std::atomic<uint64_t> sam_text_bytes{0};  // text made; sam_off counts what goes to the file
-	Failure fail;
-	if (samout) {
-		if (opt->discard_sam) sink.open_discard();
-		else if (!sink.open(samout)) { say(std::string("Cannot create ") + samout); release(); return URMAPX_E_IO; }
-		if (range.header || bam) {  // (every shard of a BAM run is a BAM file: each has the header block)
-			std::string hdr;
-			if (bam) append_bam_header(hdr, I, opt->cmdline);
-			else append_sam_header_text(hdr, I, opt->cmdline);
-			sam_text_bytes += hdr.size();
-			if (bgzf && !bgzf_members(hdr)) { say("out of memory"); release(); return URMAPX_E_NOMEM; }  // (members of its own: the chunks' come from the device)
-			if (!sink.write_at(hdr.data(), hdr.size(), 0, 1)) { say(std::string("Cannot write ") + samout); release(); return URMAPX_E_IO; }
-			sam_off = hdr.size();
+			if (rcs[(size_t)g]) return failed(rcs[(size_t)g], msg, std::string("Uploading index to the GPU: ") + urmapx_strerror(rcs[(size_t)g]));
+		for (int l = 0; l < n_lanes; ++l) {
+			if (pool_lanes && l % gpus == 0 && LanePool::get().take(I, phys(0), P, lane_veryfast, lane_pair_info, ctxs[(size_t)l], texts[(size_t)l])) continue;
+			rc = urmapx_ctx_create(replicas[(size_t)(l % gpus)], phys(l % gpus), &P, &ctxs[(size_t)l]);
+			if (!rc && paired && opt.veryfast) rc = urmapx_ctx_set_pe_veryfast(ctxs[(size_t)l], 1);
+			if (!rc && paired && tabout) rc = urmapx_ctx_set_pair_info(ctxs[(size_t)l], 1);
+			if (rc) return failed(rc, msg, std::string("Creating mapping context: ") + urmapx_strerror(rc));
 		}
-		medium_name = sink.medium();
-	}
-	// -tabbedout (outfiles.cpp:7-12): State2::OutputTab2's line per pair; only -map2 writes it
-	FILE *ftab = nullptr;
-	if (tabout) {
-		ftab = fopen(tabout, "wb");
-		if (!ftab) { say(std::string("Cannot create ") + tabout); release(); return URMAPX_E_IO; }
-	}
-	FastqReader rd, rd2;
-	{
+		places.resize((size_t)gpus);
+		for (int g = 0; g < gpus; ++g) places[(size_t)g] = place_of_device(phys(g));
+		one_node = places[0].ok;
+		for (int g = 1; g < gpus; ++g) one_node = one_node && places[(size_t)g].ok && places[(size_t)g].node == places[0].node;
+		std::string placement;
+		for (int g = 0; g < gpus; ++g)
+			placement += (g ? " gpu" : "gpu") + std::to_string(phys(g)) + (places[(size_t)g].ok ? "@node" + std::to_string(places[(size_t)g].node) : std::string("@any"));
+		placement += one_node ? "; reader+writer@node" + std::to_string(places[0].node) : std::string("; reader+writer@any");
+		snprintf(rep.placement, sizeof rep.placement, "%s", placement.c_str());
+		omp_team(host_threads);
+		CPU_ZERO(&caller_mask);
+		(void)sched_getaffinity(0, sizeof caller_mask, &caller_mask);
+		rep.host_threads = host_threads; rep.lanes = n_lanes; rep.write_threads = 1; rep.shards = 1;
+		if (samout) {
+			if (opt.discard_sam) sink.open_discard();
+			else if (!sink.open(samout)) return failed(URMAPX_E_IO, msg, std::string("Cannot create ") + samout);
+			if (range.header || bam) {  // (every shard of a BAM run is a BAM file: each has the header block)
+				std::string hdr;
+				if (bam) append_bam_header(hdr, I, opt.cmdline);
+				else append_sam_header_text(hdr, I, opt.cmdline);
+				rep.sam_text_bytes += hdr.size();
+				if (bgzf && !bgzf_members(hdr)) return failed(URMAPX_E_NOMEM, msg, "out of memory");  // (members of its own: the chunks' come from the device)
+				if (!sink.write_at(hdr.data(), hdr.size(), 0, 1)) return failed(URMAPX_E_IO, msg, std::string("Cannot write ") + samout);
+				rep.sam_file_bytes = hdr.size();
+			}
+		}
+		snprintf(rep.medium, sizeof rep.medium, "%s", have_sam ? sink.medium() : "none");
+		if (tabout) {
+			ftab.reset(fopen(tabout, "wb"));
+			if (!ftab) return failed(URMAPX_E_IO, msg, std::string("Cannot create ") + tabout);
+		}
 		std::string e;
-		if (!rd.open(fastq1, e) || (paired && !rd2.open(fastq2, e))) {
-			say(e);
-			if (ftab) fclose(ftab);
-			release();
-			return URMAPX_E_IO;
+		if (!rd.open(fastq1, e) || (paired && !rd2.open(fastq2, e))) return failed(URMAPX_E_IO, msg, e);
+		if (range.on) {  // the host reader, should it be needed, starts and stops where the shard does
+			if (!rd.resume_at(range.lo[0], range.lines_before) || (paired && !rd2.resume_at(range.lo[1], range.lines_before)))
+				return failed(URMAPX_E_IO, msg, std::string("Cannot read a part of ") + fastq1);
+			rd.set_limit(range.hi[0]);
+			if (paired) rd2.set_limit(range.hi[1]);
+			if (range.lazy_lines) rd.set_lazy_line_base(range.lazy_lines);
 		}
+		t1 = now();
+		trace.t0 = t1;
+		return 0;
 	}
-	if (range.on) {  // the host reader, should it be needed, starts and stops where the shard does
-		if (!rd.resume_at(range.lo[0], range.lines_before) || (paired && !rd2.resume_at(range.lo[1], range.lines_before))) {
-			say(std::string("Cannot read a part of ") + fastq1);
-			if (ftab) fclose(ftab);
-			release();
-			return URMAPX_E_IO;
+	// the tab file, then the lanes -- back to the pool or destroyed -- and only then the other devices' replicas
+	void close() {
+		ftab.reset();
+		for (size_t l = 0; l < ctxs.size(); ++l) {
+			urmapx_ctx *C = ctxs[l];
+			urmapx_text *T = texts[l];
+			// (a lane of the caller's own index only: the other devices' replicas are closed below.  set_deferred refuses while a text is on its way)
+			if (C && pool_lanes && run_ok && l % (size_t)gpus == 0 && replicas[0] == I && (!T || urmapx_text_set_deferred(T, 0) == URMAPX_OK))
+				LanePool::get().give(PooledLane{I, phys(0), P, lane_veryfast, lane_pair_info, C, T, env_knobs()});
+			else LanePool::destroy(PooledLane{I, 0, P, false, false, C, T, 0});
 		}
-		rd.set_limit(range.hi[0]);
-		if (paired) rd2.set_limit(range.hi[1]);
-		if (range.lazy_lines) rd.set_lazy_line_base(range.lazy_lines);
+		for (size_t g = 1; g < replicas.size(); ++g) urmapx_index_close(replicas[g]);
+		ctxs.clear(); texts.clear(); replicas.clear();  // (the destructor's pass finds nothing)
 	}
-	const auto t1 = std::chrono::steady_clock::now();
-	Trace trace;
-	unsigned long long n_reads = 0, n_accept = 0, n_reject = 0, n_nohit = 0, n_unsupported = 0;
-	double t_parse = 0, t_gpu = 0, t_format = 0, t_write = 0;  // busy seconds per stage
-	double dev_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // a lane's stream time by events: copy in, parse, map, SAM text, copy out (text phase)
-	auto now = [] { return std::chrono::steady_clock::now(); };
-	auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-	std::mutex gpu_time_lock;
+	int finish(urmapx_map_report *report, std::string &msg) {
+		if (bgzf && !fail.set.load()) {  // htslib's empty member: the file is complete
+			std::string eof;
+			(void)bgzf_members(eof, 1);
+			if (!sink.write_at(eof.data(), eof.size(), rep.sam_file_bytes, 1)) cannot_write_sam();
+			rep.sam_file_bytes += eof.size();
+		}
+		if (have_sam && !sink.finish(rep.sam_file_bytes)) cannot_write_sam();
+		ftab.reset();  // (inside the run's clock; the lanes are let go outside it)
+		const auto t2 = now();
+		range.t_begin = std::chrono::duration<double>(t1.time_since_epoch()).count();
+		range.t_end = std::chrono::duration<double>(t2.time_since_epoch()).count();
+		trace.dump();
+		run_ok = !fail.set.load();
+		close();
+		if (report) {
+			rep.seconds = secs(t1, t2);
+			memcpy(&rep.shard_scan_s, &report->shard_scan_s, sizeof rep.shard_scan_s);  // the sharded caller's field (alloc_* are filled by urmapx_map_files afterwards)
+			*report = rep;
+		}
+		if (fail.set.load()) return failed(fail.code, msg, fail.msg);
+		return rep.unsupported ? URMAPX_E_UNSUPPORTED : URMAPX_OK;
+	}
+};
 
-	// ---- text phase: reads from plain files, FASTQ bytes -> device -> SAM bytes ----
-	bool host_phase = true;
-	{
-		auto open_plain = [&](const char *path, uint64_t &size) {  // a regular file that is not .gz, else -1
-			const size_t l = strlen(path);
-			if ((l > 3 && !strcmp(path + l - 3, ".gz")) || !strcmp(path, "-")) return -1;
-			const int fd = open(path, O_RDONLY);
-			struct stat st;
-			if (fd >= 0 && (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size == 0)) { close(fd); return -1; }
-			if (fd >= 0) size = (uint64_t)st.st_size;
-			return fd;
-		};
-		uint64_t fsize = 0, fsize2 = 0;
-		int fq = -1, fq2 = -1;
+// ---- text phase: reads from plain files, FASTQ bytes -> device -> SAM bytes ----
+// Threads: reader (stream or plain file), a lane per context, writer.  Chunk b: free_jobs -> reader -> parsed[b mod lanes] -> lane -> mapped[b mod lanes] -> writer.
+struct TextPhase {
+	using TextChannel = Channel<std::unique_ptr<TextJob>>;
+	Run &R;
+	std::vector<std::unique_ptr<TextChannel>> parsed, mapped;
+	const int n_jobs = 3 * R.n_lanes + 2;  // per lane: one waiting for it, one being mapped, one whose text is crossing PCIe; reader, writer
+	TextChannel free_jobs{(size_t)n_jobs};
+	int fq = -1, fq2 = -1;
+	uint64_t fsize = 0, fsize2 = 0;
+	SeqSource src1, src2;
+	bool streamed = false;
+	size_t chunk_bytes = 0;
+	const int read_threads = std::max(1, R.host_threads / 2);
+	// write() calls on one file take turns (inode lock): more threads only add hand-overs
+	const int write_threads = R.sink.writer_threads(R.host_threads);
+	std::atomic<bool> stop{false};  // set by the writer: a chunk was handed back
+	// No page-locked memory for a chunk (memlock limit, little host memory), or none on the device for the text kernels:
+	// the text phase ends there and the host reader / formatter, which need neither, continue from that chunk.
+	std::atomic<bool> nomem{false};
+	// -- the reader thread's; read by leaves_work() after the joins --
+	uint64_t off = R.range.on ? R.range.lo[0] : 0, off2 = R.range.on ? R.range.lo[1] : 0;  // first byte of each file the reader did not hand to a lane
+	bool stream_done = false;  // streamed input: the reader handed every byte of the input(s) to a lane
+	// streamed input: bytes read from each source and not handed to a lane yet (behind the last cut; a whole buffer the
+	// reader gave up on).  Pipes: they go to the host reader in front of the rest of the pipe, behind pipe_back.
+	std::vector<char> carry, carry2;
+	double bytes2_per_byte1 = 1.0;
+	std::vector<size_t> per;
+	// -- the writer thread's; read by leaves_work() after the joins --
+	bool handed_back = false;
+	uint64_t resume_off = 0, resume_off2 = 0, lines_done = R.range.on ? R.range.lines_before : 0;  // lines_done: per file
+	std::vector<char> pipe_back, pipe_back2;
+	bool going() const { return !stop.load() && !R.fail.set.load() && !nomem.load(); }
+	// false: this input does not take the text road (no SAM wanted, a tab file without pairs, URMAPX_HOST_TEXT, a file that cannot be opened)
+	bool open_input() {
+		// -tabbedout (pairs only): the SAM text is made on the device all the same; the lines of the tab file are formatted by
+		// host threads from the chunk's results and pair records (urmapx_text_fetch_pairs), with the labels read in place
+		if (!R.have_sam || (R.ftab && !R.paired) || getenv("URMAPX_HOST_TEXT")) return false;
 		// .gz input: the same phase with the chunks cut out of the inflated stream (SeqSource).  A pipe (FIFO, standard input)
 		// is streamed the same way; it has no way back to a chunk the device parser hands back, so the bytes of that chunk
 		// and of everything read behind it are kept and given to the host reader in front of the rest of the pipe.
-		auto is_gz_name = [](const char *path) { const size_t l = strlen(path); return l > 3 && !strcmp(path + l - 3, ".gz"); };
-		SeqSource src1, src2;
-		bool streamed = false;
-		// -tabbedout (pairs only): the SAM text is made on the device all the same; the lines of the tab file are formatted by
-		// host threads from the chunk's results and pair records (urmapx_text_fetch_pairs), with the labels read in place
-		if (have_sam && (!ftab || paired) && !getenv("URMAPX_HOST_TEXT")) {
-			auto open_src = [&](SeqSource &src, FastqReader &r, const char *path) {
-				if (r.is_pipe()) return src.open_pipe(r.fd());
-				return strcmp(path, "-") != 0 && src.open(path, is_gz_name(path));
-			};
-			if (is_gz_name(fastq1) || (paired && is_gz_name(fastq2)) || rd.is_pipe() || (paired && rd2.is_pipe())) {
-				streamed = open_src(src1, rd, fastq1) && (!paired || open_src(src2, rd2, fastq2));
-				src1.set_gz_threads(host_threads);  // a plain gzip stream: the inflater is what the run waits for
-				src2.set_gz_threads(host_threads);
-			} else {
-				fq = open_plain(fastq1, fsize);
-				if (fq >= 0 && paired) {
-					fq2 = open_plain(fastq2, fsize2);
-					if (fq2 < 0) { close(fq); fq = -1; }
-				}
-				if (fq >= 0 && range.on) { fsize = range.hi[0]; fsize2 = range.hi[1]; }  // a shard: its part of the file(s) is the file
-			}
+		auto open_src = [](SeqSource &src, FastqReader &r, const char *path) {
+			if (r.is_pipe()) return src.open_pipe(r.fd());
+			return strcmp(path, "-") != 0 && src.open(path, is_gz_name(path));
+		};
+		if (is_gz_name(R.fastq1) || (R.paired && is_gz_name(R.fastq2)) || R.rd.is_pipe() || (R.paired && R.rd2.is_pipe())) {
+			streamed = open_src(src1, R.rd, R.fastq1) && (!R.paired || open_src(src2, R.rd2, R.fastq2));
+			src1.set_gz_threads(R.host_threads);  // a plain gzip stream: the inflater is what the run waits for
+			src2.set_gz_threads(R.host_threads);
+			return streamed;
 		}
-		if (fq >= 0 || streamed) {
-			size_t chunk_bytes = (size_t)std::min(330.0 * (double)(paired ? std::max(1u, batch / 2) : batch), 536870912.0);  // streamed: a 150-base record
-			if (streamed && !opt->batch && src1.is_gz()) {
-				// no -batch given: larger chunks for a large file, as for plain input below (FASTQ text is 4-5 times its gzip size)
-				const double est = 4.0 * (double)src1.compressed_size() / 330.0 * (paired ? 2.0 : 1.0);
-				const double reads = std::min(524288.0, std::max((double)batch, est / (4.0 * (double)n_lanes)));
-				chunk_bytes = (size_t)std::min(330.0 * (paired ? std::max(1.0, reads / 2) : reads), 536870912.0);
+		fq = open_plain(R.fastq1, fsize);
+		if (fq >= 0 && R.paired) {
+			fq2 = open_plain(R.fastq2, fsize2);
+			if (fq2 < 0) { close(fq); fq = -1; }
+		}
+		if (fq >= 0 && R.range.on) { fsize = R.range.hi[0]; fsize2 = R.range.hi[1]; }  // a shard: its part of the file(s) is the file
+		return fq >= 0;
+	}
+	void choose_chunk_bytes() {
+		const bool paired = R.paired;
+		const uint32_t batch = R.batch;
+		chunk_bytes = (size_t)std::min(330.0 * (double)(paired ? std::max(1u, batch / 2) : batch), 536870912.0);  // streamed: a 150-base record
+		if (streamed && !R.opt.batch && src1.is_gz()) {
+			// no -batch given: larger chunks for a large file, as for plain input below (FASTQ text is 4-5 times its gzip size)
+			const double est = 4.0 * (double)src1.compressed_size() / 330.0 * (paired ? 2.0 : 1.0);
+			const double reads = std::min(524288.0, std::max((double)batch, est / (4.0 * (double)R.n_lanes)));
+			chunk_bytes = (size_t)std::min(330.0 * (paired ? std::max(1.0, reads / 2) : reads), 536870912.0);
+		}
+		if (streamed) return;
+		// `batch` reads (pairs: batch / 2 of each file) at the record size the head of the file shows
+		std::vector<char> head(1u << 16);
+		const ssize_t k = pread(fq, head.data(), head.size(), 0);
+		size_t nl = 0, last = 0;
+		for (ssize_t i = 0; i < k; ++i)
+			if (head[(size_t)i] == '\n' && (++nl & 3) == 0) last = (size_t)i + 1;
+		const double rec = nl >= 4 ? (double)last / (double)(nl / 4) : 512.0;
+		double reads_per_chunk = (double)batch;
+		if (!R.opt.batch) {
+			// no -batch given: a chunk pays 3-4 ms of fixed cost on the device (launch tails, the second pass's empty launches) --
+			// two thirds of a 262 144-read chunk's mapping time at 46 M reads/s -- so a large file is cut into larger chunks, up to
+			// 524 288 reads, as long as every lane still gets four of them (the lanes overlap each other's copies).  Measured on
+			// 10 M reads (profiles/r5/e2e_by_chunk.txt): 262 144 -> 29.2 M reads/s with the SAM text dropped, 524 288 -> 31.2 M;
+			// 1 M-read chunks need 0.7 GB of page-locked memory each, six of them outgrow the pool and the run stalls in
+			// hipHostMalloc / hipHostFree (6.5 M reads/s)
+			const double est = (double)(fsize - (R.range.on ? R.range.lo[0] : 0)) / rec * (paired ? 2.0 : 1.0);
+			reads_per_chunk = std::min(524288.0, std::max((double)batch, est / (4.0 * (double)R.n_lanes)));
+			if (const char *e = getenv("URMAPX_TEST_CHUNK_READS")) reads_per_chunk = std::max(4.0, atof(e));  // test aid: the library's own choice, small (the ramp below on a small file)
+		}
+		chunk_bytes = (size_t)std::min(std::max(rec * (paired ? std::max(1.0, reads_per_chunk / 2) : reads_per_chunk), 4096.0), 536870912.0);
+	}
+	void run() {
+		choose_chunk_bytes();
+		for (int l = 0; l < R.n_lanes; ++l) {
+			parsed.emplace_back(new TextChannel(1));
+			mapped.emplace_back(new TextChannel(1));
+		}
+		for (int k = 0; k < n_jobs; ++k) free_jobs.push(std::make_unique<TextJob>());
+		R.rep.write_threads = write_threads;
+		R.rep.text_on_device = 1;
+		std::thread treader([this] { reader(); });
+		std::thread twriter([this] { writer(); });
+		std::vector<std::thread> tlanes;
+		for (int l = 0; l < R.n_lanes; ++l) tlanes.emplace_back([this, l] { lane(l); });
+		for (auto &t : tlanes) t.join();
+		treader.join();
+		twriter.join();
+		const auto tf = now();
+		std::unique_ptr<TextJob> j;
+		while (free_jobs.try_pop(j)) j.reset();
+		R.trace.add("unpin", -1, 0, tf);
+		if (fq >= 0) close(fq);
+		if (fq2 >= 0) close(fq2);
+	}
+	// After the joins: does the host phase have work?  Then the host readers stand where the text phase stopped.
+	bool leaves_work() {
+		if (!handed_back) { resume_off = off; resume_off2 = off2; }
+		if (R.fail.set.load()) return false;
+		if (streamed ? !(handed_back || !stream_done) : !(resume_off < fsize || (R.paired && resume_off2 < fsize2))) return false;
+		// a seekable source continues at its (uncompressed) offset; a pipe with the bytes taken from it and not mapped
+		auto resume = [&](FastqReader &r, SeqSource &src, uint64_t at, std::vector<char> &back, std::vector<char> &rest) {
+			if (!streamed || !src.is_pipe()) return r.resume_at(at, lines_done);  // (a shard's reader: positioned again, same rules)
+			back.insert(back.end(), rest.begin(), rest.end());
+			return r.resume_with_prefix(std::move(back), lines_done);
+		};
+		if (!resume(R.rd, src1, resume_off, pipe_back, carry) || (R.paired && !resume(R.rd2, src2, resume_off2, pipe_back2, carry2)))
+			R.fail.raise(URMAPX_E_IO, std::string("Cannot continue reading ") + R.fastq1);
+		return !R.fail.set.load();
+	}
+	void to_lane(std::unique_ptr<TextJob> &j, size_t b, const char *what, Clock::time_point since) {
+		R.rep.parse_s += secs(since, now());
+		R.trace.add(what, -1, b, since);
+		off += j->nbytes; off2 += j->nbytes2;
+		parsed[b % (size_t)R.n_lanes]->push(std::move(j));
+	}
+	void reader() {
+		const bool pinned = R.one_node && pin_to(R.places[0]);  // the page-locked chunk buffers are first touched here
+		Unpin unpin{pinned, R.caller_mask, read_threads};
+		omp_team(read_threads);
+		if (streamed) read_stream();
+		else read_plain();
+		for (auto &c : parsed) c->close();
+	}
+	// Chunks are cut out of the inflated stream: fill the job's buffer (what the last cut left over first), cut it at its last record
+	// start, keep the rest for the next chunk.  Offsets are those of the uncompressed text: that is where the host reader (gzseek) takes
+	// over if a chunk is handed back.
+	void read_stream() {
+		bool eof1 = false, eof2 = false;
+		for (size_t b = 0; going(); ++b) {
+			if (eof1 && carry.empty()) { stream_done = !R.paired || (eof2 && carry2.empty()); break; }
+			std::unique_ptr<TextJob> j;
+			if (!free_jobs.pop(j)) break;
+			if (stop.load()) { free_jobs.push(std::move(j)); break; }
+			const auto tp0 = now();
+			(void)hipSetDevice(R.phys(0));
+			size_t area1 = chunk_bytes + chunk_bytes / 8 + carry.size() + (1u << 20);  // room for this file's chunk
+			const size_t area2 = R.paired ? (size_t)((double)area1 * bytes2_per_byte1 * 1.25) + carry2.size() + (4u << 20) : 0;
+			if (!TextJob::grow(j->in, j->in_cap, area1 + 4096 + area2)) { nomem.store(true); break; }
+			size_t n = carry.size(), cut = 0;
+			if (n) memcpy(j->in, carry.data(), n);
+			carry.clear();
+			size_t target = std::max(chunk_bytes, n + 1);
+			for (;;) {
+				while (n < target && !eof1) {
+					const size_t k = src1.read(j->in + n, std::min(area1, target + (64u << 10)) - n, read_threads);
+					if (k == 0) eof1 = true;
+					n += k;
+					// a gzip stream's reader hands out whole rounds written straight into this buffer and returns short when the next round
+					// would not fit (pgzip.cpp): a chunk that is three quarters full is a chunk -- asking for the rest would cost a copy of a whole round
+					if (src1.returns_whole_rounds() && n >= target - target / 4) break;
+				}
+				if (src1.failed()) break;
+				cut = eof1 ? n : last_record_start(j->in, n);
+				if (cut || eof1) break;
+				target *= 2;  // less than one record start in the buffer: records of a size beyond reason, or not FASTQ
+				if (target > (1u << 30)) break;
+				if (target + (64u << 10) > area1) {
+					area1 = target + target / 8 + (1u << 20);
+					if (!regrow(*j, area1 + 4096 + area2, n)) { nomem.store(true); break; }
+				}
 			}
-			// `batch` reads (pairs: batch / 2 of each file) at the record size the head of the file shows
-			if (!streamed) {
-				std::vector<char> head(1u << 16);
-				const ssize_t k = pread(fq, head.data(), head.size(), 0);
-				size_t nl = 0, last = 0;
-				for (ssize_t i = 0; i < k; ++i)
-					if (head[(size_t)i] == '\n' && (++nl & 3) == 0) last = (size_t)i + 1;
-				const double rec = nl >= 4 ? (double)last / (double)(nl / 4) : 512.0;
-				double reads_per_chunk = (double)batch;
-				if (!opt->batch) {
-					// no -batch given: a chunk pays 3-4 ms of fixed cost on the device (launch tails, the second pass's empty launches) --
-					// two thirds of a 262 144-read chunk's mapping time at 46 M reads/s -- so a large file is cut into larger chunks, up to
-					// 524 288 reads, as long as every lane still gets four of them (the lanes overlap each other's copies).  Measured on
-					// 10 M reads (profiles/r5/e2e_by_chunk.txt): 262 144 -> 29.2 M reads/s with the SAM text dropped, 524 288 -> 31.2 M;
-					// 1 M-read chunks need 0.7 GB of page-locked memory each, six of them outgrow the pool and the run stalls in
-					// hipHostMalloc / hipHostFree (6.5 M reads/s)
-					const double est = (double)(fsize - (range.on ? range.lo[0] : 0)) / rec * (paired ? 2.0 : 1.0);
-					reads_per_chunk = std::min(524288.0, std::max((double)batch, est / (4.0 * (double)n_lanes)));
-					if (const char *e = getenv("URMAPX_TEST_CHUNK_READS")) reads_per_chunk = std::max(4.0, atof(e));  // test aid: the library's own choice, small (the ramp below on a small file)
-				}
-				chunk_bytes = (size_t)std::min(std::max(rec * (paired ? std::max(1.0, reads_per_chunk / 2) : reads_per_chunk), 4096.0), 536870912.0);
+			if (R.fail.set.load() || nomem.load()) { carry.assign(j->in, j->in + n); break; }
+			if (src1.failed()) { R.fail.raise(URMAPX_E_IO, std::string(src1.is_pipe() ? "Error reading " : "Error reading gzip file ") + R.fastq1); break; }
+			if (cut == 0) { carry.assign(j->in, j->in + n); free_jobs.push(std::move(j)); break; }  // the host reader says what is wrong with it
+			carry.assign(j->in + cut, j->in + n);
+			j->nbytes = cut; j->file_off = off; j->nbytes2 = 0; j->file_off2 = off2; j->in2 = nullptr;
+			if (R.paired && !cut_mate_stream(*j, cut, area1, area2, eof1 && carry.empty(), eof2)) { free_jobs.push(std::move(j)); break; }
+			to_lane(j, b, "inflate", tp0);
+		}
+	}
+	// The mate stream's chunk: as many lines as j's first `cut` bytes hold; every byte is looked at once (`scanned`).  false: the chunk stays
+	// with the reader, both files' bytes are back in the carries.
+	bool cut_mate_stream(TextJob &j, size_t cut, size_t area1, size_t area2, bool last, bool &eof2) {
+		const size_t lines = count_lines(j.in, cut, read_threads, per);
+		MateChunk m{j, cut, (area1 + 4095) & ~(size_t)4095};
+		if (carry2.size() > area2) {
+			area2 = carry2.size() + carry2.size() / 4 + (4u << 20);
+			if (!m.grow(area2)) { nomem.store(true); m.give_up = true; }
+		}
+		if (!m.give_up) {
+			if (!carry2.empty()) memcpy(m.dst(), carry2.data(), carry2.size());
+			m.have = carry2.size();
+			carry2.clear();
+		}
+		size_t seen = 0, scanned = 0;
+		while (!m.found && !m.give_up) {
+			// newlines of dst[scanned, have): the chunk ends behind line number `lines`
+			const char *c = m.dst() + scanned, *e = m.dst() + m.have;
+			while (c < e && (last || seen < lines)) {
+				const char *nl = (const char *)memchr(c, '\n', (size_t)(e - c));
+				if (!nl) break;
+				++seen;
+				c = nl + 1;
+				if (!last && seen == lines) m.end_at((size_t)(c - m.dst()));
 			}
-			using TextChannel = Channel<std::unique_ptr<TextJob>>;
-			std::vector<std::unique_ptr<TextChannel>> tparsed, tmapped;
-			for (int l = 0; l < n_lanes; ++l) {
-				tparsed.emplace_back(new TextChannel(1));
-				tmapped.emplace_back(new TextChannel(1));
+			scanned = (size_t)(c - m.dst());
+			if (m.found) break;
+			if (eof2) { if (last) m.end_at(m.have); else m.give_up = true; break; }  // the mate file ends first: the host reader words that
+			if (m.have == area2) {
+				if (area2 > 8 * area1 + (64u << 20)) { m.give_up = true; break; }
+				if (!m.grow(2 * area2)) { nomem.store(true); m.give_up = true; break; }
+				area2 *= 2;
 			}
-			const int n_jobs = 3 * n_lanes + 2;  // per lane: one waiting for it, one being mapped, one whose text is crossing PCIe; reader, writer
-			TextChannel tfree((size_t)n_jobs);
-			for (int k = 0; k < n_jobs; ++k) tfree.push(std::make_unique<TextJob>());
-			std::atomic<bool> stop{false};
-			uint64_t reader_end = 0, reader_end2 = 0;  // first byte of each file the reader did not hand to a lane
-			const int read_threads = std::max(1, host_threads / 2);
-			// [off, off + n) of a file into dst, by several threads
-			auto read_range = [&](int fd, char *dst, uint64_t off, size_t n) {
-				std::atomic<bool> ok{true};
-#pragma omp parallel for schedule(static, 1) num_threads(read_threads)
-				for (int t = 0; t < read_threads; ++t) {
-					const size_t lo = n * (size_t)t / (size_t)read_threads, hi = n * (size_t)(t + 1) / (size_t)read_threads;
-					size_t done = lo;
-					while (done < hi) {
-						ssize_t k = pread(fd, dst + done, hi - done, (off_t)(off + done));
-						if (k <= 0) { ok.store(false); break; }
-						done += (size_t)k;
-					}
-				}
-				return ok.load();
-			};
-			// '\n' count of each of read_threads slices of p[0, n)
-			auto count_lines = [&](const char *p, size_t n, std::vector<size_t> &per) {
-				per.assign((size_t)read_threads, 0);
-#pragma omp parallel for schedule(static, 1) num_threads(read_threads)
-				for (int t = 0; t < read_threads; ++t) {
-					const char *c = p + n * (size_t)t / (size_t)read_threads, *e = p + n * (size_t)(t + 1) / (size_t)read_threads;
-					size_t k = 0;
-					while (c < e) {
-						const char *nl = (const char *)memchr(c, '\n', (size_t)(e - c));
-						if (!nl) break;
-						++k;
-						c = nl + 1;
-					}
-					per[(size_t)t] = k;
-				}
-			};
-			// No page-locked memory for a chunk (memlock limit, little host memory), or none on the device for the text kernels:
-			// the text phase ends there and the host reader / formatter, which need neither, continue from that chunk.
-			std::atomic<bool> text_nomem{false};
-			bool stream_done = false;  // streamed input: the reader handed every byte of the input(s) to a lane
-			// streamed input: bytes read from each source and not handed to a lane yet (behind the last cut; a whole buffer the
-			// reader gave up on).  Pipes: they go to the host reader in front of the rest of the pipe, behind pipe_back.
-			std::vector<char> carry, carry2, pipe_back, pipe_back2;
-			std::thread treader([&] {
-				const bool pinned = one_node && pin_to(places[0]);  // the page-locked chunk buffers are first touched here
-				struct Unpin { bool on; const cpu_set_t &m; int n; ~Unpin() { unpin_team(on, m, n); } } unpin{pinned, caller_mask, read_threads};
-				omp_workers_sleep_when_idle();
-				omp_set_num_threads(read_threads);
-				uint64_t off = range.on ? range.lo[0] : 0, off2 = range.on ? range.lo[1] : 0;
-				double bytes2_per_byte1 = 1.0;
-				std::vector<size_t> per;
-				if (streamed) {
-					// chunks are cut out of the inflated stream: fill the job's buffer (what the last cut left over first),
-					// cut it at its last record start, keep the rest for the next chunk.  Offsets are those of the
-					// uncompressed text: that is where the host reader (gzseek) takes over if a chunk is handed back.
-					bool eof1 = false, eof2 = false;
-					auto regrow = [&](TextJob &j, size_t want, size_t keep) {  // a larger page-locked buffer holding the first `keep` bytes
-						size_t ncap = 0;
-						char *nb = HostPool::get().acquire(want, ncap);
-						if (!nb) return false;
-						if (keep) memcpy(nb, j.in, keep);
-						HostPool::get().release(j.in, j.in_cap);
-						j.in = nb; j.in_cap = ncap;
-						return true;
-					};
-					for (size_t b = 0; !stop.load() && !fail.set.load() && !text_nomem.load(); ++b) {
-						if (eof1 && carry.empty()) { stream_done = !paired || (eof2 && carry2.empty()); break; }
-						std::unique_ptr<TextJob> j;
-						if (!tfree.pop(j)) break;
-						if (stop.load()) { tfree.push(std::move(j)); break; }
-						const auto tp0 = now();
-						const double ta = trace.ms();
-						(void)hipSetDevice(phys(0));
-						size_t area1 = chunk_bytes + chunk_bytes / 8 + carry.size() + (1u << 20);  // room for this file's chunk
-						size_t area2 = paired ? (size_t)((double)area1 * bytes2_per_byte1 * 1.25) + carry2.size() + (4u << 20) : 0;
-						if (!TextJob::grow(j->in, j->in_cap, area1 + 4096 + area2)) { text_nomem.store(true); break; }
-						size_t n = carry.size(), cut = 0;
-						if (n) memcpy(j->in, carry.data(), n);
-						carry.clear();
-						size_t target = std::max(chunk_bytes, n + 1);
-						for (;;) {
-							while (n < target && !eof1) {
-								const size_t k = src1.read(j->in + n, std::min(area1, target + (64u << 10)) - n, read_threads);
-								if (k == 0) eof1 = true;
-								n += k;
-								// a gzip stream's reader hands out whole rounds written straight into this buffer and returns short when the next round
-								// would not fit (pgzip.cpp): a chunk that is three quarters full is a chunk -- asking for the rest would cost a copy of a whole round
-								if (src1.returns_whole_rounds() && n >= target - target / 4) break;
-							}
-							if (src1.failed()) break;
-							cut = eof1 ? n : last_record_start(j->in, n);
-							if (cut || eof1) break;
-							target *= 2;  // less than one record start in the buffer: records of a size beyond reason, or not FASTQ
-							if (target > (1u << 30)) break;
-							if (target + (64u << 10) > area1) {
-								area1 = target + target / 8 + (1u << 20);
-								if (!regrow(*j, area1 + 4096 + area2, n)) { text_nomem.store(true); break; }
-							}
-						}
-						if (fail.set.load() || text_nomem.load()) { carry.assign(j->in, j->in + n); break; }
-						if (src1.failed()) { fail.raise(URMAPX_E_IO, std::string(src1.is_pipe() ? "Error reading " : "Error reading gzip file ") + fastq1); break; }
-						if (cut == 0) { carry.assign(j->in, j->in + n); tfree.push(std::move(j)); break; }  // the host reader says what is wrong with it
-						carry.assign(j->in + cut, j->in + n);
-						j->nbytes = cut; j->file_off = off; j->nbytes2 = 0; j->file_off2 = off2; j->in2 = nullptr;
-						if (paired) {
-							count_lines(j->in, cut, per);
-							size_t lines = 0;
-							for (size_t k : per) lines += k;
-							const bool last = eof1 && carry.empty();  // last chunk: whatever the mate file still holds
-							size_t n_pad = (area1 + 4095) & ~(size_t)4095;
-							size_t have = carry2.size(), n2 = 0, seen = 0, scanned = 0;
-							bool found = false, give_up = false;
-							if (have > area2) {
-								area2 = have + have / 4 + (4u << 20);
-								if (!regrow(*j, n_pad + area2, cut)) { text_nomem.store(true); carry.insert(carry.begin(), j->in, j->in + cut); break; }
-							}
-							char *dst = j->in + n_pad;
-							if (have) memcpy(dst, carry2.data(), have);
-							carry2.clear();
-							for (;;) {
-								// newlines of dst[scanned, have): the chunk ends behind line number `lines`
-								const char *c = dst + scanned, *e = dst + have;
-								while (c < e && (last || seen < lines)) {
-									const char *nl = (const char *)memchr(c, '\n', (size_t)(e - c));
-									if (!nl) break;
-									++seen;
-									c = nl + 1;
-									if (!last && seen == lines) { n2 = (size_t)(c - dst); found = true; }
-								}
-								scanned = found ? have : (size_t)(c - dst);
-								if (found) break;
-								if (eof2) { if (last) { n2 = have; found = true; } else give_up = true; break; }  // the mate file ends first: the host reader words that
-								if (have == area2) {
-									if (area2 > 8 * area1 + (64u << 20)) { give_up = true; break; }
-									const size_t na = 2 * area2;
-									size_t ncap = 0;
-									char *nb = HostPool::get().acquire(n_pad + na, ncap);
-									if (!nb) { text_nomem.store(true); give_up = true; break; }
-									memcpy(nb, j->in, cut);
-									memcpy(nb + n_pad, dst, have);
-									HostPool::get().release(j->in, j->in_cap);
-									j->in = nb; j->in_cap = ncap; area2 = na; dst = nb + n_pad;
-								}
-								const size_t want = std::min(area2 - have, std::max<size_t>(1u << 20, (size_t)((double)cut * bytes2_per_byte1) + (64u << 10) - std::min(have, (size_t)((double)cut * bytes2_per_byte1))));
-								const size_t k = src2.read(dst + have, want, read_threads);
-								if (k == 0) eof2 = true;
-								have += k;
-								if (src2.failed()) { fail.raise(URMAPX_E_IO, std::string(src2.is_pipe() ? "Error reading " : "Error reading gzip file ") + fastq2); give_up = true; break; }
-							}
-							if (give_up || fail.set.load() || text_nomem.load()) {  // this chunk stays with the reader: both files' bytes back into the carries
-								carry.insert(carry.begin(), j->in, j->in + cut);
-								carry2.assign(dst, dst + have);
-								tfree.push(std::move(j));
-								break;
-							}
-							carry2.assign(dst + n2, dst + have);
-							j->in2 = dst; j->nbytes2 = n2;
-							if (cut && n2) bytes2_per_byte1 = (double)n2 / (double)cut;
-						}
-						t_parse += secs(tp0, now());
-						trace.add("inflate", -1, b, ta);
-						const size_t adv = j->nbytes, adv2 = j->nbytes2;
-						tparsed[b % (size_t)n_lanes]->push(std::move(j));
-						off += adv;
-						off2 += adv2;
-					}
-					reader_end = off; reader_end2 = off2;
-					for (auto &c : tparsed) c->close();
-					return;
-				}
-				// Round 6: the library's own chunk size (no -batch given) is ramped.  The first chunk of a lane is a quarter of the size, its second
-				// a half: the lanes start after 40 MB have been read instead of 165 MB, and the second lane a quarter-chunk later instead of a whole
-				// one.  The last round of chunks is cut in halves again and again (down to an eighth), so that the run does not end with one lane
-				// mapping a whole chunk while the others have nothing left (10 M reads: 19 chunks of 13 ms, of which the first and the last ran
-				// beside an idle lane).  URMAPX_NO_CHUNK_RAMP=1: every chunk the same size (measurement).
-				const bool ramp = !opt->batch && !getenv("URMAPX_NO_CHUNK_RAMP");
-				for (size_t b = 0; off < fsize && !stop.load() && !fail.set.load() && !text_nomem.load(); ++b) {
-					uint64_t end = fsize;
-					size_t this_chunk = chunk_bytes;
-					if (ramp) {
-						if (b < (size_t)n_lanes) this_chunk = chunk_bytes / 4;
-						else if (b < 2 * (size_t)n_lanes) this_chunk = chunk_bytes / 2;
-						const uint64_t left = fsize - off;
-						if (left <= (uint64_t)n_lanes * chunk_bytes) this_chunk = (size_t)std::min<uint64_t>(this_chunk, std::max<uint64_t>(left / (2 * (uint64_t)n_lanes), chunk_bytes / 8));
-						this_chunk = std::max<size_t>(this_chunk, 1024);
-					}
-					if (off + this_chunk < fsize) {
-						end = find_record_start(fq, off + this_chunk, fsize);
-						if (end == 0) break;  // no record start in sight: the host reader takes it from here
-					}
-					std::unique_ptr<TextJob> j;
-					if (!tfree.pop(j)) break;
-					if (stop.load()) break;
-					const size_t n = (size_t)(end - off);
-					const auto tp0 = now();
-					const double ta = trace.ms();
-					(void)hipSetDevice(phys(0));
-					const size_t n_pad = (n + 4095) & ~(size_t)4095;  // the mate file's chunk starts here
-					size_t want = n + n / 16 + 4096;
-					if (paired) want = n_pad + (size_t)((double)n * bytes2_per_byte1 * 1.25) + (4u << 20);
-					if (!TextJob::grow(j->in, j->in_cap, want)) { text_nomem.store(true); break; }
-					if (!read_range(fq, j->in, off, n)) { fail.raise(URMAPX_E_IO, std::string("Error reading ") + fastq1); break; }
-					j->nbytes = n; j->file_off = off; j->nbytes2 = 0; j->file_off2 = off2; j->in2 = nullptr;
-					if (paired) {
-						// the mate file's chunk: as many lines as this one holds
-						count_lines(j->in, n, per);
-						size_t lines = 0;
-						for (size_t k : per) lines += k;
-						char *dst = j->in + n_pad;
-						size_t room = j->in_cap - n_pad;
-						const uint64_t left2 = fsize2 - off2;
-						size_t have = 0, n2 = 0;
-						bool found = false, give_up = false;
-						// the mate chunk outgrew the buffer (its records are longer than the first file's were so far): a larger
-						// one, with what has been read
-						auto more_room = [&](size_t need_room) {
-							size_t ncap = 0;
-							char *nb = HostPool::get().acquire(n_pad + need_room + (4u << 20), ncap);
-							if (!nb) return false;
-							memcpy(nb, j->in, n);
-							if (have) memcpy(nb + n_pad, dst, have);
-							HostPool::get().release(j->in, j->in_cap);
-							j->in = nb; j->in_cap = ncap;
-							dst = nb + n_pad; room = ncap - n_pad;
-							return true;
-						};
-						if (end == fsize) {  // last chunk: whatever the mate file still holds (the device parser says if it is not the same count)
-							if (left2 > room && (left2 > 8ull * n + (64u << 20) || !more_room((size_t)left2))) give_up = true;
-							else { have = (size_t)left2; found = true; n2 = have; if (have && !read_range(fq2, dst, off2, have)) { fail.raise(URMAPX_E_IO, std::string("Error reading ") + fastq2); break; } }
-						}
-						while (!found && !give_up) {
-							size_t upto = have ? have + have / 4 + (1u << 20) : (size_t)((double)n * bytes2_per_byte1) + (1u << 16);
-							upto = (size_t)std::min<uint64_t>(std::min<uint64_t>(upto, room), left2);
-							if (upto <= have) {
-								if (have < left2 && room < 8 * n + (64u << 20) && more_room(2 * room)) continue;  // out of room, not out of file
-								give_up = true;  // out of file with too few lines (the host reader words that), or a chunk beyond reason
-								break;
-							}
-							if (!read_range(fq2, dst + have, off2 + have, upto - have)) { fail.raise(URMAPX_E_IO, std::string("Error reading ") + fastq2); give_up = true; break; }
-							have = upto;
-							count_lines(dst, have, per);
-							size_t cum = 0;
-							for (int t = 0; t < read_threads && !found; ++t) {
-								if (cum + per[(size_t)t] >= lines && lines > 0) {  // the chunk ends in this slice: walk to its last '\n'
-									const char *c = dst + have * (size_t)t / (size_t)read_threads, *e = dst + have * (size_t)(t + 1) / (size_t)read_threads;
-									size_t need = lines - cum;
-									while (need) {
-										const char *nl = (const char *)memchr(c, '\n', (size_t)(e - c));
-										c = nl + 1;
-										--need;
-									}
-									n2 = (size_t)(c - dst);
-									found = true;
-								}
-								cum += per[(size_t)t];
-							}
-							if (!found && have == left2) give_up = true;  // the mate file ends first: the host reader words that
-						}
-						if (fail.set.load() || text_nomem.load()) break;
-						if (give_up) { tfree.push(std::move(j)); break; }
-						j->in2 = dst; j->nbytes2 = n2;
-						if (n && n2) bytes2_per_byte1 = (double)n2 / (double)n;
-					}
-					t_parse += secs(tp0, now());
-					trace.add("read", -1, b, ta);
-					const size_t adv2 = j->nbytes2;
-					tparsed[b % (size_t)n_lanes]->push(std::move(j));
-					off = end;
-					off2 += adv2;
-				}
-				reader_end = off; reader_end2 = off2;
-				for (auto &c : tparsed) c->close();
-			});
-			bool handed_back = false;
-			uint64_t resume_off = 0, resume_off2 = 0, lines_done = range.on ? range.lines_before : 0;  // lines_done: per file
-			// write() calls on one file take turns (inode lock): more threads only add hand-overs
-			const int write_threads = sink.writer_threads(host_threads);
-			write_threads_used = write_threads;
-			text_on_device = true;
-			std::thread twriter([&] {
-				const bool pinned = one_node && pin_to(places[0]);
-				struct Unpin { bool on; const cpu_set_t &m; int n; ~Unpin() { unpin_team(on, m, n); } } unpin{pinned, caller_mask, host_threads};
-				omp_workers_sleep_when_idle();
-				omp_set_num_threads(host_threads);
-				std::unique_ptr<TextJob> j;
-				for (size_t b = 0; tmapped[b % (size_t)n_lanes]->pop(j); ++b) {
-					if (!handed_back && !fail.set.load()) {
-						if (j->rc == URMAPX_E_NOMEM) { j->rc = 0; j->rep.reason = 0xFFFEu; text_nomem.store(true); }
-						if (j->rc) fail.raise(j->rc, std::string(paired ? "urmapx_text_map_pe: " : "urmapx_text_map_se: ") + urmapx_strerror(j->rc));
-						else if (j->rep.reason) { handed_back = true; stop.store(true); resume_off = j->file_off; resume_off2 = j->file_off2; }
-					}
-					if (handed_back && streamed) {  // pipes: this chunk's bytes and those of every chunk behind it, in order
-						if (src1.is_pipe()) pipe_back.insert(pipe_back.end(), j->in, j->in + j->nbytes);
-						if (paired && src2.is_pipe() && j->in2) pipe_back2.insert(pipe_back2.end(), j->in2, j->in2 + j->nbytes2);
-					}
-					if (!handed_back && !fail.set.load()) {
-						const auto tw0 = now();
-						const double ta = trace.ms();
-#ifdef URX_FAULT_OFF32  // fault injection for the suite's own check (profiles/r6/fault_off32.txt): the writer's file offset cut to 32 bits
-						const uint64_t at = (uint32_t)sam_off;
-#else
-						const uint64_t at = sam_off;
-#endif
-						if (!sink.write_at(j->out, (size_t)j->rep.sam_bytes, at, write_threads))
-							fail.raise(URMAPX_E_IO, std::string("Error writing ") + samout);
-						sam_off += j->rep.sam_bytes;
-						sam_text_bytes += j->rep.sam_text_bytes;
-						if (ftab && !j->tab.empty() && fwrite(j->tab.data(), 1, j->tab.size(), ftab) != j->tab.size())
-							fail.raise(URMAPX_E_IO, std::string("Error writing ") + tabout);
-						t_write += secs(tw0, now());
-						trace.add("write", -1, b, ta);
-						n_reads += j->rep.records; n_accept += j->rep.mapped_q; n_reject += j->rep.mapped_lowq;
-						n_nohit += j->rep.unmapped; n_unsupported += j->rep.unsupported;
-						dev_ms[0] += j->rep.ms_h2d; dev_ms[1] += j->rep.ms_parse; dev_ms[2] += j->rep.ms_map; dev_ms[3] += j->rep.ms_format; dev_ms[4] += j->rep.ms_d2h;
-						dev_ms[5] += j->rep.ms_map_search; dev_ms[6] += j->rep.ms_map_dp; dev_ms[7] += j->rep.ms_map_enqueue;
-						lines_done += (paired ? 2ull : 4ull) * j->rep.records;
-						input_bytes += j->nbytes + j->nbytes2;
-					}
-					tfree.push(std::move(j));
-				}
-			});
-			std::vector<std::thread> tlanes;
-			for (int l = 0; l < n_lanes; ++l)
-				tlanes.emplace_back([&, l] {
-					omp_workers_sleep_when_idle();
-					const bool pinned = pin_to(places[(size_t)(l % gpus)]);
-					struct Unpin { bool on; const cpu_set_t &m; int n; ~Unpin() { unpin_team(on, m, n); } } unpin{pinned, caller_mask, std::max(1, host_threads / n_lanes)};
-					(void)hipSetDevice(phys(l % gpus));
-					urmapx_text *T = texts[(size_t)l];
-					const double tc = trace.ms();
-					const int trc = T ? URMAPX_OK : urmapx_text_create(ctxs[(size_t)l], &T);
-					texts[(size_t)l] = T;  // released with the lane's context (kept for the next call, or destroyed)
-					trace.add("create", l, 0, tc);
-					size_t nj = 0;
-					double sam_per_fastq = 1.12;
-					if (trc == URMAPX_E_NOMEM) text_nomem.store(true);  // T stays null: this lane's chunks go back unmapped
-					else if (trc) fail.raise(trc, std::string("urmapx_text_create: ") + urmapx_strerror(trc));
-					// The copy back is a stage of its own (urmapx_text_set_deferred): chunk i's text crosses PCIe while the lane's stream takes
-					// chunk i + 1 in and maps it; the lane waits for chunk i's copy when chunk i + 1 has been enqueued to its end.
-					// URMAPX_NO_DEFERRED_COPY=1 (measurement): every chunk is waited for before the next is taken.
-					if (T) {
-						const int brc = urmapx_text_set_bgzf(T, bgzf ? 1 : 0);  // (a lane from the pool keeps what its last run set)
-						int brc2 = 0;
-						if (brc == URMAPX_E_NOMEM) { text_nomem.store(true); T = nullptr; }
-						else if (brc) fail.raise(brc, std::string("urmapx_text_set_bgzf: ") + urmapx_strerror(brc));
-						else if ((brc2 = urmapx_text_set_bam(T, bam ? 1 : 0))) fail.raise(brc2, std::string("urmapx_text_set_bam: ") + urmapx_strerror(brc2));
-					}
-					const bool defer = T && !getenv("URMAPX_NO_DEFERRED_COPY") && urmapx_text_set_deferred(T, 1) == URMAPX_OK;
-					auto ok_so_far = [](const TextJob &q) { return !q.rc && (q.rep.reason == 0 || q.rep.reason == URMAPX_TEXT_DEFERRED); };
-					auto hand_on = [&](std::unique_ptr<TextJob> &q) {
-						if (!q->rc && q->rep.reason == URMAPX_TEXT_DEFERRED) {
-							const auto tw0 = now();
-							const double ta = trace.ms();
-							q->rc = urmapx_text_wait(T, &q->rep);
-							trace.add("wait", l, 0, ta);
-							std::lock_guard<std::mutex> g(gpu_time_lock);
-							t_gpu += secs(tw0, now());
-						}
-						tmapped[(size_t)l]->push(std::move(q));
-					};
-					std::unique_ptr<TextJob> j, prev;
-					while (tparsed[(size_t)l]->pop(j)) {
-						memset(&j->rep, 0, sizeof j->rep);
-						j->rc = 0;
-						if (T && !fail.set.load() && !stop.load()) {
-							const auto tg0 = now();
-							const double ta = trace.ms();
-							// the SAM buffer is sized from the previous chunk's text (150-base reads: 1.09 x their FASTQ text); a chunk
-							// that needs more says so and its text is fetched into a larger one
-							const size_t fq_bytes = j->nbytes + j->nbytes2;
-							if (!TextJob::grow(j->out, j->out_cap, (size_t)((double)fq_bytes * sam_per_fastq * 1.04) + (1u << 20))) j->rc = URMAPX_E_NOMEM;
-							if (!j->rc)
-								j->rc = paired ? urmapx_text_map_pe(T, j->in, j->nbytes, j->in2, j->nbytes2, minq, j->out, j->out_cap, &j->rep)
-								               : urmapx_text_map_se(T, j->in, j->nbytes, minq, j->out, j->out_cap, &j->rep);
-							if (!j->rc && j->rep.reason == URMAPX_TEXT_SAM_CAP) {
-								if (!TextJob::grow(j->out, j->out_cap, (size_t)j->rep.sam_bytes + j->rep.sam_bytes / 16 + (1u << 20))) j->rc = URMAPX_E_NOMEM;
-								else j->rc = urmapx_text_fetch_sam(T, j->out, j->out_cap, &j->rep);
-							}
-							// (under bgzf the buffer takes the worst case of the text, a 2100th more than the text itself)
-							if (ok_so_far(*j) && fq_bytes && j->rep.records) sam_per_fastq = (double)j->rep.sam_text_bytes / (double)fq_bytes * (bgzf ? 1.001 : 1.0);
-							j->tab.clear();
-							if (ok_so_far(*j) && ftab && j->rep.records) {
-								const uint32_t np = j->rep.records / 2;
-								j->tab_res.resize((size_t)2 * np); j->tab_info.resize(np); j->tab_ends.resize((size_t)4 * np); j->tab_lens2.resize(np);
-								j->rc = urmapx_text_fetch_pairs(T, np, j->tab_res.data(), j->tab_info.data(), j->tab_ends.data(), j->tab_lens2.data());
-								if (!j->rc) {
-									const auto tf0 = now();
-									const int TT = std::max(1, host_threads / n_lanes);
-									std::vector<std::string> part((size_t)TT);
+			const size_t expect = (size_t)((double)cut * bytes2_per_byte1);
+			const size_t want = std::min(area2 - m.have, std::max<size_t>(1u << 20, expect + (64u << 10) - std::min(m.have, expect)));
+			const size_t k = src2.read(m.dst() + m.have, want, read_threads);
+			if (k == 0) eof2 = true;
+			m.have += k;
+			if (src2.failed()) { R.fail.raise(URMAPX_E_IO, std::string(src2.is_pipe() ? "Error reading " : "Error reading gzip file ") + R.fastq2); m.give_up = true; }
+		}
+		if (m.give_up || R.fail.set.load() || nomem.load()) {
+			carry.insert(carry.begin(), j.in, j.in + cut);
+			carry2.insert(carry2.begin(), m.dst(), m.dst() + m.have);
+			return false;
+		}
+		carry2.assign(m.dst() + m.n2, m.dst() + m.have);
+		m.hand_to_job(bytes2_per_byte1);
+		return true;
+	}
+	void read_plain() {
+		// Round 6: the library's own chunk size (no -batch given) is ramped.  The first chunk of a lane is a quarter of the size, its second
+		// a half: the lanes start after 40 MB have been read instead of 165 MB, and the second lane a quarter-chunk later instead of a whole
+		// one.  The last round of chunks is cut in halves again and again (down to an eighth), so that the run does not end with one lane
+		// mapping a whole chunk while the others have nothing left (10 M reads: 19 chunks of 13 ms, of which the first and the last ran
+		// beside an idle lane).  URMAPX_NO_CHUNK_RAMP=1: every chunk the same size (measurement).
+		const bool ramp = !R.opt.batch && !getenv("URMAPX_NO_CHUNK_RAMP");
+		const size_t n_lanes = (size_t)R.n_lanes;
+		for (size_t b = 0; off < fsize && going(); ++b) {
+			uint64_t end = fsize;
+			size_t this_chunk = chunk_bytes;
+			if (ramp) {
+				if (b < n_lanes) this_chunk = chunk_bytes / 4;
+				else if (b < 2 * n_lanes) this_chunk = chunk_bytes / 2;
+				const uint64_t left = fsize - off;
+				if (left <= (uint64_t)n_lanes * chunk_bytes) this_chunk = (size_t)std::min<uint64_t>(this_chunk, std::max<uint64_t>(left / (2 * (uint64_t)n_lanes), chunk_bytes / 8));
+				this_chunk = std::max<size_t>(this_chunk, 1024);
+			}
+			if (off + this_chunk < fsize) {
+				end = find_record_start(fq, off + this_chunk, fsize);
+				if (end == 0) break;  // no record start in sight: the host reader takes it from here
+			}
+			std::unique_ptr<TextJob> j;
+			if (!free_jobs.pop(j)) break;
+			if (stop.load()) break;
+			const size_t n = (size_t)(end - off);
+			const auto tp0 = now();
+			(void)hipSetDevice(R.phys(0));
+			const size_t n_pad = (n + 4095) & ~(size_t)4095;  // the mate file's chunk starts here
+			size_t want = n + n / 16 + 4096;
+			if (R.paired) want = n_pad + (size_t)((double)n * bytes2_per_byte1 * 1.25) + (4u << 20);
+			if (!TextJob::grow(j->in, j->in_cap, want)) { nomem.store(true); break; }
+			if (!read_range(fq, j->in, off, n, read_threads)) { R.fail.raise(URMAPX_E_IO, std::string("Error reading ") + R.fastq1); break; }
+			j->nbytes = n; j->file_off = off; j->nbytes2 = 0; j->file_off2 = off2; j->in2 = nullptr;
+			if (R.paired && !cut_mate_plain(*j, n, n_pad, end == fsize)) { free_jobs.push(std::move(j)); break; }
+			to_lane(j, b, "read", tp0);
+		}
+	}
+	// The mate file's chunk: as many lines as j's first n bytes hold; what has been read is counted again by all reader threads after
+	// every piece.  false: the chunk stays with the reader, the host reader continues at its first byte.
+	bool cut_mate_plain(TextJob &j, size_t n, size_t n_pad, bool last) {
+		const size_t lines = count_lines(j.in, n, read_threads, per);
+		MateChunk m{j, n, n_pad};
+		auto room = [&] { return j.in_cap - n_pad; };
+		const uint64_t left2 = fsize2 - off2;
+		auto read_to = [&](size_t upto) {
+			const bool ok = read_range(fq2, m.dst() + m.have, off2 + m.have, upto - m.have, read_threads);
+			if (!ok) { R.fail.raise(URMAPX_E_IO, std::string("Error reading ") + R.fastq2); m.give_up = true; }
+			m.have = upto;
+			return ok;
+		};
+		if (last) {  // last chunk: whatever the mate file still holds (the device parser says if it is not the same count)
+			if (left2 > room() && (left2 > 8ull * n + (64u << 20) || !m.grow((size_t)left2 + (4u << 20)))) m.give_up = true;
+			else if (read_to((size_t)left2)) m.end_at(m.have);
+		}
+		while (!m.found && !m.give_up) {
+			size_t upto = m.have ? m.have + m.have / 4 + (1u << 20) : (size_t)((double)n * bytes2_per_byte1) + (1u << 16);
+			upto = (size_t)std::min<uint64_t>(std::min<uint64_t>(upto, room()), left2);
+			if (upto <= m.have) {
+				if (m.have < left2 && room() < 8 * n + (64u << 20) && m.grow(2 * room() + (4u << 20))) continue;  // out of room, not out of file
+				m.give_up = true;  // out of file with too few lines (the host reader words that), or a chunk beyond reason
+				break;
+			}
+			if (!read_to(upto)) break;
+			count_lines(m.dst(), m.have, read_threads, per);
+			if (const size_t n2 = nth_line_end(m.dst(), m.have, per, lines)) m.end_at(n2);
+			else if (m.have == left2) m.give_up = true;  // the mate file ends first: the host reader words that
+		}
+		if (m.give_up || R.fail.set.load() || nomem.load()) return false;
+		m.hand_to_job(bytes2_per_byte1);
+		return true;
+	}
+	void format_tab(TextJob &j) {
+		const uint32_t np = j.rep.records / 2;
+		const int TT = std::max(1, R.host_threads / R.n_lanes);
+		std::vector<std::string> parts((size_t)TT);
 #pragma omp parallel for schedule(static, 1) num_threads(TT)
-									for (int t = 0; t < TT; ++t) {
-										std::string &o = part[(size_t)t];
-										const uint32_t lo = (uint32_t)((uint64_t)np * (uint64_t)t / (uint64_t)TT), hi = (uint32_t)((uint64_t)np * (uint64_t)(t + 1) / (uint64_t)TT);
-										o.reserve((size_t)(hi - lo) * 72);
-										for (uint32_t u = lo; u < hi; ++u) {
-											const uint32_t *e = j->tab_ends.data() + (size_t)4 * u;
-											const uint32_t s0 = (u ? e[-1] + 1u : 0u) + 1u;  // behind the '@'
-											append_tab_pe(o, I, &j->tab_res[(size_t)2 * u], &j->tab_res[(size_t)2 * u + 1], &j->tab_info[u], j->in + s0, e[0] - s0,
-											              e[1] - e[0] - 1u, j->tab_lens2[u], have_sam ? 1 : 0);
-										}
-									}
-									for (const std::string &o : part) j->tab += o;
-									std::lock_guard<std::mutex> g(gpu_time_lock);
-									t_format += secs(tf0, now());
-								}
-							}
-							trace.add("gpu", l, (size_t)l + nj * (size_t)n_lanes, ta);
-							std::lock_guard<std::mutex> g(gpu_time_lock);
-							t_gpu += secs(tg0, now());
-						} else
-							j->rep.reason = 0xFFFFu;  // not mapped: the phase is ending
-						if (prev) hand_on(prev);
-						if (defer) prev = std::move(j);
-						else tmapped[(size_t)l]->push(std::move(j));
-						++nj;
+		for (int t = 0; t < TT; ++t) {
+			std::string &o = parts[(size_t)t];
+			const uint32_t lo = (uint32_t)part(np, t, TT), hi = (uint32_t)part(np, t + 1, TT);
+			o.reserve((size_t)(hi - lo) * 72);
+			for (uint32_t u = lo; u < hi; ++u) {
+				const uint32_t *e = j.tab_ends.data() + (size_t)4 * u;
+				const uint32_t s0 = (u ? e[-1] + 1u : 0u) + 1u;  // behind the '@'
+				append_tab_pe(o, R.I, &j.tab_res[(size_t)2 * u], &j.tab_res[(size_t)2 * u + 1], &j.tab_info[u], j.in + s0, e[0] - s0,
+				              e[1] - e[0] - 1u, j.tab_lens2[u], R.have_sam ? 1 : 0);
+			}
+		}
+		for (const std::string &o : parts) j.tab += o;
+	}
+	void lane(int l) {
+		omp_workers_sleep_when_idle();
+		const bool pinned = pin_to(R.places[(size_t)(l % R.gpus)]);
+		Unpin unpin{pinned, R.caller_mask, std::max(1, R.host_threads / R.n_lanes)};
+		(void)hipSetDevice(R.phys(l % R.gpus));
+		urmapx_text *T = R.texts[(size_t)l];
+		const auto tc = now();
+		const int trc = T ? URMAPX_OK : urmapx_text_create(R.ctxs[(size_t)l], &T);
+		R.texts[(size_t)l] = T;  // released with the lane's context (kept for the next call, or destroyed)
+		R.trace.add("create", l, 0, tc);
+		size_t nj = 0;
+		double sam_per_fastq = 1.12;
+		if (trc == URMAPX_E_NOMEM) nomem.store(true);  // T stays null: this lane's chunks go back unmapped
+		else if (trc) R.fail.raise(trc, std::string("urmapx_text_create: ") + urmapx_strerror(trc));
+		if (T) {
+			const int brc = urmapx_text_set_bgzf(T, R.bgzf ? 1 : 0);  // (a lane from the pool keeps what its last run set)
+			int brc2 = 0;
+			if (brc == URMAPX_E_NOMEM) { nomem.store(true); T = nullptr; }
+			else if (brc) R.fail.raise(brc, std::string("urmapx_text_set_bgzf: ") + urmapx_strerror(brc));
+			else if ((brc2 = urmapx_text_set_bam(T, R.bam ? 1 : 0))) R.fail.raise(brc2, std::string("urmapx_text_set_bam: ") + urmapx_strerror(brc2));
+		}
+		// The copy back is a stage of its own (urmapx_text_set_deferred): chunk i's text crosses PCIe while the lane's stream takes
+		// chunk i + 1 in and maps it; the lane waits for chunk i's copy when chunk i + 1 has been enqueued to its end.
+		// URMAPX_NO_DEFERRED_COPY=1 (measurement): every chunk is waited for before the next is taken.
+		const bool defer = T && !getenv("URMAPX_NO_DEFERRED_COPY") && urmapx_text_set_deferred(T, 1) == URMAPX_OK;
+		auto ok_so_far = [](const TextJob &q) { return !q.rc && (q.rep.reason == 0 || q.rep.reason == URMAPX_TEXT_DEFERRED); };
+		auto hand_on = [&](std::unique_ptr<TextJob> &q) {
+			if (!q->rc && q->rep.reason == URMAPX_TEXT_DEFERRED) {
+				const auto tw0 = now();
+					q->rc = urmapx_text_wait(T, &q->rep);
+				R.trace.add("wait", l, 0, tw0);
+				R.add_lane_time(&Rep::gpu_s, tw0);
+			}
+			mapped[(size_t)l]->push(std::move(q));
+		};
+		std::unique_ptr<TextJob> j, prev;
+		while (parsed[(size_t)l]->pop(j)) {
+			memset(&j->rep, 0, sizeof j->rep);
+			j->rc = 0;
+			if (T && !R.fail.set.load() && !stop.load()) {
+				const auto tg0 = now();
+					// the SAM buffer is sized from the previous chunk's text (150-base reads: 1.09 x their FASTQ text); a chunk
+				// that needs more says so and its text is fetched into a larger one
+				const size_t fq_bytes = j->nbytes + j->nbytes2;
+				if (!TextJob::grow(j->out, j->out_cap, (size_t)((double)fq_bytes * sam_per_fastq * 1.04) + (1u << 20))) j->rc = URMAPX_E_NOMEM;
+				if (!j->rc)
+					j->rc = R.paired ? urmapx_text_map_pe(T, j->in, j->nbytes, j->in2, j->nbytes2, R.minq, j->out, j->out_cap, &j->rep)
+					                 : urmapx_text_map_se(T, j->in, j->nbytes, R.minq, j->out, j->out_cap, &j->rep);
+				if (!j->rc && j->rep.reason == URMAPX_TEXT_SAM_CAP) {
+					if (!TextJob::grow(j->out, j->out_cap, (size_t)j->rep.sam_bytes + j->rep.sam_bytes / 16 + (1u << 20))) j->rc = URMAPX_E_NOMEM;
+					else j->rc = urmapx_text_fetch_sam(T, j->out, j->out_cap, &j->rep);
+				}
+				// (under bgzf the buffer takes the worst case of the text, a 2100th more than the text itself)
+				if (ok_so_far(*j) && fq_bytes && j->rep.records) sam_per_fastq = (double)j->rep.sam_text_bytes / (double)fq_bytes * (R.bgzf ? 1.001 : 1.0);
+				j->tab.clear();
+				if (ok_so_far(*j) && R.ftab && j->rep.records) {
+					const uint32_t np = j->rep.records / 2;
+					j->tab_res.resize((size_t)2 * np); j->tab_info.resize(np); j->tab_ends.resize((size_t)4 * np); j->tab_lens2.resize(np);
+					j->rc = urmapx_text_fetch_pairs(T, np, j->tab_res.data(), j->tab_info.data(), j->tab_ends.data(), j->tab_lens2.data());
+					if (!j->rc) {
+						const auto tf0 = now();
+						format_tab(*j);
+						R.add_lane_time(&Rep::format_s, tf0);
 					}
-					if (prev) hand_on(prev);
-					tmapped[(size_t)l]->close();
-				});
-			for (auto &t : tlanes) t.join();
-			treader.join();
-			twriter.join();
-			{
-				const double tf = trace.ms();
-				std::unique_ptr<TextJob> j;
-				while (tfree.try_pop(j)) j.reset();
-				trace.add("unpin", -1, 0, tf);
+				}
+				R.trace.add("gpu", l, (size_t)l + nj * (size_t)R.n_lanes, tg0);
+				R.add_lane_time(&Rep::gpu_s, tg0);
+			} else
+				j->rep.reason = 0xFFFFu;  // not mapped: the phase is ending
+			if (prev) hand_on(prev);
+			if (defer) prev = std::move(j);
+			else mapped[(size_t)l]->push(std::move(j));
+			++nj;
+		}
+		if (prev) hand_on(prev);
+		mapped[(size_t)l]->close();
+	}
+	// Chunks come back in input order (the lanes in turn).  The first one the device parser did not take ends the phase: nothing from it on
+	// is written; a pipe's bytes are kept for the host reader.
+	void writer() {
+		const bool pinned = R.one_node && pin_to(R.places[0]);
+		Unpin unpin{pinned, R.caller_mask, R.host_threads};
+		omp_team(R.host_threads);
+		std::unique_ptr<TextJob> j;
+		for (size_t b = 0; mapped[b % (size_t)R.n_lanes]->pop(j); ++b) {
+			if (!handed_back && !R.fail.set.load()) {
+				if (j->rc == URMAPX_E_NOMEM) { j->rc = 0; j->rep.reason = 0xFFFEu; nomem.store(true); }
+				if (j->rc) R.fail.raise(j->rc, std::string(R.paired ? "urmapx_text_map_pe: " : "urmapx_text_map_se: ") + urmapx_strerror(j->rc));
+				else if (j->rep.reason) { handed_back = true; stop.store(true); resume_off = j->file_off; resume_off2 = j->file_off2; }
 			}
-			if (fq >= 0) close(fq);
-			if (fq2 >= 0) close(fq2);
-			if (!handed_back) { resume_off = reader_end; resume_off2 = reader_end2; }
-			host_phase = !fail.set.load() && (streamed ? (handed_back || !stream_done) : (resume_off < fsize || (paired && resume_off2 < fsize2)));
-			if (host_phase) {
-				// a seekable source continues at its (uncompressed) offset; a pipe with the bytes taken from it and not mapped
-				auto resume = [&](FastqReader &r, SeqSource &src, uint64_t at, std::vector<char> &back, std::vector<char> &rest) {
-					if (!streamed || !src.is_pipe()) return r.resume_at(at, lines_done);  // (a shard's reader: positioned again, same rules)
-					back.insert(back.end(), rest.begin(), rest.end());
-					return r.resume_with_prefix(std::move(back), lines_done);
-				};
-				if (!resume(rd, src1, resume_off, pipe_back, carry) || (paired && !resume(rd2, src2, resume_off2, pipe_back2, carry2)))
-					fail.raise(URMAPX_E_IO, std::string("Cannot continue reading ") + fastq1);
+			if (handed_back && streamed) {  // pipes: this chunk's bytes and those of every chunk behind it, in order
+				if (src1.is_pipe()) pipe_back.insert(pipe_back.end(), j->in, j->in + j->nbytes);
+				if (R.paired && src2.is_pipe() && j->in2) pipe_back2.insert(pipe_back2.end(), j->in2, j->in2 + j->nbytes2);
 			}
-			if (fail.set.load()) host_phase = false;
+			if (!handed_back && !R.fail.set.load()) {
+				const auto tw0 = now();
+	#ifdef URX_FAULT_OFF32  // fault injection for the suite's own check (profiles/r6/fault_off32.txt): the writer's file offset cut to 32 bits
+				const uint64_t at = (uint32_t)R.rep.sam_file_bytes;
+#else
+				const uint64_t at = R.rep.sam_file_bytes;
+#endif
+				if (!R.sink.write_at(j->out, (size_t)j->rep.sam_bytes, at, write_threads)) R.cannot_write_sam();
+				R.rep.sam_file_bytes += j->rep.sam_bytes;
+				if (R.ftab && !j->tab.empty() && fwrite(j->tab.data(), 1, j->tab.size(), R.ftab.get()) != j->tab.size())
+					R.fail.raise(URMAPX_E_IO, std::string("Error writing ") + R.tabout);
+				R.rep.write_s += secs(tw0, now());
+				R.trace.add("write", -1, b, tw0);
+				urmapx_map_report &r = R.rep;
+				const urmapx_text_report &c = j->rep;
+				r.reads += c.records; r.mapped_q += c.mapped_q; r.mapped_lowq += c.mapped_lowq; r.unmapped += c.unmapped; r.unsupported += c.unsupported;
+				r.sam_text_bytes += c.sam_text_bytes;
+				r.dev_h2d_s += c.ms_h2d * 1e-3; r.dev_parse_s += c.ms_parse * 1e-3; r.dev_map_s += c.ms_map * 1e-3; r.dev_format_s += c.ms_format * 1e-3;
+				r.dev_d2h_s += c.ms_d2h * 1e-3; r.dev_map_search_s += c.ms_map_search * 1e-3; r.dev_map_dp_s += c.ms_map_dp * 1e-3;
+				r.map_enqueue_s += c.ms_map_enqueue * 1e-3;
+				lines_done += (R.paired ? 2ull : 4ull) * j->rep.records;
+				R.rep.input_bytes += j->nbytes + j->nbytes2;
+			}
+			free_jobs.push(std::move(j));
 		}
 	}
-	if (host_phase) {
+};
 
-	// batch b travels through parsed[b mod lanes] -> lane thread -> mapped[b mod lanes]; the writer visits the lanes in the
-	// same round-robin order, so batches come back in input order without a reorder buffer
+// ---- host phase: FASTQ parsed, SAM formatted and written by host threads; the lanes map arrays of reads ----
+// Batch b travels through parsed[b mod lanes] -> lane thread -> mapped[b mod lanes]; the formatter visits the lanes in the same
+// round-robin order, so batches come back in input order without a reorder buffer
+struct HostPhase {
 	using JobChannel = Channel<std::unique_ptr<Job>>;
+	// SAM text of a batch is formatted by all host threads, each on a contiguous range of reads (pairs); the pieces go to
+	// the flusher thread, which writes them at their file offsets (input order) while the next batch is being formatted.
+	struct Text { std::vector<std::string> outs; std::vector<uint64_t> at; };
+	struct Cnt { unsigned long long accept = 0, reject = 0, nohit = 0, unsupported = 0, text = 0; };  // of one formatting thread's share of a batch
+	Run &R;
 	std::vector<std::unique_ptr<JobChannel>> parsed, mapped;
-	for (int l = 0; l < n_lanes; ++l) {
-		parsed.emplace_back(new JobChannel(2));
-		mapped.emplace_back(new JobChannel(1));
-	}
-	JobChannel recycled((size_t)(8 + 6 * n_lanes));  // finished jobs go back to the reader: their arrays are reused
+	JobChannel recycled{(size_t)(8 + 6 * R.n_lanes)};  // finished jobs go back to the reader: their arrays are reused
 	// -map2: the second file is parsed by its own thread while the reader parses the first
-	struct Side { FastqBatch b; std::string e; bool more = false; } side2;
-	Channel<int> go2(1), done2(1);
-	std::thread reader2;
-	if (paired)
-		reader2 = std::thread([&] {
-			omp_workers_sleep_when_idle();
-			omp_set_num_threads(std::max(1, host_threads / 2));  // a new thread starts from the default team size, not main's
-			int x;
-			while (go2.pop(x)) {
-				side2.b.clear();
-				side2.e.clear();
-				side2.more = rd2.next_batch(side2.b, batch / 2, side2.e);
-				done2.push(1);
-			}
-		});
-	std::thread reader([&] {
-		omp_workers_sleep_when_idle();
-		omp_set_num_threads(paired ? std::max(1, host_threads - host_threads / 2) : host_threads);
+	struct Side { FastqBatch b; std::string e; bool more = false; } side2;  // the mate reader's between go2 and done2, else the reader's
+	Channel<int> go2{1}, done2{1};
+	Channel<std::unique_ptr<Text>> to_flush{2}, text_pool{4};
+	void run() {
+		for (int l = 0; l < R.n_lanes; ++l) {
+			parsed.emplace_back(new JobChannel(2));
+			mapped.emplace_back(new JobChannel(1));
+		}
+		std::thread treader2;
+		if (R.paired) treader2 = std::thread([this] { mate_reader(); });
+		std::thread treader([this] { reader(); });
+		std::thread tflusher([this] { flusher(); });
+		std::thread tformatter([this] { formatter(); });
+		std::vector<std::thread> tlanes;
+		for (int l = 0; l < R.n_lanes; ++l) tlanes.emplace_back([this, l] { lane(l); });
+		for (auto &t : tlanes) t.join();
+		treader.join();
+		if (treader2.joinable()) treader2.join();
+		tformatter.join();
+		tflusher.join();
+		// page-locked arrays are released before their contexts go
+		std::unique_ptr<Job> j;
+		while (recycled.try_pop(j)) j.reset();
+	}
+	void mate_reader() {
+		omp_team(std::max(1, R.host_threads / 2));  // a new thread starts from the default team size, not main's
+		int x;
+		while (go2.pop(x)) {
+			side2.b.clear();
+			side2.e.clear();
+			side2.more = R.rd2.next_batch(side2.b, R.batch / 2, side2.e);
+			done2.push(1);
+		}
+	}
+	void reader() {
+		const int own_team = R.paired ? std::max(1, R.host_threads - R.host_threads / 2) : R.host_threads;
+		omp_team(own_team);
 		FastqBatch a;
-		for (size_t b = 0; !fail.set.load(); ++b) {
+		for (size_t b = 0; !R.fail.set.load(); ++b) {
 			std::unique_ptr<Job> j;
 			if (!recycled.try_pop(j)) j = std::make_unique<Job>();
 			j->reads.clear();
 			std::string e;
 			bool more;
 			const auto tp0 = now();
-			if (!paired)
-				more = rd.next_batch(j->reads, batch, e);
+			if (!R.paired)
+				more = R.rd.next_batch(j->reads, R.batch, e);
 			else {  // mates interleaved: reads 2i, 2i+1 (map2.cpp:27-32 reads one record from each file under one lock)
 				go2.push(1);
 				a.clear();
-				more = rd.next_batch(a, batch / 2, e);
+				more = R.rd.next_batch(a, R.batch / 2, e);
 				int x;
 				done2.pop(x);
 				const FastqBatch &bb = side2.b;
 				if (e.empty()) e = side2.e;
 				if (e.empty() && (more != side2.more || a.size() != bb.size())) e = std::string("Premature end of file in FASTQ") + (a.size() > bb.size() ? "2" : "1");
 				if (e.empty()) {
-					omp_workers_sleep_when_idle();
-					omp_set_num_threads(host_threads);
+					omp_team(R.host_threads);
 					interleave_batches(a, bb, j->reads);
-					omp_workers_sleep_when_idle();
-					omp_set_num_threads(std::max(1, host_threads - host_threads / 2));
+					omp_team(own_team);
 				}
 			}
-			t_parse += secs(tp0, now());
-			if (!e.empty()) { fail.raise(URMAPX_E_FORMAT, e); break; }
+			R.rep.parse_s += secs(tp0, now());
+			if (!e.empty()) { R.fail.raise(URMAPX_E_FORMAT, e); break; }
 			if (!more) break;
-			parsed[b % (size_t)n_lanes]->push(std::move(j));
+			parsed[b % (size_t)R.n_lanes]->push(std::move(j));
 		}
 		for (auto &c : parsed) c->close();
 		go2.close();
-	});
-	// SAM text of a batch is formatted by all host threads, each on a contiguous range of reads (pairs); the pieces go to
-	// the flusher thread, which writes them at their file offsets (input order) while the next batch is being formatted.
-	struct Text { std::vector<std::string> outs; std::vector<uint64_t> at; };
-	Channel<std::unique_ptr<Text>> to_flush(2), text_pool(4);
-	std::thread flusher([&] {
-		std::unique_ptr<Text> x;
-		while (to_flush.pop(x)) {
-			const auto tw0 = now();
-			if (!fail.set.load()) {
-				if (!sink.reserve(x->at[(size_t)host_threads])) fail.raise(URMAPX_E_IO, std::string("Error writing ") + samout);
-				if (!sink.seekable()) {  // a pipe: the pieces one after the other
-					for (int t = 0; t < host_threads; ++t) {
-						const std::string &out = x->outs[(size_t)t];
-						if (!sink.write_at(out.data(), out.size(), x->at[(size_t)t], 1)) { fail.raise(URMAPX_E_IO, std::string("Error writing ") + samout); break; }
-					}
-				} else {
-#pragma omp parallel for schedule(static, 1) num_threads(host_threads)
-				for (int t = 0; t < host_threads; ++t) {
-					const std::string &out = x->outs[(size_t)t];
-					if (!sink.write_at(out.data(), out.size(), x->at[(size_t)t], 1)) fail.raise(URMAPX_E_IO, std::string("Error writing ") + samout);
-				}
-				}
-			}
-			t_write += secs(tw0, now());
-			text_pool.push(std::move(x));
-		}
-	});
-	std::thread writer([&] {
+	}
+	void lane(int l) {
+		urmapx_ctx *C = R.ctxs[(size_t)l];
 		omp_workers_sleep_when_idle();
-		omp_set_num_threads(host_threads);
+		const bool pinned = pin_to(R.places[(size_t)(l % R.gpus)]);
+		Unpin unpin{pinned, R.caller_mask, 1};
+		(void)hipSetDevice(R.phys(l % R.gpus));
+		std::unique_ptr<Job> j;
+		while (parsed[(size_t)l]->pop(j)) {
+			const uint32_t n = j->reads.size();
+			if (!R.fail.set.load()) {
+				j->results.resize(n);
+				j->ops.resize((size_t)n * URMAPX_MAX_PATH_OPS);
+				// page-lock what crosses PCIe (the arrays are recycled, so this happens once per job object and size)
+				if (!getenv("URMAPX_NO_PIN")) {
+					j->pin_bases.hold(j->reads.bases);
+					j->pin_offs.hold(j->reads.offs);
+					j->pin_results.hold(j->results);
+					j->pin_ops.hold(j->ops);
+				}
+				size_t used = 0;
+				const auto tg0 = now();
+				int mrc = R.paired ? urmapx_map_pe(C, j->reads.bases.data(), j->reads.offs.data(), n / 2, j->results.data(), j->ops.data(),
+				                                   j->ops.size(), &used)
+				                   : urmapx_map_se(C, j->reads.bases.data(), j->reads.offs.data(), n, j->results.data(), j->ops.data(),
+				                                   j->ops.size(), &used);
+				if (mrc != URMAPX_OK && mrc != URMAPX_E_UNSUPPORTED)
+					R.fail.raise(mrc, std::string(R.paired ? "urmapx_map_pe: " : "urmapx_map_se: ") + urmapx_strerror(mrc));
+				else if (R.paired && R.ftab) {
+					j->info.resize(n / 2);
+					mrc = urmapx_ctx_get_pair_info(C, j->info.data(), n / 2);
+					if (mrc) R.fail.raise(mrc, std::string("urmapx_ctx_get_pair_info: ") + urmapx_strerror(mrc));
+				}
+				R.add_lane_time(&Rep::gpu_s, tg0);
+			}
+			mapped[(size_t)l]->push(std::move(j));
+		}
+		mapped[(size_t)l]->close();
+	}
+	void format_batch(const Job &j, std::vector<std::string> &outs, std::vector<Cnt> &cnt) {
+		const bool paired = R.paired;
+		const uint32_t n = j.reads.size(), units = paired ? n / 2 : n;
+		const int T = R.host_threads;
+#pragma omp parallel for schedule(static, 1) num_threads(T)
+		for (int t = 0; t < T; ++t) {
+			std::string &out = outs[(size_t)t];
+			out.clear();
+			Cnt &c = cnt[(size_t)t];
+			const uint32_t u0 = (uint32_t)part(units, t, T), u1 = (uint32_t)part(units, t + 1, T);
+			std::vector<char> pbuf;
+			for (uint32_t i = paired ? 2 * u0 : u0; i < (paired ? 2 * u1 : u1); ++i) {
+				const urmapx_result &r = j.results[i];
+				const uint64_t off = j.reads.offs[i];
+				const unsigned L = (unsigned)(j.reads.offs[i + 1] - off);
+				if (paired && R.have_sam && (i & 1) == 0) {  // a pair's two records; BAM: the host encoders (sam.cpp) write the bytes the device writes for the same read
+					const uint64_t off2 = j.reads.offs[i + 1];
+					const unsigned L2 = (unsigned)(j.reads.offs[i + 2] - off2);
+					const size_t names = strlen(j.reads.label(i)) + strlen(j.reads.label(i + 1));
+					pbuf.resize(names + (R.bam ? 2 * (size_t)(L + L2) + 4 * ((size_t)r.path_nops + j.results[i + 1].path_nops) : 3 * (size_t)(L + L2)) + 2048);
+					const size_t k = (R.bam ? urmapx_bam_pe : urmapx_sam_pe)(R.I, &j.results[i], &j.results[i + 1], j.ops.data(), j.reads.label(i),
+					                                                         j.reads.bases.data() + off, j.reads.quals.data() + off, L, j.reads.label(i + 1),
+					                                                         j.reads.bases.data() + off2, j.reads.quals.data() + off2, L2, pbuf.data(), pbuf.size());
+					if (R.bam && k == URMAPX_BAM_LONG_NAME) R.fail.raise(URMAPX_E_FORMAT, bam_long_name(strlen(j.reads.label(i)) >= strlen(j.reads.label(i + 1)) ? j.reads.label(i) : j.reads.label(i + 1)));
+					else out.append(pbuf.data(), k);
+				} else if (!paired && R.bam) {
+					if (!append_bam_record(out, R.I, r, j.ops.data(), 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, j.reads.label(i),
+					                       j.reads.bases.data() + off, j.reads.quals.data() + off, L))
+						R.fail.raise(URMAPX_E_FORMAT, bam_long_name(j.reads.label(i)));
+				} else if (!paired && R.have_sam)
+					append_sam_record(out, R.I, r, j.ops.data(), 0, "*", 0xFFFFFFFFu, 0, j.reads.label(i),
+					                  j.reads.bases.data() + off, j.reads.quals.data() + off, L);
+				// HitStats counters (output1.cpp:20-30)
+				if (r.status) ++c.unsupported;
+				if (r.dbpos == 0xFFFFFFFFu) ++c.nohit;
+				else if (r.mapq >= R.minq) ++c.accept;
+				else ++c.reject;
+			}
+			c.text = out.size();
+			if (R.bgzf && !bgzf_members(out)) R.fail.raise(URMAPX_E_NOMEM, "out of memory");
+		}
+	}
+	// tab lines: formatted by all host threads (pair ranges), written in order
+	void write_tab_lines(const Job &j) {
+		const uint32_t units = j.reads.size() / 2;
+		const int T = R.host_threads;
+		std::vector<std::string> tabs((size_t)T);
+#pragma omp parallel for schedule(static, 1) num_threads(T)
+		for (int t = 0; t < T; ++t) {
+			char line[4096];
+			for (uint32_t u = (uint32_t)part(units, t, T); u < (uint32_t)part(units, t + 1, T); ++u) {
+				const uint32_t i = 2 * u;
+				const unsigned L1 = (unsigned)(j.reads.offs[i + 1] - j.reads.offs[i]), L2 = (unsigned)(j.reads.offs[i + 2] - j.reads.offs[i + 1]);
+				const size_t k = urmapx_tab_pe(R.I, &j.results[i], &j.results[i + 1], &j.info[u], j.reads.label(i), L1, L2,
+				                               R.have_sam ? 1 : 0, line, sizeof line);
+				tabs[(size_t)t].append(line, k);
+			}
+		}
+		for (const std::string &tb : tabs)
+			if (fwrite(tb.data(), 1, tb.size(), R.ftab.get()) != tb.size()) R.fail.raise(URMAPX_E_IO, std::string("Error writing ") + R.tabout);
+	}
+	void formatter() {
+		omp_team(R.host_threads);
+		const size_t T = (size_t)R.host_threads;
 		std::unique_ptr<Job> j;
 		std::unique_ptr<Text> text;
-		struct Cnt { unsigned long long accept = 0, reject = 0, nohit = 0, unsupported = 0; };
-		for (size_t b = 0; mapped[b % (size_t)n_lanes]->pop(j); ++b) {
-			if (fail.set.load()) { recycled.push(std::move(j)); continue; }
-			const uint32_t n = j->reads.size();
-			const uint32_t units = paired ? n / 2 : n;
-			std::vector<Cnt> cnt((size_t)host_threads);
+		for (size_t b = 0; mapped[b % (size_t)R.n_lanes]->pop(j); ++b) {
+			if (R.fail.set.load()) { recycled.push(std::move(j)); continue; }
+			std::vector<Cnt> cnt(T);
 			if (!text && !text_pool.try_pop(text)) text = std::make_unique<Text>();
-			text->outs.resize((size_t)host_threads);
-			std::vector<std::string> &outs = text->outs;
+			text->outs.resize(T);
 			const auto tf0 = now();
-#pragma omp parallel for schedule(static, 1) num_threads(host_threads)
-			for (int t = 0; t < host_threads; ++t) {
-				std::string &out = outs[(size_t)t];
-				out.clear();
-				Cnt &c = cnt[(size_t)t];
-				const uint32_t u0 = (uint32_t)((uint64_t)units * (uint64_t)t / (uint64_t)host_threads);
-				const uint32_t u1 = (uint32_t)((uint64_t)units * (uint64_t)(t + 1) / (uint64_t)host_threads);
-				std::vector<char> pbuf;
-				for (uint32_t i = paired ? 2 * u0 : u0; i < (paired ? 2 * u1 : u1); ++i) {
-					const urmapx_result &r = j->results[i];
-					const uint64_t off = j->reads.offs[i];
-					const unsigned L = (unsigned)(j->reads.offs[i + 1] - off);
-					if (bam) {  // the host encoders (sam.cpp): the bytes the device writes for the same read
-						if (!paired) {
-							if (!append_bam_record(out, I, r, j->ops.data(), 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, j->reads.label(i),
-							                       j->reads.bases.data() + off, j->reads.quals.data() + off, L))
-								fail.raise(URMAPX_E_FORMAT, bam_long_name(j->reads.label(i)));
-						} else if ((i & 1) == 0) {
-							const uint64_t off2 = j->reads.offs[i + 1];
-							const unsigned L2 = (unsigned)(j->reads.offs[i + 2] - off2);
-							pbuf.resize(strlen(j->reads.label(i)) + strlen(j->reads.label(i + 1)) + 2 * (size_t)(L + L2) + 4 * ((size_t)r.path_nops + j->results[i + 1].path_nops) + 2048);
-							const size_t k = urmapx_bam_pe(I, &j->results[i], &j->results[i + 1], j->ops.data(), j->reads.label(i),
-							                               j->reads.bases.data() + off, j->reads.quals.data() + off, L,
-							                               j->reads.label(i + 1), j->reads.bases.data() + off2,
-							                               j->reads.quals.data() + off2, L2, pbuf.data(), pbuf.size());
-							if (k == URMAPX_BAM_LONG_NAME) fail.raise(URMAPX_E_FORMAT, bam_long_name(strlen(j->reads.label(i)) >= strlen(j->reads.label(i + 1)) ? j->reads.label(i) : j->reads.label(i + 1)));
-							else out.append(pbuf.data(), k);
-						}
-					}
-					if (have_sam && !bam && !paired)
-						append_sam_record(out, I, r, j->ops.data(), 0, "*", 0xFFFFFFFFu, 0, j->reads.label(i),
-						                  j->reads.bases.data() + off, j->reads.quals.data() + off, L);
-					if (have_sam && !bam && paired && (i & 1) == 0) {
-						const uint64_t off2 = j->reads.offs[i + 1];
-						const unsigned L2 = (unsigned)(j->reads.offs[i + 2] - off2);
-						pbuf.resize(strlen(j->reads.label(i)) + strlen(j->reads.label(i + 1)) + 3 * (size_t)(L + L2) + 2048);
-						size_t k = urmapx_sam_pe(I, &j->results[i], &j->results[i + 1], j->ops.data(), j->reads.label(i),
-						                         j->reads.bases.data() + off, j->reads.quals.data() + off, L,
-						                         j->reads.label(i + 1), j->reads.bases.data() + off2,
-						                         j->reads.quals.data() + off2, L2, pbuf.data(), pbuf.size());
-						out.append(pbuf.data(), k);
-					}
-					// HitStats counters (output1.cpp:20-30)
-					if (r.status) ++c.unsupported;
-					if (r.dbpos == 0xFFFFFFFFu) ++c.nohit;
-					else if (r.mapq >= minq) ++c.accept;
-					else ++c.reject;
-				}
-				sam_text_bytes += out.size();
-				if (bgzf && !bgzf_members(out)) fail.raise(URMAPX_E_NOMEM, "out of memory");
+			format_batch(*j, text->outs, cnt);
+			for (const Cnt &c : cnt) {
+				R.rep.mapped_q += c.accept; R.rep.mapped_lowq += c.reject; R.rep.unmapped += c.nohit; R.rep.unsupported += c.unsupported;
+				R.rep.sam_text_bytes += c.text;
 			}
-			for (const Cnt &c : cnt) { n_accept += c.accept; n_reject += c.reject; n_nohit += c.nohit; n_unsupported += c.unsupported; }
-			n_reads += n;
-			const auto tf1 = now();
-			t_format += secs(tf0, tf1);
-			if (have_sam) {
+			R.rep.reads += j->reads.size();
+			R.rep.format_s += secs(tf0, now());
+			if (R.have_sam) {
 				std::vector<uint64_t> &at = text->at;
-				at.assign((size_t)host_threads + 1, 0);
-				at[0] = sam_off;
-				for (int t = 0; t < host_threads; ++t) at[(size_t)t + 1] = at[(size_t)t] + outs[(size_t)t].size();
-				sam_off = at[(size_t)host_threads];
+				at.assign(T + 1, 0);
+				at[0] = R.rep.sam_file_bytes;
+				for (size_t t = 0; t < T; ++t) at[t + 1] = at[t] + text->outs[t].size();
+				R.rep.sam_file_bytes = at[T];
 				to_flush.push(std::move(text));
 			}
-			if (ftab && paired) {  // tab lines: formatted by all host threads (pair ranges), written in order
-				std::vector<std::string> tabs((size_t)host_threads);
-#pragma omp parallel for schedule(static, 1) num_threads(host_threads)
-				for (int t = 0; t < host_threads; ++t) {
-					const uint32_t u0 = (uint32_t)((uint64_t)units * (uint64_t)t / (uint64_t)host_threads);
-					const uint32_t u1 = (uint32_t)((uint64_t)units * (uint64_t)(t + 1) / (uint64_t)host_threads);
-					char line[4096];
-					for (uint32_t u = u0; u < u1; ++u) {
-						const uint32_t i = 2 * u;
-						const unsigned L1 = (unsigned)(j->reads.offs[i + 1] - j->reads.offs[i]), L2 = (unsigned)(j->reads.offs[i + 2] - j->reads.offs[i + 1]);
-						const size_t k = urmapx_tab_pe(I, &j->results[i], &j->results[i + 1], &j->info[u], j->reads.label(i), L1, L2,
-						                               have_sam ? 1 : 0, line, sizeof line);
-						tabs[(size_t)t].append(line, k);
-					}
-				}
-				for (const std::string &tb : tabs)
-					if (fwrite(tb.data(), 1, tb.size(), ftab) != tb.size()) fail.raise(URMAPX_E_IO, std::string("Error writing ") + tabout);
-			}
+			if (R.ftab && R.paired) write_tab_lines(*j);
 			recycled.push(std::move(j));
 		}
 		to_flush.close();
-	});
-	std::vector<std::thread> lanes;
-	for (int l = 0; l < n_lanes; ++l)
-		lanes.emplace_back([&, l] {
-			urmapx_ctx *C = ctxs[(size_t)l];
-			omp_workers_sleep_when_idle();
-			const bool pinned = pin_to(places[(size_t)(l % gpus)]);
-			struct Unpin { bool on; const cpu_set_t &m; int n; ~Unpin() { unpin_team(on, m, n); } } unpin{pinned, caller_mask, 1};
-			(void)hipSetDevice(phys(l % gpus));
-			std::unique_ptr<Job> j;
-			while (parsed[(size_t)l]->pop(j)) {
-				const uint32_t n = j->reads.size();
-				if (!fail.set.load()) {
-					j->results.resize(n);
-					j->ops.resize((size_t)n * URMAPX_MAX_PATH_OPS);
-					// page-lock what crosses PCIe (the arrays are recycled, so this happens once per job object and size)
-					if (!getenv("URMAPX_NO_PIN")) {
-						j->pin_bases.hold(j->reads.bases);
-						j->pin_offs.hold(j->reads.offs);
-						j->pin_results.hold(j->results);
-						j->pin_ops.hold(j->ops);
-					}
-					size_t used = 0;
-					const auto tg0 = now();
-					int mrc = paired ? urmapx_map_pe(C, j->reads.bases.data(), j->reads.offs.data(), n / 2, j->results.data(), j->ops.data(),
-					                                 j->ops.size(), &used)
-					                 : urmapx_map_se(C, j->reads.bases.data(), j->reads.offs.data(), n, j->results.data(), j->ops.data(),
-					                                 j->ops.size(), &used);
-					if (mrc != URMAPX_OK && mrc != URMAPX_E_UNSUPPORTED)
-						fail.raise(mrc, std::string(paired ? "urmapx_map_pe: " : "urmapx_map_se: ") + urmapx_strerror(mrc));
-					else if (paired && ftab) {
-						j->info.resize(n / 2);
-						mrc = urmapx_ctx_get_pair_info(C, j->info.data(), n / 2);
-						if (mrc) fail.raise(mrc, std::string("urmapx_ctx_get_pair_info: ") + urmapx_strerror(mrc));
-					}
-					std::lock_guard<std::mutex> g(gpu_time_lock);
-					t_gpu += secs(tg0, now());
+	}
+	void flusher() {
+		const int T = R.host_threads;
+		std::unique_ptr<Text> x;
+		while (to_flush.pop(x)) {
+			const auto tw0 = now();
+			if (!R.fail.set.load()) {
+				if (!R.sink.reserve(x->at[(size_t)T])) R.cannot_write_sam();
+				// (a pipe: the pieces one after the other; behind a piece that failed the others are refused, their offset is not the file's end)
+#pragma omp parallel for schedule(static, 1) num_threads(T) if (R.sink.seekable())
+				for (int t = 0; t < T; ++t) {
+					const std::string &out = x->outs[(size_t)t];
+					if (!R.sink.write_at(out.data(), out.size(), x->at[(size_t)t], 1)) R.cannot_write_sam();
 				}
-				mapped[(size_t)l]->push(std::move(j));
 			}
-			mapped[(size_t)l]->close();
-		});
-	for (auto &t : lanes) t.join();
-	reader.join();
-	if (reader2.joinable()) reader2.join();
-	writer.join();
-	flusher.join();
-	{  // page-locked arrays are released before their contexts go
-		std::unique_ptr<Job> j;
-		while (recycled.try_pop(j)) j.reset();
+			R.rep.write_s += secs(tw0, now());
+			text_pool.push(std::move(x));
+		}
 	}
-	}  // host phase
-	if (bgzf && !fail.set.load()) {  // htslib's empty member: the file is complete
-		std::string eof;
-		(void)bgzf_members(eof, 1);
-		if (!sink.write_at(eof.data(), eof.size(), sam_off, 1)) fail.raise(URMAPX_E_IO, std::string("Error writing ") + samout);
-		sam_off += eof.size();
+};
+
+int map_files_impl(urmapx_index *I, const urmapx_map_options *opt, const InputRange &range, const char *fastq1, const char *fastq2,
+                   const char *samout, const char *tabout, urmapx_map_report *report, char *err, size_t errcap) {
+	if (err && errcap) err[0] = 0;
+	if (!I || !opt || !fastq1) return URMAPX_E_ARG;
+	Run R{I, *opt, range, fastq1, fastq2, samout, tabout};
+	std::string msg;
+	int rc = R.open(msg);
+	if (!rc) {
+		bool host_work = true;
+		{
+			TextPhase text{R};
+			if (text.open_input()) {
+				text.run();
+				host_work = text.leaves_work();
+			}
+		}
+		if (host_work) HostPhase{R}.run();
+		rc = R.finish(report, msg);
 	}
-	if (have_sam && !sink.finish(sam_off)) fail.raise(URMAPX_E_IO, std::string("Error writing ") + samout);
-	if (ftab) fclose(ftab);
-	const auto t2 = std::chrono::steady_clock::now();
-	range.t_begin = std::chrono::duration<double>(t1.time_since_epoch()).count();
-	range.t_end = std::chrono::duration<double>(t2.time_since_epoch()).count();
-	trace.dump();
-	run_ok = !fail.set.load();
-	release();
-	if (report) {
-		report->reads = n_reads; report->mapped_q = n_accept; report->mapped_lowq = n_reject; report->unmapped = n_nohit;
-		report->unsupported = n_unsupported;
-		report->seconds = secs(t1, t2); report->parse_s = t_parse; report->gpu_s = t_gpu; report->format_s = t_format; report->write_s = t_write;
-		report->host_threads = host_threads; report->lanes = n_lanes;
-		report->write_threads = write_threads_used; report->text_on_device = text_on_device ? 1 : 0; report->input_bytes = input_bytes;
-		snprintf(report->medium, sizeof report->medium, "%s", have_sam ? medium_name.c_str() : "none");
-		report->dev_h2d_s = dev_ms[0] * 1e-3; report->dev_parse_s = dev_ms[1] * 1e-3; report->dev_map_s = dev_ms[2] * 1e-3;
-		report->dev_format_s = dev_ms[3] * 1e-3; report->dev_d2h_s = dev_ms[4] * 1e-3;
-		report->dev_map_search_s = dev_ms[5] * 1e-3; report->dev_map_dp_s = dev_ms[6] * 1e-3; report->map_enqueue_s = dev_ms[7] * 1e-3;
-		report->shards = 1;
-		report->sam_text_bytes = sam_text_bytes.load(); report->sam_file_bytes = have_sam ? sam_off : 0;
-		snprintf(report->placement, sizeof report->placement, "%s", placement.c_str());
-	}
-	if (fail.set.load()) { say(fail.msg); return fail.code; }
-	return n_unsupported ? URMAPX_E_UNSUPPORTED : URMAPX_OK;
+	say(err, errcap, msg);
+	return rc;
 }
 
 }  // namespace
@@ -1763,112 +1795,80 @@ int map_files_impl(urmapx_index *I, const urmapx_map_options *opt, const InputRa
 // input with its own SAM file, devices and writer (the reference appends every record to one file under one lock,
 // output1.cpp:10-16: one output stream is what bounds a run on several GPUs)
 static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const char *fastq1, const char *fastq2,
-                           const char *samout, const char *tabout, urmapx_map_report *report, char *err, size_t errcap);
-extern "C" int urmapx_map_files(urmapx_index *I, const urmapx_map_options *opt, const char *fastq1, const char *fastq2,
-                                const char *samout, const char *tabout, urmapx_map_report *report, char *err, size_t errcap) {
-	// what the call spent in allocation calls (all of its threads): device arrays of the lanes' contexts, page-locked chunk buffers
-	AllocClock &ac = alloc_clock();
-	const uint64_t ns0[2] = {ac.ns[0].load(), ac.ns[1].load()}, c0[2] = {ac.calls[0].load(), ac.calls[1].load()};
-	const int rc = map_files_entry(I, opt, fastq1, fastq2, samout, tabout, report, err, errcap);
-	if (report) {
-		report->alloc_dev_s = (double)(ac.ns[0].load() - ns0[0]) * 1e-9; report->alloc_pinned_s = (double)(ac.ns[1].load() - ns0[1]) * 1e-9;
-		report->alloc_dev_calls = (uint32_t)(ac.calls[0].load() - c0[0]); report->alloc_pinned_calls = (uint32_t)(ac.calls[1].load() - c0[1]);
-	}
-	return rc;
-}
-static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const char *fastq1, const char *fastq2,
                            const char *samout, const char *tabout, urmapx_map_report *report, char *err, size_t errcap) {
 	if (err && errcap) err[0] = 0;
 	if (!I || !opt || !fastq1) return URMAPX_E_ARG;
-	if (opt->bam && opt->bgzf) {
-		if (err && errcap) snprintf(err, errcap, "bam and bgzf together: a BAM file is always BGZF");
-		return URMAPX_E_ARG;
-	}
+	if (opt->bam && opt->bgzf) { say(err, errcap, "bam and bgzf together: a BAM file is always BGZF"); return URMAPX_E_ARG; }
 	const int shards = opt->sam_shards > 1 ? opt->sam_shards : 1;
 	if (shards == 1) return map_files_impl(I, opt, InputRange(), fastq1, fastq2, samout, tabout, report, err, errcap);
-	auto say = [&](const std::string &s) {
-		if (err && errcap) snprintf(err, errcap, "%s", s.c_str());
-	};
 	const bool paired = fastq2 != nullptr;
 	const int gpus = opt->gpus > 0 ? opt->gpus : 1;
-	if (!samout) { say("-samshards needs -samout (the shards are named after it)"); return URMAPX_E_ARG; }
-	if (shards > 64) { say("-samshards must be 1..64"); return URMAPX_E_ARG; }
-	if (gpus % shards != 0 && shards % gpus != 0) { say("-samshards must divide -gpus or be a multiple of it"); return URMAPX_E_ARG; }
-	const int host_threads = opt->host_threads > 0 ? opt->host_threads : std::min(16, std::max(1, (int)std::thread::hardware_concurrency()));
+	if (!samout) { say(err, errcap, "-samshards needs -samout (the shards are named after it)"); return URMAPX_E_ARG; }
+	if (shards > 64) { say(err, errcap, "-samshards must be 1..64"); return URMAPX_E_ARG; }
+	if (gpus % shards != 0 && shards % gpus != 0) { say(err, errcap, "-samshards must divide -gpus or be a multiple of it"); return URMAPX_E_ARG; }
+	const int host_threads = host_threads_of(*opt);
 	// plain seekable files are cut; anything else (.gz, a pipe) goes to shard 0 whole
-	auto plain_size = [](const char *path, int &fd) -> uint64_t {
-		fd = -1;
-		const size_t l = strlen(path);
-		if ((l > 3 && !strcmp(path + l - 3, ".gz")) || !strcmp(path, "-")) return 0;
-		fd = open(path, O_RDONLY);
-		struct stat st;
-		if (fd >= 0 && (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size == 0)) { close(fd); fd = -1; }
-		return fd >= 0 ? (uint64_t)st.st_size : 0;
-	};
-	int fd1 = -1, fd2 = -1;
-	const uint64_t fsize1 = plain_size(fastq1, fd1), fsize2 = paired ? plain_size(fastq2, fd2) : 0;
+	uint64_t fsize1 = 0, fsize2 = 0;
+	const int fd1 = open_plain(fastq1, fsize1), fd2 = paired ? open_plain(fastq2, fsize2) : -1;
 	const bool cut = fd1 >= 0 && (!paired || fd2 >= 0) && !getenv("URMAPX_HOST_TEXT_NO_SHARDS");
-	std::vector<InputRange> ranges((size_t)shards);
 	// the cutting (and, for pairs, the line counts that place the cuts of the mates' file) belongs to the run: it is inside
 	// report->seconds and reported as shard_scan_s
-	const auto t_scan0 = std::chrono::steady_clock::now();
-	{
-		// shard s starts at the first record start at or behind byte fsize * s / shards of the first file -- and, for pairs, at
-		// the same line of the second file
-		std::vector<uint64_t> at((size_t)shards + 1, 0), at2((size_t)shards + 1, 0), lines((size_t)shards + 1, 0);
-		at[(size_t)shards] = fsize1; at2[(size_t)shards] = fsize2;
-		if (cut) {
-			for (int s = 1; s < shards; ++s) {
-				const uint64_t nominal = fsize1 / (uint64_t)shards * (uint64_t)s;
-				uint64_t a = nominal > at[(size_t)s - 1] ? find_record_start(fd1, nominal, fsize1) : at[(size_t)s - 1];
-				if (a == 0 || a < at[(size_t)s - 1]) a = fsize1;  // no record start in sight: the shard in front takes the rest
-				at[(size_t)s] = a;
-			}
-			if (paired) {  // the mates' file is cut at the same LINES: the first file's parts are counted, the second's offsets looked up
-				for (int s = 1; s < shards; ++s) lines[(size_t)s] = lines[(size_t)s - 1] + count_newlines(fd1, at[(size_t)s - 1], at[(size_t)s], host_threads);
-				const std::vector<uint64_t> o2 = line_offsets(fd2, fsize2, std::vector<uint64_t>(lines.begin() + 1, lines.begin() + shards), host_threads);
-				for (int s = 1; s < shards; ++s) at2[(size_t)s] = o2[(size_t)s - 1];
-			}
+	const auto t_scan0 = now();
+	// shard s starts at the first record start at or behind byte fsize * s / shards of the first file -- and, for pairs, at
+	// the same line of the second file
+	std::vector<InputRange> ranges((size_t)shards);
+	std::vector<uint64_t> at((size_t)shards + 1, 0), at2((size_t)shards + 1, 0), lines((size_t)shards + 1, 0);
+	at[(size_t)shards] = fsize1; at2[(size_t)shards] = fsize2;
+	if (cut) {
+		for (int s = 1; s < shards; ++s) {
+			const uint64_t nominal = fsize1 / (uint64_t)shards * (uint64_t)s;
+			uint64_t a = nominal > at[(size_t)s - 1] ? find_record_start(fd1, nominal, fsize1) : at[(size_t)s - 1];
+			if (a == 0 || a < at[(size_t)s - 1]) a = fsize1;  // no record start in sight: the shard in front takes the rest
+			at[(size_t)s] = a;
 		}
-		for (int s = 0; s < shards; ++s) {
-			InputRange &r = ranges[(size_t)s];
-			r.header = s == 0;
-			r.on = cut;
-			r.lo[0] = at[(size_t)s]; r.hi[0] = at[(size_t)s + 1]; r.lo[1] = at2[(size_t)s]; r.hi[1] = at2[(size_t)s + 1];
-			r.lines_before = lines[(size_t)s];
-			if (cut && !paired && s > 0) {
-				// single-end: nothing needs the line counts but a message about a malformed record -- the shard's reader counts then
-				const std::string path = fastq1;
-				const uint64_t upto = at[(size_t)s];
-				r.lazy_lines = [path, upto, host_threads]() -> uint64_t {
-					const int fd = open(path.c_str(), O_RDONLY);
-					if (fd < 0) return 0;
-					const uint64_t n = count_newlines(fd, 0, upto, host_threads);
-					close(fd);
-					return n;
-				};
-			}
+		if (paired) {  // the mates' file is cut at the same LINES: the first file's parts are counted, the second's offsets looked up
+			for (int s = 1; s < shards; ++s) lines[(size_t)s] = lines[(size_t)s - 1] + count_newlines(fd1, at[(size_t)s - 1], at[(size_t)s], host_threads);
+			const std::vector<uint64_t> o2 = line_offsets(fd2, fsize2, std::vector<uint64_t>(lines.begin() + 1, lines.begin() + shards), host_threads);
+			for (int s = 1; s < shards; ++s) at2[(size_t)s] = o2[(size_t)s - 1];
 		}
-		if (paired && cut) ranges[(size_t)shards - 1].hi[1] = fsize2;
 	}
+	for (int s = 0; s < shards; ++s) {
+		InputRange &r = ranges[(size_t)s];
+		r.header = s == 0;
+		r.on = cut;
+		r.lo[0] = at[(size_t)s]; r.hi[0] = at[(size_t)s + 1]; r.lo[1] = at2[(size_t)s]; r.hi[1] = at2[(size_t)s + 1];
+		r.lines_before = lines[(size_t)s];
+		if (cut && !paired && s > 0) {
+			// single-end: nothing needs the line counts but a message about a malformed record -- the shard's reader counts then
+			const std::string path = fastq1;
+			const uint64_t upto = at[(size_t)s];
+			r.lazy_lines = [path, upto, host_threads]() -> uint64_t {
+				const int fd = open(path.c_str(), O_RDONLY);
+				if (fd < 0) return 0;
+				const uint64_t n = count_newlines(fd, 0, upto, host_threads);
+				close(fd);
+				return n;
+			};
+		}
+	}
+	if (paired && cut) ranges[(size_t)shards - 1].hi[1] = fsize2;
 	if (fd1 >= 0) close(fd1);
 	if (fd2 >= 0) close(fd2);
-	const double scan_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_scan0).count();
+	const double scan_s = secs(t_scan0, now());
 	// a shard without records: an empty file, under -bgzf the end-of-file member alone (every shard is a complete BGZF file), under
 	// -bamout the header block in a member of its own in front of that (every shard is a complete BAM file)
-	auto empty_sam = [&](const std::string &path) {
-		FILE *f = fopen(path.c_str(), "wb");
-		if (!f) return;
-		std::string eof;
-		if (opt->bam) append_bam_header(eof, I, opt->cmdline);
-		if ((opt->bgzf || opt->bam) && bgzf_members(eof, 1)) (void)fwrite(eof.data(), 1, eof.size(), f);
-		fclose(f);
-	};
-	auto empty_shards_from = [&](int s0) {
-		for (int s = s0; s < shards; ++s) {
-			empty_sam(std::string(samout) + "." + std::to_string(s));
-			if (tabout) { FILE *f = fopen((std::string(tabout) + "." + std::to_string(s)).c_str(), "wb"); if (f) fclose(f); }
+	auto empty_shard = [&](int s) {
+		if (FILE *f = fopen(shard_name(samout, s).c_str(), "wb")) {
+			std::string eof;
+			if (opt->bam) append_bam_header(eof, I, opt->cmdline);
+			if ((opt->bgzf || opt->bam) && bgzf_members(eof, 1)) (void)fwrite(eof.data(), 1, eof.size(), f);
+			fclose(f);
 		}
+		if (tabout) create_empty(shard_name(tabout, s));
+	};
+	auto remove_shard = [&](int s) {
+		remove(shard_name(samout, s).c_str());
+		if (tabout) remove(shard_name(tabout, s).c_str());
 	};
 	if (!cut) {
 		// Input that cannot be cut (.gz, BGZF, a pipe): ONE pipeline with all the devices and lanes the caller gave writes shard 0, the
@@ -1876,29 +1876,28 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
 		// the devices: `-gpus 8 -samshards 8 reads.fq.gz` mapped the whole file on one GPU.)
 		urmapx_map_options o = *opt;
 		o.sam_shards = 0;
-		const std::string sam0 = std::string(samout) + ".0", tab0 = tabout ? std::string(tabout) + ".0" : std::string();
+		const std::string sam0 = shard_name(samout, 0), tab0 = tabout ? shard_name(tabout, 0) : std::string();
 		const int rc1 = map_files_impl(I, &o, InputRange(), fastq1, fastq2, sam0.c_str(), tabout ? tab0.c_str() : nullptr, report, err, errcap);
-		if (rc1 == URMAPX_OK || rc1 == URMAPX_E_UNSUPPORTED) empty_shards_from(1);
-		else { remove(sam0.c_str()); if (tabout) remove(tab0.c_str()); }
+		if (rc1 == URMAPX_OK || rc1 == URMAPX_E_UNSUPPORTED)
+			for (int s = 1; s < shards; ++s) empty_shard(s);
+		else remove_shard(0);
 		if (report) report->shards = shards;
 		return rc1;
 	}
 	// devices: shard s takes gpus / shards of them, or shares device s mod gpus
-	const char *forced = getenv("URMAPX_FORCE_DEVICE");
-	auto phys = [&](int g) { return forced ? atoi(forced) : opt->first_gpu + g; };
 	const int per = gpus >= shards ? gpus / shards : 1;
 	// one replica of the index on the first device of every shard (a shard with several devices makes the others' itself)
 	std::vector<urmapx_index *> replicas((size_t)gpus, nullptr);
-	int rc = urmapx_index_upload(I, phys(0));
+	int rc = urmapx_index_upload(I, phys_device(*opt, 0));
 	replicas[0] = I;
-	for (int g = per; g < gpus && !rc; g += per) rc = urmapx_index_replicate(I, phys(g), &replicas[(size_t)g]);
+	for (int g = per; g < gpus && !rc; g += per) rc = urmapx_index_replicate(I, phys_device(*opt, g), &replicas[(size_t)g]);
 	auto release = [&]() { for (int g = 1; g < gpus; ++g) urmapx_index_close(replicas[(size_t)g]); };
-	if (rc) { say(std::string("Uploading index to the GPU: ") + urmapx_strerror(rc)); release(); return rc; }
+	if (rc) { say(err, errcap, std::string("Uploading index to the GPU: ") + urmapx_strerror(rc)); release(); return rc; }
 	std::vector<urmapx_map_report> reps((size_t)shards);
 	std::vector<int> rcs((size_t)shards, 0);
 	std::vector<std::string> errs((size_t)shards);
 	std::vector<std::thread> th;
-	const auto t0 = std::chrono::steady_clock::now();
+	const auto t0 = now();
 	for (int s = 0; s < shards; ++s)
 		th.emplace_back([&, s] {
 			urmapx_map_options o = *opt;
@@ -1909,22 +1908,17 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
 			const int g0 = gpus >= shards ? s * per : s % gpus;
 			o.first_gpu = opt->first_gpu + g0;
 			o.host_threads = std::max(2, host_threads / shards);
-			const std::string sam = std::string(samout) + "." + std::to_string(s);
-			const std::string tab = tabout ? std::string(tabout) + "." + std::to_string(s) : std::string();
+			const std::string sam = shard_name(samout, s), tab = tabout ? shard_name(tabout, s) : std::string();
 			char e[512];
 			e[0] = 0;
 			memset(&reps[(size_t)s], 0, sizeof reps[(size_t)s]);
 			const InputRange &r = ranges[(size_t)s];
-			if (r.lo[0] >= r.hi[0]) {  // nothing left for this shard (fewer records than shards)
-				empty_sam(sam);
-				if (tabout) { FILE *f = fopen(tab.c_str(), "wb"); if (f) fclose(f); }
-				return;
-			}
+			if (r.lo[0] >= r.hi[0]) { empty_shard(s); return; }  // nothing left for this shard (fewer records than shards)
 			rcs[(size_t)s] = map_files_impl(replicas[(size_t)g0], &o, r, fastq1, fastq2, sam.c_str(), tabout ? tab.c_str() : nullptr, &reps[(size_t)s], e, sizeof e);
 			errs[(size_t)s] = e;
 		});
 	for (auto &t : th) t.join();
-	double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+	double wall = secs(t0, now());
 	{
 		double b = 0, e = 0;
 		for (const InputRange &r : ranges)
@@ -1935,22 +1929,15 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
 	release();
 	int out_rc = URMAPX_OK;
 	for (int s = 0; s < shards; ++s)
-		if (rcs[(size_t)s] && rcs[(size_t)s] != URMAPX_E_UNSUPPORTED && out_rc == URMAPX_OK) { out_rc = rcs[(size_t)s]; say(errs[(size_t)s]); }
+		if (rcs[(size_t)s] && rcs[(size_t)s] != URMAPX_E_UNSUPPORTED && out_rc == URMAPX_OK) { out_rc = rcs[(size_t)s]; say(err, errcap, errs[(size_t)s]); }
 	if (out_rc != URMAPX_OK)  // a failed run leaves no partial shard files behind (the first error is the one reported)
-		for (int s = 0; s < shards; ++s) {
-			remove((std::string(samout) + "." + std::to_string(s)).c_str());
-			if (tabout) remove((std::string(tabout) + "." + std::to_string(s)).c_str());
-		}
+		for (int s = 0; s < shards; ++s) remove_shard(s);
 	if (report) {
 		memset(report, 0, sizeof *report);
 		for (const urmapx_map_report &r : reps) {
-			report->reads += r.reads; report->mapped_q += r.mapped_q; report->mapped_lowq += r.mapped_lowq; report->unmapped += r.unmapped;
-			report->unsupported += r.unsupported; report->parse_s += r.parse_s; report->gpu_s += r.gpu_s; report->format_s += r.format_s;
-			report->sam_text_bytes += r.sam_text_bytes; report->sam_file_bytes += r.sam_file_bytes;
-			report->write_s += r.write_s; report->lanes += r.lanes; report->host_threads += r.host_threads; report->input_bytes += r.input_bytes;
-			report->dev_h2d_s += r.dev_h2d_s; report->dev_parse_s += r.dev_parse_s; report->dev_map_s += r.dev_map_s;
-			report->dev_format_s += r.dev_format_s; report->dev_d2h_s += r.dev_d2h_s;
-			report->dev_map_search_s += r.dev_map_search_s; report->dev_map_dp_s += r.dev_map_dp_s; report->map_enqueue_s += r.map_enqueue_s;
+			for (auto f : kReportCounts) report->*f += r.*f;
+			for (auto f : kReportTimes) report->*f += r.*f;
+			report->lanes += r.lanes; report->host_threads += r.host_threads;
 			report->write_threads = std::max(report->write_threads, r.write_threads);
 			report->text_on_device |= r.text_on_device;
 			if (r.medium[0]) memcpy(report->medium, r.medium, sizeof report->medium);
@@ -1967,6 +1954,18 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
 	return report && report->unsupported ? URMAPX_E_UNSUPPORTED : URMAPX_OK;
 }
 
+extern "C" int urmapx_map_files(urmapx_index *I, const urmapx_map_options *opt, const char *fastq1, const char *fastq2,
+                                const char *samout, const char *tabout, urmapx_map_report *report, char *err, size_t errcap) {
+	// what the call spent in allocation calls (all of its threads): device arrays of the lanes' contexts, page-locked chunk buffers
+	AllocClock &ac = alloc_clock();
+	const uint64_t ns0[2] = {ac.ns[0].load(), ac.ns[1].load()}, c0[2] = {ac.calls[0].load(), ac.calls[1].load()};
+	const int rc = map_files_entry(I, opt, fastq1, fastq2, samout, tabout, report, err, errcap);
+	if (report) {
+		report->alloc_dev_s = (double)(ac.ns[0].load() - ns0[0]) * 1e-9; report->alloc_pinned_s = (double)(ac.ns[1].load() - ns0[1]) * 1e-9;
+		report->alloc_dev_calls = (uint32_t)(ac.calls[0].load() - c0[0]); report->alloc_pinned_calls = (uint32_t)(ac.calls[1].load() - c0[1]);
+	}
+	return rc;
+}
 extern "C" void urmapx_host_pool_trim(void) {
 	LanePool::get().purge(nullptr);
 	HostPool::get().trim();

@@ -45,8 +45,9 @@ static int cmd_map(int argc, char **argv) {
 	urmapx_map_report rep;
 	char err[512];
 	const int rc = urmapx_map_files(I, &o, fq1, fq2, sam, tab, &rep, err, sizeof err);
-	printf("rc=%d reads=%llu mapped_q=%llu mapped_lowq=%llu unmapped=%llu text_on_device=%d shards=%d lanes=%d err=%s\n", rc, (unsigned long long)rep.reads,
-	       (unsigned long long)rep.mapped_q, (unsigned long long)rep.mapped_lowq, (unsigned long long)rep.unmapped, rep.text_on_device, rep.shards, rep.lanes, err);
+	printf("rc=%d reads=%llu mapped_q=%llu mapped_lowq=%llu unmapped=%llu text_on_device=%d input_bytes=%llu shards=%d lanes=%d err=%s\n", rc, (unsigned long long)rep.reads,
+	       (unsigned long long)rep.mapped_q, (unsigned long long)rep.mapped_lowq, (unsigned long long)rep.unmapped, rep.text_on_device, (unsigned long long)rep.input_bytes, rep.shards,
+	       rep.lanes, err);
 	urmapx_index_close(I);
 	urmapx_host_pool_trim();
 	return rc == URMAPX_OK ? 0 : 1;
