@@ -575,6 +575,11 @@ int urmapx_bgzf_compress_host(const void *in, size_t n, void *out, size_t cap, s
  * URMAPX_E_NODEVICE without a usable device.  _timed: *ms = the compress launches alone, by events. */
 int urmapx_bgzf_compress(int device, const void *in, size_t n, void *out, size_t cap, size_t *used, int with_eof);
 int urmapx_bgzf_compress_timed(int device, const void *in, size_t n, void *out, size_t cap, size_t *used, int with_eof, float *ms);
+/* Diagnostic: the compressor's code-length stage alone, on the device, by the function the piece kernel calls.  counts[n] of an alphabet
+ * of n <= 286 symbols -> lengths[n] of a complete prefix code of at most maxbits (1..15) bits, 0 for a count of 0.  force2 != 0: with
+ * fewer than two symbols in use the lowest unused ones count once (the distance and the code-length alphabet).  URMAPX_E_ARG: n < 2 or
+ * > 286, maxbits outside 1..15, fewer than two symbols in use (after force2) or more than 2^maxbits, counts that sum past 2^32 - 1. */
+int urmapx_bgzf_code_lengths(int device, const uint32_t *counts, uint32_t n, uint32_t maxbits, int force2, uint8_t *lengths);
 /* The same with everything resident in the HBM of `device`, asynchronous on the stream the compressor was created with (a hipStream_t;
  * NULL: the default stream): d_in[n] -> d_out[out_cap >= urmapx_bgzf_bound(n)], the size to *d_used (device memory).  The compressor
  * object owns the launch's scratch (a staging slot per piece, 1024 token arenas of 255 KiB): one per stream, one call at a time. */

@@ -254,6 +254,9 @@ def test_file_to_file_call_and_gpu_builder_fail_loudly_without_a_device(gold_ufi
     with pytest.raises(api.UrmapxError) as e2:
         api.make_ufi_gpu(0, os.path.join(GOLD, "g.fa"), os.path.join(tmp_path, "x.ufi"), 100003)
     assert e2.value.code == api.E_NODEVICE
+    with pytest.raises(api.UrmapxError) as e3:  # the diagnostic entry of the deflate kernel's code-length stage: no host stand-in either
+        api.bgzf_code_lengths([5, 3, 0, 1], 15)
+    assert e3.value.code == api.E_NODEVICE
     out = os.path.join(tmp_path, "cli.ufi")
     r = subprocess.run([os.path.join(ROOT, "urmap_amd", "urmap"), "-make_ufi", os.path.join(GOLD, "g.fa"), "-output", out],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
@@ -263,6 +266,21 @@ def test_file_to_file_call_and_gpu_builder_fail_loudly_without_a_device(gold_ufi
     r = subprocess.run([os.path.join(ROOT, "urmap_amd", "urmap"), "-map", os.path.join(GOLD, "se150.fq"), "-ufi", gold_ufi,
                         "-samout", os.path.join(tmp_path, "y.sam")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert r.returncode == 1 and b"Fatal error" in r.stderr and b"Uploading index" in r.stderr
+
+
+@pytest.mark.parametrize("counts,maxbits,force2", [
+    ([1] * 287, 15, False),             # more symbols than the literal/length histogram holds
+    ([1], 15, True), ([], 15, True),    # no room for two symbols
+    ([1, 1], 0, False), ([1, 1], 16, False),
+    ([0, 0, 0], 15, False), ([0, 7, 0], 15, False),  # fewer than two symbols in use and nothing forced: no tree
+    ([1] * 129, 7, False), ([1, 1, 1], 1, False), ([0, 0, 0], 0, True),  # more symbols in use than codes of maxbits bits
+    ([0xffffffff, 1], 15, False),       # node weights are 32 bits wide
+])
+def test_code_length_entry_refuses_what_its_kernel_cannot_take(counts, maxbits, force2):
+    """urmapx_bgzf_code_lengths checks its arguments before it looks for a device, so the refusals show here"""
+    with pytest.raises(api.UrmapxError) as e:
+        api.bgzf_code_lengths(counts, maxbits, force2)
+    assert e.value.code == api.E_ARG
 
 
 @pytest.mark.parametrize("key", ["load_factor_0.3", "load_factor_0.9_veryfast", "notrunclabels", "trunclabels_default"])

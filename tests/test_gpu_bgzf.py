@@ -48,7 +48,7 @@ EDGE = {
     "no_repeat_600": None,
     "far_copy": None,
     "piece_minus_1": None, "piece": None, "piece_plus_1": None, "three_pieces_and_7": None,
-    "window_edge": None,
+    "window_edge": None, "window_edge_flushed": None,
 }
 
 
@@ -59,7 +59,12 @@ def edge_input(name):
         return no_repeat_600()
     if name == "far_copy":  # the copy's source is 40 000 back: beyond the window, it must not be referenced
         return rnd + rnd[:30000]
-    if name == "window_edge":  # sources exactly 32 768 back (the largest distance) and 32 769 back (one too many)
+    if name == "window_edge":
+        # y's source is 32 769 back (one too many: it must come as literals), x's exactly 32 768 back (the largest distance).  Between them
+        # a run, which enters one hash only: a matcher that keeps the latest position per hash still holds x's when the copy comes
+        x, y = seeded_bytes(300, 12), seeded_bytes(300, 13)
+        return y + b"A" + x + b"A" * (32768 - 300 - 300) + y + x
+    if name == "window_edge_flushed":  # the same distances with random bytes between: they take every hash over several times
         a, b = seeded_bytes(32768, 12), seeded_bytes(1, 13)
         return a[:300] + a[300:] + a[:300] + seeded_bytes(32769 - 600, 14) + b + a[:300]
     reps = (sam * (4 * PIECE // len(sam) + 1))

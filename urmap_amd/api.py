@@ -39,7 +39,7 @@ EXPORTS = (
     "urmapx_bitvec_word_length", "urmapx_bitvec_bytes", "urmapx_bitvec_popcount", "urmapx_bitvec_search", "urmapx_bitvec_search_device",
     "urmapx_bitvec_sync", "urmapx_bitvec_last_ms", "urmapx_bitvec_close", "urmapx_make_bitvec", "urmapx_search_bitvec_files",
     "urmapx_index_stats", "urmapx_index_slot_counts", "urmapx_ufi_info",
-    "urmapx_bgzf_bound", "urmapx_bgzf_compress_host", "urmapx_bgzf_compress", "urmapx_bgzf_compress_timed", "urmapx_bgzf_create",
+    "urmapx_bgzf_bound", "urmapx_bgzf_compress_host", "urmapx_bgzf_compress", "urmapx_bgzf_compress_timed", "urmapx_bgzf_code_lengths", "urmapx_bgzf_create",
     "urmapx_bgzf_destroy", "urmapx_bgzf_compress_device", "urmapx_text_set_bgzf",
     "urmapx_text_set_bam", "urmapx_bam_header", "urmapx_bam_se", "urmapx_bam_pe",
 )
@@ -599,6 +599,16 @@ def bgzf_compress_timed(data, device=0, eof=True):
     ms = C.c_float()
     out = _bgzf("urmapx_bgzf_compress_timed", (int(device),), data, eof, None, (C.cast(C.byref(ms), C.c_void_p),))
     return out, float(ms.value)
+
+
+def bgzf_code_lengths(counts, maxbits, force2=False, device=0):
+    """symbol counts -> code lengths of at most maxbits bits, by the device compressor's own stage (huff_lengths of bgzf_gpu.hip)"""
+    cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+    out = np.zeros(max(1, len(cnt)), dtype=np.uint8)
+    fn = lib().urmapx_bgzf_code_lengths
+    fn.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
+    _check(fn(int(device), cnt.ctypes.data if len(cnt) else None, len(cnt), int(maxbits), int(bool(force2)), out.ctypes.data), "urmapx_bgzf_code_lengths")
+    return out[: len(cnt)]
 
 
 def _seq_arrays(seqs):

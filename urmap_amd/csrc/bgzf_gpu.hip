@@ -18,6 +18,7 @@
 // A second kernel scans the members' sizes, a third moves them back to back into the caller's array.
 #include "internal.h"
 
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -480,6 +481,15 @@ __global__ __launch_bounds__(NT) void bgzf_piece_kernel(const uint8_t *text, uin
 	}
 }
 
+// huff_lengths alone (urmapx_bgzf_code_lengths): one workgroup, counts[n] through the literal/length histogram of the piece kernel's LDS
+__global__ __launch_bounds__(NT) void bgzf_code_lengths_kernel(const uint32_t *counts, uint32_t n, uint32_t maxbits, int force2, uint8_t *out) {
+	__shared__ Lds S;
+	for (uint32_t s = threadIdx.x; s < n; s += NT) S.cnt_ll[s] = counts[s];
+	__syncthreads();
+	huff_lengths(S, S.cnt_ll, n, maxbits, S.len_ll, force2 != 0);
+	for (uint32_t s = threadIdx.x; s < n; s += NT) out[s] = S.len_ll[s];
+}
+
 // exclusive prefix sum of the members' sizes; the end-of-file member and the total
 __global__ __launch_bounds__(1024) void bgzf_scan_kernel(const uint32_t *sizes, uint32_t n_pieces, uint64_t *offs, uint8_t *out, int with_eof, uint64_t *used) {
 	__shared__ uint64_t part[1024];
@@ -557,10 +567,21 @@ void urmapx_bgzf_destroy(urmapx_bgzf *Z) {
 	delete Z;
 }
 
+// workgroups of a piece launch at most: MAX_SLOTS, or fewer under the test aid URMAPX_TEST_BGZF_SLOTS=N (1..MAX_SLOTS), which makes
+// a workgroup take a second piece on a small input.  The arenas are sized by it and the launch's grid is it: one value for both
+static uint32_t bgzf_slots() {
+	static const uint32_t slots = [] {
+		const char *e = getenv("URMAPX_TEST_BGZF_SLOTS");
+		const long v = e ? atol(e) : 0;
+		return v >= 1 && v < (long)MAX_SLOTS ? (uint32_t)v : MAX_SLOTS;
+	}();
+	return slots;
+}
+
 // the launches' scratch for n bytes of text; a no-op once it is large enough
 static int bgzf_reserve(urmapx_bgzf *Z, size_t n) {
 	const uint32_t n_pieces = (uint32_t)((n + PIECE - 1) / PIECE);
-	const uint32_t grid = n_pieces < MAX_SLOTS ? n_pieces : MAX_SLOTS;
+	const uint32_t grid = n_pieces < bgzf_slots() ? n_pieces : bgzf_slots();
 	int rc;
 	// (a growing array is replaced: what the stream still reads from the old one has to be over)
 	if (Z->stage.cap < (size_t)n_pieces * STRIDE || Z->tokens.cap < (size_t)grid * PIECE || Z->sizes.cap < n_pieces + 1u || Z->offs.cap < n_pieces + 1u)
@@ -577,7 +598,7 @@ int urmapx_bgzf_compress_device(int device, const void *d_in, size_t n, void *d_
 	if (out_cap < urmapx_bgzf_bound(n) || n > ((size_t)1 << 36)) return URMAPX_E_ARG;
 	HIP_TRY(hipSetDevice(device));
 	const uint32_t n_pieces = (uint32_t)((n + PIECE - 1) / PIECE);
-	const uint32_t grid = n_pieces < MAX_SLOTS ? n_pieces : MAX_SLOTS;
+	const uint32_t grid = n_pieces < bgzf_slots() ? n_pieces : bgzf_slots();
 	int rc;
 	if ((rc = bgzf_reserve(Z, n))) return rc;
 	if (n_pieces) {
@@ -635,6 +656,35 @@ int urmapx_bgzf_compress_timed(int device, const void *in, size_t n, void *out, 
 
 int urmapx_bgzf_compress(int device, const void *in, size_t n, void *out, size_t cap, size_t *used, int with_eof) {
 	return urmapx_bgzf_compress_timed(device, in, n, out, cap, used, with_eof, nullptr);
+}
+
+int urmapx_bgzf_code_lengths(int device, const uint32_t *counts, uint32_t n, uint32_t maxbits, int force2, uint8_t *lengths) {
+	if (!counts || !lengths || n < 2 || n > NLL || maxbits < 1 || maxbits > 15) return URMAPX_E_ARG;
+	// what huff_lengths relies on: two symbols in use at least (its tree has used - 1 >= 1 nodes), a code of maxbits bits that can hold
+	// them, node weights that fit 32 bits
+	uint32_t used = 0;
+	uint64_t sum = 0;
+	for (uint32_t s = 0; s < n; ++s) { used += counts[s] != 0; sum += counts[s]; }
+	if (force2 && used < 2) { sum += 2 - used; used = 2; }
+	if (used < 2 || used > (1u << maxbits) || sum > 0xffffffffull) return URMAPX_E_ARG;
+	int count = 0;
+	if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) { (void)hipGetLastError(); return URMAPX_E_NODEVICE; }
+	HIP_TRY(hipSetDevice(device));
+	DevBuf<uint32_t> d_cnt;
+	DevBuf<uint8_t> d_len;
+	auto run = [&]() -> int {
+		int r;
+		if ((r = d_cnt.ensure(n))) return r;
+		if ((r = d_len.ensure(n))) return r;
+		HIP_TRY(hipMemcpy(d_cnt.p, counts, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+		hipLaunchKernelGGL(bgzf_code_lengths_kernel, dim3(1), dim3(NT), 0, nullptr, d_cnt.p, n, maxbits, force2, d_len.p);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpy(lengths, d_len.p, n, hipMemcpyDeviceToHost));
+		return URMAPX_OK;
+	};
+	const int rc = run();
+	d_cnt.release(); d_len.release();
+	return rc;
 }
 
 }  // extern "C"
