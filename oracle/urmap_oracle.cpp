@@ -721,7 +721,7 @@ struct Searcher {
 
 	// extendpen.cpp:9-95
 	int ExtendPen(uint32_t SeedPosQ, uint32_t SeedPosDB, bool Plus) {
-		if (SeedPosDB < SeedPosQ) return -1;
+		if (SeedPosDB < SeedPosQ) { ++C.n_ext_underflow; return -1; }
 		uint32_t DBLo = SeedPosDB - SeedPosQ;
 		if (OverlapsHit(DBLo)) return -1;
 		const byte *QSeq = Plus ? Q : QRC.data();
@@ -733,6 +733,7 @@ struct Searcher {
 		int EndPos = int(SeedPosQ) + W - 1;
 		for (int p = EndPos + 1; p < int(QL); ++p) {
 			++C.n_extbases;
+			if (DBLo + uint32_t(p) >= X->SeqDataSize) ++C.n_tail_bytes;
 			if (QSeq[p] == DBSeq[p]) {
 				if (++Score > Best) { Best = Score; EndPos = p; }
 			} else {
@@ -772,7 +773,7 @@ struct Searcher {
 		H.Aligned = true;
 		int TotalPen = int(H.Length) - H.Score;
 		int TotalScore = H.Score;
-		if (TotalPen > MaxPenalty) return UINT_MAX;
+		if (TotalPen > MaxPenalty) { ++C.n_ahsp_capped; return UINT_MAX; }
 		++C.n_alignhsp;
 		const unsigned StartPosQ = H.StartPosQ, StartPosDB = H.StartPosDB, Len = H.Length;
 		const bool Plus = H.Plus;
@@ -784,15 +785,15 @@ struct Searcher {
 		std::string LeftPath, RightPath;
 
 		if (StartPosQ > 0) {
-			if (StartPosDB < StartPosQ) return UINT_MAX;
+			if (StartPosDB < StartPosQ) { ++C.n_ahsp_start_underflow; return UINT_MAX; }
 			unsigned LeftQL = StartPosQ;
 			unsigned LeftTHi = StartPosDB - 1;
 			unsigned LeftTL = LeftQL + BR;
-			if (LeftTL >= LeftTHi) return UINT_MAX;
+			if (LeftTL >= LeftTHi) { ++C.n_ahsp_left_long; return UINT_MAX; }
 			unsigned LeftTLo = LeftTHi - LeftTL + 1;
 			const byte *LeftT = T + LeftTLo;
 			for (unsigned i = 0; i < LeftTL; ++i)
-				if (LeftT[i] == '-') return UINT_MAX;
+				if (LeftT[i] == '-') { ++C.n_ahsp_left_pad; return UINT_MAX; }
 			++C.n_viterbi; C.n_dptarget += LeftTL;
 			int LeftScore = (int)dp.Viterbi(P, Qs, LeftQL, LeftT, LeftTL, true, false, LeftPath);
 			// TrimLeftIs, pathinfo.cpp:153-171
@@ -811,11 +812,12 @@ struct Searcher {
 			unsigned RightQL = QL - RightQLo;
 			unsigned RightTLo = StartPosDB + Len;
 			unsigned RightTHi = RightTLo + RightQL + BR;
-			if (RightTHi >= TL) RightTHi = TL - 1;
+			if (RightTHi >= TL) { RightTHi = TL - 1; ++C.n_ahsp_right_clipped; }
 			unsigned RightTL = RightTHi - RightTLo + 1;
+			if (RightTL == 0) ++C.n_ahsp_right_empty;
 			const byte *RightT = T + RightTLo;
 			for (unsigned i = 0; i < RightTL; ++i)
-				if (RightT[i] == '-') return UINT_MAX;
+				if (RightT[i] == '-') { ++C.n_ahsp_right_pad; return UINT_MAX; }
 			++C.n_viterbi; C.n_dptarget += RightTL;
 			int RightScore = (int)dp.Viterbi(P, Qs + RightQLo, RightQL, RightT, RightTL, false, true, RightPath);
 			// TrimRightIs, pathinfo.cpp:173-190: never trims index 0
@@ -1015,7 +1017,7 @@ struct Searcher {
 	// extendscan.cpp:51-187: no overlap test, and the leftward loop never adds to Pen (quirk)
 	unsigned ExtendScan(uint32_t SeedPosQ, uint32_t SeedPosDB, bool Plus) {
 		++C.n_extscan;
-		if (SeedPosDB < SeedPosQ) return UINT_MAX;
+		if (SeedPosDB < SeedPosQ) { ++C.n_ext_underflow; return UINT_MAX; }
 		uint32_t DBLo = SeedPosDB - SeedPosQ;
 		const byte *QSeq = Plus ? Q : QRC.data();
 		const byte *DBSeq = X->SeqData + DBLo;
@@ -1024,6 +1026,7 @@ struct Searcher {
 		int Pen = 0, Score = W, Best = 0;
 		int EndPos = int(SeedPosQ) + W - 1;
 		for (int p = EndPos + 1; p < int(QL); ++p) {
+			if (DBLo + uint32_t(p) >= X->SeqDataSize) ++C.n_tail_bytes;
 			if (QSeq[p] == DBSeq[p]) { if (++Score > Best) { Best = Score; EndPos = p; } }
 			else {
 				Pen -= P.mismatch_score;
@@ -1056,6 +1059,8 @@ struct Searcher {
 		const byte *Seg = X->SeqData + DBLo;
 		uint64_t Word = 0;
 		byte K = 0;
+		if (DBLo + DBSegLength > X->SeqDataSize)
+			C.n_tail_bytes += DBLo >= X->SeqDataSize ? DBSegLength : DBLo + DBSegLength - X->SeqDataSize;
 		for (uint32_t p = 0; p < DBSegLength; ++p) {
 			byte L = g_Letter[Seg[p]];
 			if (L == 0xff) { K = 0; Word = 0; continue; }
@@ -1076,6 +1081,7 @@ struct Searcher {
 		int SavedMaxPenalty = MaxPenalty;
 		unsigned SavedHitCount = HitCount;
 		++C.n_scan;
+		if (memchr(X->SeqData + DBPos, '-', DBSegLength)) ++C.n_scan_pad;
 		MaxPenalty = 130;
 		ScanSlots(DBPos, DBSegLength, Plus);
 		MaxPenalty = SavedMaxPenalty;
@@ -1085,6 +1091,8 @@ struct Searcher {
 		const byte *Qs = Plus ? Q : QRC.data();
 		std::string Path;
 		++C.n_viterbi; C.n_dptarget += DBSegLength;
+		if (DBPos + DBSegLength > X->SeqDataSize)
+			C.n_tail_bytes += DBPos >= X->SeqDataSize ? DBSegLength : DBPos + DBSegLength - X->SeqDataSize;
 		float Score = dp.Viterbi(P, Qs, QL, X->SeqData + DBPos, DBSegLength, true, true, Path);
 		if (Score >= QL / 3.0) {
 			unsigned nI = 0;
@@ -1513,6 +1521,7 @@ struct PairSearcher {
 			if (H.Score < F.SecondBestScore) continue;
 			if (H.Plus) R.Scan(H.DBStartPos, SEG, false, DoVitF);
 			else if (H.DBStartPos >= SEG) R.Scan(H.DBStartPos - SEG, SEG + 2 * QLx, true, DoVitF);
+			else ++R.C.n_scan_low;
 		}
 		for (unsigned j = 0; j < HCr; ++j) {
 			const unsigned QLx = F.QL;
@@ -1520,6 +1529,7 @@ struct PairSearcher {
 			if (H.Score < R.SecondBestScore) continue;
 			if (H.Plus) F.Scan(H.DBStartPos, SEG, false, DoVitR);
 			else if (H.DBStartPos >= SEG) F.Scan(H.DBStartPos - SEG, SEG + 2 * QLx, true, DoVitR);
+			else ++F.C.n_scan_low;
 		}
 	}
 

@@ -14,6 +14,8 @@ outputs are what the reference itself wrote:
   se_alpha.fq/.sam, pe_alpha_1/2.fq + .sam + .tab, each .gz   560 reads / 300 pairs of 150 bp in the letter classes of tests/alphabet_lib.py (N at
                   the ends and in runs, lower case, IUPAC, U / u, letters without a complement, reads that keep the store's N), the
                   classes of the two mates drawn independently; python make_golden.py alpha regenerates only these
+  edges.fa, edges_rescue.fa, edges_se.fq/.sam, edges_pe_1/2.fq + .sam, the read files .gz   reads and pairs at the first and last bases of sequences
+                  and of the sequence store (tests/edges_lib.py): written by make_golden_edges.py, not by this script
   r.fa, r.ufi.gz, pe120_rep_*               repeat-rich second genome: pairs with a second-best pair (see make_repeat_set)
 
   ufi_opts.json   sha256 / slot count / labels of the reference's .ufi for -make_ufi option sets (-load_factor, -veryfast,
