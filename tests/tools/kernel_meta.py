@@ -12,6 +12,7 @@ import tempfile
 
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 OBJCOPY = "/opt/rocm/lib/llvm/bin/llvm-objcopy"
+OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 FIELDS = {"vgpr": ".vgpr_count", "agpr": ".agpr_count", "sgpr": ".sgpr_count", "vgpr_spill": ".vgpr_spill_count", "sgpr_spill": ".sgpr_spill_count",
           "scratch": ".private_segment_fixed_size", "lds": ".group_segment_fixed_size", "max_threads": ".max_flat_workgroup_size"}
@@ -123,6 +124,51 @@ def code_digests(so_path):
     return sorted(out, key=lambda e: e["kernels"])
 
 
+def _blank_pc_literals(lines):
+    """the listing with the 32-bit literals of the s_add_u32 / s_addc_u32 pair behind an s_getpc_b64 blanked: a pc-relative address (a call to
+    a function that was not inlined, a constant's address), which moves with the order the compiler emitted the functions in"""
+    out, after_getpc = [], 0
+    for ln in lines:
+        op = ln.split(None, 1)[0] if ln.strip() else ""
+        if after_getpc and op == ("s_add_u32", "s_addc_u32")[2 - after_getpc]:
+            ln = ln.rsplit(",", 1)[0] + ", <pcrel>"
+            after_getpc -= 1
+        else:
+            after_getpc = 2 if op == "s_getpc_b64" else 0
+        out.append(ln)
+    return out
+
+
+def function_digests(so_path):
+    """sorted [(mangled name, sha256 of its disassembly with the pc-relative literals blanked)] over the FUNC symbols of every code object (a
+    helper two translation units compile appears twice).  Unlike the sections' digests these do not depend on the order of the functions
+    inside a code object."""
+    out = []
+    for co in code_objects(so_path):
+        with tempfile.NamedTemporaryFile(suffix=".elf") as f:
+            f.write(co)
+            f.flush()
+            syms = subprocess.run([READELF, "--symbols", "--wide", f.name], capture_output=True, text=True, check=True).stdout
+            funcs = {ln.split()[7] for ln in syms.split("\n") if len(ln.split()) >= 8 and ln.split()[3] == "FUNC"}
+            txt = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", "--no-leading-addr", f.name], capture_output=True, text=True, check=True).stdout
+        body = {}
+        cur = None
+        for ln in txt.split("\n"):
+            m = re.match(r"^(?:[0-9a-f]+ )?<(.+)>:$", ln)
+            if m:
+                if m.group(1) in funcs:
+                    cur = body.setdefault(m.group(1), [])
+                continue
+            if cur is not None and ln.strip():
+                cur.append(re.sub(r"\s+", " ", ln.split("//")[0].strip()))  # (behind "//": the address and the encoding, whatever the switches say)
+        assert set(body) == funcs, sorted(funcs ^ set(body))
+        for lines in body.values():
+            while lines and lines[-1] == "...":  # zero bytes up to the next function's alignment: they depend on what follows
+                lines.pop()
+        out += [(name, hashlib.sha256("\n".join(_blank_pc_literals(lines)).encode()).hexdigest()) for name, lines in body.items()]
+    return sorted(out)
+
+
 def _print_rows(t, pat=""):
     print(f"{'kernel':64s} {'vgpr':>5s} {'sgpr':>5s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s} {'lds':>6s} {'waves':>5s}")
     for k in sorted(t):
@@ -134,9 +180,12 @@ def _print_rows(t, pat=""):
 if __name__ == "__main__":
     import sys
     here = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    args = [a for a in sys.argv[1:] if a != "--digests"]
+    args = [a for a in sys.argv[1:] if a not in ("--digests", "--functions")]
     so = args[0] if len(args) > 0 else os.path.join(here, "urmap_amd", "liburmapx.so")
-    if "--digests" in sys.argv[1:]:  # kernel_meta.py --digests [library]: what has to agree between two builds of the same device code
+    if "--functions" in sys.argv[1:]:  # kernel_meta.py --functions [library]: name and digest of every device function, sorted
+        for name, d in function_digests(so):
+            print(name, d)
+    elif "--digests" in sys.argv[1:]:  # kernel_meta.py --digests [library]: what has to agree between two builds of the same device code
         for n, e in enumerate(code_digests(so)):
             print(f"code object {n}: {len(e['kernels'])} kernels\n  .text   sha256 {e['text']}\n  .rodata sha256 {e['rodata']}")
             _print_rows(e["rows"])

@@ -1,9 +1,11 @@
 // kernels.h -- launch wrappers of the gfx950 device code (kernels.hip), called by the C ABI (urmapx.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/urmapx.h"
+#include "launch_plan.h"
 
 namespace urx {
 
@@ -69,41 +71,45 @@ static_assert(sizeof(DpJob) == 32, "DpJob layout");
 // flank window unusable (alignhsp.cpp:104-117 / 148-150); right flank not run (penalty already over the job's cap);
 // path longer than URMAPX_MAX_PATH_OPS runs
 static constexpr uint8_t DPJ_LEFT_FAIL = 1, DPJ_RIGHT_FAIL = 2, DPJ_RIGHT_SKIPPED = 4, DPJ_PATH_LONG = 8, DPJ_GATED = 16, DPJ_RIGHT_ABORTED = 32;
-// The jobs of a read are run in rounds of growing size, [0,2) [2,16) [16,inf) by index: after each round the ordered
-// replay consumes that round's jobs and the penalty cap it arrives at gates the next round's DPs -- most of a repeat
-// read's HSPs fail AlignHSP's first test once the first few alignments have tightened the cap.
-// Round 5: the boundaries are chosen per call (SearchWork::dp_bounds): [0,2) [2,16) [16,inf) for reads of up to 192 bases, [0,2) [2,8)
-// [8,32) [32,inf) beyond (250-base reads with 5 % errors bring 13 HSPs each to phase 6: the fourth round's tighter gate is worth more
-// than its two launches cost -- measured in round 4).  DP_ROUNDS = the most rounds a call may have.
-static constexpr int DP_ROUNDS = 4;
-struct DpBounds {
-	int rounds;                    // rounds in use, 1 .. DP_ROUNDS
-	uint32_t lo[DP_ROUNDS + 1];    // round rd = jobs with lo[rd] <= k < lo[rd + 1]; lo[rounds] = 0xFFFFFFFF, unused rounds are empty
-};
-inline DpBounds dp_bounds_default(bool long_reads) {
-	DpBounds b;
-	if (long_reads) { b.rounds = 4; b.lo[0] = 0; b.lo[1] = 2; b.lo[2] = 8; b.lo[3] = 32; b.lo[4] = 0xFFFFFFFFu; }
-	else { b.rounds = 3; b.lo[0] = 0; b.lo[1] = 2; b.lo[2] = 16; b.lo[3] = 0xFFFFFFFFu; b.lo[4] = 0xFFFFFFFFu; }
-	return b;
-}
 static constexpr int DP_TICKET_WORDS = 16;  // per pass: [rd] work counter of round rd, [8 + rd] length of its job list
 static_assert(DP_ROUNDS <= 8, "DP_TICKET_WORDS");
 static constexpr int DP_JOB_OPS = URMAPX_MAX_PATH_OPS;  // ops slice per job
-// SearchWork::stage_events: [0] start, [1] search end (with phase 3 parked: the end of the resume launch), {dp end, finalize end} x DP_ROUNDS,
+// The head of the work buffer (urmapx_ctx::dpbuf), 256 bytes: what the launcher zeroes with one fill before a call and what
+// urmapx_ctx_dp_stats / urmapx_ctx_phase3 read back.  [0] first pass, [1] second pass, [2] phase 3 parked.
+struct DpHead {
+	uint32_t counters[3][4];                // DpWork::counters
+	uint32_t pad[4];
+	uint32_t tickets[3][DP_TICKET_WORDS];   // DpWork::tickets
+};
+static_assert(offsetof(DpHead, counters[1]) == 16 && offsetof(DpHead, counters[2]) == 32 && offsetof(DpHead, tickets[0]) == 64 &&
+              offsetof(DpHead, tickets[1]) == 128 && offsetof(DpHead, tickets[2]) == 192 && sizeof(DpHead) == 256, "DpHead layout");  // (tests/test_launch_plan_cpu.py relies on this)
+// The diagnostics buffer (urmapx_ctx::statsbuf), in 32-bit words: 0/1 the diagnostic kernels' controls (stop step, "no timing"), 2..47 their
+// cycle stamps; the words the stamps never touch are claimed here
+enum StatsWord {
+	STATS_TICKET3 = 58,      // work counter of the launch over the reads parked at phase 3
+	STATS_GATHER_SINK = 60,  // the gather microbenchmark's sink
+	STATS_TICKET = 62,       // and 63: the work counters of the first and the second pass
+	STATS_READ_CYCLES = 64,  // from here: cycles per read (the diagnostic kernels)
+};
+// SearchWork::stage_events: start, search end (with phase 3 parked: the end of the resume launch), {dp end, finalize end} x DP_ROUNDS,
 // second search end, {dp end, finalize end} x DP_ROUNDS, [STAGE_LAST] after the general kernel (recorded by the caller); then the two stamps
 // inside the search stage when phase 3 is parked: [STAGE_P3_MAIN] end of the first search launch, [STAGE_P3_DP] end of phase 3's DP launch
-static constexpr int STAGE_LAST = 3 + 4 * DP_ROUNDS;
+static constexpr int STAGE_START = 0, STAGE_SEARCH_END = 1, STAGE_SEARCH2_END = 2 + 2 * DP_ROUNDS;
+constexpr int stage_dp_end(int pass, int rd) { return 2 + (2 * DP_ROUNDS + 1) * pass + 2 * rd; }  // the event before it: the launch's start
+constexpr int stage_fin_end(int pass, int rd) { return stage_dp_end(pass, rd) + 1; }
+static constexpr int STAGE_LAST = stage_fin_end(1, DP_ROUNDS - 1) + 1;
 static constexpr int STAGE_P3_MAIN = STAGE_LAST + 1, STAGE_P3_DP = STAGE_LAST + 2;
 static constexpr int STAGE_EVENTS = STAGE_LAST + 3;
+static_assert(STAGE_SEARCH2_END == stage_fin_end(0, DP_ROUNDS - 1) + 1 && stage_dp_end(1, 0) == STAGE_SEARCH2_END + 1 && STAGE_LAST == 3 + 4 * DP_ROUNDS, "stage events");
 
 struct DpWork {
 	DpJob *jobs = nullptr;          // jobs_cap entries
 	uint16_t *ops = nullptr;        // jobs_cap * DP_JOB_OPS: the accepted alignment's path per job
 	uint16_t *kidx = nullptr;       // jobs_cap: DpJob::k again, contiguous (a round scans it 64 jobs per load)
 	uint32_t jobs_cap = 0;
-	uint32_t *tickets = nullptr;    // [rd] work counter of dp_kernel's round rd, [8 + rd] length of the round's job list; zeroed with the counters
+	uint32_t *tickets = nullptr;    // DpHead::tickets[i]: [rd] work counter of dp_kernel's round rd, [8 + rd] length of the round's job list
 	uint32_t *round_list = nullptr; // DP_ROUNDS x jobs_cap: the jobs (indices) of each round, dealt out by dp_round_lists_kernel after the search
-	uint32_t *counters = nullptr;   // [0] jobs made, [1] reads parked, [2] jobs the ordered replay needed, [3] jobs a round's gate dropped before their DP (statistics)
+	uint32_t *counters = nullptr;   // DpHead::counters[i]: [0] jobs made, [1] reads parked, [2] jobs the ordered replay needed, [3] jobs a round's gate dropped before their DP (statistics)
 	uint32_t *fin_list = nullptr;   // per parked read: read, first job, job count, read length (16 bytes, one load)
 	uint32_t *state = nullptr;      // per parked read: search state (dp_state_words(ovf) words each)
 	uint32_t fin_cap = 0;
@@ -121,6 +127,8 @@ struct SearchWork {
 	uint32_t *ticket3 = nullptr;  // one more word: work counter of the launch over the reads parked at phase 3
 	int hsp_lds_cap = 0;    // 0 = default; test aid (URMAPX_TEST_HSP_LDS_CAP) to exercise the HSP overflow list
 	uint32_t *ovf_list = nullptr;  // device: [0] = count, [1..n] = reads queued for the second pass
+	DpHead *head = nullptr;        // device: the counters and work counters of dp[0], dp[1] and dp3 (nullptr with them)
+	bool no_k2 = false;            // URMAPX_NO_K2: 150-base reads on the three-chunk instance (launch_plan.h)
 	DpWork dp[2];                  // [0] first pass, [1] second pass; jobs == nullptr: phase 6 stays inside the search kernel
 	// Round 5: phase 3 (AlignHSP when the best HSP of phases 1-2 is long, search1m6.cpp:162-171) parked the same way: the first
 	// launch ends a read there, dp_kernel runs the flank DPs, and a second launch of the search kernel (PART 2) takes the read up

@@ -1987,16 +1987,6 @@ size_t dp_scratch_stride(uint32_t max_read_len) {
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-static int nch_for(uint32_t max_read_len) {
-	if (max_read_len <= 128) return 2;  // 100 bp reads: two mask words, 8 window loads
-	if (max_read_len <= 192) return 3;
-	if (max_read_len <= 256) return 4;  // 250 bp reads: smaller per-read state than the 320-base class, one more wave per SIMD
-	if (max_read_len <= 320) return 5;
-	if (max_read_len <= 512) return 8;  // 1 wave per SIMD: eight mask words and 32 window loads per lane
-	if (max_read_len <= 1024) return 16;
-	return 0;
-}
-
 size_t search_scratch_stride(uint32_t max_read_len) {
 	const int nch = nch_for(max_read_len);
 	return (search_scratch_bytes(nch) + 255) & ~(size_t)255;
@@ -2010,13 +2000,12 @@ int search_block_count(uint32_t max_read_len, int device) {
 	hipDeviceProp_t prop;
 	if (hipGetDeviceProperties(&prop, device) != hipSuccess) return 0;
 	int per_cu = 0;
-	const int nchq = nch_for(max_read_len);
-	hipError_t e = nchq == 2   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_se_kernel<2, false, false, true>, 64, 0)
-	               : nchq == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_se_kernel<3, false, false, true>, 64, 0)
-	               : nchq == 4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_se_kernel<4, false, false, true>, 64, 0)
-	               : nchq == 5 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_se_kernel<5, false, false, true>, 64, 0)
-	               : nchq == 8 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_se_kernel<8, false, false>, 64, 0)
-	                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_se_kernel<16, false, false>, 64, 0);
+	// The occupancy asked for is the row-layout instance's (classes of up to 320 bases) or the hop-by-hop instance's (512, 1024), NOT that of the
+	// slot16 instance which normally runs: the grid sizes the project was measured with come from these, and they stay
+	const hipError_t e = dispatch_nch<2, 3, 4, 5, 8, 16>(nch_for(max_read_len), [&](auto nch) {
+		constexpr int N = decltype(nch)::value;
+		return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_se_kernel<N, false, false, (N <= 5 ? 1 : 0)>, 64, 0);
+	});
 	if (e != hipSuccess || per_cu < 1) per_cu = 8;
 	// measurement aid: fewer resident waves with the same code (is the kernel bound by issue or by latency? DESIGN.md 5.0)
 	if (const char *t = getenv("URMAPX_TEST_BLOCKS_PER_CU")) { const int v = atoi(t); if (v >= 1 && v < per_cu) per_cu = v; }
@@ -2146,16 +2135,67 @@ size_t viterbi_batch_scratch_stride() { return (WideScratch::bytes(VB_WIDE_LA, V
 hipError_t launch_seed_probe(const DevIndex &X, const uint8_t *d_bases, const uint64_t *d_offs, uint32_t n,
                              uint32_t max_read_len, ProbeOut out, hipStream_t s) {
 	if (n == 0) return hipSuccess;
-	const int nch = nch_for(max_read_len);
-	dim3 block(256), grid((n + 3) / 4);
-	if (nch == 2) hipLaunchKernelGGL(seed_probe_kernel<2>, grid, block, 0, s, X, d_bases, d_offs, n, out);
-	else if (nch == 3) hipLaunchKernelGGL(seed_probe_kernel<3>, grid, block, 0, s, X, d_bases, d_offs, n, out);
-	else if (nch == 4) hipLaunchKernelGGL(seed_probe_kernel<4>, grid, block, 0, s, X, d_bases, d_offs, n, out);
-	else if (nch == 5) hipLaunchKernelGGL(seed_probe_kernel<5>, grid, block, 0, s, X, d_bases, d_offs, n, out);
-	else if (nch == 8) hipLaunchKernelGGL(seed_probe_kernel<8>, grid, block, 0, s, X, d_bases, d_offs, n, out);
-	else hipLaunchKernelGGL(seed_probe_kernel<16>, grid, block, 0, s, X, d_bases, d_offs, n, out);
+	dispatch_nch<2, 3, 4, 5, 8, 16>(nch_for(max_read_len), [&](auto nch) {
+		hipLaunchKernelGGL(seed_probe_kernel<decltype(nch)::value>, dim3((n + 3) / 4), dim3(256), 0, s, X, d_bases, d_offs, n, out);
+	});
 	return hipGetLastError();
 }
+
+namespace {
+// one launch_search_se call: what all of its launches share
+struct SeCall {
+	const DevIndex &X; const urmapx_params &P; const uint8_t *bases; const uint64_t *offs; uint32_t n;
+	urmapx_result *results; urmapx_path_op *path_ops; uint32_t *path_used; const SearchWork &wk; hipStream_t s;
+
+	void stamp(int i) const { if (wk.stage_events) (void)hipEventRecord(wk.stage_events[i], s); }
+
+	template <int NCH, bool OVF, bool DBG, int ROWS, int PART, int KCH>
+	void search(int grid, uint32_t *stats, uint32_t *ticket, const DpWork &dp, const DpWork &dp3) const {
+		uint2 *const hsp_ovf = reinterpret_cast<uint2 *>(wk.scratch + (size_t)wk.blocks * wk.scratch_stride);  // HSP lists beyond LDS
+		hipLaunchKernelGGL((search_se_kernel<NCH, OVF, DBG, ROWS, PART, KCH>), dim3((unsigned)grid), dim3(64), 0, s, X, P, bases, offs, n, results,
+		                   path_ops, path_used, stats, wk.scratch, wk.scratch_stride, X.seq, X.blob, X.seqp, ticket, wk.hsp_lds_cap, wk.ovf_list,
+		                   hsp_ovf, dp, dp3);
+	}
+	// the first pass in one launch (wk.stats is set only where the plan chose Diagnostic, Rows or Hops)
+	template <int NCH, FirstPass V>
+	void first() const {
+		constexpr SearchInstance I = first_pass_instance(V, NCH);
+		search<I.nch, I.ovf, I.dbg, I.rows, I.part, I.kch>(wk.blocks, wk.stats, wk.ticket, V == FirstPass::Diagnostic ? DpWork() : wk.dp[0], DpWork());
+	}
+	// phase 3 parked (round 5): the first launch (PART 1: no banded DP inside), phase 3's flank DPs (every job made, no round lists),
+	// the second launch over the reads parked there (PART 2; wk.ticket3: a work counter of its own)
+	template <int NCH>
+	void parked3() const {
+		constexpr SearchInstance I = first_pass_instance(FirstPass::ParkedPhase3, NCH);
+		search<I.nch, I.ovf, I.dbg, I.rows, 1, I.kch>(wk.blocks, nullptr, wk.ticket, wk.dp[0], wk.dp3);
+		stamp(STAGE_P3_MAIN);
+		hipLaunchKernelGGL((dp_kernel<NCH>), dim3((unsigned)wk.dp_blocks), dim3(64), 0, s, X, P, bases, offs, wk.dp3, wk.dp_scratch,
+		                   wk.dp_scratch_stride, X.seq, 0u, 0xFFFFFFFFu, wk.dp3.tickets, (const uint32_t *)nullptr, wk.dp3.counters);
+		stamp(STAGE_P3_DP);
+		search<I.nch, I.ovf, I.dbg, I.rows, 2, I.kch>(wk.blocks, nullptr, wk.ticket3, wk.dp[0], wk.dp3);
+	}
+	// phase 6 of the reads a pass parked: per round their flank DPs, then the ordered part.  A round (or a pass) that does not run records its events all the same.
+	void skip_round(int pass, int rd) const { stamp(stage_dp_end(pass, rd)); stamp(stage_fin_end(pass, rd)); }
+	void skip_phase6(int pass) const { for (int rd = 0; rd < DP_ROUNDS; ++rd) skip_round(pass, rd); }
+	template <int NCH, bool OVF>
+	void phase6(int pass) const {
+		const DpWork &dp = wk.dp[pass];
+		// the second pass is a few reads with many jobs each, usually none at all: smaller grids for the launches that go by reads
+		const unsigned fing = (unsigned)(wk.fin_blocks > 0 ? wk.fin_blocks : wk.blocks), fing2 = pass && fing > 1024u ? 1024u : fing;
+		const uint32_t *const lo = wk.dp_bounds.lo;
+		hipLaunchKernelGGL(dp_round_lists_kernel, dim3(pass ? 128 : 2048), dim3(256), 0, s, dp, wk.dp_bounds);
+		for (int rd = 0; rd < DP_ROUNDS; ++rd) {
+			if (rd >= wk.dp_bounds.rounds) { skip_round(pass, rd); continue; }
+			hipLaunchKernelGGL((dp_kernel<NCH>), dim3((unsigned)wk.dp_blocks), dim3(64), 0, s, X, P, bases, offs, dp, wk.dp_scratch, wk.dp_scratch_stride,
+			                   X.seq, lo[rd], lo[rd + 1], dp.tickets + rd, dp.round_list + (size_t)rd * dp.jobs_cap, dp.tickets + 8 + rd);
+			stamp(stage_dp_end(pass, rd));
+			hipLaunchKernelGGL((finalize_se_kernel<NCH, OVF>), dim3(fing2), dim3(64), 0, s, X, P, offs, dp, results, path_ops, path_used,
+			                   wk.hsp_lds_cap, wk.ovf_list, lo[rd], lo[rd + 1]);
+			stamp(stage_fin_end(pass, rd));
+		}
+	}
+};
+}  // namespace
 
 hipError_t launch_search_se(const DevIndex &X, const urmapx_params &P, const uint8_t *d_bases, const uint64_t *d_offs,
                             uint32_t n, uint32_t max_read_len, urmapx_result *d_results,
@@ -2165,177 +2205,49 @@ hipError_t launch_search_se(const DevIndex &X, const urmapx_params &P, const uin
 	{
 		hipError_t e = hipMemsetAsync(wk.ticket, 0, 8, s);  // two words: the first pass's ticket counter and the second pass's
 		if (e == hipSuccess && wk.ticket3) e = hipMemsetAsync(wk.ticket3, 0, 4, s);  // the work counter of the launch over the reads parked at phase 3
+		if (e == hipSuccess && wk.stats) e = hipMemsetAsync(wk.stats + 2, 0, 184, s);
+		if (e == hipSuccess) e = hipMemsetAsync(wk.ovf_list, 0, 4, s);
+		// both passes' counters and work counters, and phase 3's behind them when it is parked: one fill of the work buffer's head
+		if (e == hipSuccess && wk.head) e = hipMemsetAsync(wk.head, 0, offsetof(DpHead, tickets) + (wk.dp3.jobs ? 3 : 2) * sizeof(wk.head->tickets[0]), s);
 		if (e != hipSuccess) return e;
 	}
-	if (wk.stats) {
-		hipError_t e = hipMemsetAsync(wk.stats + 2, 0, 184, s);
-		if (e != hipSuccess) return e;
-	}
-	{
-		hipError_t e = hipMemsetAsync(wk.ovf_list, 0, 4, s);
-		if (e != hipSuccess) return e;
-	}
-	dim3 block(64), grid((unsigned)wk.blocks);
-	uint2 *const no_ovf = reinterpret_cast<uint2 *>(wk.scratch + (size_t)wk.blocks * wk.scratch_stride);  // HSP lists beyond LDS
-	const DpWork no_dp;
-	auto stamp = [&](int i) { if (wk.stage_events) (void)hipEventRecord(wk.stage_events[i], s); };
-	if (wk.dp[0].jobs && wk.dp[1].jobs && wk.dp[1].counters == wk.dp[0].counters + 4 && wk.dp[0].tickets == wk.dp[0].counters + 16 &&
-	    wk.dp[1].tickets == wk.dp[0].tickets + DP_TICKET_WORDS) {
-		// both passes' counters and work counters (and phase 3's behind them) are one block of the work buffer's head (urmapx.hip): one fill
-		const bool with3 = wk.dp3.jobs && wk.dp3.counters == wk.dp[0].counters + 8 && wk.dp3.tickets == wk.dp[0].tickets + 2 * DP_TICKET_WORDS;
-		hipError_t e = hipMemsetAsync(wk.dp[0].counters, 0, 64 + (with3 ? 3 : 2) * 4 * DP_TICKET_WORDS, s);
-		if (e == hipSuccess && wk.dp3.jobs && !with3) {
-			e = hipMemsetAsync(wk.dp3.counters, 0, 16, s);
-			if (e == hipSuccess) e = hipMemsetAsync(wk.dp3.tickets, 0, 4 * DP_TICKET_WORDS, s);
+	const SeCall c{X, P, d_bases, d_offs, n, d_results, d_path_ops, d_path_used, wk, s};
+	const SearchPlan plan = plan_search_se({nch, X.rowinfo != nullptr, X.slot16 != nullptr, wk.stats != nullptr, wk.dp[0].jobs != nullptr,
+	                                        wk.dp3.jobs != nullptr, wk.dp_blocks, max_read_len, X.W, wk.no_k2});
+	return dispatch_nch<2, 3, 4, 5, 8, 16>(nch, [&](auto nch_c) {
+		constexpr int N = decltype(nch_c)::value;
+		c.stamp(STAGE_START);
+		switch (plan.first) {  // (the plan's own restrictions again, at compile time: no instance beyond those the plan can name)
+		case FirstPass::ParkedPhase3: if constexpr (N <= 5) c.parked3<N>(); break;
+		case FirstPass::Slot16K2: if constexpr (N == 3) c.first<N, FirstPass::Slot16K2>(); break;
+		case FirstPass::Diagnostic: if constexpr (N == 3 || N == 4) c.first<N, FirstPass::Diagnostic>(); break;
+		case FirstPass::Slot16: c.first<N, FirstPass::Slot16>(); break;
+		case FirstPass::Rows: c.first<N, FirstPass::Rows>(); break;
+		case FirstPass::Hops: c.first<N, FirstPass::Hops>(); break;
 		}
-		if (e != hipSuccess) return e;
-	} else
-		for (int pass = 0; pass < 2; ++pass)
-			if (wk.dp[pass].jobs) {
-				hipError_t e = hipMemsetAsync(wk.dp[pass].counters, 0, 16, s);
-				if (e == hipSuccess) e = hipMemsetAsync(wk.dp[pass].tickets, 0, 4 * DP_TICKET_WORDS, s);
-				if (e != hipSuccess) return e;
-			}
-#define URX_LAUNCH_SE(NCH_, OVF_, DBG_, GRID_, STATS_, OVFBASE_, DP_)                                                             \
-	hipLaunchKernelGGL((search_se_kernel<NCH_, OVF_, DBG_>), GRID_, block, 0, s, X, P, d_bases, d_offs, n, d_results,                \
-	                   d_path_ops, d_path_used, STATS_, wk.scratch, wk.scratch_stride, X.seq, X.blob, X.seqp,                    \
-	                   wk.ticket + ((OVF_) ? 1 : 0), wk.hsp_lds_cap, wk.ovf_list, OVFBASE_, DP_, no_dp)
-#define URX_LAUNCH_SE_ROWS(NCH_, GRID_, STATS_, OVFBASE_, DP_)                                                                      \
-	hipLaunchKernelGGL((search_se_kernel<NCH_, false, false, true>), GRID_, block, 0, s, X, P, d_bases, d_offs, n, d_results,          \
-	                   d_path_ops, d_path_used, STATS_, wk.scratch, wk.scratch_stride, X.seq, X.blob, X.seqp, wk.ticket,         \
-	                   wk.hsp_lds_cap, wk.ovf_list, OVFBASE_, DP_, no_dp)
-#define URX_LAUNCH_SE_S16(NCH_, GRID_, OVFBASE_, DP_)                                                                               \
-	hipLaunchKernelGGL((search_se_kernel<NCH_, false, false, 2>), GRID_, block, 0, s, X, P, d_bases, d_offs, n, d_results,            \
-	                   d_path_ops, d_path_used, no_stats3, wk.scratch, wk.scratch_stride, X.seq, X.blob, X.seqp, wk.ticket,          \
-	                   wk.hsp_lds_cap, wk.ovf_list, OVFBASE_, DP_, no_dp)
-	// the same with fewer k-mer chunks than byte chunks (SearchWave: KCH) and the row store in LDS
-#define URX_LAUNCH_SE_S16K(NCH_, KCH_, GRID_, OVFBASE_, DP_)                                                                        \
-	hipLaunchKernelGGL((search_se_kernel<NCH_, false, false, 2, 0, KCH_>), GRID_, block, 0, s, X, P, d_bases, d_offs, n, d_results,   \
-	                   d_path_ops, d_path_used, no_stats3, wk.scratch, wk.scratch_stride, X.seq, X.blob, X.seqp, wk.ticket,          \
-	                   wk.hsp_lds_cap, wk.ovf_list, OVFBASE_, DP_, no_dp)
-	// phase 3 parked (round 5): the first launch (PART 1: no banded DP inside), phase 3's flank DPs (every job made, no round lists),
-	// the second launch over the reads parked there (PART 2; wk.ticket + 2: a work counter of its own)
-#define URX_LAUNCH_SE_P3(NCH_)                                                                                                      \
-	do {                                                                                                                            \
-	hipLaunchKernelGGL((search_se_kernel<NCH_, false, false, true, 1>), grid, block, 0, s, X, P, d_bases, d_offs, n, d_results,       \
-	                   d_path_ops, d_path_used, no_stats3, wk.scratch, wk.scratch_stride, X.seq, X.blob, X.seqp, wk.ticket,          \
-	                   wk.hsp_lds_cap, wk.ovf_list, no_ovf, wk.dp[0], wk.dp3);                                                       \
-	stamp(STAGE_P3_MAIN);                                                                                                           \
-	hipLaunchKernelGGL((dp_kernel<NCH_>), dim3((unsigned)wk.dp_blocks), block, 0, s, X, P, d_bases, d_offs, wk.dp3,                   \
-	                   wk.dp_scratch, wk.dp_scratch_stride, X.seq, 0u, 0xFFFFFFFFu, wk.dp3.tickets, (const uint32_t *)nullptr,       \
-	                   wk.dp3.counters);                                                                                             \
-	stamp(STAGE_P3_DP);                                                                                                             \
-	hipLaunchKernelGGL((search_se_kernel<NCH_, false, false, true, 2>), grid, block, 0, s, X, P, d_bases, d_offs, n, d_results,       \
-	                   d_path_ops, d_path_used, no_stats3, wk.scratch, wk.scratch_stride, X.seq, X.blob, X.seqp, wk.ticket3,         \
-	                   wk.hsp_lds_cap, wk.ovf_list, no_ovf, wk.dp[0], wk.dp3);                                                       \
-	} while (0)
-	// phase 6 of the reads a pass parked: their flank DPs, then the ordered part
-#define URX_LAUNCH_DP(NCH_, OVF_, PASS_)                                                                                          \
-	do { /* the second pass is a few reads with many jobs each, usually none at all: smaller grids for the launches that go by reads */ \
-	const unsigned dpg = (unsigned)wk.dp_blocks;                                                                                  \
-	const unsigned fing = (unsigned)(wk.fin_blocks > 0 ? wk.fin_blocks : wk.blocks), fing2 = PASS_ && fing > 1024u ? 1024u : fing;  \
-	const uint32_t *const DP_ROUND_LO = wk.dp_bounds.lo;                                                                          \
-	hipLaunchKernelGGL(dp_round_lists_kernel, dim3(PASS_ ? 128 : 2048), dim3(256), 0, s, wk.dp[PASS_], wk.dp_bounds);             \
-	for (int rd = 0; rd < DP_ROUNDS; ++rd) {                                                                                      \
-		if (rd >= wk.dp_bounds.rounds) { stamp(2 + (2 * DP_ROUNDS + 1) * PASS_ + 2 * rd); stamp(3 + (2 * DP_ROUNDS + 1) * PASS_ + 2 * rd); continue; } \
-		hipLaunchKernelGGL((dp_kernel<NCH_>), dim3(dpg), block, 0, s, X, P, d_bases, d_offs, wk.dp[PASS_],                        \
-		                   wk.dp_scratch, wk.dp_scratch_stride, X.seq, DP_ROUND_LO[rd], DP_ROUND_LO[rd + 1],                      \
-		                   wk.dp[PASS_].tickets + rd, wk.dp[PASS_].round_list + (size_t)rd * wk.dp[PASS_].jobs_cap,               \
-		                   wk.dp[PASS_].tickets + 8 + rd);                                                                       \
-		stamp(2 + (2 * DP_ROUNDS + 1) * PASS_ + 2 * rd);                                                                            \
-		hipLaunchKernelGGL((finalize_se_kernel<NCH_, OVF_>), dim3(fing2), block,                                                  \
-		                   0, s, X, P, d_offs, wk.dp[PASS_], d_results, d_path_ops, d_path_used, wk.hsp_lds_cap, wk.ovf_list,        \
-		                   DP_ROUND_LO[rd], DP_ROUND_LO[rd + 1]);                                                                  \
-		stamp(3 + (2 * DP_ROUNDS + 1) * PASS_ + 2 * rd);                                                                            \
-	} } while (0)
-	stamp(0);
-	const bool diag = wk.stats != nullptr && (nch == 3 || nch == 4);  // diagnostic instantiations: 150 / 250 bp classes, phase 6 inline
-	uint32_t *const no_stats3 = nullptr;
-	// phase 3 parked: reads of up to 320 bases on an index with the row layout, phase 6 as launches of its own (the default)
-	// round 6: every read of the batch has at most 128 k-mer starts (150 bases at W = 24): the instance that keeps two chunks of them (URMAPX_NO_K2=1: A/B, tests)
-	const bool k2 = getenv("URMAPX_NO_K2") == nullptr && max_read_len >= X.W && max_read_len - (X.W - 1) <= 128u;
-	const bool p3 = !diag && wk.dp3.jobs && wk.dp[0].jobs && wk.dp_blocks > 0 && X.rowinfo && nch <= 5 && wk.stats == nullptr;
-	if (p3 && nch == 2) URX_LAUNCH_SE_P3(2);
-	else if (p3 && nch == 3) URX_LAUNCH_SE_P3(3);
-	else if (p3 && nch == 4) URX_LAUNCH_SE_P3(4);
-	else if (p3) URX_LAUNCH_SE_P3(5);
-	else if (!diag && X.slot16 && wk.stats == nullptr && nch == 2) URX_LAUNCH_SE_S16(2, grid, no_ovf, wk.dp[0]);  // slots, row lengths and second positions in one gather
-	else if (!diag && X.slot16 && wk.stats == nullptr && nch == 3 && k2) URX_LAUNCH_SE_S16K(3, 2, grid, no_ovf, wk.dp[0]);  // 150-base reads: 127 k-mer starts
-	else if (!diag && X.slot16 && wk.stats == nullptr && nch == 3) URX_LAUNCH_SE_S16(3, grid, no_ovf, wk.dp[0]);
-	else if (!diag && X.slot16 && wk.stats == nullptr && nch == 4) URX_LAUNCH_SE_S16(4, grid, no_ovf, wk.dp[0]);
-	else if (!diag && X.slot16 && wk.stats == nullptr && nch == 5) URX_LAUNCH_SE_S16(5, grid, no_ovf, wk.dp[0]);
-	else if (!diag && X.slot16 && wk.stats == nullptr && nch == 8) URX_LAUNCH_SE_S16(8, grid, no_ovf, wk.dp[0]);
-	else if (!diag && X.slot16 && wk.stats == nullptr && nch == 16) URX_LAUNCH_SE_S16(16, grid, no_ovf, wk.dp[0]);
-	else if (diag && nch == 3) URX_LAUNCH_SE(3, false, true, grid, wk.stats, no_ovf, no_dp);
-	else if (diag) URX_LAUNCH_SE(4, false, true, grid, wk.stats, no_ovf, no_dp);
-	else if (nch == 2 && X.rowinfo) URX_LAUNCH_SE_ROWS(2, grid, wk.stats, no_ovf, wk.dp[0]);  // the chain rows are looked up in the layout built with the index
-	else if (nch == 3 && X.rowinfo) URX_LAUNCH_SE_ROWS(3, grid, wk.stats, no_ovf, wk.dp[0]);
-	else if (nch == 4 && X.rowinfo) URX_LAUNCH_SE_ROWS(4, grid, wk.stats, no_ovf, wk.dp[0]);
-	else if (nch == 5 && X.rowinfo) URX_LAUNCH_SE_ROWS(5, grid, wk.stats, no_ovf, wk.dp[0]);
-	else if (nch == 8 && X.rowinfo) URX_LAUNCH_SE_ROWS(8, grid, wk.stats, no_ovf, wk.dp[0]);
-	else if (nch == 16 && X.rowinfo) URX_LAUNCH_SE_ROWS(16, grid, wk.stats, no_ovf, wk.dp[0]);
-	else if (nch == 2) URX_LAUNCH_SE(2, false, false, grid, wk.stats, no_ovf, wk.dp[0]);
-	else if (nch == 3) URX_LAUNCH_SE(3, false, false, grid, wk.stats, no_ovf, wk.dp[0]);
-	else if (nch == 4) URX_LAUNCH_SE(4, false, false, grid, wk.stats, no_ovf, wk.dp[0]);
-	else if (nch == 5) URX_LAUNCH_SE(5, false, false, grid, wk.stats, no_ovf, wk.dp[0]);
-	else if (nch == 8) URX_LAUNCH_SE(8, false, false, grid, wk.stats, no_ovf, wk.dp[0]);
-	else URX_LAUNCH_SE(16, false, false, grid, wk.stats, no_ovf, wk.dp[0]);
-	if (!p3) { stamp(STAGE_P3_MAIN); stamp(STAGE_P3_DP); }
-	stamp(1);
-	if (wk.dp[0].jobs && !diag) {
-		if (nch == 2) URX_LAUNCH_DP(2, false, 0);
-		else if (nch == 3) URX_LAUNCH_DP(3, false, 0);
-		else if (nch == 4) URX_LAUNCH_DP(4, false, 0);
-		else if (nch == 5) URX_LAUNCH_DP(5, false, 0);
-		else if (nch == 8) URX_LAUNCH_DP(8, false, 0);
-		else URX_LAUNCH_DP(16, false, 0);
-	} else
-		for (int i = 0; i < 2 * DP_ROUNDS; ++i) stamp(2 + i);
-	{
-		hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return e;
-	}
-	// second pass over the reads whose HSP or hit list outgrew the first pass's (the blocks read the count and leave
-	// when it is zero): the same search with the lists continued in global scratch
-	dim3 grid2((unsigned)(wk.blocks < SEARCH_OVF_BLOCKS ? wk.blocks : SEARCH_OVF_BLOCKS));
-	uint2 *ovf_base = reinterpret_cast<uint2 *>(wk.scratch + (size_t)wk.blocks * wk.scratch_stride);
-	uint32_t *const no_stats = nullptr;
-	if (nch == 2) URX_LAUNCH_SE(2, true, false, grid2, no_stats, ovf_base, wk.dp[1]);
-	else if (nch == 3) URX_LAUNCH_SE(3, true, false, grid2, no_stats, ovf_base, wk.dp[1]);
-	else if (nch == 4) URX_LAUNCH_SE(4, true, false, grid2, no_stats, ovf_base, wk.dp[1]);
-	else if (nch == 5) URX_LAUNCH_SE(5, true, false, grid2, no_stats, ovf_base, wk.dp[1]);
-	else if (nch == 8) URX_LAUNCH_SE(8, true, false, grid2, no_stats, ovf_base, wk.dp[1]);
-	else URX_LAUNCH_SE(16, true, false, grid2, no_stats, ovf_base, wk.dp[1]);
-	stamp(2 + 2 * DP_ROUNDS);
-	if (wk.dp[1].jobs) {
-		if (nch == 2) URX_LAUNCH_DP(2, true, 1);
-		else if (nch == 3) URX_LAUNCH_DP(3, true, 1);
-		else if (nch == 4) URX_LAUNCH_DP(4, true, 1);
-		else if (nch == 5) URX_LAUNCH_DP(5, true, 1);
-		else if (nch == 8) URX_LAUNCH_DP(8, true, 1);
-		else URX_LAUNCH_DP(16, true, 1);
-	} else
-		for (int i = 0; i < 2 * DP_ROUNDS; ++i) stamp(3 + 2 * DP_ROUNDS + i);
-#undef URX_LAUNCH_SE
-#undef URX_LAUNCH_SE_ROWS
-#undef URX_LAUNCH_SE_P3
-#undef URX_LAUNCH_SE_S16
-#undef URX_LAUNCH_SE_S16K
-#undef URX_LAUNCH_DP
-	return hipGetLastError();
+		if (plan.first != FirstPass::ParkedPhase3) { c.stamp(STAGE_P3_MAIN); c.stamp(STAGE_P3_DP); }
+		c.stamp(STAGE_SEARCH_END);
+		if (plan.phase6_launches) c.phase6<N, false>(0);
+		else c.skip_phase6(0);
+		if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+		// second pass over the reads whose HSP or hit list outgrew the first pass's (the blocks read the count and leave
+		// when it is zero): the same search with the lists continued in global scratch
+		constexpr SearchInstance I2 = second_pass_instance(N);
+		c.search<I2.nch, I2.ovf, I2.dbg, I2.rows, I2.part, I2.kch>(wk.blocks < SEARCH_OVF_BLOCKS ? wk.blocks : SEARCH_OVF_BLOCKS, nullptr, wk.ticket + 1, wk.dp[1], DpWork());
+		c.stamp(STAGE_SEARCH2_END);
+		if (wk.dp[1].jobs) c.phase6<N, true>(1);
+		else c.skip_phase6(1);
+		return hipGetLastError();
+	});
 }
 
 int dp_block_count(uint32_t max_read_len, int device) {
 	hipDeviceProp_t prop;
 	if (hipGetDeviceProperties(&prop, device) != hipSuccess) return 0;
 	int per_cu = 0;
-	const int nchq = nch_for(max_read_len);
-	hipError_t e = nchq == 2   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dp_kernel<2>, 64, 0)
-	               : nchq == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dp_kernel<3>, 64, 0)
-	               : nchq == 4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dp_kernel<4>, 64, 0)
-	               : nchq == 5 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dp_kernel<5>, 64, 0)
-	               : nchq == 8 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dp_kernel<8>, 64, 0)
-	                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dp_kernel<16>, 64, 0);
+	const hipError_t e = dispatch_nch<2, 3, 4, 5, 8, 16>(nch_for(max_read_len), [&](auto nch) {
+		return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dp_kernel<decltype(nch)::value>, 64, 0);
+	});
 	if (e != hipSuccess || per_cu < 1) per_cu = 8;
 	return per_cu * prop.multiProcessorCount;
 }
@@ -2345,13 +2257,9 @@ int fin_block_count(uint32_t max_read_len, int device) {
 	hipDeviceProp_t prop;
 	if (hipGetDeviceProperties(&prop, device) != hipSuccess) return 0;
 	int per_cu = 0;
-	const int nchq = nch_for(max_read_len);
-	hipError_t e = nchq == 2   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, finalize_se_kernel<2, false>, 64, 0)
-	               : nchq == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, finalize_se_kernel<3, false>, 64, 0)
-	               : nchq == 4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, finalize_se_kernel<4, false>, 64, 0)
-	               : nchq == 5 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, finalize_se_kernel<5, false>, 64, 0)
-	               : nchq == 8 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, finalize_se_kernel<8, false>, 64, 0)
-	                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, finalize_se_kernel<16, false>, 64, 0);
+	const hipError_t e = dispatch_nch<2, 3, 4, 5, 8, 16>(nch_for(max_read_len), [&](auto nch) {
+		return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, finalize_se_kernel<decltype(nch)::value, false>, 64, 0);
+	});
 	if (e != hipSuccess || per_cu < 1) per_cu = 16;
 	return per_cu * prop.multiProcessorCount;
 }

@@ -1485,9 +1485,7 @@ __global__ __launch_bounds__(64, TIER == 2 ? 1 : NCH <= 3 ? 4 : 2) void search_p
 
 #undef hot
 
-static int pe_nch_for(uint32_t max_read_len) {
-	return max_read_len <= 128 ? 2 : max_read_len <= 192 ? 3 : max_read_len <= 256 ? 4 : max_read_len <= 320 ? 5 : 0;
-}
+static int pe_nch_for(uint32_t max_read_len) { return max_read_len <= 320 ? nch_for(max_read_len) : 0; }
 
 // behind the rows: the trace cells of the banded DP
 __host__ __device__ inline size_t pe_tb_offset(int qmax) {
@@ -1513,11 +1511,9 @@ int search_pe_block_count(uint32_t max_read_len, int device) {
 	hipDeviceProp_t prop;
 	if (hipGetDeviceProperties(&prop, device) != hipSuccess) return 0;
 	int per_cu = 0;
-	const int nchq = pe_nch_for(max_read_len);
-	hipError_t e = nchq == 2   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_pe_kernel<2, 0>, 64, 0)
-	               : nchq == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_pe_kernel<3, 0>, 64, 0)
-	               : nchq == 4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_pe_kernel<4, 0>, 64, 0)
-	                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_pe_kernel<5, 0>, 64, 0);
+	const hipError_t e = dispatch_nch<2, 3, 4, 5>(pe_nch_for(max_read_len), [&](auto nch) {
+		return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_pe_kernel<decltype(nch)::value, 0>, 64, 0);
+	});
 	if (e != hipSuccess || per_cu < 1) per_cu = 4;
 	if (const char *t = getenv("URMAPX_TEST_BLOCKS_PER_CU")) { const int v = atoi(t); if (v >= 1 && v < per_cu) per_cu = v; }  // measurement aid (see search_block_count)
 	return per_cu * prop.multiProcessorCount;
@@ -1537,33 +1533,25 @@ hipError_t launch_search_pe(const DevIndex &X, const urmapx_params &P, const uin
 		e = hipMemsetAsync(ovf_list2, 0, 4, s);
 		if (e != hipSuccess) return e;
 	}
-	dim3 block(64);
-	const int nch = pe_nch_for(max_read_len);
 	uint2 *const ovf_base = reinterpret_cast<uint2 *>(wk.scratch + (size_t)wk.blocks * wk.scratch_stride);  // HSP lists beyond LDS
-#define URX_LAUNCH_PE(NCH_, TIER_, GRID_, IN_, OUT_)                                                                          \
-	hipLaunchKernelGGL((search_pe_kernel<NCH_, TIER_>), GRID_, block, 0, s, X, P, d_bases, d_offs, npairs, d_results,      \
-	                   d_path_ops, d_path_used, wk.scratch, wk.scratch_stride, X.seq, X.blob, X.seqp, veryfast, wk.ticket,        \
-	                   pair_info, wk.hsp_lds_cap, IN_, OUT_, ovf_base, pe_hsp_area_blocks(wk.blocks))
-#define URX_LAUNCH_PE_TIER(TIER_, GRID_, IN_, OUT_)                                                                            \
-	do {                                                                                                                        \
-		if (nch == 2) URX_LAUNCH_PE(2, TIER_, GRID_, IN_, OUT_);                                                                  \
-		else if (nch == 3) URX_LAUNCH_PE(3, TIER_, GRID_, IN_, OUT_);                                                             \
-		else if (nch == 4) URX_LAUNCH_PE(4, TIER_, GRID_, IN_, OUT_);                                                             \
-		else URX_LAUNCH_PE(5, TIER_, GRID_, IN_, OUT_);                                                                           \
-		hipError_t e_ = hipGetLastError();                                                                                        \
-		if (e_ != hipSuccess) return e_;                                                                                          \
-		e_ = hipMemsetAsync(wk.ticket, 0, 4, s);                                                                                  \
-		if (e_ != hipSuccess) return e_;                                                                                          \
-	} while (0)
-	uint32_t *const none = nullptr;
-	URX_LAUNCH_PE_TIER(0, dim3((unsigned)wk.blocks), none, wk.ovf_list);
-	// second pass over the pairs whose HSP or hit lists outgrew the first pass's (see launch_search_se); third pass over
-	// the pairs with more than 256 hits on a mate.  Both find their work lists on the device and usually leave at once.
-	URX_LAUNCH_PE_TIER(1, dim3((unsigned)(wk.blocks < PE_OVF_BLOCKS ? wk.blocks : PE_OVF_BLOCKS)), wk.ovf_list, ovf_list2);
-	URX_LAUNCH_PE_TIER(2, dim3((unsigned)(wk.blocks < PE_T2_BLOCKS ? wk.blocks : PE_T2_BLOCKS)), ovf_list2, none);
-#undef URX_LAUNCH_PE_TIER
-#undef URX_LAUNCH_PE
-	return hipGetLastError();
+	return dispatch_nch<2, 3, 4, 5>(pe_nch_for(max_read_len), [&](auto nch) {
+		constexpr int N = decltype(nch)::value;
+		// one pass: its launch, then the work counter zeroed for the next
+		auto pass = [&](auto tier, int grid, uint32_t *in, uint32_t *out) {
+			hipLaunchKernelGGL((search_pe_kernel<N, decltype(tier)::value>), dim3((unsigned)(wk.blocks < grid ? wk.blocks : grid)), dim3(64), 0, s, X, P, d_bases,
+			                   d_offs, npairs, d_results, d_path_ops, d_path_used, wk.scratch, wk.scratch_stride, X.seq, X.blob, X.seqp, veryfast, wk.ticket,
+			                   pair_info, wk.hsp_lds_cap, in, out, ovf_base, pe_hsp_area_blocks(wk.blocks));
+			hipError_t e = hipGetLastError();
+			return e != hipSuccess ? e : hipMemsetAsync(wk.ticket, 0, 4, s);
+		};
+		using std::integral_constant;
+		hipError_t e = pass(integral_constant<int, 0>{}, wk.blocks, nullptr, wk.ovf_list);
+		// second pass over the pairs whose HSP or hit lists outgrew the first pass's (see launch_search_se); third pass over
+		// the pairs with more than 256 hits on a mate.  Both find their work lists on the device and usually leave at once.
+		if (e == hipSuccess) e = pass(integral_constant<int, 1>{}, PE_OVF_BLOCKS, wk.ovf_list, ovf_list2);
+		if (e == hipSuccess) e = pass(integral_constant<int, 2>{}, PE_T2_BLOCKS, ovf_list2, nullptr);
+		return e != hipSuccess ? e : hipGetLastError();
+	});
 }
 
 }  // namespace urx

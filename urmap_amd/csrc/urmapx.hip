@@ -93,15 +93,15 @@ struct urmapx_ctx {
 	DevBuf<uint8_t> dpbuf, dpscratch;  // phase 6 as its own launches: jobs, paths, parked read states (kernels.h: DpWork)
 	DevBuf<uint8_t> slowscratch;       // the general kernel's per-block lists (kernels_slow.hip)
 	DevBuf<uint32_t> slowlist;
-	int dp_blocks[6] = {0, 0, 0, 0, 0, 0};
-	int fin_blocks[6] = {0, 0, 0, 0, 0, 0};
+	int dp_blocks[READ_CLASSES] = {};  // by read_class(), like fin_blocks, pe_blocks and blocks
+	int fin_blocks[READ_CLASSES] = {};
 	hipEvent_t stage_ev[STAGE_EVENTS] = {};
 	bool stage_valid = false;
 	bool p3_parked = false;  // the last single-end call ran with phase 3 parked (URMAPX_PARK_PHASE3 and the row layout resident): urmapx_ctx_phase3 reports only then
 	uint32_t pairinfo_n = 0;
 	uint32_t stats_reads = 0;  // diagnostics: reads of the last single-end call with per-read cycle counts
-	int pe_blocks[4] = {0, 0, 0, 0};
-	int blocks[6] = {0, 0, 0, 0, 0, 0};  // persistent grid size of the search kernel for read length classes <=192, <=320, <=256, <=128, <=512, <=1024
+	int pe_blocks[READ_CLASSES] = {};
+	int blocks[READ_CLASSES] = {};  // persistent grid size of the search kernel per read-length class
 };
 
 namespace urx {
@@ -116,6 +116,33 @@ hipStream_t ctx_stream(urmapx_ctx *C) { return C->stream; }
 int ctx_device(const urmapx_ctx *C) { return C->device; }
 const urmapx_index *ctx_index(const urmapx_ctx *C) { return C->index; }
 }  // namespace urx
+
+// The work buffer (urmapx_ctx::dpbuf) of phase 6 and of phase 3 parked: its head (kernels.h: DpHead), then per DpWork, in this order, kidx, jobs,
+// ops, fin_list, state and (the two passes only) round_list.  With base = 0 a layout only measures: `need` is what the buffer has to hold.
+struct DpCarver {
+	uintptr_t base;
+	size_t need = sizeof(DpHead);
+	template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(base + off); }
+	template <class T> T *take(size_t bytes, bool round64 = true) {
+		const size_t off = need;
+		need += round64 ? (bytes + 63) & ~(size_t)63 : bytes;
+		return at<T>(off);
+	}
+	// i: the DpWork's place in the head (0, 1: the passes, 2: phase 3)
+	DpWork work(int i, uint32_t jobs_cap, uint32_t fin_cap, size_t state_words, bool round_list) {
+		DpWork d;
+		d.kidx = take<uint16_t>((size_t)jobs_cap * 2);
+		d.jobs = take<DpJob>((size_t)jobs_cap * sizeof(DpJob), false);
+		d.ops = take<uint16_t>((size_t)jobs_cap * DP_JOB_OPS * 2);
+		d.fin_list = take<uint32_t>((size_t)fin_cap * 16);
+		d.state = take<uint32_t>((size_t)fin_cap * state_words * 4, false);
+		if (round_list) d.round_list = take<uint32_t>((size_t)jobs_cap * 4 * DP_ROUNDS);
+		d.counters = at<uint32_t>(offsetof(DpHead, counters) + i * sizeof(DpHead::counters[0]));
+		d.tickets = at<uint32_t>(offsetof(DpHead, tickets) + i * sizeof(DpHead::tickets[0]));
+		d.jobs_cap = jobs_cap; d.fin_cap = fin_cap;
+		return d;
+	}
+};
 
 extern "C" {
 
@@ -613,15 +640,13 @@ int urmapx_ctx_stage_ms(urmapx_ctx *C, float ms[7]) {
 	HIP_TRY(hipEventSynchronize(C->stage_ev[STAGE_LAST]));
 	auto span = [&](int a, int b, float &out) -> hipError_t { float t = 0; hipError_t e = hipEventElapsedTime(&t, C->stage_ev[a], C->stage_ev[b]); out += t; return e; };
 	for (int i = 0; i < 7; ++i) ms[i] = 0;
-	HIP_TRY(span(0, 1, ms[0]));
-	for (int p = 0; p < 2; ++p) {
-		const int b = 1 + (2 * DP_ROUNDS + 1) * p;  // the event before this pass's first dp launch
+	HIP_TRY(span(STAGE_START, STAGE_SEARCH_END, ms[0]));
+	for (int p = 0; p < 2; ++p)
 		for (int rd = 0; rd < DP_ROUNDS; ++rd) {
-			HIP_TRY(span(b + 2 * rd, b + 2 * rd + 1, ms[1 + 3 * p]));
-			HIP_TRY(span(b + 2 * rd + 1, b + 2 * rd + 2, ms[2 + 3 * p]));
+			HIP_TRY(span(stage_dp_end(p, rd) - 1, stage_dp_end(p, rd), ms[1 + 3 * p]));
+			HIP_TRY(span(stage_dp_end(p, rd), stage_fin_end(p, rd), ms[2 + 3 * p]));
 		}
-	}
-	HIP_TRY(span(1 + 2 * DP_ROUNDS, 2 + 2 * DP_ROUNDS, ms[3]));
+	HIP_TRY(span(STAGE_SEARCH2_END - 1, STAGE_SEARCH2_END, ms[3]));
 	HIP_TRY(span(STAGE_LAST - 1, STAGE_LAST, ms[6]));
 	return URMAPX_OK;
 }
@@ -636,12 +661,10 @@ int urmapx_ctx_phase3(urmapx_ctx *C, float ms[3], uint32_t stats[2]) {
 	// once another context's launches share the device)
 	if (!C->stage_valid || !C->dpbuf.p || !C->p3_parked) return URMAPX_OK;
 	HIP_TRY(hipEventSynchronize(C->stage_ev[STAGE_LAST]));
-	HIP_TRY(hipEventElapsedTime(&ms[0], C->stage_ev[0], C->stage_ev[STAGE_P3_MAIN]));
+	HIP_TRY(hipEventElapsedTime(&ms[0], C->stage_ev[STAGE_START], C->stage_ev[STAGE_P3_MAIN]));
 	HIP_TRY(hipEventElapsedTime(&ms[1], C->stage_ev[STAGE_P3_MAIN], C->stage_ev[STAGE_P3_DP]));
-	HIP_TRY(hipEventElapsedTime(&ms[2], C->stage_ev[STAGE_P3_DP], C->stage_ev[1]));
-	uint32_t buf[2];
-	HIP_TRY(hipMemcpy(buf, C->dpbuf.p + 32, sizeof buf, hipMemcpyDeviceToHost));
-	stats[0] = buf[0]; stats[1] = buf[1];
+	HIP_TRY(hipEventElapsedTime(&ms[2], C->stage_ev[STAGE_P3_DP], C->stage_ev[STAGE_SEARCH_END]));
+	HIP_TRY(hipMemcpy(stats, C->dpbuf.p + offsetof(DpHead, counters[2]), 2 * sizeof *stats, hipMemcpyDeviceToHost));
 	return URMAPX_OK;
 }
 
@@ -652,7 +675,8 @@ int urmapx_ctx_round_ms(urmapx_ctx *C, float ms[16], int *rounds) {
 	*rounds = C->dp_rounds_used;
 	if (!C->stage_valid) return URMAPX_OK;
 	HIP_TRY(hipEventSynchronize(C->stage_ev[STAGE_LAST]));
-	for (int i = 0; i < 2 * C->dp_rounds_used; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], C->stage_ev[1 + i], C->stage_ev[2 + i]));
+	// the first pass's rounds: their events follow one another from the search's end on
+	for (int i = 0, e = stage_dp_end(0, 0); i < 2 * C->dp_rounds_used; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], C->stage_ev[e - 1 + i], C->stage_ev[e + i]));
 	return URMAPX_OK;
 }
 
@@ -668,10 +692,8 @@ int urmapx_ctx_dp_rounds(urmapx_ctx *C, uint32_t lo[8], int *rounds) {
 int urmapx_ctx_dp_stats(urmapx_ctx *C, uint32_t out[8]) {
 	if (!C || !out || !C->dpbuf.p) return URMAPX_E_ARG;
 	HIP_TRY(hipStreamSynchronize(C->stream));
-	uint32_t buf[8];
-	HIP_TRY(hipMemcpy(buf, C->dpbuf.p, sizeof buf, hipMemcpyDeviceToHost));
-	for (int p = 0; p < 2; ++p)
-		for (int i = 0; i < 4; ++i) out[4 * p + i] = buf[4 * p + i];
+	static_assert(offsetof(DpHead, counters[2]) == 8 * sizeof *out, "out[8]: the counters of the two passes");
+	HIP_TRY(hipMemcpy(out, C->dpbuf.p + offsetof(DpHead, counters), 8 * sizeof *out, hipMemcpyDeviceToHost));
 	return URMAPX_OK;
 }
 
@@ -679,7 +701,7 @@ int urmapx_ctx_dp_stats(urmapx_ctx *C, uint32_t out[8]) {
 int urmapx_ctx_read_cycles(urmapx_ctx *C, uint32_t *out, uint32_t n) {
 	if (!C || !out || !C->statsbuf.p || n > C->stats_reads) return URMAPX_E_ARG;
 	HIP_TRY(hipStreamSynchronize(C->stream));
-	HIP_TRY(hipMemcpy(out, C->statsbuf.p + 64, (size_t)n * 4, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(out, C->statsbuf.p + STATS_READ_CYCLES, (size_t)n * 4, hipMemcpyDeviceToHost));
 	return URMAPX_OK;
 }
 
@@ -718,7 +740,7 @@ int urmapx_map_se_device(urmapx_ctx *C, const void *d_bases, const void *d_offs,
 	// fast passes flag) go to the general kernel afterwards
 	const uint32_t slow_qcap = max_read_len < URMAPX_MAX_QL ? URMAPX_MAX_QL : max_read_len;
 	if (max_read_len > URMAPX_MAX_QL) max_read_len = URMAPX_MAX_QL;
-	const int cls = max_read_len <= 128 ? 3 : max_read_len <= 192 ? 0 : max_read_len <= 256 ? 2 : max_read_len <= 320 ? 1 : max_read_len <= 512 ? 4 : 5;
+	const int cls = read_class(max_read_len);
 	if (C->blocks[cls] == 0) {
 		C->blocks[cls] = search_block_count(max_read_len, C->device);
 		if (getenv("URMAPX_VERBOSE")) fprintf(stderr, "urmapx: search_se_kernel grid = %d persistent blocks (read class %d)\n", C->blocks[cls], cls);
@@ -732,11 +754,12 @@ int urmapx_map_se_device(urmapx_ctx *C, const void *d_bases, const void *d_offs,
 	wk.ovf_list = C->ovflist.p;
 	const char *ds = getenv("URMAPX_DEBUG_STOP");
 	const bool diag = getenv("URMAPX_PHASE_STATS") || ds;
-	if ((rc = C->statsbuf.ensure(64 + (diag ? (size_t)n : 0)))) return rc;  // diagnostics: words 64.. = cycles per read
+	if ((rc = C->statsbuf.ensure(STATS_READ_CYCLES + (diag ? (size_t)n : 0)))) return rc;
 	C->stats_reads = diag ? n : 0;
 	wk.scratch = C->scratch.p;
-	wk.ticket = C->statsbuf.p + 62;  // words 62/63 of the diagnostics buffer are never touched by the stamps
-	wk.ticket3 = C->statsbuf.p + 58; // nor is word 58 (60 is the gather microbenchmark's sink)
+	wk.ticket = C->statsbuf.p + STATS_TICKET;
+	wk.ticket3 = C->statsbuf.p + STATS_TICKET3;
+	wk.no_k2 = getenv("URMAPX_NO_K2") != nullptr;  // read on every call: tests flip it between calls
 	if (const char *e = getenv("URMAPX_TEST_HSP_LDS_CAP")) wk.hsp_lds_cap = atoi(e);
 	// diagnostics: URMAPX_PHASE_STATS = per-phase cycle counters; URMAPX_DEBUG_STOP=N = cut the schedule after step N
 	// (results are then NOT the reference's).  Words 0/1 of the buffer: stop step, "no timing" flag.
@@ -754,24 +777,7 @@ int urmapx_map_se_device(urmapx_ctx *C, const void *d_bases, const void *d_offs,
 		wk.fin_blocks = C->fin_blocks[cls] > 0 ? C->fin_blocks[cls] : 0;
 		wk.dp_scratch_stride = dp_scratch_stride(max_read_len);
 		// phase 6's rounds: three for reads of up to 192 bases, four beyond (kernels.h); URMAPX_DP_BOUNDS="0,2,8,32" (measurement) sets them
-		wk.dp_bounds = dp_bounds_default(max_read_len > 192);
-		if (const char *e = getenv("URMAPX_DP_BOUNDS")) {
-			DpBounds b;
-			b.rounds = 0;
-			for (const char *c = e; *c && b.rounds < DP_ROUNDS;) {
-				char *end;
-				const unsigned long v = strtoul(c, &end, 10);
-				if (end == c) break;
-				b.lo[b.rounds++] = (uint32_t)v;
-				c = *end == ',' ? end + 1 : end;
-			}
-			bool ok = b.rounds >= 1 && b.lo[0] == 0;
-			for (int i = 1; i < b.rounds; ++i) ok = ok && b.lo[i] > b.lo[i - 1];
-			if (ok) {
-				for (int i = b.rounds; i <= DP_ROUNDS; ++i) b.lo[i] = 0xFFFFFFFFu;
-				wk.dp_bounds = b;
-			}
-		}
+		wk.dp_bounds = parse_dp_bounds(getenv("URMAPX_DP_BOUNDS"), dp_bounds_default(max_read_len > 192));
 		C->dp_rounds_used = wk.dp_bounds.rounds;
 		for (int i = 0; i <= DP_ROUNDS; ++i) C->dp_bounds_used[i] = wk.dp_bounds.lo[i];
 		if ((rc = C->dpscratch.ensure(wk.dp_scratch_stride * (size_t)wk.dp_blocks))) return rc;
@@ -780,16 +786,6 @@ int urmapx_map_se_device(urmapx_ctx *C, const void *d_bases, const void *d_offs,
 		const uint32_t jobs_cap[2] = {(uint32_t)(jc < (1ull << 30) ? jc : (1ull << 30)) + 4096u,
 		                              (uint32_t)(jc < (1ull << 30) ? jc : (1ull << 30)) + 65536u};
 		const uint32_t fin_cap[2] = {n, n / 8u + 1024u};
-		size_t need = 256, at[2][7];  // head: counters (2 x 16 bytes), then the work counters and list lengths (2 x 64 bytes from byte 64)
-		for (int p = 0; p < 2; ++p) {
-			at[p][5] = need; need += (((size_t)jobs_cap[p] * 2) + 63) & ~(size_t)63;
-			at[p][0] = need; need += (size_t)jobs_cap[p] * sizeof(DpJob);
-			at[p][1] = need; need += (((size_t)jobs_cap[p] * DP_JOB_OPS * 2) + 63) & ~(size_t)63;
-			at[p][2] = need; need += (((size_t)fin_cap[p] * 16) + 63) & ~(size_t)63;
-			at[p][3] = need; need += (size_t)fin_cap[p] * dp_state_words(p == 1) * 4;
-			at[p][4] = 16 * (size_t)p;
-			at[p][6] = need; need += (((size_t)jobs_cap[p] * 4 * DP_ROUNDS) + 63) & ~(size_t)63;
-		}
 		// phase 3 parked (kernels.h: SearchWork::dp3): jobs, their path slices, the parking lot with its larger records.
 		// Off by default: measured on the hg38-scale bench it LOSES 6 % at 150 bases and 4 % at 250 (the first launch gets 1.9 ms
 		// shorter, phase 3's DP launch and the second search launch cost 3.3 ms).  URMAPX_PARK_PHASE3=1 turns it on (tests, measurement).
@@ -807,39 +803,16 @@ int urmapx_map_se_device(urmapx_ctx *C, const void *d_bases, const void *d_offs,
 		// test aids: a job array / parking lot too small for the batch -- reads that find no room are mapped by the second pass
 		if (const char *e = getenv("URMAPX_TEST_P3_JOBS_CAP")) jobs_cap3 = (uint32_t)atoi(e) + 1u;
 		if (const char *e = getenv("URMAPX_TEST_P3_FIN_CAP")) fin_cap3 = std::min<uint32_t>(n, (uint32_t)atoi(e));
-		size_t at3[5] = {0, 0, 0, 0, 0};
-		if (p3w) {
-			at3[4] = need; need += (((size_t)jobs_cap3 * 2) + 63) & ~(size_t)63;
-			at3[0] = need; need += (size_t)jobs_cap3 * sizeof(DpJob);
-			at3[1] = need; need += (((size_t)jobs_cap3 * DP_JOB_OPS * 2) + 63) & ~(size_t)63;
-			at3[2] = need; need += (((size_t)fin_cap3 * 16) + 63) & ~(size_t)63;
-			at3[3] = need; need += (size_t)fin_cap3 * p3w * 4;
-		}
-		if ((rc = C->dpbuf.ensure(need))) return rc;
+		auto lay_out = [&](uint8_t *base) {
+			DpCarver carve{reinterpret_cast<uintptr_t>(base)};
+			for (int p = 0; p < 2; ++p) wk.dp[p] = carve.work(p, jobs_cap[p], fin_cap[p], dp_state_words(p == 1), true);
+			if (p3w) wk.dp3 = carve.work(2, jobs_cap3, fin_cap3, p3w, false);
+			return carve.need;
+		};
+		if ((rc = C->dpbuf.ensure(lay_out(nullptr)))) return rc;  // measured first, then laid out over the buffer
+		lay_out(C->dpbuf.p);
+		wk.head = reinterpret_cast<DpHead *>(C->dpbuf.p);
 		C->p3_parked = p3w != 0;
-		if (p3w) {
-			DpWork &d = wk.dp3;
-			d.jobs = reinterpret_cast<DpJob *>(C->dpbuf.p + at3[0]);
-			d.ops = reinterpret_cast<uint16_t *>(C->dpbuf.p + at3[1]);
-			d.kidx = reinterpret_cast<uint16_t *>(C->dpbuf.p + at3[4]);
-			d.fin_list = reinterpret_cast<uint32_t *>(C->dpbuf.p + at3[2]);
-			d.state = reinterpret_cast<uint32_t *>(C->dpbuf.p + at3[3]);
-			d.counters = reinterpret_cast<uint32_t *>(C->dpbuf.p + 32);
-			d.tickets = reinterpret_cast<uint32_t *>(C->dpbuf.p + 64 + 4 * DP_TICKET_WORDS * (size_t)2);
-			d.jobs_cap = jobs_cap3; d.fin_cap = fin_cap3;
-		}
-		for (int p = 0; p < 2; ++p) {
-			DpWork &d = wk.dp[p];
-			d.jobs = reinterpret_cast<DpJob *>(C->dpbuf.p + at[p][0]);
-			d.ops = reinterpret_cast<uint16_t *>(C->dpbuf.p + at[p][1]);
-			d.kidx = reinterpret_cast<uint16_t *>(C->dpbuf.p + at[p][5]);
-			d.round_list = reinterpret_cast<uint32_t *>(C->dpbuf.p + at[p][6]);
-			d.fin_list = reinterpret_cast<uint32_t *>(C->dpbuf.p + at[p][2]);
-			d.state = reinterpret_cast<uint32_t *>(C->dpbuf.p + at[p][3]);
-			d.counters = reinterpret_cast<uint32_t *>(C->dpbuf.p + at[p][4]);
-			d.tickets = reinterpret_cast<uint32_t *>(C->dpbuf.p + 64 + 4 * DP_TICKET_WORDS * (size_t)p);
-			d.jobs_cap = jobs_cap[p]; d.fin_cap = fin_cap[p];
-		}
 	}
 	// stage stamps: one event per launch group (urmapx_ctx_stage_ms); URMAPX_NO_STAGE_STAMPS=1 leaves them out (measurement
 	// of what the stamps themselves cost: DESIGN.md 5.0)
@@ -938,7 +911,7 @@ int urmapx_map_pe_device(urmapx_ctx *C, const void *d_bases, const void *d_offs,
 	int rc;
 	(void)total_bases;
 	C->stage_valid = false;  // the stage stamps are a single-end batch's: none of an earlier batch may be reported for this one
-	const int cls = max_read_len <= 128 ? 3 : max_read_len <= 192 ? 0 : (max_read_len <= 256 ? 2 : 1);
+	const int cls = read_class(max_read_len);
 	if (C->pe_blocks[cls] == 0) C->pe_blocks[cls] = search_pe_block_count(max_read_len, C->device);
 	if (C->pe_blocks[cls] <= 0) return URMAPX_E_NODEVICE;
 	SearchWork wk;
@@ -952,8 +925,8 @@ int urmapx_map_pe_device(urmapx_ctx *C, const void *d_bases, const void *d_offs,
 	if (const char *e = getenv("URMAPX_TEST_HSP_LDS_CAP")) wk.hsp_lds_cap = atoi(e);
 	wk.scratch = C->pe_scratch.p;
 	wk.stats = nullptr;
-	if ((rc = C->statsbuf.ensure(64))) return rc;
-	wk.ticket = C->statsbuf.p + 62;
+	if ((rc = C->statsbuf.ensure(STATS_READ_CYCLES))) return rc;
+	wk.ticket = C->statsbuf.p + STATS_TICKET;
 	HIP_TRY(hipMemsetAsync(d_path_used, 0, 4, C->stream));
 	// seed + probe run inside search_pe_kernel (round 3; round 4: without probe arrays in HBM); the two stamps bracket
 	// nothing and stay for urmapx_ctx_stage_ms
@@ -1084,9 +1057,9 @@ int urmapx_ctx_gather_microbench(urmapx_ctx *C, uint64_t n_loads, double *loads_
 	hipEvent_t e0, e1;
 	HIP_TRY(hipEventCreate(&e0));
 	HIP_TRY(hipEventCreate(&e1));
-	HIP_TRY(launch_gather_bench(C->X, blocks, 1, C->statsbuf.p + 60, C->stream));  // warm-up
+	HIP_TRY(launch_gather_bench(C->X, blocks, 1, C->statsbuf.p + STATS_GATHER_SINK, C->stream));  // warm-up
 	HIP_TRY(hipEventRecord(e0, C->stream));
-	HIP_TRY(launch_gather_bench(C->X, blocks, iters, C->statsbuf.p + 60, C->stream));
+	HIP_TRY(launch_gather_bench(C->X, blocks, iters, C->statsbuf.p + STATS_GATHER_SINK, C->stream));
 	HIP_TRY(hipEventRecord(e1, C->stream));
 	HIP_TRY(hipEventSynchronize(e1));
 	float ms = 0;
