@@ -1570,14 +1570,14 @@ struct PairSearcher {
 				Qf.push_back(QPosf); Pf.push_back(Plusf); Df.push_back(DBPosf);
 				for (size_t i = 0; i < Qr.size(); ++i) {
 					int64_t TL = std::llabs(int64_t(DBPosf) - int64_t(Dr[i])) + int64_t(QL2);
-					if (TL <= MAX_TL && ExtendBoth1Pair4(QPosf, DBPosf, Plusf, Qr[i], Dr[i])) return;
+					if (TL <= MAX_TL && ExtendBoth1Pair4(QPosf, DBPosf, Plusf, Qr[i], Dr[i])) { ++F.C.n_pair_seedloop; return; }
 				}
 			}
 			if (kr != UINT_MAX) {
 				Qr.push_back(QPosr); Pr.push_back(Plusr); Dr.push_back(DBPosr);
 				for (size_t i = 0; i < Qf.size(); ++i) {
 					int64_t TL = std::llabs(int64_t(Df[i]) - int64_t(DBPosr)) + int64_t(QL2);
-					if (TL <= MAX_TL && ExtendBoth1Pair4(Qf[i], Df[i], !Plusr, QPosr, DBPosr)) return;
+					if (TL <= MAX_TL && ExtendBoth1Pair4(Qf[i], Df[i], !Plusr, QPosr, DBPosr)) { ++F.C.n_pair_seedloop; return; }
 				}
 			}
 			if (kf != UINT_MAX) kf = F.GetNextBoth1Seed(kf, QPosf, Plusf, DBPosf);
@@ -1588,12 +1588,17 @@ struct PairSearcher {
 		if (veryfast) { F.SearchPE_Pending(); R.SearchPE_Pending(); return; }
 		if (F.BestScore >= int((Lf * 9) / 10) && R.BestScore >= int((Lr * 9) / 10)) {
 			int64_t TL = std::llabs(int64_t(F.Hits[F.TopHit].DBStartPos) - int64_t(R.Hits[R.TopHit].DBStartPos)) + int64_t(QL2);
-			if (TL <= MAX_TL) { F.Mapq = 40; R.Mapq = 40; return; }
+			if (TL <= MAX_TL) { F.Mapq = 40; R.Mapq = 40; ++F.C.n_pair_shortcut; return; }
 		}
 		F.SearchPE_Pending();
 		R.SearchPE_Pending();
 		FindPairs();
-		if (PairScore.empty()) { ScanPair(); FindPairs(); }
+		if (!PairScore.empty()) ++F.C.n_pair_found;
+		else {
+			ScanPair(); FindPairs();
+			if (!PairScore.empty()) ++F.C.n_pair_rescued;
+			else ++F.C.n_pair_none;
+		}
 		AdjustTopHitsAndMapqs();
 	}
 };

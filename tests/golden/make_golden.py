@@ -16,6 +16,8 @@ outputs are what the reference itself wrote:
                   classes of the two mates drawn independently; python make_golden.py alpha regenerates only these
   edges.fa, edges_rescue.fa, edges_se.fq/.sam, edges_pe_1/2.fq + .sam, the read files .gz   reads and pairs at the first and last bases of sequences
                   and of the sequence store (tests/edges_lib.py): written by make_golden_edges.py, not by this script
+  geometry.fa, geometry_1/2.fq + .sam + .tab + _nosam.tab, all but the FASTA .gz   pairs at the template-length limit, in every orientation, on
+                  neighbouring sequences and beside copies of a locus (tests/geometry_lib.py): written by make_golden_geometry.py
   r.fa, r.ufi.gz, pe120_rep_*               repeat-rich second genome: pairs with a second-best pair (see make_repeat_set)
 
   ufi_opts.json   sha256 / slot count / labels of the reference's .ufi for -make_ufi option sets (-load_factor, -veryfast,

@@ -39,8 +39,10 @@ assert PAIR_INFO_DTYPE.itemsize == 28
 COUNTER_NAMES = ("n_reads", "n_getblob", "n_rowcalls", "n_rowhop", "n_extend", "n_extbases",
                  "n_alignhsp", "n_viterbi", "n_dpcells", "n_dptarget", "n_qbases", "n_scan", "n_extscan", "n_scan_vit", "n_scan_hits",
                  "n_ahsp_start_underflow", "n_ahsp_left_long", "n_ahsp_left_pad", "n_ahsp_right_pad", "n_ahsp_right_clipped",
-                 "n_ahsp_right_empty", "n_ext_underflow", "n_tail_bytes", "n_scan_low", "n_scan_pad", "n_ahsp_capped")
-EDGE_COUNTERS = COUNTER_NAMES[COUNTER_NAMES.index("n_ahsp_start_underflow"):]
+                 "n_ahsp_right_empty", "n_ext_underflow", "n_tail_bytes", "n_scan_low", "n_scan_pad", "n_ahsp_capped",
+                 "n_pair_seedloop", "n_pair_shortcut", "n_pair_found", "n_pair_rescued", "n_pair_none")
+EDGE_COUNTERS = COUNTER_NAMES[COUNTER_NAMES.index("n_ahsp_start_underflow"):COUNTER_NAMES.index("n_pair_seedloop")]
+PAIR_COUNTERS = COUNTER_NAMES[COUNTER_NAMES.index("n_pair_seedloop"):]
 
 
 class Counters(C.Structure):
