@@ -416,6 +416,14 @@ typedef struct urmapx_map_options {
 	                     * device for the chunks the device formats and by urmapx_bam_se / _pe for the others.  With sam_shards every shard is
 	                     * a complete BAM file with the header.  A QNAME over 254 bytes does not fit a BAM record: URMAPX_E_FORMAT, the read
 	                     * named in err.  0: SAM */
+	int bam_sort;       /* -sort (with bam): the records of samout in coordinate order (see "Sorted BAM output" below) and their index in
+	                     * samout + ".bai".  The header text begins with "@HD\tVN:1.6\tSO:coordinate".  The lanes hand over raw records,
+	                     * which are kept in host memory in input order; behind the last one they go to first_gpu once (urmapx_bam_sort; when
+	                     * no chunk took the device road, urmapx_bam_sort_host) and the file and its index are written: header block in a
+	                     * member of its own, the sorted stream cut every 65 280 bytes, the end-of-file member.  The inflated bytes do not
+	                     * depend on gpus, streams, batch or host_threads.  If the device has no room (urmapx_bam_sort_device_bytes) the kept
+	                     * lanes are let go first; then URMAPX_E_NOMEM with the bytes needed and free in err.  URMAPX_E_ARG without bam, with
+	                     * sam_shards > 1 or with discard_sam; samout must be a regular file.  A failed run removes both files */
 } urmapx_map_options;
 typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:593-632) and where the time went */
 	uint64_t reads, mapped_q, mapped_lowq, unmapped, unsupported;
@@ -443,6 +451,7 @@ typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:59
 	                                                  * hipHostMalloc / hipHostFree of page-locked chunk buffers (kept for the next call: 0 calls when warm) */
 	uint32_t alloc_dev_calls, alloc_pinned_calls;
 	uint64_t sam_text_bytes, sam_file_bytes;         /* SAM text (bam: header block and records) made, bytes written to samout: equal unless bgzf / bam */
+	double sort_s;                                   /* bam_sort: last record mapped .. last byte of samout and samout.bai written; inside `seconds` */
 } urmapx_map_report;
 /* fastq2 NULL: single-end (-map); else the mates' file (-map2 ... -reverse).  samout / tabout may be NULL.  The index
  * needs its host arrays, or to be resident on first_gpu already (the other devices' replicas are then copied from there).  Batch b is mapped on device
@@ -608,6 +617,56 @@ size_t urmapx_bam_se(const urmapx_index *, const urmapx_result *r, const urmapx_
 size_t urmapx_bam_pe(const urmapx_index *, const urmapx_result *r1, const urmapx_result *r2, const urmapx_path_op *path_ops,
                      const char *label1, const uint8_t *seq1, const uint8_t *qual1, uint32_t len1, const char *label2,
                      const uint8_t *seq2, const uint8_t *qual2, uint32_t len2, char *buf, size_t cap);
+
+/* ---- Sorted BAM output (-bamout ... -sort): coordinate order and a .bai index (SAM/BAM specification v1, section 5.2) ----
+ * records[n_bytes]: BAM alignment records back to back on the host, each led by its block_size, as urmapx_text_set_bam, urmapx_bam_se
+ * and urmapx_bam_pe make them.  A record's key is what it carries: refID read as unsigned (-1 sorts behind every reference), then pos
+ * read as unsigned, then its place in the input (the sort is stable).  The result:
+ *   bgzf / bgzf_bytes   the sorted records as BGZF members, cut every 65 280 bytes counted from the first byte of the first record:
+ *                       no header block in front, no end-of-file member behind
+ *   stream_bytes        the bytes those members inflate to (= n_bytes)
+ *   bai / bai_bytes     the index file of a BAM file that holds bytes_in_front bytes (its compressed header block), then these members,
+ *                       then the end-of-file member.  A place u of the sorted stream is written as the virtual offset
+ *                       (file offset of member u / 65280) << 16 | u % 65280; the end of the stream, where it falls on a cut, points at
+ *                       the end-of-file member.  Per reference: the bins present in ascending order, each with its chunks -- maximal runs
+ *                       of records that follow one another in the file and share the bin (reg2bin of pos and pos + the reference bases
+ *                       of the CIGAR, at least one) --, then the pseudo-bin 37450 (where the reference's records begin and end; how many
+ *                       there are without and with flag 4), then the linear index: for every 16 384-base window the smallest place of
+ *                       a record that overlaps it, a window without one taking the next one's value, cut off behind the last window
+ *                       that has one.  n_no_coor counts the records with refID -1.  The bins cover positions below 2^29: records
+ *                       beyond are sorted like the others, but no reader finds them through the index.
+ * Both byte arrays are the result's until urmapx_bam_sort_free.  The times are seconds of the calling thread in the steps named.
+ * urmapx_bam_sort runs on `device` (bam_sort.hip): the record starts come from one walk along the block_size chain on the host, which
+ * also checks the chain; keys, a least-significant-digit radix sort of (key, record number) in 8-bit digits over as many digits as n_ref
+ * and the largest pos need, the gather of the records into sorted order, the index arrays and the deflate are kernels.  The sorted
+ * stream is made, compressed and copied back in slices of a multiple of 65 280 bytes (URMAPX_TEST_SORT_SLICE=N: of N members), so the
+ * device holds the unsorted records, the per-record arrays (urmapx_bam_sort_device_bytes says how much in all) and one slice.
+ * urmapx_bam_sort_host: the same contract by std::stable_sort, plain loops and urmapx_bgzf_compress_host; no device.  The two give the
+ * same inflated stream and, expressed in places of the stream, the same index; their compressed bytes differ.
+ * starts[n_starts] (optional, NULL / 0: none): offsets in `records`, ascending, at which the caller knows a record to begin (the pieces
+ * it put the array together from).  The walk along the chain -- one pass over all the bytes at one thread's pace otherwise -- then runs
+ * from all of them at once, each up to the next, which it must hit exactly (URMAPX_E_FORMAT if not).
+ * URMAPX_E_FORMAT: the bytes are no chain of records (a block_size that runs past the end or does not hold its own name and CIGAR, a
+ * refID outside -1 .. n_ref - 1, a pos below -1, a refID without a pos); URMAPX_E_NOMEM; URMAPX_E_NODEVICE. */
+typedef struct urmapx_bam_sort_result {
+	void *bgzf, *bai;
+	size_t bgzf_bytes, bai_bytes;
+	uint64_t stream_bytes, records, no_coor;
+	uint32_t sort_passes;    /* histogram-scan-scatter rounds of the coordinate sort (device) */
+	uint32_t slices;         /* pieces the sorted stream was made in (device) */
+	double scan_s;           /* the walk along the block_size chain (host, both versions) */
+	double alloc_s;          /* device: hipMalloc and hipFree of the call's arrays (inside no other part) */
+	double upload_s, sort_s, gather_s, deflate_s, copy_s, index_s;  /* records to the device; key + sort launches; gather launches; the
+	                          * compressor; members back to the host; index kernels and the .bai bytes.  Host version: sort_s (the sort),
+	                          * gather_s (the copy into order), deflate_s, index_s */
+} urmapx_bam_sort_result;
+int urmapx_bam_sort(int device, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
+                    size_t n_starts, urmapx_bam_sort_result *out);
+int urmapx_bam_sort_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts, size_t n_starts,
+                         urmapx_bam_sort_result *out);
+void urmapx_bam_sort_free(urmapx_bam_sort_result *);
+/* device memory urmapx_bam_sort takes for n_bytes of records in n_records records (slice and compressor scratch included) */
+uint64_t urmapx_bam_sort_device_bytes(size_t n_bytes, uint64_t n_records);
 
 const char *urmapx_strerror(int code);
 /* "gfx950" etc. of the ctx's device; NULL without a device */

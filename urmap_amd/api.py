@@ -42,6 +42,7 @@ EXPORTS = (
     "urmapx_bgzf_bound", "urmapx_bgzf_compress_host", "urmapx_bgzf_compress", "urmapx_bgzf_compress_timed", "urmapx_bgzf_code_lengths", "urmapx_bgzf_create",
     "urmapx_bgzf_destroy", "urmapx_bgzf_compress_device", "urmapx_text_set_bgzf",
     "urmapx_text_set_bam", "urmapx_bam_header", "urmapx_bam_se", "urmapx_bam_pe",
+    "urmapx_bam_sort", "urmapx_bam_sort_host", "urmapx_bam_sort_free", "urmapx_bam_sort_device_bytes",
 )
 
 BV_MAGIC = 0x42563130
@@ -65,7 +66,7 @@ class Params(C.Structure):
 class MapOptions(C.Structure):
     _fields_ = [("first_gpu", C.c_int), ("gpus", C.c_int), ("streams", C.c_int), ("host_threads", C.c_int), ("batch", C.c_uint32),
                 ("veryfast", C.c_int), ("minq", C.c_uint), ("cmdline", C.c_char_p), ("sam_shards", C.c_int), ("discard_sam", C.c_int), ("bgzf", C.c_int),
-                ("bam", C.c_int)]
+                ("bam", C.c_int), ("bam_sort", C.c_int)]
 
 
 class MapReport(C.Structure):
@@ -77,7 +78,14 @@ class MapReport(C.Structure):
                 ("dev_d2h_s", C.c_double), ("shards", C.c_int), ("placement", C.c_char * 256), ("shard_scan_s", C.c_double),
                 ("dev_map_search_s", C.c_double), ("dev_map_dp_s", C.c_double), ("map_enqueue_s", C.c_double),
                 ("alloc_dev_s", C.c_double), ("alloc_pinned_s", C.c_double), ("alloc_dev_calls", C.c_uint32), ("alloc_pinned_calls", C.c_uint32),
-                ("sam_text_bytes", C.c_uint64), ("sam_file_bytes", C.c_uint64)]
+                ("sam_text_bytes", C.c_uint64), ("sam_file_bytes", C.c_uint64), ("sort_s", C.c_double)]
+
+
+class BamSortResult(C.Structure):
+    _fields_ = [("bgzf", C.c_void_p), ("bai", C.c_void_p), ("bgzf_bytes", C.c_size_t), ("bai_bytes", C.c_size_t),
+                ("stream_bytes", C.c_uint64), ("records", C.c_uint64), ("no_coor", C.c_uint64), ("sort_passes", C.c_uint32),
+                ("slices", C.c_uint32), ("scan_s", C.c_double), ("alloc_s", C.c_double), ("upload_s", C.c_double), ("sort_s", C.c_double),
+                ("gather_s", C.c_double), ("deflate_s", C.c_double), ("copy_s", C.c_double), ("index_s", C.c_double)]
 
 
 class ValidateReport(C.Structure):
@@ -547,11 +555,13 @@ def gunzip_file(gz_path, out_path, threads=0):
 
 
 def map_files(index: "Index", fastq1, fastq2=None, samout=None, tabout=None, first_gpu=0, gpus=1, streams=2, host_threads=0,
-              batch=0, veryfast=False, minq=10, cmdline=None, allow_unsupported=False, sam_shards=0, discard_sam=False, bgzf=False, bam=False):
+              batch=0, veryfast=False, minq=10, cmdline=None, allow_unsupported=False, sam_shards=0, discard_sam=False, bgzf=False, bam=False,
+              bam_sort=False):
     """urmap -map / -map2 file to file (cmd_map / cmd_map2) on an index that has its host arrays or is resident on
-    first_gpu.  bgzf: samout is a BGZF file (-bgzf).  bam: samout is a BAM file (-bamout).  -> dict of State1::HitStats' counters and stage times."""
+    first_gpu.  bgzf: samout is a BGZF file (-bgzf).  bam: samout is a BAM file (-bamout).  bam_sort (with bam):
+    its records in coordinate order, with the index samout + ".bai" beside it (-sort).  -> dict of State1::HitStats' counters and stage times."""
     o = MapOptions(first_gpu, gpus, streams, host_threads, batch, int(veryfast), minq, cmdline.encode() if cmdline else None,
-                   int(sam_shards), int(discard_sam), int(bgzf), int(bam))
+                   int(sam_shards), int(discard_sam), int(bgzf), int(bam), int(bam_sort))
     rep = MapReport()
     err = C.create_string_buffer(1024)
     enc = lambda p: os.fsencode(p) if p else None
@@ -559,6 +569,38 @@ def map_files(index: "Index", fastq1, fastq2=None, samout=None, tabout=None, fir
     if rc != 0 and not (rc == E_UNSUPPORTED and allow_unsupported):
         raise UrmapxError(rc, "urmapx_map_files: " + err.value.decode("latin-1"))
     return {k: getattr(rep, k) for k, _ in MapReport._fields_}
+
+
+def _bam_sort(fn_name, head, records, n_ref, in_front, report, starts=None):
+    src = np.frombuffer(bytes(records), dtype=np.uint8)
+    res = BamSortResult()
+    L = lib()
+    fn = getattr(L, fn_name)
+    fn.argtypes = [C.c_int] * len(head) + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(BamSortResult)]
+    L.urmapx_bam_sort_free.argtypes = [C.POINTER(BamSortResult)]
+    L.urmapx_bam_sort_free.restype = None
+    st = np.ascontiguousarray(starts if starts is not None else [], dtype=np.uint64)
+    _check(fn(*head, src.ctypes.data if len(src) else None, len(src), int(n_ref), int(in_front), st.ctypes.data if len(st) else None, len(st),
+              C.byref(res)), fn_name)
+    try:
+        out = (C.string_at(res.bgzf, res.bgzf_bytes) if res.bgzf_bytes else b"", C.string_at(res.bai, res.bai_bytes))
+        rep = {k: getattr(res, k) for k, _ in BamSortResult._fields_ if k not in ("bgzf", "bai")}
+    finally:
+        L.urmapx_bam_sort_free(C.byref(res))
+    return out + (rep,) if report else out
+
+
+def bam_sort(records: bytes, n_ref, device=0, bytes_in_front=0, report=False, starts=None):
+    """BAM alignment records back to back -> (the records in coordinate order as BGZF members, the bytes of their .bai index), sorted on
+    the device (urmapx_bam_sort; bam_sort.hip).  bytes_in_front: what the file holds in front of the first member, for the index's
+    virtual offsets.  report: a third item, the call's counters and step times.  starts: offsets at which records are known to begin (the
+    chain is then walked from all of them at once)."""
+    return _bam_sort("urmapx_bam_sort", (int(device),), records, n_ref, bytes_in_front, report, starts)
+
+
+def bam_sort_host(records: bytes, n_ref, bytes_in_front=0, report=False, starts=None):
+    """the same contract on the host, no device (urmapx_bam_sort_host): std::stable_sort and zlib inside the BGZF framing"""
+    return _bam_sort("urmapx_bam_sort_host", (), records, n_ref, bytes_in_front, report, starts)
 
 
 BGZF_PIECE = 65280

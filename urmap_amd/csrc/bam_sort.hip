@@ -1,0 +1,536 @@
+// bam_sort.hip -- BAM records into coordinate order on the device, with the arrays of their .bai index (urmapx_bam_sort; the
+// contract is in include/urmapx.h "Sorted BAM output", what is shared with the host version in bam_sort.h).
+//
+// The records lie in HBM as they came, back to back, with the start of each (from the host's walk along the block_size chain).
+//
+//   keys_kernel      one THREAD per record: its packed key (KeyLayout: reference, then position), its number, its end on the reference
+//                    (the CIGAR is read byte by byte: a record starts at any address)
+//   hist / scatter   one pass of the stable least-significant-digit radix sort of (key, number), 8 bits a pass.  A workgroup owns a
+//                    contiguous range of records and walks it 256 at a time.  hist_kernel counts the range's digits; the counts, laid
+//                    out digit-major ([digit][workgroup]), go through one exclusive scan and are then each workgroup's first free
+//                    place per digit.  scatter_kernel ranks the 64 records of a wavefront among themselves with eight ballots (the
+//                    lanes that agree with mine on every bit of the digit; the ones below me are in front of me), the four
+//                    wavefronts through their counts in LDS: no atomic decides an order, so equal keys keep their order
+//   scan             exclusive prefix sums: a thread sums a contiguous run, one workgroup scans the runs' sums, the threads write
+//   gather_kernel    64 records of a slice of the sorted stream per wavefront at a time: every LANE fetches where one of them lies and
+//                    goes, then the wavefront copies them one after the other with all its lanes -- the part of the record that lies
+//                    in the slice, from any address to any address: bytes up to the destination's next word, whole words, bytes
+//   bounds / extent / lin / bin_key / chunk_*   the index: first and last record of every reference and its largest end, the smallest
+//                    stream offset per 16 384-base window (atomicMin), a second sort of the record numbers by (reference, bin) with
+//                    the same two sort kernels, a flag where a chunk begins, a scan of the flags, the chunks
+#include "bam_sort.h"
+#include "internal.h"
+
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+
+using namespace urx::bamsort;
+
+namespace {
+
+constexpr int NT = 256;                   // threads of a sort workgroup: four wavefronts
+constexpr uint32_t TILE = 4 * NT;         // records a workgroup takes when every workgroup takes the least
+constexpr uint32_t MAX_BLOCKS = 512;      // workgroups of a sort pass: beyond MAX_BLOCKS * TILE records each takes several tiles
+constexpr uint32_t SCAN_NT = 1024;
+constexpr uint32_t MAX_RUNS = 65536;      // threads of a large scan
+constexpr uint32_t DEFAULT_SLICE = 2048;  // members of 65 280 bytes in one slice of the sorted stream
+
+__device__ __forceinline__ uint32_t load4(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
+__device__ __forceinline__ uint64_t bcast64(uint64_t v, uint32_t from) {  // lane `from`'s value, in every lane
+	return (uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)from, 64) << 32 | (uint32_t)__shfl((int)(uint32_t)v, (int)from, 64);
+}
+
+__global__ __launch_bounds__(NT) void keys_kernel(const uint8_t *rec, const uint64_t *off, uint32_t n, KeyLayout K, uint64_t *key, uint32_t *val,
+                                                  uint32_t *end) {
+	for (uint32_t i = blockIdx.x * NT + threadIdx.x; i < n; i += gridDim.x * NT) {
+		const uint8_t *r = rec + off[i];
+		const uint32_t ref_id = load_u32(r + 4), pos = load_u32(r + 8);
+		key[i] = K.key(ref_id, pos);
+		val[i] = i;
+		end[i] = ref_id == 0xFFFFFFFFu ? 0u : (uint32_t)ref_end(r, (uint32_t)(off[i + 1] - off[i]), pos);
+	}
+}
+
+// ---- one radix pass ----
+// workgroup b owns records [b * per_block, min(n, (b + 1) * per_block)); per_block is a multiple of NT
+__global__ __launch_bounds__(NT) void hist_kernel(const uint64_t *key, uint32_t n, uint32_t shift, uint32_t per_block, uint32_t *hist) {
+	__shared__ uint32_t h[256];
+	h[threadIdx.x] = 0;
+	__syncthreads();
+	const uint64_t lo = (uint64_t)blockIdx.x * per_block, hi = lo + per_block < n ? lo + per_block : n;
+	for (uint64_t i = lo + threadIdx.x; i < hi; i += NT) atomicAdd(&h[(uint32_t)(key[i] >> shift) & 255u], 1u);
+	__syncthreads();
+	hist[threadIdx.x * gridDim.x + blockIdx.x] = h[threadIdx.x];
+}
+
+__global__ __launch_bounds__(NT) void scatter_kernel(const uint64_t *key_in, const uint32_t *val_in, uint64_t *key_out, uint32_t *val_out, uint32_t n,
+                                                     uint32_t shift, uint32_t per_block, const uint32_t *first) {
+	__shared__ uint32_t s_next[256];     // next free place of every digit for this workgroup
+	__shared__ uint32_t s_count[4][256]; // this round: records of a digit in each wavefront
+	const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+	s_next[t] = first[t * gridDim.x + blockIdx.x];
+	for (int k = 0; k < 4; ++k) s_count[k][t] = 0;
+	__syncthreads();
+	const uint64_t lo = (uint64_t)blockIdx.x * per_block, hi = lo + per_block < n ? lo + per_block : n;
+	for (uint64_t base = lo; base < hi; base += NT) {  // (the same trips for every thread: there are barriers inside)
+		const uint64_t i = base + t;
+		const bool on = i < hi;
+		const uint64_t k = on ? key_in[i] : 0;
+		const uint32_t v = on ? val_in[i] : 0;
+		const uint32_t d = (uint32_t)(k >> shift) & 255u;
+		uint64_t same = __ballot(on);
+#pragma unroll
+		for (uint32_t bit = 0; bit < 8u; ++bit) {
+			const bool mine = (d >> bit) & 1u;
+			const uint64_t set = __ballot(mine);
+			same &= mine ? set : ~set;
+		}
+		const uint32_t rank = (uint32_t)__popcll(same & (((uint64_t)1 << lane) - 1u));
+		if (on && rank == 0) s_count[w][d] = (uint32_t)__popcll(same);
+		__syncthreads();
+		if (on) {
+			uint32_t at = s_next[d] + rank;
+			for (uint32_t k2 = 0; k2 < w; ++k2) at += s_count[k2][d];
+			if (at < n) { key_out[at] = k; val_out[at] = v; }  // (always: the places are hist_kernel's counts of these very records)
+		}
+		__syncthreads();
+		s_next[t] += s_count[0][t] + s_count[1][t] + s_count[2][t] + s_count[3][t];
+		for (int k2 = 0; k2 < 4; ++k2) s_count[k2][t] = 0;
+		__syncthreads();
+	}
+}
+
+// ---- exclusive scans ----
+// one workgroup: out[i] = in[0] + .. + in[i - 1] for i < m (out may be in), the total to out[m] if with_total
+template <class TI, class TO>
+__global__ __launch_bounds__(SCAN_NT) void scan_block_kernel(const TI *in, TO *out, uint32_t m, int with_total) {
+	__shared__ uint64_t part[SCAN_NT];
+	const uint32_t t = threadIdx.x, run = (m + SCAN_NT - 1) / SCAN_NT;
+	const uint64_t lo = (uint64_t)t * run < m ? (uint64_t)t * run : m, hi = lo + run < m ? lo + run : m;
+	uint64_t sum = 0;
+	for (uint64_t i = lo; i < hi; ++i) sum += in[i];
+	part[t] = sum;
+	__syncthreads();
+	for (uint32_t s = 1; s < SCAN_NT; s <<= 1) {
+		const uint64_t a = t >= s ? part[t - s] : 0;
+		__syncthreads();
+		part[t] += a;
+		__syncthreads();
+	}
+	uint64_t at = part[t] - sum;
+	for (uint64_t i = lo; i < hi; ++i) {
+		const uint64_t x = in[i];
+		out[i] = (TO)at;
+		at += x;
+	}
+	if (with_total && t == SCAN_NT - 1) out[m] = (TO)part[t];
+}
+// n values in runs of `run`: the runs' sums
+template <class TI>
+__global__ __launch_bounds__(NT) void scan_sums_kernel(const TI *in, uint32_t n, uint32_t run, uint32_t n_runs, uint64_t *sums) {
+	const uint32_t g = blockIdx.x * NT + threadIdx.x;
+	if (g >= n_runs) return;
+	const uint64_t lo = (uint64_t)g * run, hi = lo + run < n ? lo + run : n;
+	uint64_t sum = 0;
+	for (uint64_t i = lo; i < hi; ++i) sum += in[i];
+	sums[g] = sum;
+}
+// the scanned sums back onto the runs; out[n] = the total (out is not in)
+template <class TI, class TO>
+__global__ __launch_bounds__(NT) void scan_write_kernel(const TI *in, uint32_t n, uint32_t run, uint32_t n_runs, const uint64_t *sums, TO *out) {
+	const uint32_t g = blockIdx.x * NT + threadIdx.x;
+	if (g >= n_runs) return;
+	const uint64_t lo = (uint64_t)g * run, hi = lo + run < n ? lo + run : n;
+	uint64_t at = sums[g];
+	for (uint64_t i = lo; i < hi; ++i) {
+		out[i] = (TO)at;
+		at += in[i];
+	}
+	if (g == n_runs - 1) out[n] = (TO)at;
+}
+
+// ---- the sorted stream ----
+__global__ __launch_bounds__(NT) void sorted_len_kernel(const uint32_t *val, const uint64_t *off, uint32_t n, uint32_t *len) {
+	for (uint32_t k = blockIdx.x * NT + threadIdx.x; k < n; k += gridDim.x * NT) len[k] = (uint32_t)(off[val[k] + 1] - off[val[k]]);
+}
+
+// the sorted records that have a byte in [s0, s1) of the stream: range[0] .. range[1] - 1.  One thread.
+__global__ void slice_range_kernel(const uint64_t *dst, uint32_t n, uint64_t s0, uint64_t s1, uint32_t *range) {
+	uint32_t a = 0, b = n;  // first k whose end dst[k + 1] lies behind s0
+	while (a < b) {
+		const uint32_t m = a + (b - a) / 2;
+		if (dst[m + 1] > s0) b = m; else a = m + 1;
+	}
+	range[0] = a;
+	b = n;  // first k at or behind a that starts at or behind s1
+	while (a < b) {
+		const uint32_t m = a + (b - a) / 2;
+		if (dst[m] >= s1) b = m; else a = m + 1;
+	}
+	range[1] = a;
+}
+
+__global__ __launch_bounds__(NT) void gather_kernel(const uint8_t *rec, const uint64_t *off, const uint32_t *val, const uint64_t *dst, const uint32_t *range,
+                                                    uint64_t s0, uint64_t s1, uint8_t *out) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint64_t wave = ((uint64_t)blockIdx.x * NT + threadIdx.x) >> 6, n_waves = (uint64_t)gridDim.x * (NT / 64);
+	const uint64_t k1 = range[1];
+	// 64 records at a time: every LANE fetches where one of them lies and goes (three dependent loads, once for the 64), then the
+	// wavefront copies them one after the other with all its lanes
+	for (uint64_t base = range[0] + wave * 64u; base < k1; base += n_waves * 64u) {
+		const uint64_t k = base + lane;
+		uint64_t my_d0 = 0, my_d1 = 0, my_src = 0;
+		if (k < k1) { my_d0 = dst[k]; my_d1 = dst[k + 1]; my_src = off[val[k]]; }
+		const uint32_t cnt = (uint32_t)(k1 - base < 64u ? k1 - base : 64u);
+		for (uint32_t t = 0; t < cnt; ++t) {
+			const uint64_t d0 = bcast64(my_d0, t), d1 = bcast64(my_d1, t);
+			const uint64_t lo = d0 > s0 ? d0 : s0, hi = d1 < s1 ? d1 : s1;  // a record may begin in front of the slice or end behind it
+			if (hi <= lo) continue;
+			const uint8_t *src = rec + bcast64(my_src, t) + (lo - d0);
+			uint8_t *to = out + (lo - s0);
+			const uint32_t len = (uint32_t)(hi - lo);
+			const uint32_t to_word = (uint32_t)((4u - ((uintptr_t)to & 3u)) & 3u), head = len < to_word ? len : to_word;
+			if (lane < head) to[lane] = src[lane];
+			const uint32_t words = (len - head) >> 2;
+			uint32_t *tw = (uint32_t *)(to + head);
+			const uint8_t *sw = src + head;
+			for (uint32_t i = lane; i < words; i += 64u) tw[i] = load4(sw + 4u * i);
+			const uint32_t done = head + 4u * words;
+			if (lane < len - done) to[done + lane] = src[done + lane];
+		}
+	}
+}
+
+// ---- the index ----
+// per sorted record: where its reference's records begin and end; the reference's largest end (one atomic per wavefront where its 64
+// records share the reference, which in sorted order is nearly everywhere); its records with flag 4
+__global__ __launch_bounds__(NT) void bounds_kernel(const uint8_t *rec, const uint64_t *off, const uint64_t *key, const uint32_t *val, const uint32_t *end,
+                                                    uint32_t n, KeyLayout K, uint32_t *first, uint32_t *last, uint32_t *max_end, uint32_t *flag4) {
+	const uint32_t rounds = (n + gridDim.x * NT - 1) / (gridDim.x * NT);
+	for (uint32_t it = 0; it < rounds; ++it) {  // (whole wavefronts stay together for the shuffles)
+		const uint32_t k = (it * gridDim.x + blockIdx.x) * NT + threadIdx.x;
+		const bool on = k < n;
+		const uint32_t r = on ? K.ref_of(key[k]) : 0xFFFFFFFFu;
+		uint32_t e = 0;
+		if (on) {
+			if (k == 0 || K.ref_of(key[k - 1]) != r) first[r] = k;
+			if (k == n - 1 || K.ref_of(key[k + 1]) != r) last[r] = k;
+			if (r < K.n_ref) {
+				e = end[val[k]];
+				if (load_u32(rec + off[val[k]] + 16) >> 16 & 4u) atomicAdd(&flag4[r], 1u);
+			}
+		}
+		const uint32_t r0 = __shfl(r, 0, 64);
+		if (__all(r == r0)) {
+			for (int d = 32; d; d >>= 1) { const uint32_t o = __shfl_xor(e, d, 64); e = o > e ? o : e; }
+			if ((threadIdx.x & 63) == 0 && r0 < K.n_ref) atomicMax(&max_end[r0], e);
+		} else if (on && r < K.n_ref) atomicMax(&max_end[r], e);
+	}
+}
+__global__ __launch_bounds__(NT) void extent_kernel(const uint32_t *first, const uint32_t *last, const uint64_t *dst, uint32_t n_ref1, uint64_t *beg, uint64_t *end) {
+	const uint32_t r = blockIdx.x * NT + threadIdx.x;
+	if (r >= n_ref1) return;
+	const bool any = first[r] != 0xFFFFFFFFu;
+	beg[r] = any ? dst[first[r]] : 0;
+	end[r] = any ? dst[last[r] + 1] : 0;
+}
+__global__ __launch_bounds__(NT) void lin_kernel(const uint64_t *key, const uint32_t *val, const uint32_t *end, const uint64_t *dst, uint32_t m, KeyLayout K,
+                                                 const uint64_t *win_base, unsigned long long *lin) {
+	for (uint32_t k = blockIdx.x * NT + threadIdx.x; k < m; k += gridDim.x * NT) {
+		const uint32_t r = K.ref_of(key[k]);
+		const uint64_t w0 = win_base[r], n_win = win_base[r + 1] - w0;
+		const uint64_t a = K.pos_of(key[k]) >> WINDOW_SHIFT, b = ((uint64_t)end[val[k]] - 1u) >> WINDOW_SHIFT;
+		for (uint64_t w = a; w <= b && w < n_win; ++w) atomicMin(&lin[w0 + w], (unsigned long long)dst[k]);
+	}
+}
+__global__ __launch_bounds__(NT) void bin_key_kernel(const uint64_t *key, const uint32_t *val, const uint32_t *end, uint32_t m, KeyLayout K, uint32_t bin_bits,
+                                                     uint64_t *key2, uint32_t *val2) {
+	for (uint32_t k = blockIdx.x * NT + threadIdx.x; k < m; k += gridDim.x * NT) {
+		key2[k] = (uint64_t)K.ref_of(key[k]) << bin_bits | reg2bin(K.pos_of(key[k]), end[val[k]]);
+		val2[k] = k;
+	}
+}
+// a chunk begins where the (reference, bin) changes or the record is not the file's next one
+__global__ __launch_bounds__(NT) void chunk_flag_kernel(const uint64_t *key2, const uint32_t *val2, uint32_t m, uint32_t *flag) {
+	for (uint32_t j = blockIdx.x * NT + threadIdx.x; j < m; j += gridDim.x * NT)
+		flag[j] = j == 0 || key2[j] != key2[j - 1] || val2[j] != val2[j - 1] + 1u;
+}
+__global__ __launch_bounds__(NT) void chunk_write_kernel(const uint64_t *key2, const uint32_t *val2, const uint32_t *flag, const uint32_t *index, const uint64_t *dst,
+                                                         uint32_t m, uint32_t bin_bits, uint32_t n_chunks, Chunk *chunks) {
+	for (uint32_t j = blockIdx.x * NT + threadIdx.x; j < m; j += gridDim.x * NT) {
+		const uint32_t c = index[j] + flag[j] - 1u;  // (index: chunks that begin in front of j)
+		if (c >= n_chunks) continue;
+		if (flag[j]) {
+			chunks[c].ref = (uint32_t)(key2[j] >> bin_bits);
+			chunks[c].bin = (uint32_t)(key2[j] & (((uint64_t)1 << bin_bits) - 1u));
+			chunks[c].beg = dst[val2[j]];
+		}
+		if (j == m - 1 || flag[j + 1]) chunks[c].end = dst[val2[j] + 1];
+	}
+}
+
+// ---- host side ----
+using Clock = std::chrono::steady_clock;
+double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::now() - t).count(); }
+
+// device array of exactly the size asked for
+thread_local double t_alloc_s = 0;  // what this thread's call has spent in hipMalloc and hipFree (urmapx_bam_sort_result.alloc_s)
+template <class T>
+struct Dev {
+	T *p = nullptr;
+	int alloc(size_t n) {
+		urx::AllocTimer at(0);
+		const auto t0 = Clock::now();
+		const hipError_t e = hipMalloc((void **)&p, (n ? n : 1) * sizeof(T));
+		t_alloc_s += since(t0);
+		if (e != hipSuccess) { p = nullptr; (void)hipGetLastError(); return urx::hip_rc(e); }
+		return URMAPX_OK;
+	}
+	~Dev() {
+		if (!p) return;
+		urx::AllocTimer at(0);
+		const auto t0 = Clock::now();
+		(void)hipFree(p);
+		t_alloc_s += since(t0);
+	}
+};
+
+uint32_t grid_for(uint64_t n, uint32_t most = 4096) {
+	const uint64_t g = (n + NT - 1) / NT;
+	return (uint32_t)(g < 1 ? 1 : g > most ? most : g);
+}
+
+uint32_t slice_members() {
+	const char *e = getenv("URMAPX_TEST_SORT_SLICE");
+	const long v = e ? atol(e) : 0;
+	return v >= 1 && v <= (long)DEFAULT_SLICE ? (uint32_t)v : DEFAULT_SLICE;
+}
+
+// out[0 .. n] = exclusive sums of in[0 .. n), the total in out[n]; sums: MAX_RUNS + 1 entries of scratch
+template <class TI, class TO>
+void scan_launch(const TI *in, uint32_t n, TO *out, uint64_t *sums) {
+	uint32_t run = (n + MAX_RUNS - 1) / MAX_RUNS;
+	if (run < 16) run = 16;
+	const uint32_t n_runs = (n + run - 1) / run;
+	if (n_runs == 0) { hipLaunchKernelGGL((scan_block_kernel<TI, TO>), dim3(1), dim3(SCAN_NT), 0, nullptr, in, out, 0u, 1); return; }
+	hipLaunchKernelGGL((scan_sums_kernel<TI>), dim3(grid_for(n_runs)), dim3(NT), 0, nullptr, in, n, run, n_runs, sums);
+	hipLaunchKernelGGL((scan_block_kernel<uint64_t, uint64_t>), dim3(1), dim3(SCAN_NT), 0, nullptr, (const uint64_t *)sums, sums, n_runs, 0);
+	hipLaunchKernelGGL((scan_write_kernel<TI, TO>), dim3(grid_for(n_runs)), dim3(NT), 0, nullptr, in, n, run, n_runs, (const uint64_t *)sums, out);
+}
+
+// stable sort of (key, val)[0 .. n) by the low `bits` bits of the key, between two pairs of arrays; `in` says where the result is
+struct SortArrays {
+	uint64_t *key[2];
+	uint32_t *val[2];
+	int in = 0;
+};
+uint32_t radix_sort(SortArrays &S, uint32_t n, uint32_t bits, uint32_t *hist) {
+	if (n == 0) return 0;
+	const uint32_t tiles = (n + TILE - 1) / TILE, blocks = tiles < MAX_BLOCKS ? tiles : MAX_BLOCKS;
+	const uint32_t per_block = (tiles + blocks - 1) / blocks * TILE;
+	uint32_t passes = 0;
+	for (uint32_t shift = 0; shift < bits; shift += 8, ++passes) {
+		const int a = S.in, b = 1 - S.in;
+		hipLaunchKernelGGL(hist_kernel, dim3(blocks), dim3(NT), 0, nullptr, (const uint64_t *)S.key[a], n, shift, per_block, hist);
+		hipLaunchKernelGGL((scan_block_kernel<uint32_t, uint32_t>), dim3(1), dim3(SCAN_NT), 0, nullptr, (const uint32_t *)hist, hist, 256u * blocks, 0);
+		hipLaunchKernelGGL(scatter_kernel, dim3(blocks), dim3(NT), 0, nullptr, (const uint64_t *)S.key[a], (const uint32_t *)S.val[a], S.key[b], S.val[b], n, shift,
+		                   per_block, (const uint32_t *)hist);
+		S.in = b;
+	}
+	return passes;
+}
+
+size_t slice_scratch_bytes(size_t slice_bytes) {
+	// the slice, its members at their worst, the compressor's staging slot per member and its token arenas (bgzf_gpu.hip)
+	return slice_bytes + urmapx_bgzf_bound(slice_bytes) + slice_bytes + slice_bytes / 64 + ((size_t)1024 * 255 << 10);
+}
+
+int sort_device(int device, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts,
+                urmapx_bam_sort_result *out) {
+	auto t = Clock::now();
+	std::vector<uint64_t> offs;
+	uint32_t max_pos = 0;
+	int rc = scan_records(rec, n_bytes, n_ref, starts, n_starts, offs, max_pos);
+	if (rc) return rc;
+	out->scan_s = since(t);
+	const uint32_t n = (uint32_t)(offs.size() - 1);
+	out->records = n;
+	const KeyLayout K = key_layout(n_ref, max_pos);
+	const uint32_t bin_bits = max_pos < (1u << 29) ? 16u : 18u;  // (reg2bin's largest value: 37 448 below 2^29, 4681 + 2^17 in all)
+	const size_t n_ref1 = (size_t)n_ref + 1;
+
+	HIP_TRY(hipSetDevice(device));
+	Dev<uint8_t> d_rec;
+	Dev<uint64_t> d_off, d_dst, d_key[2], d_sums, d_ext[2], d_win, d_lin;
+	Dev<uint32_t> d_val[3], d_end, d_hist, d_range, d_ref[4];
+	Dev<Chunk> d_chunks;
+	if ((rc = d_rec.alloc(n_bytes + 16)) || (rc = d_off.alloc((size_t)n + 1)) || (rc = d_dst.alloc((size_t)n + 1)) || (rc = d_key[0].alloc((size_t)n + 2)) ||
+	    (rc = d_key[1].alloc((size_t)n + 2)) || (rc = d_val[0].alloc((size_t)n + 1)) || (rc = d_val[1].alloc((size_t)n + 1)) ||
+	    (rc = d_val[2].alloc((size_t)n + 1)) || (rc = d_end.alloc(n)) || (rc = d_hist.alloc((size_t)256 * MAX_BLOCKS)) || (rc = d_sums.alloc(MAX_RUNS + 1)) ||
+	    (rc = d_range.alloc(2)) || (rc = d_ext[0].alloc(n_ref1)) || (rc = d_ext[1].alloc(n_ref1)) || (rc = d_win.alloc(n_ref1 + 1)))
+		return rc;
+	for (int k = 0; k < 4; ++k)
+		if ((rc = d_ref[k].alloc(n_ref1))) return rc;
+
+	t = Clock::now();
+	if (n_bytes) HIP_TRY(hipMemcpy(d_rec.p, rec, n_bytes, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(d_off.p, offs.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+	out->upload_s = since(t);
+
+	// keys and the coordinate sort
+	t = Clock::now();
+	SortArrays S{{d_key[0].p, d_key[1].p}, {d_val[0].p, d_val[1].p}, 0};
+	if (n) hipLaunchKernelGGL(keys_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, (const uint8_t *)d_rec.p, (const uint64_t *)d_off.p, n, K, S.key[0], S.val[0], d_end.p);
+	out->sort_passes = radix_sort(S, n, K.bits(), d_hist.p);
+	uint64_t *const key_s = S.key[S.in], *const key_f = S.key[1 - S.in];
+	uint32_t *const val_s = S.val[S.in], *const val_f = S.val[1 - S.in];
+	// where every sorted record goes: the lengths in sorted order, scanned
+	if (n) hipLaunchKernelGGL(sorted_len_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, (const uint32_t *)val_s, (const uint64_t *)d_off.p, n, val_f);
+	scan_launch<uint32_t, uint64_t>(val_f, n, d_dst.p, d_sums.p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(nullptr));
+	out->sort_s = since(t);
+
+	// the index arrays
+	t = Clock::now();
+	IndexArrays X;
+	X.refs.assign(n_ref, RefExtent());
+	X.win_base.assign(n_ref1, 0);
+	std::vector<uint32_t> first(n_ref1, 0xFFFFFFFFu), last(n_ref1, 0), max_end(n_ref1, 0), flag4(n_ref1, 0);
+	std::vector<uint64_t> ext_beg(n_ref1, 0), ext_end(n_ref1, 0);
+	HIP_TRY(hipMemset(d_ref[0].p, 0xFF, n_ref1 * 4));
+	for (int k = 1; k < 4; ++k) HIP_TRY(hipMemset(d_ref[k].p, 0, n_ref1 * 4));
+	if (n) {
+		hipLaunchKernelGGL(bounds_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, (const uint8_t *)d_rec.p, (const uint64_t *)d_off.p, (const uint64_t *)key_s,
+		                   (const uint32_t *)val_s, (const uint32_t *)d_end.p, n, K, d_ref[0].p, d_ref[1].p, d_ref[2].p, d_ref[3].p);
+		hipLaunchKernelGGL(extent_kernel, dim3(grid_for(n_ref1, 1u << 22)), dim3(NT), 0, nullptr, (const uint32_t *)d_ref[0].p, (const uint32_t *)d_ref[1].p,
+		                   (const uint64_t *)d_dst.p, (uint32_t)n_ref1, d_ext[0].p, d_ext[1].p);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpy(first.data(), d_ref[0].p, n_ref1 * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(last.data(), d_ref[1].p, n_ref1 * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(max_end.data(), d_ref[2].p, n_ref1 * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(flag4.data(), d_ref[3].p, n_ref1 * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(ext_beg.data(), d_ext[0].p, n_ref1 * 8, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(ext_end.data(), d_ext[1].p, n_ref1 * 8, hipMemcpyDeviceToHost));
+	}
+	for (uint32_t r = 0; r < n_ref; ++r) {
+		if (first[r] != 0xFFFFFFFFu) {
+			const uint64_t cnt = (uint64_t)last[r] - first[r] + 1u;
+			X.refs[r].beg = ext_beg[r]; X.refs[r].end = ext_end[r];
+			X.refs[r].n_unmapped = flag4[r]; X.refs[r].n_mapped = cnt - flag4[r];
+		}
+		X.win_base[r + 1] = X.win_base[r] + (max_end[r] ? (((uint64_t)max_end[r] - 1u) >> WINDOW_SHIFT) + 1u : 0u);
+	}
+	X.n_no_coor = first[n_ref] != 0xFFFFFFFFu ? (uint64_t)last[n_ref] - first[n_ref] + 1u : 0u;
+	out->no_coor = X.n_no_coor;
+	const uint32_t m = n - (uint32_t)X.n_no_coor;  // the placed records: the first m of the sorted ones
+	const size_t n_win = (size_t)X.win_base[n_ref];
+	X.lin.assign(n_win, NONE);
+	uint32_t n_chunks = 0;
+	if (m) {
+		if ((rc = d_lin.alloc(n_win))) return rc;
+		HIP_TRY(hipMemset(d_lin.p, 0xFF, n_win * 8));
+		HIP_TRY(hipMemcpy(d_win.p, X.win_base.data(), n_ref1 * 8, hipMemcpyHostToDevice));
+		hipLaunchKernelGGL(lin_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, (const uint64_t *)key_s, (const uint32_t *)val_s, (const uint32_t *)d_end.p,
+		                   (const uint64_t *)d_dst.p, m, K, (const uint64_t *)d_win.p, (unsigned long long *)d_lin.p);
+		// the record numbers by (reference, bin): key_s is used up by then, val_f (the sorted lengths) too; val_s stays for the gather
+		SortArrays S2{{key_f, key_s}, {d_val[2].p, val_f}, 0};
+		hipLaunchKernelGGL(bin_key_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, (const uint64_t *)key_s, (const uint32_t *)val_s, (const uint32_t *)d_end.p, m, K,
+		                   bin_bits, S2.key[0], S2.val[0]);
+		(void)radix_sort(S2, m, K.ref_bits + bin_bits, d_hist.p);
+		const uint64_t *key2 = S2.key[S2.in];
+		const uint32_t *val2 = S2.val[S2.in];
+		uint32_t *flag = (uint32_t *)S2.key[1 - S2.in], *index = flag + m;  // (2 m + 1 words in an array of 2 n + 4)
+		hipLaunchKernelGGL(chunk_flag_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, key2, val2, m, flag);
+		scan_launch<uint32_t, uint32_t>(flag, m, index, d_sums.p);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpy(&n_chunks, index + m, 4, hipMemcpyDeviceToHost));
+		if (n_chunks > m) return URMAPX_E_NODEVICE;
+		if ((rc = d_chunks.alloc(n_chunks))) return rc;
+		hipLaunchKernelGGL(chunk_write_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, key2, val2, (const uint32_t *)flag, (const uint32_t *)index,
+		                   (const uint64_t *)d_dst.p, m, bin_bits, n_chunks, d_chunks.p);
+		HIP_TRY(hipGetLastError());
+		X.chunks.resize(n_chunks);
+		HIP_TRY(hipMemcpy(X.chunks.data(), d_chunks.p, (size_t)n_chunks * sizeof(Chunk), hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(X.lin.data(), d_lin.p, n_win * 8, hipMemcpyDeviceToHost));
+	}
+	out->index_s = since(t);
+
+	// the sorted stream, a slice at a time: gather, deflate, copy back
+	const size_t slice_bytes = (size_t)slice_members() * MEMBER;
+	const size_t slice_cap = slice_bytes < n_bytes ? slice_bytes : n_bytes, z_cap = urmapx_bgzf_bound(slice_cap);
+	Dev<uint8_t> d_slice, d_z;
+	Dev<uint64_t> d_used;
+	if ((rc = d_slice.alloc(slice_cap + 16)) || (rc = d_z.alloc(z_cap + 16)) || (rc = d_used.alloc(1))) return rc;
+	urmapx_bgzf *Z = nullptr;
+	if ((rc = urmapx_bgzf_create(device, nullptr, &Z))) return rc;
+	const size_t host_cap = urmapx_bgzf_bound(n_bytes);
+	uint8_t *z = (uint8_t *)malloc(host_cap ? host_cap : 1);
+	size_t z_bytes = 0;
+	auto slices = [&]() -> int {
+		if (!z) return URMAPX_E_NOMEM;
+		for (uint64_t s0 = 0; s0 < n_bytes; s0 += slice_bytes) {
+			const uint64_t s1 = s0 + slice_bytes < n_bytes ? s0 + slice_bytes : n_bytes;
+			auto t0 = Clock::now();
+			hipLaunchKernelGGL(slice_range_kernel, dim3(1), dim3(1), 0, nullptr, (const uint64_t *)d_dst.p, n, s0, s1, d_range.p);
+			hipLaunchKernelGGL(gather_kernel, dim3(4096), dim3(NT), 0, nullptr, (const uint8_t *)d_rec.p, (const uint64_t *)d_off.p, (const uint32_t *)val_s,
+			                   (const uint64_t *)d_dst.p, (const uint32_t *)d_range.p, s0, s1, d_slice.p);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipStreamSynchronize(nullptr));
+			out->gather_s += since(t0);
+			t0 = Clock::now();
+			int r = urmapx_bgzf_compress_device(device, d_slice.p, (size_t)(s1 - s0), d_z.p, z_cap, d_used.p, 0, Z);
+			if (r) return r;
+			uint64_t used = 0;
+			HIP_TRY(hipMemcpy(&used, d_used.p, 8, hipMemcpyDeviceToHost));
+			out->deflate_s += since(t0);
+			if (used > z_cap || z_bytes + used > host_cap) return URMAPX_E_NODEVICE;
+			t0 = Clock::now();
+			if (used) HIP_TRY(hipMemcpy(z + z_bytes, d_z.p, (size_t)used, hipMemcpyDeviceToHost));
+			out->copy_s += since(t0);
+			z_bytes += (size_t)used;
+			++out->slices;
+		}
+		return URMAPX_OK;
+	};
+	rc = slices();
+	urmapx_bgzf_destroy(Z);
+	if (rc) { free(z); return rc; }
+	if (uint8_t *fit = (uint8_t *)realloc(z, z_bytes ? z_bytes : 1)) z = fit;
+	t = Clock::now();
+	rc = finish_result(out, z, z_bytes, n_bytes, in_front, X, n_ref);
+	out->index_s += since(t);
+	return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t urmapx_bam_sort_device_bytes(size_t n_bytes, uint64_t n_records) {
+	const size_t slice = (size_t)slice_members() * MEMBER;
+	// off, dst, two keys: 8 bytes each; three record-number arrays and the ends: 4 bytes each
+	return (uint64_t)n_bytes + 48u * n_records + slice_scratch_bytes(slice < n_bytes ? slice : n_bytes) + ((uint64_t)1 << 20);
+}
+
+int urmapx_bam_sort(int device, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
+                    size_t n_starts, urmapx_bam_sort_result *out) {
+	if (!out || (n_bytes && !records) || (n_starts && !starts)) return URMAPX_E_ARG;
+	memset(out, 0, sizeof *out);
+	int count = 0;
+	if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) { (void)hipGetLastError(); return URMAPX_E_NODEVICE; }
+	int rc;
+	try {
+		t_alloc_s = 0;
+		rc = sort_device(device, (const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, out);
+	} catch (const std::bad_alloc &) {
+		rc = URMAPX_E_NOMEM;
+	}
+	out->alloc_s = t_alloc_s;  // (the arrays are freed by now)
+	if (rc) urmapx_bam_sort_free(out);
+	return rc;
+}
+
+}  // extern "C"

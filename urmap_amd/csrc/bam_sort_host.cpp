@@ -1,0 +1,280 @@
+// bam_sort_host.cpp -- the coordinate sort of BAM records without a device (urmapx_bam_sort_host), and what it shares with the
+// device sort of bam_sort.hip: the walk along the block_size chain, the members' table, the .bai writer.  See include/urmapx.h
+// "Sorted BAM output" for the contract and bam_sort.h for the pieces.
+#include "bam_sort.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+
+namespace urx {
+namespace bamsort {
+
+namespace {
+// the chain from `at` to exactly `stop`
+int walk(const uint8_t *rec, uint64_t at, uint64_t stop, uint32_t n_ref, std::vector<uint64_t> &offs, uint32_t &max_pos) {
+	const uint64_t n_bytes = stop;
+	max_pos = 0;
+	while (at < n_bytes) {
+		if (n_bytes - at < CORE) return URMAPX_E_FORMAT;
+		const uint8_t *r = rec + at;
+		const uint64_t len = (uint64_t)load_u32(r) + 4u;
+		const uint32_t ref_id = load_u32(r + 4), pos = load_u32(r + 8);
+		const uint32_t l_name = load_u32(r + 12) & 0xFFu, n_cigar = load_u32(r + 16) & 0xFFFFu;
+		if (len > n_bytes - at || (uint64_t)CORE + l_name + 4ull * n_cigar > len) return URMAPX_E_FORMAT;
+		if (ref_id != 0xFFFFFFFFu && (ref_id >= n_ref || pos == 0xFFFFFFFFu)) return URMAPX_E_FORMAT;
+		if (pos != 0xFFFFFFFFu) {
+			if (pos >> 31) return URMAPX_E_FORMAT;
+			max_pos = std::max(max_pos, pos);
+		}
+		if (offs.size() >= 0x7FFFFFFFu) return URMAPX_E_FORMAT;  // record numbers are 32 bits
+		offs.push_back(at);
+		at += len;
+	}
+	return URMAPX_OK;
+}
+}  // namespace
+
+int scan_records(const uint8_t *rec, size_t n_bytes, uint32_t n_ref, const uint64_t *starts, size_t n_starts, std::vector<uint64_t> &offs, uint32_t &max_pos) {
+	offs.clear();
+	max_pos = 0;
+	std::vector<uint64_t> cut{0};  // piece p is [cut[p], cut[p + 1])
+	for (size_t k = 0; k < n_starts; ++k) {
+		if (starts[k] < cut.back() || starts[k] > n_bytes) return URMAPX_E_FORMAT;
+		if (starts[k] > cut.back()) cut.push_back(starts[k]);
+	}
+	if (cut.back() < n_bytes) cut.push_back(n_bytes);
+	const int64_t P = (int64_t)cut.size() - 1;
+	std::vector<std::vector<uint64_t>> part((size_t)P);
+	std::vector<uint32_t> top((size_t)P, 0);
+	std::vector<int> rcs((size_t)P, 0);
+#pragma omp parallel for schedule(dynamic, 1) if (P > 1)
+	for (int64_t p = 0; p < P; ++p) {
+		part[(size_t)p].reserve((size_t)((cut[(size_t)p + 1] - cut[(size_t)p]) / 200));
+		rcs[(size_t)p] = walk(rec, cut[(size_t)p], cut[(size_t)p + 1], n_ref, part[(size_t)p], top[(size_t)p]);
+	}
+	size_t n = 0;
+	for (int64_t p = 0; p < P; ++p) {
+		if (rcs[(size_t)p]) return rcs[(size_t)p];
+		n += part[(size_t)p].size();
+		max_pos = std::max(max_pos, top[(size_t)p]);
+	}
+	if (n >= 0x7FFFFFFFu) return URMAPX_E_FORMAT;
+	offs.resize(n + 1);
+	std::vector<size_t> first((size_t)P + 1, 0);
+	for (int64_t p = 0; p < P; ++p) first[(size_t)p + 1] = first[(size_t)p] + part[(size_t)p].size();
+#pragma omp parallel for schedule(dynamic, 1) if (P > 1)
+	for (int64_t p = 0; p < P; ++p)
+		if (!part[(size_t)p].empty()) memcpy(&offs[first[(size_t)p]], part[(size_t)p].data(), part[(size_t)p].size() * sizeof(uint64_t));
+	offs[n] = n_bytes;
+	return URMAPX_OK;
+}
+
+bool member_table(const uint8_t *z, size_t n, uint64_t in_front, std::vector<uint64_t> &coffs) {
+	coffs.clear();
+	size_t at = 0;
+	while (at < n) {
+		// 18 bytes of header, the 'BC' field with BSIZE = the member's size - 1 at 16 (urmapx.h "BGZF output")
+		if (n - at < 28 || z[at] != 0x1f || z[at + 1] != 0x8b || z[at + 12] != 'B' || z[at + 13] != 'C') return false;
+		const size_t size = ((size_t)z[at + 16] | (size_t)z[at + 17] << 8) + 1u;
+		if (size < 26 || size > n - at) return false;
+		coffs.push_back(in_front + at);
+		at += size;
+	}
+	coffs.push_back(in_front + at);
+	return true;
+}
+
+namespace {
+void put32(std::vector<uint8_t> &o, uint32_t v) { for (int k = 0; k < 4; ++k) o.push_back((uint8_t)(v >> (8 * k))); }
+void put64(std::vector<uint8_t> &o, uint64_t v) { for (int k = 0; k < 8; ++k) o.push_back((uint8_t)(v >> (8 * k))); }
+}  // namespace
+
+std::vector<uint8_t> write_bai(const IndexArrays &X, uint32_t n_ref, const std::vector<uint64_t> &coffs) {
+	auto voff = [&](uint64_t u) {
+		const uint64_t m = u / MEMBER;
+		return (m < coffs.size() ? coffs[(size_t)m] : coffs.back()) << 16 | u % MEMBER;
+	};
+	std::vector<uint8_t> o;
+	o.reserve(16 + 24 * X.chunks.size() + 8 * X.lin.size() + 64 * (size_t)n_ref);
+	o.insert(o.end(), {'B', 'A', 'I', 1});
+	put32(o, n_ref);
+	size_t c = 0;
+	for (uint32_t r = 0; r < n_ref; ++r) {
+		const RefExtent &E = X.refs[r];
+		const bool any = E.n_mapped + E.n_unmapped != 0;
+		const size_t c0 = c;
+		uint32_t n_bin = 0;
+		for (; c < X.chunks.size() && X.chunks[c].ref == r; ++c)
+			if (c == c0 || X.chunks[c].bin != X.chunks[c - 1].bin) ++n_bin;
+		put32(o, n_bin + (any ? 1u : 0u));
+		for (size_t a = c0; a < c;) {
+			size_t b = a;
+			while (b < c && X.chunks[b].bin == X.chunks[a].bin) ++b;
+			put32(o, X.chunks[a].bin);
+			put32(o, (uint32_t)(b - a));
+			for (; a < b; ++a) { put64(o, voff(X.chunks[a].beg)); put64(o, voff(X.chunks[a].end)); }
+		}
+		if (any) {
+			put32(o, PSEUDO_BIN);
+			put32(o, 2);
+			put64(o, voff(E.beg)); put64(o, voff(E.end));
+			put64(o, E.n_mapped); put64(o, E.n_unmapped);
+		}
+		const uint64_t w0 = X.win_base[r], w1 = X.win_base[r + 1];
+		put32(o, (uint32_t)(w1 - w0));
+		const size_t at = o.size();
+		o.resize(at + 8 * (size_t)(w1 - w0));
+		uint64_t next = 0;  // (the last window of a reference is never empty: the windows end behind the last record)
+		for (uint64_t w = w1; w-- > w0;) {
+			if (X.lin[(size_t)w] != NONE) next = voff(X.lin[(size_t)w]);
+			for (int k = 0; k < 8; ++k) o[at + 8 * (size_t)(w - w0) + (size_t)k] = (uint8_t)(next >> (8 * k));
+		}
+	}
+	put64(o, X.n_no_coor);
+	return o;
+}
+
+int finish_result(urmapx_bam_sort_result *out, uint8_t *bgzf, size_t bgzf_bytes, uint64_t stream_bytes, uint64_t in_front,
+                  const IndexArrays &X, uint32_t n_ref) {
+	out->bgzf = bgzf;
+	out->bgzf_bytes = bgzf_bytes;
+	out->stream_bytes = stream_bytes;
+	std::vector<uint64_t> coffs;
+	if (!member_table(bgzf, bgzf_bytes, in_front, coffs) || coffs.size() != (size_t)((stream_bytes + MEMBER - 1) / MEMBER) + 1u) return URMAPX_E_FORMAT;
+	try {
+		const std::vector<uint8_t> bai = write_bai(X, n_ref, coffs);
+		out->bai = malloc(bai.size());
+		if (!out->bai) return URMAPX_E_NOMEM;
+		memcpy(out->bai, bai.data(), bai.size());
+		out->bai_bytes = bai.size();
+	} catch (const std::bad_alloc &) {
+		return URMAPX_E_NOMEM;
+	}
+	return URMAPX_OK;
+}
+
+}  // namespace bamsort
+}  // namespace urx
+
+using namespace urx::bamsort;
+
+namespace {
+using Clock = std::chrono::steady_clock;
+double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::now() - t).count(); }
+
+int sort_host(const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts, urmapx_bam_sort_result *out) {
+	auto t = Clock::now();
+	std::vector<uint64_t> offs;
+	uint32_t max_pos = 0;
+	int rc = scan_records(rec, n_bytes, n_ref, starts, n_starts, offs, max_pos);
+	if (rc) return rc;
+	out->scan_s = since(t);
+	const size_t n = offs.size() - 1;
+	out->records = n;
+	const KeyLayout K = key_layout(n_ref, max_pos);
+
+	t = Clock::now();
+	std::vector<uint64_t> key(n);
+	std::vector<uint32_t> perm(n);
+	for (size_t i = 0; i < n; ++i) {
+		key[i] = K.key(load_u32(rec + offs[i] + 4), load_u32(rec + offs[i] + 8));
+		perm[i] = (uint32_t)i;
+	}
+	std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+	out->sort_s = since(t);
+
+	t = Clock::now();
+	std::vector<uint8_t> stream(n_bytes);
+	std::vector<uint64_t> dst(n + 1);
+	uint64_t at = 0;
+	for (size_t k = 0; k < n; ++k) {
+		const uint64_t a = offs[perm[k]], len = offs[perm[k] + 1] - a;
+		dst[k] = at;
+		if (len) memcpy(stream.data() + at, rec + a, (size_t)len);
+		at += len;
+	}
+	dst[n] = at;
+	out->gather_s = since(t);
+
+	t = Clock::now();
+	IndexArrays X;
+	X.refs.assign(n_ref, RefExtent());
+	X.win_base.assign((size_t)n_ref + 1, 0);
+	std::vector<uint64_t> max_end(n_ref, 0), end_of(n);
+	std::vector<uint32_t> bin_of(n), placed;
+	for (size_t k = 0; k < n; ++k) {
+		const uint32_t r = K.ref_of(key[perm[k]]);
+		if (r == n_ref) { ++X.n_no_coor; continue; }
+		const uint8_t *p = rec + offs[perm[k]];
+		const uint64_t beg = K.pos_of(key[perm[k]]), end = ref_end(p, (uint32_t)(dst[k + 1] - dst[k]), beg);
+		RefExtent &E = X.refs[r];
+		if (E.n_mapped + E.n_unmapped == 0) E.beg = dst[k];
+		E.end = dst[k + 1];
+		if (load_u32(p + 16) >> 16 & 4u) ++E.n_unmapped; else ++E.n_mapped;
+		max_end[r] = std::max(max_end[r], end);
+		end_of[k] = end;
+		bin_of[k] = reg2bin(beg, end);
+		placed.push_back((uint32_t)k);
+	}
+	for (uint32_t r = 0; r < n_ref; ++r) X.win_base[r + 1] = X.win_base[r] + (max_end[r] ? ((max_end[r] - 1) >> WINDOW_SHIFT) + 1 : 0);
+	X.lin.assign((size_t)X.win_base[n_ref], NONE);
+	for (uint32_t k : placed) {
+		const uint32_t r = K.ref_of(key[perm[k]]);
+		for (uint64_t w = K.pos_of(key[perm[k]]) >> WINDOW_SHIFT; w <= (end_of[k] - 1) >> WINDOW_SHIFT; ++w) {
+			uint64_t &v = X.lin[(size_t)(X.win_base[r] + w)];
+			if (dst[k] < v) v = dst[k];
+		}
+	}
+	auto ref_bin = [&](uint32_t k) { return (uint64_t)K.ref_of(key[perm[k]]) << 32 | bin_of[k]; };
+	std::stable_sort(placed.begin(), placed.end(), [&](uint32_t a, uint32_t b) { return ref_bin(a) < ref_bin(b); });
+	for (size_t j = 0; j < placed.size(); ++j) {
+		const uint32_t k = placed[j];
+		if (j && ref_bin(placed[j - 1]) == ref_bin(k) && placed[j - 1] + 1 == k) X.chunks.back().end = dst[k + 1];
+		else X.chunks.push_back(Chunk{K.ref_of(key[perm[k]]), bin_of[k], dst[k], dst[k + 1]});
+	}
+	out->no_coor = X.n_no_coor;
+	out->index_s = since(t);
+
+	t = Clock::now();
+	const size_t cap = urmapx_bgzf_bound(n_bytes);
+	uint8_t *z = (uint8_t *)malloc(cap ? cap : 1);
+	if (!z) return URMAPX_E_NOMEM;
+	size_t used = 0;
+	rc = urmapx_bgzf_compress_host(stream.data(), n_bytes, z, cap, &used, 0);
+	out->deflate_s = since(t);
+	if (rc) { free(z); return rc; }
+	t = Clock::now();
+	rc = finish_result(out, z, used, n_bytes, in_front, X, n_ref);
+	out->index_s += since(t);
+	return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int urmapx_bam_sort_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts, size_t n_starts,
+                         urmapx_bam_sort_result *out) {
+	if (!out || (n_bytes && !records) || (n_starts && !starts)) return URMAPX_E_ARG;
+	memset(out, 0, sizeof *out);
+	int rc;
+	try {
+		rc = sort_host((const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, out);
+	} catch (const std::bad_alloc &) {
+		rc = URMAPX_E_NOMEM;
+	}
+	if (rc) urmapx_bam_sort_free(out);
+	return rc;
+}
+
+void urmapx_bam_sort_free(urmapx_bam_sort_result *R) {
+	if (!R) return;
+	free(R->bgzf);
+	free(R->bai);
+	R->bgzf = R->bai = nullptr;
+	R->bgzf_bytes = R->bai_bytes = 0;
+}
+
+}  // extern "C"

@@ -200,7 +200,15 @@ struct Failure {
 // works (parallel page faults; write() on one file is serialised by the inode lock), else with pwrite.
 class FileSink {
 public:
-	~FileSink() { if (fd_ >= 0) ::close(fd_); }
+	~FileSink() { if (fd_ >= 0) ::close(fd_); free(mem_); }
+	// bam_sort: the pieces are kept at their offsets in host memory instead (the file is written once they are sorted); write_through()
+	// ends that, and what write_at gets from then on goes to the file
+	void keep_in_memory() { memory_ = true; }
+	void write_through() { memory_ = false; }
+	const char *kept() const { return mem_; }
+	// where the pieces began, ascending: record starts all of them (urmapx_bam_sort walks the chain from each)
+	std::vector<uint64_t> kept_starts() { std::sort(mem_starts_.begin(), mem_starts_.end()); return mem_starts_; }
+	void drop_kept() { free(mem_); mem_ = nullptr; mem_cap_ = 0; }
 	// measurement (urmapx_map_options.discard_sam): the text is taken and dropped
 	void open_discard() { discard_ = true; }
 	bool open(const char *path) {
@@ -240,13 +248,25 @@ public:
 	}
 	// makes the file at least `end` bytes long (pieces below `end` can then be written from several threads at once)
 	bool reserve(uint64_t end) {
-		if (!use_map_ || end <= size_) return true;
+		if (memory_ || !use_map_ || end <= size_) return true;
 		if (ftruncate(fd_, (off_t)end) != 0) { use_map_ = false; return true; }
 		size_ = end;
 		return true;
 	}
 	bool write_at(const char *p, size_t n, uint64_t off, int threads) {
 		if (n == 0 || discard_) return true;
+		if (memory_) {  // (pieces arrive from several threads, each at an offset of its own; only growing moves the array)
+			std::lock_guard<std::mutex> g(mem_lock_);
+			if (off + n > mem_cap_) {
+				const size_t want = std::max<size_t>((size_t)(off + n), mem_cap_ + mem_cap_ / 2 + (1u << 20));
+				char *m = (char *)realloc(mem_, want);
+				if (!m) return false;
+				mem_ = m; mem_cap_ = want;
+			}
+			memcpy(mem_ + off, p, n);
+			mem_starts_.push_back(off);
+			return true;
+		}
 		if (threads < 1) threads = 1;
 		if (sequential_) {  // the callers hand pieces over in file order when seekable() is false
 			if (off != size_) return false;
@@ -303,7 +323,11 @@ public:
 
 private:
 	int fd_ = -1;
-	bool sequential_ = false, discard_ = false;
+	bool sequential_ = false, discard_ = false, memory_ = false;
+	std::mutex mem_lock_;
+	char *mem_ = nullptr;
+	size_t mem_cap_ = 0;
+	std::vector<uint64_t> mem_starts_;
 	std::atomic<bool> use_map_{false};
 	std::atomic<uint64_t> size_{0};
 };
@@ -932,7 +956,8 @@ struct Run {
 	const unsigned minq = paired ? opt.minq : 10;  // only cmd_map2 reads -minq (map2.cpp:76); -map keeps State1::m_Minq = 10
 	const bool have_sam = samout != nullptr;
 	const bool bam = opt.bam != 0 && have_sam;  // -bamout: BAM records where the SAM text was, always inside BGZF members
-	const bool bgzf = (opt.bgzf != 0 || bam) && have_sam;
+	const bool sort = opt.bam_sort != 0 && bam;  // -sort: the lanes' raw records are kept in host memory; finish() sorts them and writes samout and its index
+	const bool bgzf = (opt.bgzf != 0 || bam) && have_sam && !sort;
 	const bool pool_lanes = LanePool::enabled(), lane_veryfast = paired && opt.veryfast, lane_pair_info = paired && tabout != nullptr;
 	urmapx_params P;
 	// one replica of the index per device (uploaded concurrently), K mapping contexts on each
@@ -1013,9 +1038,14 @@ struct Run {
 		(void)sched_getaffinity(0, sizeof caller_mask, &caller_mask);
 		rep.host_threads = host_threads; rep.lanes = n_lanes; rep.write_threads = 1; rep.shards = 1;
 		if (samout) {
+			if (sort) {  // (the index needs a file name to sit beside)
+				struct stat st;
+				if (stat(samout, &st) == 0 && !S_ISREG(st.st_mode)) return failed(URMAPX_E_ARG, msg, std::string("bam_sort needs a regular file, not ") + samout);
+			}
 			if (opt.discard_sam) sink.open_discard();
 			else if (!sink.open(samout)) return failed(URMAPX_E_IO, msg, std::string("Cannot create ") + samout);
-			if (range.header || bam) {  // (every shard of a BAM run is a BAM file: each has the header block)
+			if (sort) sink.keep_in_memory();  // (the header block is made in write_sorted; the records start at offset 0 of the kept bytes)
+			else if (range.header || bam) {  // (every shard of a BAM run is a BAM file: each has the header block)
 				std::string hdr;
 				if (bam) append_bam_header(hdr, I, opt.cmdline);
 				else append_sam_header_text(hdr, I, opt.cmdline);
@@ -1057,7 +1087,64 @@ struct Run {
 		for (size_t g = 1; g < replicas.size(); ++g) urmapx_index_close(replicas[g]);
 		ctxs.clear(); texts.clear(); replicas.clear();  // (the destructor's pass finds nothing)
 	}
+	// bam_sort: the kept records (rep.sam_file_bytes of them, in input order) into coordinate order, then samout -- header block with the
+	// @HD line in a member of its own, the sorted stream, the end-of-file member -- and samout.bai
+	void write_sorted() {
+		const auto t0 = now();
+		const uint64_t n_bytes = rep.sam_file_bytes;
+		const uint32_t n_ref = urmapx_index_seq_count(I);
+		std::string hdr;
+		append_bam_header(hdr, I, opt.cmdline, true);
+		rep.sam_text_bytes += hdr.size();
+		if (!bgzf_members(hdr)) { fail.raise(URMAPX_E_NOMEM, "out of memory"); return; }
+		urmapx_bam_sort_result S;
+		int rc;
+		const std::vector<uint64_t> starts = sink.kept_starts();
+		if (getenv("URMAPX_HOST_TEXT") || getenv("URMAPX_HOST_SORT"))
+			rc = urmapx_bam_sort_host(sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &S);
+		else {
+			rc = urmapx_bam_sort(phys(0), sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &S);
+			if (rc == URMAPX_E_NOMEM) {  // the device is full of lanes: this run's and the pool's go first (the mapping is over)
+				close();
+				LanePool::get().purge(nullptr);
+				rc = urmapx_bam_sort(phys(0), sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &S);
+			}
+			if (rc == URMAPX_E_NOMEM) {
+				size_t free_b = 0, total_b = 0;
+				(void)hipSetDevice(phys(0));
+				if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+				fail.raise(rc, "bam_sort: the records and the sort's arrays need " + std::to_string(urmapx_bam_sort_device_bytes((size_t)n_bytes, rep.reads)) +
+				                   " bytes on the device, " + std::to_string(free_b) + " are free");
+				return;
+			}
+		}
+		if (rc) { fail.raise(rc, std::string("bam_sort: ") + urmapx_strerror(rc)); return; }
+		sink.drop_kept();
+		sink.write_through();
+		const auto tw0 = now();
+		std::string eof;
+		(void)bgzf_members(eof, 1);
+		const int wt = sink.writer_threads(host_threads);
+		if (!sink.write_at(hdr.data(), hdr.size(), 0, 1) || !sink.write_at((const char *)S.bgzf, S.bgzf_bytes, hdr.size(), wt) ||
+		    !sink.write_at(eof.data(), eof.size(), hdr.size() + S.bgzf_bytes, 1))
+			cannot_write_sam();
+		rep.sam_file_bytes = hdr.size() + S.bgzf_bytes + eof.size();
+		const std::string bai = std::string(samout) + ".bai";
+		FILE *f = fopen(bai.c_str(), "wb");
+		if (!f || fwrite(S.bai, 1, S.bai_bytes, f) != S.bai_bytes) fail.raise(URMAPX_E_IO, "Error writing " + bai);
+		if (f && fclose(f) != 0) fail.raise(URMAPX_E_IO, "Error writing " + bai);
+		rep.write_s += secs(tw0, now());
+		rep.sort_s = secs(t0, now());
+		if (getenv("URMAPX_VERBOSE"))  // the parts of sort_s (scripts/bam_sort_bench.py reads this line)
+			fprintf(stderr, "bam_sort seconds: total %.4f scan %.4f alloc %.4f upload %.4f sort %.4f gather %.4f deflate %.4f copy %.4f index %.4f write %.4f; "
+			                "records %llu bytes %llu passes %u slices %u\n",
+			        rep.sort_s, S.scan_s, S.alloc_s, S.upload_s, S.sort_s, S.gather_s, S.deflate_s, S.copy_s, S.index_s, secs(tw0, now()),
+			        (unsigned long long)S.records, (unsigned long long)S.stream_bytes, S.sort_passes, S.slices);
+		urmapx_bam_sort_free(&S);
+		trace.add("sort", -1, 0, t0);
+	}
 	int finish(urmapx_map_report *report, std::string &msg) {
+		if (sort && !fail.set.load()) write_sorted();
 		if (bgzf && !fail.set.load()) {  // htslib's empty member: the file is complete
 			std::string eof;
 			(void)bgzf_members(eof, 1);
@@ -1065,6 +1152,10 @@ struct Run {
 			rep.sam_file_bytes += eof.size();
 		}
 		if (have_sam && !sink.finish(rep.sam_file_bytes)) cannot_write_sam();
+		if (sort && fail.set.load()) {  // a failed sorted run leaves neither file
+			remove(samout);
+			remove((std::string(samout) + ".bai").c_str());
+		}
 		ftab.reset();  // (inside the run's clock; the lanes are let go outside it)
 		const auto t2 = now();
 		range.t_begin = std::chrono::duration<double>(t1.time_since_epoch()).count();
@@ -1799,6 +1890,12 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
 	if (err && errcap) err[0] = 0;
 	if (!I || !opt || !fastq1) return URMAPX_E_ARG;
 	if (opt->bam && opt->bgzf) { say(err, errcap, "bam and bgzf together: a BAM file is always BGZF"); return URMAPX_E_ARG; }
+	if (opt->bam_sort) {
+		const char *why = !opt->bam || !samout ? "bam_sort needs bam: it sorts the records of a BAM file" :
+		                  opt->sam_shards > 1 ? "bam_sort with sam_shards: one sorted file has one index" :
+		                  opt->discard_sam ? "bam_sort with discard_sam: there is nothing to sort" : nullptr;
+		if (why) { say(err, errcap, why); return URMAPX_E_ARG; }
+	}
 	const int shards = opt->sam_shards > 1 ? opt->sam_shards : 1;
 	if (shards == 1) return map_files_impl(I, opt, InputRange(), fastq1, fastq2, samout, tabout, report, err, errcap);
 	const bool paired = fastq2 != nullptr;

@@ -644,8 +644,9 @@ bool append_bam_record(std::string &out, const urmapx_index *I, const urmapx_res
 	return true;
 }
 
-void append_bam_header(std::string &out, const urmapx_index *I, const char *cmdline) {
+void append_bam_header(std::string &out, const urmapx_index *I, const char *cmdline, bool sorted) {
 	std::string text;
+	if (sorted) text = "@HD\tVN:1.6\tSO:coordinate\n";
 	append_sam_header_text(text, I, cmdline);
 	char w[4];
 	out.append("BAM\1", 4);

@@ -130,7 +130,8 @@ bool append_bam_record(std::string &out, const urmapx_index *I, const urmapx_res
                        uint32_t mate_seq_index, uint32_t mate_pos, int tlen, const char *label, const uint8_t *seq, const uint8_t *qual,
                        unsigned QL);
 // magic, l_text, append_sam_header_text's text, n_ref, the reference list
-void append_bam_header(std::string &out, const urmapx_index *I, const char *cmdline);
+// sorted: the text begins with "@HD\tVN:1.6\tSO:coordinate"
+void append_bam_header(std::string &out, const urmapx_index *I, const char *cmdline, bool sorted = false);
 
 // 256-entry complement table of alpha.cpp:3005 (IUPAC, case preserving, 'u' and non-letters -> '?')
 const unsigned char *complement_table();

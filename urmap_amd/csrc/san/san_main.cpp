@@ -1,7 +1,7 @@
 // san_main.cpp -- driver of the sanitizer builds (make san): the host side of the drop-in path run from the command line, with the
 // device side replaced by san/stub_device.cpp.  tests/test_sanitizers_cpu.py runs it on well-formed and on damaged input; a
 // sanitizer report ends the process with exit code 99 (ASAN_OPTIONS / UBSAN_OPTIONS / TSAN_OPTIONS exitcode, set by the tests).
-//   urmap_san map <fastq1> [-2 fastq2] -o out.sam [-tab out.tab] [-batch N] [-streams K] [-gpus N] [-shards N] [-threads T] [-null] [-bgzf] [-bam] [-biglen N]
+//   urmap_san map <fastq1> [-2 fastq2] -o out.sam [-tab out.tab] [-batch N] [-streams K] [-gpus N] [-shards N] [-threads T] [-null] [-bgzf] [-bam] [-sort] [-biglen N]
 //       (-biglen: bases of the stand-in index's third sequence, 4 000 000 000 unless given; a BAM position holds 2^31 - 1)
 //   urmap_san gunzip <in.gz> <out> [threads]
 //   urmap_san fastq <file> <batch>
@@ -36,6 +36,7 @@ static int cmd_map(int argc, char **argv) {
 		else if (a == "-null") o.discard_sam = 1;
 		else if (a == "-bgzf") o.bgzf = 1;
 		else if (a == "-bam") o.bam = 1;
+		else if (a == "-sort") o.bam_sort = 1;
 		else if (a == "-biglen") biglen = (uint32_t)strtoul(val(), nullptr, 10);
 		else return 2;
 	}

@@ -342,4 +342,10 @@ int urmapx_text_fetch_pairs(urmapx_text *T, uint32_t npairs, urmapx_result *resu
 }
 // make_ufi.cpp's GPU-assisted builder has no device here
 int urmapx_build_slots_gpu(int, const uint8_t *, const void *, uint32_t, uint32_t, uint32_t, uint64_t, uint8_t *, uint32_t *) { return URMAPX_E_NODEVICE; }
+// the device sort's stand-in: the host sort (bam_sort_host.cpp), which keeps the same contract
+int urmapx_bam_sort(int, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts,
+                    urmapx_bam_sort_result *out) {
+	return urmapx_bam_sort_host(records, n_bytes, n_ref, in_front, starts, n_starts, out);
+}
+uint64_t urmapx_bam_sort_device_bytes(size_t n_bytes, uint64_t n_records) { return n_bytes + 48u * n_records; }
 }

@@ -23,6 +23,7 @@
 // (myutils.cpp:915), as the reference.
 #include <fcntl.h>
 #include <omp.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -62,6 +63,7 @@ struct Opts {
 	bool bgzf = false;  // -bgzf: -samout is a BGZF file, deflated on the device
 	std::string bamout; // -bamout: a BAM file in -samout's place, records encoded and deflated on the device
 	bool veryfast = false, quiet = false, minq_given = false, host_build = false, notrunclabels = false;
+	bool sort = false;  // -sort: the -bamout file in coordinate order, with its .bai index
 	bool trunclabels = false, wordlength_given = false;
 	double load_factor = 0.6;  // myopts.h: FLT_OPT(load_factor, 0.6, ...)
 	unsigned threads = 0, wordlength = 24, maxix = 0, minq = 10;
@@ -105,6 +107,7 @@ static Opts parse(int argc, char **argv) {
 		else if (a == "-bgzf") o.bgzf = true;
 		else if (a == "-bamout") o.bamout = val();
 		else if (a == "-host") o.host_build = true;
+		else if (a == "-sort") o.sort = true;
 		else if (a == "-quiet") o.quiet = true;
 		else if (a == "-log") o.log = val();
 		else if (a == "-load_factor") o.load_factor = atof(val());
@@ -182,6 +185,13 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 	if (bam && !o.samout.empty()) die("-bamout replaces -samout: give one of the two");
 	if (bam && o.bgzf) die("-bgzf goes with -samout: a -bamout file is always BGZF");
 	const std::string &samout = bam ? o.bamout : o.samout;
+	if (o.sort) {
+		struct stat st;
+		if (!bam) die("-sort needs -bamout: it sorts the records of a BAM file");
+		if (o.samshards > 1) die("-sort goes with one -bamout file, not with -samshards: a sorted file has one index");
+		if (stat(o.bamout.c_str(), &st) == 0 && !S_ISREG(st.st_mode)) die("-sort needs a file name for -bamout, not a pipe or %s: the index %s.bai sits beside it", o.bamout.c_str(), o.bamout.c_str());
+		if (o.host_build) setenv("URMAPX_HOST_SORT", "1", 1);  // -host: the sort too runs on the host (urmapx_bam_sort_host)
+	}
 	const auto t0 = std::chrono::steady_clock::now();
 	urmapx_index *I = nullptr;
 	// the file streams to the first device (urmapx_index_open_device); URMAPX_HOST_INDEX=1: through host arrays as before (measurement)
@@ -202,6 +212,7 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 	mo.veryfast = o.veryfast ? 1 : 0; mo.minq = o.minq; mo.cmdline = cl.c_str();
 	mo.bgzf = o.bgzf ? 1 : 0;
 	mo.bam = bam ? 1 : 0;
+	mo.bam_sort = o.sort ? 1 : 0;
 	urmapx_map_report rep;
 	memset(&rep, 0, sizeof rep);
 	char err[1024];
@@ -243,6 +254,7 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 		if ((o.bgzf && !o.samout.empty()) || bam)
 			progress_log(q, bam ? "%16s  Bytes of BAM records, %s written as BGZF (%.3f)\n\n" : "%16s  Bytes of SAM text, %s written as BGZF (%.3f)\n\n", commas(rep.sam_text_bytes).c_str(), commas(rep.sam_file_bytes).c_str(),
 			             rep.sam_text_bytes ? (double)rep.sam_file_bytes / (double)rep.sam_text_bytes : 0.0);
+		if (o.sort) progress_log(q, "%16.3f  Seconds to sort the records and write %s.bai\n\n", rep.sort_s, samout.c_str());
 		if (o.minq_given && !paired) progress_log(q, "\nWARNING: Option -minq not used\n\n");
 	}
 	urmapx_index_close(I);
@@ -548,6 +560,7 @@ int main(int argc, char **argv) {
 	                "      -bgzf: the file named by -samout is BGZF (gzip members of 64 KB of text, deflated on the GPU); `gzip -dc` gives the SAM text\n"
 	                "      -bamout out.bam: in place of -samout, a BAM file (records encoded and deflated on the GPU, unsorted, no optional fields);\n"
 	                "               with -samshards N every out.bam.0 .. out.bam.N-1 is a complete BAM file\n"
+	                "      -sort: with -bamout, the records in coordinate order (sorted on the GPU) and the index out.bam.bai beside the file\n"
 	                "  urmap -make_ufi genome.fa -output index.ufi [-slots N] [-wordlength W] [-maxix M]\n"
 	                "  urmap -ufi_validate index.ufi [-gpu D]\n"
 	                "  urmap -ufi_stats index.ufi [-log F] [-gpu D] [-quiet]\n"
