@@ -424,6 +424,10 @@ typedef struct urmapx_map_options {
 	                     * depend on gpus, streams, batch or host_threads.  If the device has no room (urmapx_bam_sort_device_bytes) the kept
 	                     * lanes are let go first; then URMAPX_E_NOMEM with the bytes needed and free in err.  URMAPX_E_ARG without bam, with
 	                     * sam_shards > 1 or with discard_sam; samout must be a regular file.  A failed run removes both files */
+	unsigned tags;      /* -tags: URMAPX_TAG_NM | _MD | _AS, the optional fields of every mapped record (see "Optional fields" below); 0: none */
+	const char *read_group; /* -rg: a complete @RG header line, tabs real, with an ID: field (urmapx_read_group_id); it goes into the header in
+	                     * front of the @PG line and every record gets RG:Z:<ID>.  NULL: neither.  URMAPX_E_ARG with the reason in err for a
+	                     * line urmapx_read_group_id refuses and for tag bits outside URMAPX_TAG_ALL */
 } urmapx_map_options;
 typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:593-632) and where the time went */
 	uint64_t reads, mapped_q, mapped_lowq, unmapped, unsupported;
@@ -605,7 +609,8 @@ int urmapx_bgzf_compress_device(int device, const void *d_in, size_t n, void *d_
  * '*' / 0), l_read_name = QNAME + NUL, mapq, bin = reg2bin(pos, pos + the reference bases the CIGAR spans, or pos + 1), the CIGAR runs
  * after the dangling-M polish as len << 4 | op, flag, l_seq, next_refID / next_pos from RNEXT ('=' is refID) / PNEXT, tlen, SEQ as
  * printed (reverse-complemented for a minus-strand hit) 4 bits a base through "=ACMGRSVTWYHKDBN" (either case; any other letter 15),
- * QUAL - 33 (0xFF throughout where the text has '*').  No optional fields: the SAM output has none.
+ * QUAL - 33 (0xFF throughout where the text has '*').  Optional fields only where asked for: NM, MD, AS and RG behind QUAL as aux fields
+ * ("Optional fields" below), in the SAM text and here alike; without -tags / -rg a record ends at QUAL.
  * urmapx_bam_header: the uncompressed header block; returns its size and writes it if it fits cap (buf may be NULL to ask). */
 size_t urmapx_bam_header(const urmapx_index *, const char *cmdline, void *buf, size_t cap);
 /* The host encoders, arguments as urmapx_sam_se / _pe: one record, the two records of a pair.  Return the bytes written, 0 if they do
@@ -617,6 +622,79 @@ size_t urmapx_bam_se(const urmapx_index *, const urmapx_result *r, const urmapx_
 size_t urmapx_bam_pe(const urmapx_index *, const urmapx_result *r1, const urmapx_result *r2, const urmapx_path_op *path_ops,
                      const char *label1, const uint8_t *seq1, const uint8_t *qual1, uint32_t len1, const char *label2,
                      const uint8_t *seq2, const uint8_t *qual2, uint32_t len2, char *buf, size_t cap);
+
+/* ---- Optional fields (-tags NM,MD,AS and -rg): SAM specification section 1.5, SAMtags ----
+ * Behind QUAL, in this order whatever order they were asked for in: NM:i, MD:Z, AS:i, RG:Z.  An unmapped record (RNAME '*') gets RG only.
+ * The alignment columns of a mapped record are what the record itself shows: POS, the CIGAR as emitted (after the dangling-M polish; it
+ * may begin or end with an I or D run) and SEQ as printed (reverse-complemented for a minus-strand hit), against the bytes of the
+ * sequence store from that sequence's offset + POS - 1 on.  Two letters match when their 4-bit BAM codes ("=ACMGRSVTWYHKDBN", either
+ * case, anything else 15) are equal and not 15, which is samtools calmd's test: case never matters, N against N is a mismatch, R against
+ * R a match.  NM = mismatching columns of M runs + bases of I runs + bases of D runs.  MD = [0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)*: a running
+ * count of matches; at a mismatch the count, the reference letter in upper case, count = 0; at a D run the count, '^', the deleted
+ * reference letters in upper case, count = 0; an I run neither prints nor resets; the final count always ("^AC0T" and a leading 0
+ * occur).  AS = urmapx_result.score of the hit the record reports.  RG = the ID of the read-group line.
+ * In BAM the same fields in the same order as aux fields: NM and AS in the smallest of C S I (value >= 0) or c s i (value < 0) that holds
+ * the value, as htslib picks; MD and RG as Z with their NUL; block_size covers them; bin and what -sort derives from a record do not change. */
+#define URMAPX_TAG_NM 1u
+#define URMAPX_TAG_MD 2u
+#define URMAPX_TAG_AS 4u
+#define URMAPX_TAG_ALL 7u
+/* What the tagged formatters take: tags = URMAPX_TAG_* bits; rg_id = the read group's ID or NULL (no RG field); ref[m] = the bytes of the
+ * sequence store under mate m's record (single-end: ref[0]), from its first reference base on and as long as the reference bases its
+ * CIGAR spans (urmapx_ref_span), or NULL: they are read from the index's host arrays (an index without them: the record is refused, 0). */
+typedef struct urmapx_tag_options {
+	unsigned tags;
+	const char *rg_id;
+	const uint8_t *ref[2];
+} urmapx_tag_options;
+/* NM and MD of one alignment by the rules above, no device and no index: ref = the reference window (ref_len bytes from the record's first
+ * reference base), cigar[n_cigar] = the emitted runs as BAM packs them (len << 4 | op, op 0 M, 1 I, 2 D), seq = SEQ as printed.  Returns
+ * the length of the MD text and writes it (no NUL) if it fits md_cap (md may be NULL to ask); *nm receives NM.  (size_t)-1: the runs
+ * leave seq[seq_len] or ref[ref_len], or an op is none of the three. */
+size_t urmapx_calmd(const uint8_t *ref, size_t ref_len, const uint32_t *cigar, uint32_t n_cigar, const uint8_t *seq, size_t seq_len,
+                    uint32_t *nm, char *md, size_t md_cap);
+/* reference bases under a result's emitted CIGAR (M and D runs; read_len for a result without a path); 0 for an unmapped result */
+uint32_t urmapx_ref_span(const urmapx_result *r, const urmapx_path_op *path_ops, uint32_t read_len);
+/* urmapx_sam_se / _pe / urmapx_bam_se / _pe with optional fields.  tags NULL: the bytes of the functions without _tags. */
+size_t urmapx_sam_se_tags(const urmapx_index *, const urmapx_result *r, const urmapx_path_op *path_ops, const char *label,
+                          const uint8_t *seq, const uint8_t *qual, uint32_t read_len, const urmapx_tag_options *tags, char *buf, size_t cap);
+size_t urmapx_sam_pe_tags(const urmapx_index *, const urmapx_result *r1, const urmapx_result *r2, const urmapx_path_op *path_ops,
+                          const char *label1, const uint8_t *seq1, const uint8_t *qual1, uint32_t len1, const char *label2,
+                          const uint8_t *seq2, const uint8_t *qual2, uint32_t len2, const urmapx_tag_options *tags, char *buf, size_t cap);
+size_t urmapx_bam_se_tags(const urmapx_index *, const urmapx_result *r, const urmapx_path_op *path_ops, const char *label,
+                          const uint8_t *seq, const uint8_t *qual, uint32_t read_len, const urmapx_tag_options *tags, char *buf, size_t cap);
+size_t urmapx_bam_pe_tags(const urmapx_index *, const urmapx_result *r1, const urmapx_result *r2, const urmapx_path_op *path_ops,
+                          const char *label1, const uint8_t *seq1, const uint8_t *qual1, uint32_t len1, const char *label2,
+                          const uint8_t *seq2, const uint8_t *qual2, uint32_t len2, const urmapx_tag_options *tags, char *buf, size_t cap);
+/* A read-group line as `bwa mem -R` takes it: "@RG" then fields separated by real tabs or by the two characters '\' 't'.  Writes the
+ * line with real tabs to line_out and the value of its ID: field to id_out (both NUL terminated; either may be NULL) and returns
+ * URMAPX_OK, or URMAPX_E_ARG with the reason in err: the line does not start with "@RG" and a tab, has no ID: field, an empty ID, or a
+ * newline. */
+int urmapx_read_group_id(const char *line, char *line_out, size_t line_cap, char *id_out, size_t id_cap, char *err, size_t errcap);
+/* The header text (@SQ lines, @PG with cmdline) and the BAM header block with a read-group line (tabs real, no '\n'; NULL: none)
+ * directly in front of the @PG line; sorted != 0: "@HD\tVN:1.6\tSO:coordinate" first, as -sort writes it.  Return the size and write
+ * it if it fits cap (buf may be NULL to ask). */
+size_t urmapx_sam_header_rg(const urmapx_index *, const char *cmdline, const char *read_group, int sorted, char *buf, size_t cap);
+size_t urmapx_bam_header_rg(const urmapx_index *, const char *cmdline, const char *read_group, int sorted, void *buf, size_t cap);
+/* The bytes of the sequence store under n spans (starts[i] = offset in the store, lens[i] bytes) back to back into out, which holds
+ * the sum of lens.  From the host arrays where the index has them; otherwise (urmapx_index_open_device) one gather on the index's
+ * device and one copy for the whole list.  URMAPX_E_ARG: a span that leaves the store, or an index with neither. */
+int urmapx_index_fetch_spans(const urmapx_index *, const uint64_t *starts, const uint32_t *lens, uint32_t n, uint8_t *out);
+/* The device text stage with optional fields: mask = URMAPX_TAG_* bits, rg_id = the read group's ID or NULL (copied).  The chunk's
+ * records then carry the fields, written by the two kernels of tags_gpu.hip around the record kernels; 0 and NULL: the records end at
+ * QUAL again.  URMAPX_E_ARG while a chunk is in flight or waiting to be fetched, and for bits outside URMAPX_TAG_ALL. */
+int urmapx_text_set_tags(urmapx_text *, unsigned mask, const char *rg_id);
+/* Device time (ms, events) of the two tag passes of the last chunk whose text was made: [0] the pass that counts, [1] the pass that
+ * writes; both 0 without tags. */
+int urmapx_text_tag_ms(urmapx_text *, float ms[2]);
+/* Stage-level entry point (the device functions the text stage runs; synchronous on the context's stream).  Host arrays: reads as
+ * urmapx_map_se takes them, results[n] and the path arena as it returns them, mask = URMAPX_TAG_* bits.  Per record: nm[i], tagged[i] = 1
+ * if the record gets NM / MD / AS (it is mapped), and its MD text at md + md_offs[i] .. md_offs[i + 1] (md_offs[n + 1]; an untagged
+ * record's is empty).  *md_used receives md_offs[n]; with md_cap smaller nothing is written to md (URMAPX_E_ARG, *md_used still set).
+ * URMAPX_E_ARG also for a result whose alignment leaves its read or its sequence. */
+int urmapx_tags_batch(urmapx_ctx *, const uint8_t *bases, const uint64_t *offs, uint32_t n, const urmapx_result *results,
+                      const urmapx_path_op *path_ops, size_t path_n, unsigned mask, uint32_t *nm, uint8_t *tagged, char *md, size_t md_cap,
+                      uint64_t *md_offs, size_t *md_used);
 
 /* ---- Sorted BAM output (-bamout ... -sort): coordinate order and a .bai index (SAM/BAM specification v1, section 5.2) ----
  * records[n_bytes]: BAM alignment records back to back on the host, each led by its block_size, as urmapx_text_set_bam, urmapx_bam_se

@@ -43,7 +43,12 @@ EXPORTS = (
     "urmapx_bgzf_destroy", "urmapx_bgzf_compress_device", "urmapx_text_set_bgzf",
     "urmapx_text_set_bam", "urmapx_bam_header", "urmapx_bam_se", "urmapx_bam_pe",
     "urmapx_bam_sort", "urmapx_bam_sort_host", "urmapx_bam_sort_free", "urmapx_bam_sort_device_bytes",
+    "urmapx_calmd", "urmapx_ref_span", "urmapx_sam_se_tags", "urmapx_sam_pe_tags", "urmapx_bam_se_tags", "urmapx_bam_pe_tags",
+    "urmapx_read_group_id", "urmapx_sam_header_rg", "urmapx_bam_header_rg", "urmapx_index_fetch_spans", "urmapx_text_set_tags",
+    "urmapx_text_tag_ms", "urmapx_tags_batch",
 )
+
+TAG_NM, TAG_MD, TAG_AS, TAG_ALL = 1, 2, 4, 7
 
 BV_MAGIC = 0x42563130
 BV_MIN_W, BV_MAX_W = 2, 20
@@ -66,7 +71,11 @@ class Params(C.Structure):
 class MapOptions(C.Structure):
     _fields_ = [("first_gpu", C.c_int), ("gpus", C.c_int), ("streams", C.c_int), ("host_threads", C.c_int), ("batch", C.c_uint32),
                 ("veryfast", C.c_int), ("minq", C.c_uint), ("cmdline", C.c_char_p), ("sam_shards", C.c_int), ("discard_sam", C.c_int), ("bgzf", C.c_int),
-                ("bam", C.c_int), ("bam_sort", C.c_int)]
+                ("bam", C.c_int), ("bam_sort", C.c_int), ("tags", C.c_uint), ("read_group", C.c_char_p)]
+
+
+class TagOptions(C.Structure):
+    _fields_ = [("tags", C.c_uint), ("rg_id", C.c_char_p), ("ref", C.c_void_p * 2)]
 
 
 class MapReport(C.Structure):
@@ -491,6 +500,67 @@ class Index:
                 raise UrmapxError(x.code, f"{x}: pair {labels[i][:60]}...") if x.code == -2 else x
         return b"".join(out)
 
+    def _tag_opts(self, tags, rg_id, refs):
+        """urmapx_tag_options; refs: per mate bytes of the reference window or None (read from the host arrays).  -> (struct, keep-alive)"""
+        keep = [np.frombuffer(r, dtype=np.uint8) if r is not None and len(r) else None for r in refs]
+        to = TagOptions(int(tags), rg_id.encode("latin-1") if isinstance(rg_id, str) else rg_id,
+                        (C.c_void_p * 2)(*[(k.ctypes.data if k is not None else None) for k in (keep + [None])[:2]]))
+        return to, keep
+
+    def records_tags(self, results, ops, labels, bases, offs, quals, tags=0, rg_id=None, bam=False, paired=False, windows=None) -> bytes:
+        """SAM text or BAM records of a mapped batch with the optional fields NM MD AS RG (urmapx_sam_se_tags / _pe_tags / urmapx_bam_se_tags /
+        _pe_tags).  tags = TAG_* bits, rg_id = the read group's ID or None.  windows: None (the reference bases come from this index's host
+        arrays) or one bytes object per record (None for an unmapped one): the store bytes under it, as urmapx_index_fetch_spans gives them."""
+        results = np.ascontiguousarray(results)
+        ops = np.ascontiguousarray(ops, dtype=np.uint16)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        ops_ptr = C.c_void_p(ops.ctypes.data if len(ops) else None)
+        name = ("urmapx_bam_" if bam else "urmapx_sam_") + ("pe_tags" if paired else "se_tags")
+        out = []
+        step = 2 if paired else 1
+        enc = lambda l: l.encode("latin-1")
+        for i in range(0, len(results), step):
+            refs = [windows[i + k] for k in range(step)] if windows is not None else [None] * step
+            to, keep = self._tag_opts(tags, rg_id, refs)
+            o, e = int(offs[i]), int(offs[i + 1])
+            args = [self.h, C.c_void_p(results[i:i + 1].ctypes.data)]
+            if paired:
+                e2 = int(offs[i + 2])
+                args += [C.c_void_p(results[i + 1:i + 2].ctypes.data), ops_ptr, enc(labels[i]), C.c_void_p(bases[o:e].ctypes.data),
+                         C.c_void_p(quals[o:e].ctypes.data), C.c_uint32(e - o), enc(labels[i + 1]), C.c_void_p(bases[e:e2].ctypes.data),
+                         C.c_void_p(quals[e:e2].ctypes.data), C.c_uint32(e2 - e)]
+            else:
+                args += [ops_ptr, enc(labels[i]), C.c_void_p(bases[o:e].ctypes.data), C.c_void_p(quals[o:e].ctypes.data), C.c_uint32(e - o)]
+            out.append(self._bam_call(name, *args, C.byref(to)))
+            del keep
+        return b"".join(out)
+
+    def header_rg(self, cmdline=None, read_group=None, sorted=False, bam=False) -> bytes:
+        """The SAM header text or (bam) the BAM header block with read_group (an @RG line, tabs real) in front of the @PG line
+        (urmapx_sam_header_rg / urmapx_bam_header_rg); sorted: the @HD line of -sort first."""
+        fn = getattr(lib(), "urmapx_bam_header_rg" if bam else "urmapx_sam_header_rg")
+        fn.restype = C.c_size_t
+        fn.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t]
+        cl = cmdline.encode() if isinstance(cmdline, str) else cmdline
+        rg = read_group.encode("latin-1") if isinstance(read_group, str) else read_group
+        n = fn(self.h, cl, rg, int(bool(sorted)), None, 0)
+        buf = C.create_string_buffer(max(1, n))
+        assert fn(self.h, cl, rg, int(bool(sorted)), buf, n) == n
+        return buf.raw[:n]
+
+    def fetch_spans(self, starts, lens):
+        """The store bytes under spans (start, length) (urmapx_index_fetch_spans): from the host arrays, else one gather on the device
+        and one copy.  -> list of bytes"""
+        st = np.ascontiguousarray(starts, dtype=np.uint64)
+        ln = np.ascontiguousarray(lens, dtype=np.uint32)
+        out = np.zeros(max(1, int(ln.sum())), dtype=np.uint8)
+        L = lib()
+        L.urmapx_index_fetch_spans.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        _check(L.urmapx_index_fetch_spans(self.h, st.ctypes.data, ln.ctypes.data, len(st), out.ctypes.data), "urmapx_index_fetch_spans")
+        cuts = np.concatenate([[0], np.cumsum(ln.astype(np.int64))])
+        return [out[int(cuts[i]):int(cuts[i + 1])].tobytes() for i in range(len(st))]
+
     def tab_pe(self, res, info, labels, offs, sam_on=True):
         """-tabbedout lines (State2::OutputTab2) for pairs interleaved as in map_pe; labels = per read."""
         L = lib()
@@ -556,12 +626,14 @@ def gunzip_file(gz_path, out_path, threads=0):
 
 def map_files(index: "Index", fastq1, fastq2=None, samout=None, tabout=None, first_gpu=0, gpus=1, streams=2, host_threads=0,
               batch=0, veryfast=False, minq=10, cmdline=None, allow_unsupported=False, sam_shards=0, discard_sam=False, bgzf=False, bam=False,
-              bam_sort=False):
+              bam_sort=False, tags=0, read_group=None):
     """urmap -map / -map2 file to file (cmd_map / cmd_map2) on an index that has its host arrays or is resident on
     first_gpu.  bgzf: samout is a BGZF file (-bgzf).  bam: samout is a BAM file (-bamout).  bam_sort (with bam):
-    its records in coordinate order, with the index samout + ".bai" beside it (-sort).  -> dict of State1::HitStats' counters and stage times."""
+    its records in coordinate order, with the index samout + ".bai" beside it (-sort).  tags: TAG_* bits (-tags), read_group: an @RG line
+    with real tabs (-rg): the optional fields of the records.  -> dict of State1::HitStats' counters and stage times."""
     o = MapOptions(first_gpu, gpus, streams, host_threads, batch, int(veryfast), minq, cmdline.encode() if cmdline else None,
-                   int(sam_shards), int(discard_sam), int(bgzf), int(bam), int(bam_sort))
+                   int(sam_shards), int(discard_sam), int(bgzf), int(bam), int(bam_sort), int(tags),
+                   (read_group.encode("latin-1") if isinstance(read_group, str) else read_group))
     rep = MapReport()
     err = C.create_string_buffer(1024)
     enc = lambda p: os.fsencode(p) if p else None
@@ -569,6 +641,43 @@ def map_files(index: "Index", fastq1, fastq2=None, samout=None, tabout=None, fir
     if rc != 0 and not (rc == E_UNSUPPORTED and allow_unsupported):
         raise UrmapxError(rc, "urmapx_map_files: " + err.value.decode("latin-1"))
     return {k: getattr(rep, k) for k, _ in MapReport._fields_}
+
+
+def calmd(ref: bytes, cigar, seq: bytes):
+    """NM and MD of one alignment (urmapx_calmd; host only): ref = the reference window, cigar = [(length, 'M' | 'I' | 'D')], seq = SEQ as
+    printed.  -> (NM, MD text); ValueError if the runs leave the window or the read."""
+    L = lib()
+    L.urmapx_calmd.restype = C.c_size_t
+    L.urmapx_calmd.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t]
+    runs = np.array([(int(n) << 4) | "MID".index(op) for n, op in cigar], dtype=np.uint32)
+    nm = C.c_uint32(0)
+    n = L.urmapx_calmd(ref, len(ref), runs.ctypes.data, len(runs), seq, len(seq), C.byref(nm), None, 0)
+    if n == C.c_size_t(-1).value:
+        raise ValueError("urmapx_calmd: the CIGAR leaves the reference window or the read")
+    buf = C.create_string_buffer(max(1, n))
+    assert L.urmapx_calmd(ref, len(ref), runs.ctypes.data, len(runs), seq, len(seq), C.byref(nm), buf, n) == n
+    return int(nm.value), buf.raw[:n].decode()
+
+
+def ref_span(result: np.ndarray, ops: np.ndarray, read_len):
+    """reference bases under the emitted CIGAR of one result (urmapx_ref_span); 0: unmapped"""
+    L = lib()
+    L.urmapx_ref_span.restype = C.c_uint32
+    L.urmapx_ref_span.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    ops = np.ascontiguousarray(ops, dtype=np.uint16)
+    r = np.ascontiguousarray(result)
+    return int(L.urmapx_ref_span(r.ctypes.data, ops.ctypes.data if len(ops) else None, int(read_len)))
+
+
+def read_group_id(line):
+    """-rg LINE as the command line takes it (urmapx_read_group_id): -> (the line with real tabs, its ID); ValueError with the refusal"""
+    L = lib()
+    L.urmapx_read_group_id.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
+    raw = line.encode("latin-1") if isinstance(line, str) else line
+    out, ident, err = C.create_string_buffer(len(raw) + 8), C.create_string_buffer(len(raw) + 8), C.create_string_buffer(1024)
+    if L.urmapx_read_group_id(raw, out, len(out), ident, len(ident), err, len(err)) != 0:
+        raise ValueError(err.value.decode("latin-1"))
+    return out.value.decode("latin-1"), ident.value.decode("latin-1")
 
 
 def _bam_sort(fn_name, head, records, n_ref, in_front, report, starts=None):
@@ -966,6 +1075,52 @@ class Mapper:
         L = lib()
         L.urmapx_text_set_bam.argtypes = [C.c_void_p, C.c_int]
         _check(L.urmapx_text_set_bam(self._text, int(bool(on))), "urmapx_text_set_bam")
+
+    def set_tags(self, tags=0, rg_id=None):
+        """The text stage of this mapper writes the optional fields NM MD AS (tags = TAG_* bits) and RG:Z:rg_id behind every record
+        (urmapx_text_set_tags; tags_gpu.hip), SAM text and BAM records alike.  0 and None: records end at QUAL again."""
+        if self._text is None:
+            t = C.c_void_p()
+            _check(lib().urmapx_text_create(self.h, C.byref(t)), "urmapx_text_create")
+            self._text = t
+        L = lib()
+        L.urmapx_text_set_tags.argtypes = [C.c_void_p, C.c_uint, C.c_char_p]
+        _check(L.urmapx_text_set_tags(self._text, int(tags), rg_id.encode("latin-1") if isinstance(rg_id, str) else rg_id), "urmapx_text_set_tags")
+
+    def tag_ms(self):
+        """device ms of the two tag passes of the last chunk (urmapx_text_tag_ms): (the counting pass, the writing pass)"""
+        ms = (C.c_float * 2)()
+        if self._text is None:
+            return 0.0, 0.0
+        _check(lib().urmapx_text_tag_ms(self._text, C.byref(ms)), "urmapx_text_tag_ms")
+        return float(ms[0]), float(ms[1])
+
+    def tags_batch(self, bases: np.ndarray, offs: np.ndarray, results: np.ndarray, ops: np.ndarray, tags=TAG_ALL):
+        """The tag passes alone on host arrays (urmapx_tags_batch; the device functions the text stage runs).
+        -> (NM per record, tagged flag per record, [MD text per record])"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        results = np.ascontiguousarray(results)
+        ops = np.ascontiguousarray(ops, dtype=np.uint16)
+        n = len(offs) - 1
+        nm = np.zeros(max(1, n), dtype=np.uint32)
+        tagged = np.zeros(max(1, n), dtype=np.uint8)
+        md_offs = np.zeros(n + 1, dtype=np.uint64)
+        cap = 2 * int(offs[-1]) + 64 * n + 1024
+        for r in results:  # a deletion's letters come on top of the read's columns
+            if r["dbpos"] != 0xFFFFFFFF and r["path_nops"]:
+                p = ops[int(r["path_off"]): int(r["path_off"]) + int(r["path_nops"])]
+                cap += 2 * int((p[(p & 3) == 2] >> 2).sum())
+        md = np.zeros(cap, dtype=np.uint8)
+        used = C.c_size_t(0)
+        L = lib()
+        L.urmapx_tags_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]
+        _check(L.urmapx_tags_batch(self.h, bases.ctypes.data, offs.ctypes.data, n, results.ctypes.data, ops.ctypes.data if len(ops) else None,
+                                   len(ops), int(tags), nm.ctypes.data, tagged.ctypes.data, md.ctypes.data, cap, md_offs.ctypes.data,
+                                   C.byref(used)), "urmapx_tags_batch")
+        texts = [md[int(md_offs[i]): int(md_offs[i + 1])].tobytes().decode() for i in range(n)]
+        return nm[:n].copy(), tagged[:n].copy(), texts
 
     def map_text_se(self, fastq: bytes, minq=10, sam_cap=None):
         """A chunk of FASTQ text (cut after a record's last newline) -> (the SAM text of its records | None, report dict).

@@ -34,17 +34,6 @@ __device__ __forceinline__ uint32_t reg2bin(uint32_t beg, uint32_t end) {
 	return 0u;
 }
 
-// 4-bit code of a SEQ letter: "=ACMGRSVTWYHKDBN", either case; every other byte is N (htslib's seq_nt16_table)
-__device__ __forceinline__ uint32_t nibble_of(uint32_t c) {
-	if (c - (uint32_t)'a' < 26u) c -= 32u;
-	const char t[] = "=ACMGRSVTWYHKDBN";
-	uint32_t v = 15u;
-#pragma unroll
-	for (uint32_t k = 0; k < 16u; ++k)
-		if (c == (uint32_t)t[k]) v = k;
-	return v;
-}
-
 // the flags SetSAM_Unmapped keeps of the ones it is given (setsam.cpp:14-27)
 __device__ __forceinline__ uint32_t unmapped_flags(uint32_t given) {
 	uint32_t flags = 0x04u;

@@ -74,4 +74,15 @@ hipStream_t ctx_stream(urmapx_ctx *);
 int ctx_device(const urmapx_ctx *);
 const urmapx_index *ctx_index(const urmapx_ctx *);
 
+// what tags_gpu.hip needs of an index (defined in urmapx.hip): the sequence store and the sequences' offsets in it as they are resident on
+// `device` (null: not resident there), the store on the host (null: the index keeps none)
+struct IndexStore {
+	const uint8_t *d_seq;
+	const uint32_t *d_seq_offsets;
+	const uint8_t *h_seq;
+	uint32_t seq_data_size, seq_count;
+	int device;
+};
+IndexStore index_store(const urmapx_index *);
+
 }  // namespace urx

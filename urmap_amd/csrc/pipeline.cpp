@@ -958,6 +958,11 @@ struct Run {
 	const bool bam = opt.bam != 0 && have_sam;  // -bamout: BAM records where the SAM text was, always inside BGZF members
 	const bool sort = opt.bam_sort != 0 && bam;  // -sort: the lanes' raw records are kept in host memory; finish() sorts them and writes samout and its index
 	const bool bgzf = (opt.bgzf != 0 || bam) && have_sam && !sort;
+	// -tags / -rg: the optional fields of the records (map_files_entry has checked both); rg_id: the ID: value of the @RG line
+	const unsigned tags = have_sam ? opt.tags & URMAPX_TAG_ALL : 0u;
+	const char *const rg_line = have_sam ? opt.read_group : nullptr;
+	std::string rg_id;
+	bool tagged() const { return tags != 0 || rg_line != nullptr; }
 	const bool pool_lanes = LanePool::enabled(), lane_veryfast = paired && opt.veryfast, lane_pair_info = paired && tabout != nullptr;
 	urmapx_params P;
 	// one replica of the index per device (uploaded concurrently), K mapping contexts on each
@@ -1004,6 +1009,11 @@ struct Run {
 		if (gpus > 64 || streams > 8) return failed(URMAPX_E_ARG, msg, "gpus must be 1..64, streams 1..8");
 		int rc = urmapx_params_for_method((opt.veryfast && !paired) ? 7 : 6, &P);  // -map2 always uses method 6 (map2.cpp:15-16)
 		if (rc) return rc;
+		if (rg_line) {
+			char id[1024], why[256];
+			if (urmapx_read_group_id(rg_line, nullptr, 0, id, sizeof id, why, sizeof why)) return failed(URMAPX_E_ARG, msg, why);
+			rg_id = id;
+		}
 		replicas.assign((size_t)gpus, nullptr);
 		ctxs.assign((size_t)n_lanes, nullptr);
 		texts.assign((size_t)n_lanes, nullptr);
@@ -1047,8 +1057,8 @@ struct Run {
 			if (sort) sink.keep_in_memory();  // (the header block is made in write_sorted; the records start at offset 0 of the kept bytes)
 			else if (range.header || bam) {  // (every shard of a BAM run is a BAM file: each has the header block)
 				std::string hdr;
-				if (bam) append_bam_header(hdr, I, opt.cmdline);
-				else append_sam_header_text(hdr, I, opt.cmdline);
+				if (bam) append_bam_header(hdr, I, opt.cmdline, false, rg_line);
+				else append_sam_header_text(hdr, I, opt.cmdline, rg_line);
 				rep.sam_text_bytes += hdr.size();
 				if (bgzf && !bgzf_members(hdr)) return failed(URMAPX_E_NOMEM, msg, "out of memory");  // (members of its own: the chunks' come from the device)
 				if (!sink.write_at(hdr.data(), hdr.size(), 0, 1)) return failed(URMAPX_E_IO, msg, std::string("Cannot write ") + samout);
@@ -1094,7 +1104,7 @@ struct Run {
 		const uint64_t n_bytes = rep.sam_file_bytes;
 		const uint32_t n_ref = urmapx_index_seq_count(I);
 		std::string hdr;
-		append_bam_header(hdr, I, opt.cmdline, true);
+		append_bam_header(hdr, I, opt.cmdline, true, rg_line);
 		rep.sam_text_bytes += hdr.size();
 		if (!bgzf_members(hdr)) { fail.raise(URMAPX_E_NOMEM, "out of memory"); return; }
 		urmapx_bam_sort_result S;
@@ -1522,6 +1532,7 @@ struct TextPhase {
 			if (brc == URMAPX_E_NOMEM) { nomem.store(true); T = nullptr; }
 			else if (brc) R.fail.raise(brc, std::string("urmapx_text_set_bgzf: ") + urmapx_strerror(brc));
 			else if ((brc2 = urmapx_text_set_bam(T, R.bam ? 1 : 0))) R.fail.raise(brc2, std::string("urmapx_text_set_bam: ") + urmapx_strerror(brc2));
+			else if ((brc2 = urmapx_text_set_tags(T, R.tags, R.rg_line ? R.rg_id.c_str() : nullptr))) R.fail.raise(brc2, std::string("urmapx_text_set_tags: ") + urmapx_strerror(brc2));
 		}
 		// The copy back is a stage of its own (urmapx_text_set_deferred): chunk i's text crosses PCIe while the lane's stream takes
 		// chunk i + 1 in and maps it; the lane waits for chunk i's copy when chunk i + 1 has been enqueued to its end.
@@ -1749,6 +1760,32 @@ struct HostPhase {
 		const bool paired = R.paired;
 		const uint32_t n = j.reads.size(), units = paired ? n / 2 : n;
 		const int T = R.host_threads;
+		// -tags NM / MD: the store bytes under every mapped record of the batch.  Where the index keeps its host arrays the formatters read
+		// them there; the command line's index lives in HBM only, so the batch's windows come back in one gather and one copy
+		// (urmapx_index_fetch_spans).  ref_at[i]: where record i's window starts in `windows`; ~0: none
+		std::vector<uint8_t> windows;
+		std::vector<uint64_t> ref_at;
+		const bool tagged = R.tagged() && R.have_sam;
+		if (tagged && (R.tags & (URMAPX_TAG_NM | URMAPX_TAG_MD)) && !index_host_seq(R.I)) {
+			std::vector<uint64_t> starts;
+			std::vector<uint32_t> lens;
+			ref_at.assign(n, ~0ull);
+			uint64_t total = 0;
+			for (uint32_t i = 0; i < n; ++i) {
+				const urmapx_result &r = j.results[i];
+				if (r.dbpos == 0xFFFFFFFFu) continue;
+				const uint32_t span = ref_span(r, j.ops.data(), (unsigned)(j.reads.offs[i + 1] - j.reads.offs[i]));
+				starts.push_back((uint64_t)urmapx_index_seq_offset(R.I, r.seq_index) + r.coord);
+				lens.push_back(span);
+				ref_at[i] = total;
+				total += span;
+			}
+			windows.resize((size_t)total + 1);
+			const int frc = urmapx_index_fetch_spans(R.I, starts.data(), lens.data(), (uint32_t)starts.size(), windows.data());
+			if (frc) R.fail.raise(frc, std::string("urmapx_index_fetch_spans: ") + urmapx_strerror(frc));
+		}
+		auto window_of = [&](uint32_t i) -> const uint8_t * { return !ref_at.empty() && ref_at[i] != ~0ull ? windows.data() + ref_at[i] : nullptr; };
+		const char *const rg_id = R.rg_line ? R.rg_id.c_str() : nullptr;
 #pragma omp parallel for schedule(static, 1) num_threads(T)
 		for (int t = 0; t < T; ++t) {
 			std::string &out = outs[(size_t)t];
@@ -1764,19 +1801,36 @@ struct HostPhase {
 					const uint64_t off2 = j.reads.offs[i + 1];
 					const unsigned L2 = (unsigned)(j.reads.offs[i + 2] - off2);
 					const size_t names = strlen(j.reads.label(i)) + strlen(j.reads.label(i + 1));
-					pbuf.resize(names + (R.bam ? 2 * (size_t)(L + L2) + 4 * ((size_t)r.path_nops + j.results[i + 1].path_nops) : 3 * (size_t)(L + L2)) + 2048);
-					const size_t k = (R.bam ? urmapx_bam_pe : urmapx_sam_pe)(R.I, &j.results[i], &j.results[i + 1], j.ops.data(), j.reads.label(i),
+					// (with fields: an MD text is at most two bytes a reference base, and the path says how many more of those than read bases)
+					pbuf.resize(names + (R.bam ? 2 * (size_t)(L + L2) + 4 * ((size_t)r.path_nops + j.results[i + 1].path_nops) : 3 * (size_t)(L + L2)) + 2048 +
+					            (tagged ? 2 * ((size_t)L + L2) + 2 * R.rg_id.size() + 1024 : 0));
+					urmapx_tag_options TO{R.tags, rg_id, {window_of(i), window_of(i + 1)}};
+					size_t k = (R.bam ? urmapx_bam_pe_tags : urmapx_sam_pe_tags)(R.I, &j.results[i], &j.results[i + 1], j.ops.data(), j.reads.label(i),
 					                                                         j.reads.bases.data() + off, j.reads.quals.data() + off, L, j.reads.label(i + 1),
-					                                                         j.reads.bases.data() + off2, j.reads.quals.data() + off2, L2, pbuf.data(), pbuf.size());
+					                                                         j.reads.bases.data() + off2, j.reads.quals.data() + off2, L2, tagged ? &TO : nullptr, pbuf.data(), pbuf.size());
+					if (tagged && k == 0) {  // (deletions longer than the allowance, or no store bytes)
+						pbuf.resize(pbuf.size() + 2 * ((size_t)ref_span(j.results[i], j.ops.data(), L) + ref_span(j.results[i + 1], j.ops.data(), L2)));
+						k = (R.bam ? urmapx_bam_pe_tags : urmapx_sam_pe_tags)(R.I, &j.results[i], &j.results[i + 1], j.ops.data(), j.reads.label(i),
+						                                                      j.reads.bases.data() + off, j.reads.quals.data() + off, L, j.reads.label(i + 1),
+						                                                      j.reads.bases.data() + off2, j.reads.quals.data() + off2, L2, &TO, pbuf.data(), pbuf.size());
+						if (k == 0) R.fail.raise(URMAPX_E_ARG, "optional fields: the index has no sequence store to compare with");
+					}
 					if (R.bam && k == URMAPX_BAM_LONG_NAME) R.fail.raise(URMAPX_E_FORMAT, bam_long_name(strlen(j.reads.label(i)) >= strlen(j.reads.label(i + 1)) ? j.reads.label(i) : j.reads.label(i + 1)));
 					else out.append(pbuf.data(), k);
 				} else if (!paired && R.bam) {
+					const size_t at = out.size();
 					if (!append_bam_record(out, R.I, r, j.ops.data(), 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, j.reads.label(i),
 					                       j.reads.bases.data() + off, j.reads.quals.data() + off, L))
 						R.fail.raise(URMAPX_E_FORMAT, bam_long_name(j.reads.label(i)));
-				} else if (!paired && R.have_sam)
+					else if (tagged && !append_record_tags(out, at, true, R.I, r, j.ops.data(), j.reads.bases.data() + off, L, R.tags, rg_id, window_of(i)))
+						R.fail.raise(URMAPX_E_ARG, "optional fields: the index has no sequence store to compare with");
+				} else if (!paired && R.have_sam) {
+					const size_t at = out.size();
 					append_sam_record(out, R.I, r, j.ops.data(), 0, "*", 0xFFFFFFFFu, 0, j.reads.label(i),
 					                  j.reads.bases.data() + off, j.reads.quals.data() + off, L);
+					if (tagged && !append_record_tags(out, at, false, R.I, r, j.ops.data(), j.reads.bases.data() + off, L, R.tags, rg_id, window_of(i)))
+						R.fail.raise(URMAPX_E_ARG, "optional fields: the index has no sequence store to compare with");
+				}
 				// HitStats counters (output1.cpp:20-30)
 				if (r.status) ++c.unsupported;
 				if (r.dbpos == 0xFFFFFFFFu) ++c.nohit;
@@ -1890,6 +1944,12 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
 	if (err && errcap) err[0] = 0;
 	if (!I || !opt || !fastq1) return URMAPX_E_ARG;
 	if (opt->bam && opt->bgzf) { say(err, errcap, "bam and bgzf together: a BAM file is always BGZF"); return URMAPX_E_ARG; }
+	if (opt->tags & ~URMAPX_TAG_ALL) { say(err, errcap, "tags: bits outside URMAPX_TAG_NM | URMAPX_TAG_MD | URMAPX_TAG_AS"); return URMAPX_E_ARG; }
+	if (opt->read_group) {
+		char why[256];
+		if (urmapx_read_group_id(opt->read_group, nullptr, 0, nullptr, 0, why, sizeof why)) { say(err, errcap, why); return URMAPX_E_ARG; }
+		if (strstr(opt->read_group, "\\t")) { say(err, errcap, "read_group: the line takes real tabs here (the command line turns \\t into them)"); return URMAPX_E_ARG; }
+	}
 	if (opt->bam_sort) {
 		const char *why = !opt->bam || !samout ? "bam_sort needs bam: it sorts the records of a BAM file" :
 		                  opt->sam_shards > 1 ? "bam_sort with sam_shards: one sorted file has one index" :
@@ -1957,7 +2017,7 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
 	auto empty_shard = [&](int s) {
 		if (FILE *f = fopen(shard_name(samout, s).c_str(), "wb")) {
 			std::string eof;
-			if (opt->bam) append_bam_header(eof, I, opt->cmdline);
+			if (opt->bam) append_bam_header(eof, I, opt->cmdline, false, opt->read_group);
 			if ((opt->bgzf || opt->bam) && bgzf_members(eof, 1)) (void)fwrite(eof.data(), 1, eof.size(), f);
 			fclose(f);
 		}

@@ -536,7 +536,7 @@ void append_sam_header(std::string &out, const urmapx_index *I, int argc, char *
 	append_sam_header_text(out, I, cl.c_str());
 }
 
-void append_sam_header_text(std::string &out, const urmapx_index *I, const char *cmdline) {
+void append_sam_header_text(std::string &out, const urmapx_index *I, const char *cmdline, const char *read_group) {
 	const uint32_t n = urmapx_index_seq_count(I);
 	for (uint32_t i = 0; i < n; ++i) {
 		out += "@SQ\tSN:";
@@ -545,6 +545,7 @@ void append_sam_header_text(std::string &out, const urmapx_index *I, const char 
 		out += std::to_string(urmapx_index_seq_length(I, i));
 		out.push_back('\n');
 	}
+	if (read_group) { out += read_group; out.push_back('\n'); }
 	out += "@PG\tID:urmap\tPN:urmap\tVN:1.0.mi355x\tCL:";
 	if (cmdline) out += cmdline;
 	out.push_back('\n');
@@ -644,10 +645,114 @@ bool append_bam_record(std::string &out, const urmapx_index *I, const urmapx_res
 	return true;
 }
 
-void append_bam_header(std::string &out, const urmapx_index *I, const char *cmdline, bool sorted) {
+// ---------------- optional fields: NM MD AS RG (include/urmapx.h, "Optional fields") ----------------
+bool nm_md(const uint8_t *ref, size_t ref_len, const uint32_t *cigar, size_t n_cigar, const uint8_t *seq, size_t seq_len, uint32_t &nm, std::string &md) {
+	size_t q = 0, t = 0;
+	uint64_t run = 0;  // matches since the last thing printed
+	nm = 0;
+	md.clear();
+	char num[24];
+	auto put_run = [&]() { md.append(num, (size_t)(put_uint(num, run) - num)); run = 0; };
+	for (size_t k = 0; k < n_cigar; ++k) {
+		const size_t len = cigar[k] >> 4;
+		const unsigned op = cigar[k] & 15u;
+		if (op == 0) {
+			if (len > seq_len - q || len > ref_len - t) return false;
+			for (size_t c = 0; c < len; ++c, ++q, ++t) {
+				const unsigned a = g_nib[seq[q]], b = g_nib[ref[t]];
+				if (a == b && a != 15u) { ++run; continue; }
+				put_run();
+				md.push_back((char)toupper(ref[t]));
+				++nm;
+			}
+		} else if (op == 1) {
+			if (len > seq_len - q) return false;
+			q += len; nm += (uint32_t)len;
+		} else if (op == 2) {
+			if (len > ref_len - t) return false;
+			put_run();
+			md.push_back('^');
+			for (size_t c = 0; c < len; ++c, ++t) md.push_back((char)toupper(ref[t]));
+			nm += (uint32_t)len;
+		} else return false;
+	}
+	put_run();
+	return true;
+}
+
+uint32_t ref_span(const urmapx_result &r, const urmapx_path_op *ops, unsigned QL) {
+	if (r.dbpos == 0xFFFFFFFFu) return 0;
+	uint64_t span = 0;
+	for_each_cigar_run(r.path_nops ? ops + r.path_off : nullptr, r.path_nops, QL, [&](unsigned len, char op) { if (op != 'I') span += len; });
+	return (uint32_t)span;
+}
+
+// one integer aux field in the smallest type that holds it, as htslib picks: C S I for v >= 0, c s i below
+static void append_aux_int(std::string &out, char a, char b, int64_t v) {
+	char w[8] = {a, b};
+	size_t n;
+	if (v >= 0) {
+		if (v <= 0xFF) { w[2] = 'C'; n = 1; }
+		else if (v <= 0xFFFF) { w[2] = 'S'; n = 2; }
+		else { w[2] = 'I'; n = 4; }
+	} else {
+		if (v >= -128) { w[2] = 'c'; n = 1; }
+		else if (v >= -32768) { w[2] = 's'; n = 2; }
+		else { w[2] = 'i'; n = 4; }
+	}
+	for (size_t k = 0; k < n; ++k) w[3 + k] = (char)((uint64_t)v >> (8 * k));
+	out.append(w, 3 + n);
+}
+
+bool append_record_tags(std::string &out, size_t rec_at, bool bam, const urmapx_index *I, const urmapx_result &r, const urmapx_path_op *ops,
+                        const uint8_t *seq, unsigned QL, unsigned tags, const char *rg_id, const uint8_t *ref) {
+	const bool mapped = r.dbpos != 0xFFFFFFFFu;
+	uint32_t nm = 0;
+	std::string md;
+	if (mapped && (tags & (URMAPX_TAG_NM | URMAPX_TAG_MD))) {
+		std::vector<uint32_t> cigar;
+		uint64_t span = 0;
+		for_each_cigar_run(r.path_nops ? ops + r.path_off : nullptr, r.path_nops, QL, [&](unsigned len, char op) {
+			cigar.push_back((uint32_t)len << 4 | (op == 'M' ? 0u : op == 'I' ? 1u : 2u));
+			if (op != 'I') span += len;
+		});
+		if (!ref) {
+			const uint8_t *store = index_host_seq(I);
+			if (!store || r.seq_index >= urmapx_index_seq_count(I)) return false;
+			const uint64_t at = (uint64_t)urmapx_index_seq_offset(I, r.seq_index) + r.coord;
+			if (at + span > urmapx_index_seqdata_size(I)) return false;
+			ref = store + at;
+		}
+		std::vector<uint8_t> printed;
+		const uint8_t *sq = seq;
+		if (!r.plus) {  // SEQ as the record prints it
+			printed.resize(QL);
+			for (unsigned i = 0; i < QL; ++i) printed[i] = g_comp[seq[QL - 1 - i]];
+			sq = printed.data();
+		}
+		if (!nm_md(ref, (size_t)span, cigar.data(), cigar.size(), sq, QL, nm, md)) return false;
+	}
+	if (!bam) {
+		out.pop_back();  // the record's '\n'
+		if (mapped && (tags & URMAPX_TAG_NM)) { out += "\tNM:i:"; append_uint(out, nm); }
+		if (mapped && (tags & URMAPX_TAG_MD)) { out += "\tMD:Z:"; out += md; }
+		if (mapped && (tags & URMAPX_TAG_AS)) { out += "\tAS:i:"; append_int(out, r.score); }
+		if (rg_id) { out += "\tRG:Z:"; out += rg_id; }
+		out.push_back('\n');
+		return true;
+	}
+	if (mapped && (tags & URMAPX_TAG_NM)) append_aux_int(out, 'N', 'M', nm);
+	if (mapped && (tags & URMAPX_TAG_MD)) { out += "MDZ"; out.append(md.c_str(), md.size() + 1); }
+	if (mapped && (tags & URMAPX_TAG_AS)) append_aux_int(out, 'A', 'S', r.score);
+	if (rg_id) { out += "RGZ"; out.append(rg_id, strlen(rg_id) + 1); }
+	put_le32(&out[rec_at], (uint32_t)(out.size() - rec_at - 4));
+	return true;
+}
+
+void append_bam_header(std::string &out, const urmapx_index *I, const char *cmdline, bool sorted, const char *read_group) {
 	std::string text;
 	if (sorted) text = "@HD\tVN:1.6\tSO:coordinate\n";
-	append_sam_header_text(text, I, cmdline);
+	append_sam_header_text(text, I, cmdline, read_group);
 	char w[4];
 	out.append("BAM\1", 4);
 	put_le32(w, (uint32_t)text.size()); out.append(w, 4);
@@ -665,14 +770,28 @@ void append_bam_header(std::string &out, const urmapx_index *I, const char *cmdl
 
 }  // namespace urx
 
-extern "C" size_t urmapx_sam_se(const urmapx_index *I, const urmapx_result *r, const urmapx_path_op *path_ops,
-                                const char *label, const uint8_t *seq, const uint8_t *qual, uint32_t read_len,
-                                char *buf, size_t cap) {
+// tags of the record just appended at out[at ..]; T null: none.  false: the fields need store bytes that are not there
+static bool tags_behind(std::string &out, size_t at, bool bam, const urmapx_index *I, const urmapx_result *r, const urmapx_path_op *path_ops,
+                        const uint8_t *seq, uint32_t len, const urmapx_tag_options *T, int mate) {
+	if (!T || (!(T->tags & URMAPX_TAG_ALL) && !T->rg_id)) return true;
+	return urx::append_record_tags(out, at, bam, I, *r, path_ops, seq, len, T->tags & URMAPX_TAG_ALL, T->rg_id, T->ref[mate]);
+}
+
+extern "C" size_t urmapx_sam_se_tags(const urmapx_index *I, const urmapx_result *r, const urmapx_path_op *path_ops, const char *label,
+                                     const uint8_t *seq, const uint8_t *qual, uint32_t read_len, const urmapx_tag_options *tags, char *buf,
+                                     size_t cap) {
 	std::string out;
 	urx::append_sam_record(out, I, *r, path_ops, 0, "*", 0xFFFFFFFFu, 0, label, seq, qual, read_len);
+	if (!tags_behind(out, 0, false, I, r, path_ops, seq, read_len, tags, 0)) return 0;
 	if (out.size() > cap) return 0;
 	memcpy(buf, out.data(), out.size());
 	return out.size();
+}
+
+extern "C" size_t urmapx_sam_se(const urmapx_index *I, const urmapx_result *r, const urmapx_path_op *path_ops,
+                                const char *label, const uint8_t *seq, const uint8_t *qual, uint32_t read_len,
+                                char *buf, size_t cap) {
+	return urmapx_sam_se_tags(I, r, path_ops, label, seq, qual, read_len, nullptr, buf, cap);
 }
 
 // ---------------- -tabbedout (State2::OutputTab2, outputtab2.cpp:85-120) ----------------
@@ -864,34 +983,82 @@ static PairFields pair_fields(const urmapx_result *r1, const urmapx_result *r2, 
 	return PairFields{m1, m2, f1, f2, tlen1, tlen2};
 }
 
-extern "C" size_t urmapx_sam_pe(const urmapx_index *I, const urmapx_result *r1, const urmapx_result *r2,
-                                const urmapx_path_op *path_ops, const char *label1, const uint8_t *seq1,
-                                const uint8_t *qual1, uint32_t len1, const char *label2, const uint8_t *seq2,
-                                const uint8_t *qual2, uint32_t len2, char *buf, size_t cap) {
+extern "C" size_t urmapx_sam_pe_tags(const urmapx_index *I, const urmapx_result *r1, const urmapx_result *r2, const urmapx_path_op *path_ops,
+                                     const char *label1, const uint8_t *seq1, const uint8_t *qual1, uint32_t len1, const char *label2,
+                                     const uint8_t *seq2, const uint8_t *qual2, uint32_t len2, const urmapx_tag_options *tags, char *buf,
+                                     size_t cap) {
 	const PairFields P = pair_fields(r1, r2, len1, len2);
 	const char *l1 = P.m1 ? urmapx_index_label(I, r1->seq_index) : "";
 	const char *l2 = P.m2 ? urmapx_index_label(I, r2->seq_index) : "";
 	std::string out;
 	urx::append_sam_record(out, I, *r1, path_ops, P.f1, l2, P.m2 ? r2->coord : 0xFFFFFFFFu, P.tlen1, label1, seq1, qual1, len1);
+	if (!tags_behind(out, 0, false, I, r1, path_ops, seq1, len1, tags, 0)) return 0;
+	const size_t at2 = out.size();
 	urx::append_sam_record(out, I, *r2, path_ops, P.f2, l1, P.m1 ? r1->coord : 0xFFFFFFFFu, P.tlen2, label2, seq2, qual2, len2);
+	if (!tags_behind(out, at2, false, I, r2, path_ops, seq2, len2, tags, 1)) return 0;
 	if (out.size() > cap) return 0;
 	memcpy(buf, out.data(), out.size());
 	return out.size();
 }
 
+extern "C" size_t urmapx_sam_pe(const urmapx_index *I, const urmapx_result *r1, const urmapx_result *r2,
+                                const urmapx_path_op *path_ops, const char *label1, const uint8_t *seq1,
+                                const uint8_t *qual1, uint32_t len1, const char *label2, const uint8_t *seq2,
+                                const uint8_t *qual2, uint32_t len2, char *buf, size_t cap) {
+	return urmapx_sam_pe_tags(I, r1, r2, path_ops, label1, seq1, qual1, len1, label2, seq2, qual2, len2, nullptr, buf, cap);
+}
+
 // ---------------- BAM: the C entry points (argument lists of urmapx_sam_se / _pe) ----------------
 extern "C" size_t urmapx_bam_header(const urmapx_index *I, const char *cmdline, void *buf, size_t cap) {
+	return urmapx_bam_header_rg(I, cmdline, nullptr, 0, buf, cap);
+}
+
+extern "C" size_t urmapx_bam_header_rg(const urmapx_index *I, const char *cmdline, const char *read_group, int sorted, void *buf, size_t cap) {
 	if (!I) return 0;
 	std::string out;
-	urx::append_bam_header(out, I, cmdline);
+	urx::append_bam_header(out, I, cmdline, sorted != 0, read_group);
 	if (buf && out.size() <= cap) memcpy(buf, out.data(), out.size());
+	return out.size();
+}
+
+extern "C" size_t urmapx_sam_header_rg(const urmapx_index *I, const char *cmdline, const char *read_group, int sorted, char *buf, size_t cap) {
+	if (!I) return 0;
+	std::string out;
+	if (sorted) out = "@HD\tVN:1.6\tSO:coordinate\n";
+	urx::append_sam_header_text(out, I, cmdline, read_group);
+	if (buf && out.size() <= cap) memcpy(buf, out.data(), out.size());
+	return out.size();
+}
+
+extern "C" size_t urmapx_bam_se_tags(const urmapx_index *I, const urmapx_result *r, const urmapx_path_op *path_ops, const char *label,
+                                     const uint8_t *seq, const uint8_t *qual, uint32_t read_len, const urmapx_tag_options *tags, char *buf,
+                                     size_t cap) {
+	std::string out;
+	if (!urx::append_bam_record(out, I, *r, path_ops, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, label, seq, qual, read_len)) return URMAPX_BAM_LONG_NAME;
+	if (!tags_behind(out, 0, true, I, r, path_ops, seq, read_len, tags, 0)) return 0;
+	if (out.size() > cap) return 0;
+	memcpy(buf, out.data(), out.size());
 	return out.size();
 }
 
 extern "C" size_t urmapx_bam_se(const urmapx_index *I, const urmapx_result *r, const urmapx_path_op *path_ops, const char *label,
                                 const uint8_t *seq, const uint8_t *qual, uint32_t read_len, char *buf, size_t cap) {
+	return urmapx_bam_se_tags(I, r, path_ops, label, seq, qual, read_len, nullptr, buf, cap);
+}
+
+extern "C" size_t urmapx_bam_pe_tags(const urmapx_index *I, const urmapx_result *r1, const urmapx_result *r2, const urmapx_path_op *path_ops,
+                                     const char *label1, const uint8_t *seq1, const uint8_t *qual1, uint32_t len1, const char *label2,
+                                     const uint8_t *seq2, const uint8_t *qual2, uint32_t len2, const urmapx_tag_options *tags, char *buf,
+                                     size_t cap) {
+	PairFields P = pair_fields(r1, r2, len1, len2);
 	std::string out;
-	if (!urx::append_bam_record(out, I, *r, path_ops, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, label, seq, qual, read_len)) return URMAPX_BAM_LONG_NAME;
+	if (!urx::append_bam_record(out, I, *r1, path_ops, P.f1, P.m2 ? r2->seq_index : 0xFFFFFFFFu, P.m2 ? r2->coord : 0xFFFFFFFFu, P.tlen1, label1, seq1, qual1, len1))
+		return URMAPX_BAM_LONG_NAME;
+	if (!tags_behind(out, 0, true, I, r1, path_ops, seq1, len1, tags, 0)) return 0;
+	const size_t at2 = out.size();
+	if (!urx::append_bam_record(out, I, *r2, path_ops, P.f2, P.m1 ? r1->seq_index : 0xFFFFFFFFu, P.m1 ? r1->coord : 0xFFFFFFFFu, P.tlen2, label2, seq2, qual2, len2))
+		return URMAPX_BAM_LONG_NAME;
+	if (!tags_behind(out, at2, true, I, r2, path_ops, seq2, len2, tags, 1)) return 0;
 	if (out.size() > cap) return 0;
 	memcpy(buf, out.data(), out.size());
 	return out.size();
@@ -900,12 +1067,50 @@ extern "C" size_t urmapx_bam_se(const urmapx_index *I, const urmapx_result *r, c
 extern "C" size_t urmapx_bam_pe(const urmapx_index *I, const urmapx_result *r1, const urmapx_result *r2, const urmapx_path_op *path_ops,
                                 const char *label1, const uint8_t *seq1, const uint8_t *qual1, uint32_t len1, const char *label2,
                                 const uint8_t *seq2, const uint8_t *qual2, uint32_t len2, char *buf, size_t cap) {
-	PairFields P = pair_fields(r1, r2, len1, len2);
-	std::string out;
-	if (!urx::append_bam_record(out, I, *r1, path_ops, P.f1, P.m2 ? r2->seq_index : 0xFFFFFFFFu, P.m2 ? r2->coord : 0xFFFFFFFFu, P.tlen1, label1, seq1, qual1, len1) ||
-	    !urx::append_bam_record(out, I, *r2, path_ops, P.f2, P.m1 ? r1->seq_index : 0xFFFFFFFFu, P.m1 ? r1->coord : 0xFFFFFFFFu, P.tlen2, label2, seq2, qual2, len2))
-		return URMAPX_BAM_LONG_NAME;
-	if (out.size() > cap) return 0;
-	memcpy(buf, out.data(), out.size());
-	return out.size();
+	return urmapx_bam_pe_tags(I, r1, r2, path_ops, label1, seq1, qual1, len1, label2, seq2, qual2, len2, nullptr, buf, cap);
+}
+
+// ---------------- optional fields: the C entry points ----------------
+extern "C" size_t urmapx_calmd(const uint8_t *ref, size_t ref_len, const uint32_t *cigar, uint32_t n_cigar, const uint8_t *seq, size_t seq_len,
+                               uint32_t *nm, char *md, size_t md_cap) {
+	uint32_t v = 0;
+	std::string text;
+	if ((ref_len && !ref) || (n_cigar && !cigar) || (seq_len && !seq)) return (size_t)-1;
+	if (!urx::nm_md(ref, ref_len, cigar, n_cigar, seq, seq_len, v, text)) return (size_t)-1;
+	if (nm) *nm = v;
+	if (md && text.size() <= md_cap) memcpy(md, text.data(), text.size());
+	return text.size();
+}
+
+extern "C" uint32_t urmapx_ref_span(const urmapx_result *r, const urmapx_path_op *path_ops, uint32_t read_len) {
+	return r ? urx::ref_span(*r, path_ops, read_len) : 0;
+}
+
+extern "C" int urmapx_read_group_id(const char *line, char *line_out, size_t line_cap, char *id_out, size_t id_cap, char *err, size_t errcap) {
+	auto refuse = [&](const std::string &why) {
+		if (err && errcap) snprintf(err, errcap, "%s", why.c_str());
+		return URMAPX_E_ARG;
+	};
+	if (!line) return refuse("-rg: no read-group line");
+	std::string s;
+	for (const char *c = line; *c; ++c) {
+		if (c[0] == '\\' && c[1] == 't') { s.push_back('\t'); ++c; }
+		else s.push_back(*c);
+	}
+	if (s.find('\n') != std::string::npos || s.find('\r') != std::string::npos) return refuse("-rg: the read-group line contains a newline");
+	if (s.compare(0, 4, "@RG\t") != 0) return refuse("-rg: the read-group line must start with @RG and a tab: '" + s + "'");
+	std::string id;
+	bool have = false;
+	for (size_t at = 4; at <= s.size() && !have;) {
+		size_t e = s.find('\t', at);
+		if (e == std::string::npos) e = s.size();
+		if (s.compare(at, 3, "ID:") == 0) { id = s.substr(at + 3, e - at - 3); have = true; }
+		at = e + 1;
+	}
+	if (!have) return refuse("-rg: the read-group line has no ID: field: '" + s + "'");
+	if (id.empty()) return refuse("-rg: the read group's ID is empty: '" + s + "'");
+	if ((line_out && s.size() + 1 > line_cap) || (id_out && id.size() + 1 > id_cap)) return refuse("-rg: the read-group line is too long");
+	if (line_out) memcpy(line_out, s.c_str(), s.size() + 1);
+	if (id_out) memcpy(id_out, id.c_str(), id.size() + 1);
+	return URMAPX_OK;
 }

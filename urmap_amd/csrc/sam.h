@@ -131,13 +131,27 @@ bool append_bam_record(std::string &out, const urmapx_index *I, const urmapx_res
                        unsigned QL);
 // magic, l_text, append_sam_header_text's text, n_ref, the reference list
 // sorted: the text begins with "@HD\tVN:1.6\tSO:coordinate"
-void append_bam_header(std::string &out, const urmapx_index *I, const char *cmdline, bool sorted = false);
+// read_group: a complete @RG line (tabs real, no '\n') that goes directly in front of the @PG line, or null
+void append_bam_header(std::string &out, const urmapx_index *I, const char *cmdline, bool sorted = false, const char *read_group = nullptr);
+
+// Optional fields (include/urmapx.h, "Optional fields").  nm_md: NM and the MD text of one alignment from the reference window under it,
+// the emitted CIGAR runs (len << 4 | op as BAM packs them) and SEQ as printed; false if the runs leave either.  Pure: no device, no index.
+bool nm_md(const uint8_t *ref, size_t ref_len, const uint32_t *cigar, size_t n_cigar, const uint8_t *seq, size_t seq_len, uint32_t &nm, std::string &md);
+// reference bases under the emitted CIGAR of a result (0: unmapped)
+uint32_t ref_span(const urmapx_result &r, const urmapx_path_op *ops, unsigned QL);
+// The fields of the record that append_sam_record / append_bam_record has just appended at out[rec_at ..]: NM MD AS (mapped records) and
+// RG, as text in front of the record's '\n' or as aux bytes behind it with block_size raised.  seq: the read as it lies in the FASTQ file.
+// ref: the store bytes under the record, or null: read from the index's host arrays; false (record left as it was) if there are none.
+bool append_record_tags(std::string &out, size_t rec_at, bool bam, const urmapx_index *I, const urmapx_result &r, const urmapx_path_op *ops,
+                        const uint8_t *seq, unsigned QL, unsigned tags, const char *rg_id, const uint8_t *ref);
+// the index's sequence store on the host, or null (urmapx.hip; san/stub_device.cpp)
+const uint8_t *index_host_seq(const urmapx_index *I);
 
 // 256-entry complement table of alpha.cpp:3005 (IUPAC, case preserving, 'u' and non-letters -> '?')
 const unsigned char *complement_table();
 
 // @SQ lines + @PG (State1::WriteSAMHeader, state1.cpp:736-752)
 void append_sam_header(std::string &out, const urmapx_index *I, int argc, char **argv);
-void append_sam_header_text(std::string &out, const urmapx_index *I, const char *cmdline);
+void append_sam_header_text(std::string &out, const urmapx_index *I, const char *cmdline, const char *read_group = nullptr);
 
 }  // namespace urx

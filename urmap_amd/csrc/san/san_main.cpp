@@ -1,7 +1,8 @@
 // san_main.cpp -- driver of the sanitizer builds (make san): the host side of the drop-in path run from the command line, with the
 // device side replaced by san/stub_device.cpp.  tests/test_sanitizers_cpu.py runs it on well-formed and on damaged input; a
 // sanitizer report ends the process with exit code 99 (ASAN_OPTIONS / UBSAN_OPTIONS / TSAN_OPTIONS exitcode, set by the tests).
-//   urmap_san map <fastq1> [-2 fastq2] -o out.sam [-tab out.tab] [-batch N] [-streams K] [-gpus N] [-shards N] [-threads T] [-null] [-bgzf] [-bam] [-sort] [-biglen N]
+//   urmap_san map <fastq1> [-2 fastq2] -o out.sam [-tab out.tab] [-batch N] [-streams K] [-gpus N] [-shards N] [-threads T] [-null] [-bgzf] [-bam] [-sort] [-biglen N] [-tags MASK] [-rg LINE]
+//       (-tags: URMAPX_TAG_* bits, -rg: an @RG line with real tabs; both need the stand-in store, which exists with -biglen up to 60 000 000)
 //       (-biglen: bases of the stand-in index's third sequence, 4 000 000 000 unless given; a BAM position holds 2^31 - 1)
 //   urmap_san gunzip <in.gz> <out> [threads]
 //   urmap_san fastq <file> <batch>
@@ -37,6 +38,8 @@ static int cmd_map(int argc, char **argv) {
 		else if (a == "-bgzf") o.bgzf = 1;
 		else if (a == "-bam") o.bam = 1;
 		else if (a == "-sort") o.bam_sort = 1;
+		else if (a == "-tags") o.tags = (unsigned)atoi(val());
+		else if (a == "-rg") o.read_group = val();
 		else if (a == "-biglen") biglen = (uint32_t)strtoul(val(), nullptr, 10);
 		else return 2;
 	}

@@ -26,6 +26,9 @@
 struct urmapx_index {
 	std::vector<std::string> labels;
 	std::vector<uint32_t> lengths, offsets;
+	// a stand-in sequence store for the optional fields (made only where it stays small: urx_stub_index): letters of both cases, N runs
+	std::vector<uint8_t> store;
+	uint32_t store_size = 0;
 };
 struct urmapx_ctx {
 	const urmapx_index *I = nullptr;
@@ -35,6 +38,10 @@ struct urmapx_ctx {
 struct urmapx_text {
 	urmapx_ctx *C = nullptr;
 	bool deferred = false, bgzf = false, bam = false;
+	unsigned tag_mask = 0;
+	bool have_rg = false;
+	std::string rg_id;
+	bool tagged() const { return tag_mask != 0 || have_rg; }
 	struct Chunk { std::string text; char *dst; urmapx_text_report rep; };
 	std::deque<Chunk> flying;   // deferred: text made, "copy" not done until urmapx_text_wait
 	std::string waiting;        // after URMAPX_TEXT_SAM_CAP
@@ -65,6 +72,9 @@ hipError_t hipMemGetInfo(size_t *f, size_t *t) { *f = (size_t)200 << 30; *t = (s
 
 namespace urx {
 AllocClock &alloc_clock() { static AllocClock c{}; return c; }
+// URX_STUB_NO_HOST_SEQ=1: the index behaves like one opened straight into device memory -- the host formatters get their reference
+// windows through urmapx_index_fetch_spans
+const uint8_t *index_host_seq(const urmapx_index *I) { return I->store.empty() || getenv("URX_STUB_NO_HOST_SEQ") ? nullptr : I->store.data(); }
 }
 
 static uint64_t fnv(const uint8_t *p, size_t n) {
@@ -119,7 +129,26 @@ urmapx_index *urx_stub_index(uint32_t n, const uint32_t *lengths, const char *co
 		I->offsets.push_back(off);
 		off += lengths[i] + 32;
 	}
+	I->store_size = off;
+	if (off <= (64u << 20)) {
+		I->store.resize(off);
+		uint64_t h = 88172645463325252ull;
+		for (uint32_t k = 0; k < off; ++k) {
+			h ^= h << 13; h ^= h >> 7; h ^= h << 17;
+			I->store[k] = (uint8_t)((k >> 9) % 23 == 5 ? 'N' : "ACGTacgt"[h % ((k >> 12) & 1 ? 8 : 4)]);
+		}
+	}
 	return I;
+}
+uint32_t urmapx_index_seqdata_size(const urmapx_index *I) { return I->store_size; }
+int urmapx_index_fetch_spans(const urmapx_index *I, const uint64_t *starts, const uint32_t *lens, uint32_t n, uint8_t *out) {
+	if (I->store.empty()) return URMAPX_E_ARG;
+	for (uint32_t i = 0; i < n; ++i) {
+		if (starts[i] > I->store_size || lens[i] > I->store_size - starts[i]) return URMAPX_E_ARG;
+		memcpy(out, I->store.data() + starts[i], lens[i]);
+		out += lens[i];
+	}
+	return URMAPX_OK;
 }
 int urmapx_index_upload(urmapx_index *, int) { return URMAPX_OK; }
 int urmapx_index_replicate(const urmapx_index *src, int, urmapx_index **out) { *out = new urmapx_index(*src); return URMAPX_OK; }
@@ -249,12 +278,16 @@ int urmapx_text_map_se(urmapx_text *T, const char *fastq, size_t n, unsigned min
 		stub_search(T->C->I, q.seq, q.L, &r);
 		count(rep, r, minq);
 		label.assign(q.label, q.label_n);
+		const size_t at = text.size();
 		if (!T->bam) urx::append_sam_record(text, T->C->I, r, nullptr, 0, "*", 0xFFFFFFFFu, 0, label.c_str(), q.seq, q.qual, q.L);
 		else if (!urx::append_bam_record(text, T->C->I, r, nullptr, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, label.c_str(), q.seq, q.qual, q.L)) {
 			memset(rep, 0, sizeof *rep);
 			rep->reason = URMAPX_TEXT_LONG_NAME;  // (the device encoder hands such a chunk back)
 			return URMAPX_OK;
 		}
+		if (T->tagged() && !urx::append_record_tags(text, at, T->bam, T->C->I, r, nullptr, q.seq, q.L, T->tag_mask, T->have_rg ? T->rg_id.c_str() : nullptr,
+		                                            T->C->I->store.empty() ? nullptr : T->C->I->store.data() + r.dbpos))
+			return URMAPX_E_ARG;
 	}
 	rep->records = (uint32_t)recs.size();
 	return deliver(T, std::move(text), sam, cap, rep);
@@ -279,8 +312,13 @@ int urmapx_text_map_pe(urmapx_text *T, const char *fq1, size_t n1, const char *f
 		stub_pair_info(r, &T->C->info[i]);
 		l1.assign(a[i].label, a[i].label_n); l2.assign(b[i].label, b[i].label_n);
 		buf.resize(l1.size() + l2.size() + 3 * (size_t)(a[i].L + b[i].L) + 2048);
-		const size_t k = (T->bam ? urmapx_bam_pe : urmapx_sam_pe)(T->C->I, &r[0], &r[1], nullptr, l1.c_str(), a[i].seq, a[i].qual, a[i].L, l2.c_str(), b[i].seq,
-		                                                          b[i].qual, b[i].L, buf.data(), buf.size());
+		const uint8_t *st = T->C->I->store.empty() ? nullptr : T->C->I->store.data();
+		const urmapx_tag_options TO{T->tag_mask, T->have_rg ? T->rg_id.c_str() : nullptr,
+		                            {st && r[0].dbpos != 0xFFFFFFFFu ? st + r[0].dbpos : nullptr, st && r[1].dbpos != 0xFFFFFFFFu ? st + r[1].dbpos : nullptr}};
+		if (T->tagged()) buf.resize(buf.size() + 2 * (size_t)(a[i].L + b[i].L) + 2 * T->rg_id.size());
+		const size_t k = (T->bam ? urmapx_bam_pe_tags : urmapx_sam_pe_tags)(T->C->I, &r[0], &r[1], nullptr, l1.c_str(), a[i].seq, a[i].qual, a[i].L, l2.c_str(), b[i].seq,
+		                                                                    b[i].qual, b[i].L, T->tagged() ? &TO : nullptr, buf.data(), buf.size());
+		if (k == 0) return URMAPX_E_ARG;
 		if (k == URMAPX_BAM_LONG_NAME) {
 			memset(rep, 0, sizeof *rep);
 			rep->reason = URMAPX_TEXT_LONG_NAME;
@@ -306,6 +344,13 @@ int urmapx_text_set_bgzf(urmapx_text *T, int on) {
 int urmapx_text_set_bam(urmapx_text *T, int on) {
 	if (!T->flying.empty() || T->have_waiting) return URMAPX_E_ARG;
 	T->bam = on != 0;
+	return URMAPX_OK;
+}
+int urmapx_text_set_tags(urmapx_text *T, unsigned mask, const char *rg_id) {
+	if (!T->flying.empty() || T->have_waiting || (mask & ~URMAPX_TAG_ALL)) return URMAPX_E_ARG;
+	T->tag_mask = mask;
+	T->have_rg = rg_id != nullptr;
+	T->rg_id = rg_id ? rg_id : "";
 	return URMAPX_OK;
 }
 int urmapx_text_wait(urmapx_text *T, urmapx_text_report *rep) {

@@ -36,6 +36,25 @@ struct SamArgs {
 void bam_len_launch(const SamArgs &A, hipStream_t st);
 void bam_launch(const SamArgs &A, hipStream_t st);
 
+// tags_gpu.hip: the optional fields NM MD AS RG of a chunk's records (include/urmapx.h, "Optional fields").  The record kernels do not
+// know of them: PASS 0 (tag_len_launch, behind the record length kernel) counts every record's field bytes and gives the prefix sum
+// slots[i] = lens[i] + tag_len[i] in place of lens[i]; PASS 1 (tag_write_launch, behind the record kernel) puts the fields where the
+// record kernel left room -- over the '\n' of a SAM record and behind it, behind a BAM record, whose block_size it raises.
+struct TagArgs {
+	SamArgs A;
+	const uint8_t *store;        // the index's sequence store on the device
+	const uint32_t *seq_offs;    // offset of every sequence in it
+	uint32_t store_size;
+	uint32_t mask;               // URMAPX_TAG_* bits
+	const char *rg_id;           // device copy of the read group's ID; null: no RG field
+	uint32_t rg_len;
+	uint32_t bam;
+	uint32_t *nm, *md_len, *tag_len;  // PASS 0 out, PASS 1 in: per record
+	uint32_t *slots;             // PASS 0 out: what the scan of the record offsets takes
+};
+void tag_len_launch(const TagArgs &G, hipStream_t st);
+void tag_write_launch(const TagArgs &G, hipStream_t st);
+
 }  // namespace urx
 
 using namespace urx;
@@ -187,6 +206,17 @@ __device__ __forceinline__ RecView record_view(const SamArgs &A, uint32_t i, con
 		V.F = side ? pair_fields(rm, r, QLm, V.QL, true) : pair_fields(r, rm, V.QL, QLm, false);
 	}
 	return V;
+}
+
+// 4-bit code of a SEQ letter: "=ACMGRSVTWYHKDBN", either case; every other byte is N (htslib's seq_nt16_table)
+__device__ __forceinline__ uint32_t nibble_of(uint32_t c) {
+	if (c - (uint32_t)'a' < 26u) c -= 32u;
+	const char t[] = "=ACMGRSVTWYHKDBN";
+	uint32_t v = 15u;
+#pragma unroll
+	for (uint32_t k = 0; k < 16u; ++k)
+		if (c == (uint32_t)t[k]) v = k;
+	return v;
 }
 
 __device__ __forceinline__ uint32_t bcast(uint32_t v, int t) { return (uint32_t)__builtin_amdgcn_readlane((int)v, t); }

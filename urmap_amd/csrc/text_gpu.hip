@@ -586,6 +586,18 @@ struct urmapx_text {
 	uint64_t *h_zused = nullptr;  // page-locked
 	// urmapx_text_set_bam: bam_gpu.hip's two kernels stand where sam_len_kernel and sam_kernel stand, `sam` holds BAM records
 	bool bam = false;
+	// urmapx_text_set_tags: tags_gpu.hip's two passes run behind the record length kernel and behind the record kernel
+	unsigned tag_mask = 0;
+	bool have_rg = false;
+	uint32_t rg_len = 0;
+	DevBuf<char> rg_id;
+	DevBuf<uint32_t> tag_arrays;  // NM, MD length, field bytes and slot of every record, one allocation (a lane's arrays grow with its chunks,
+	                              // and every hipFree waits for the whole device: the other lanes' mapping too)
+	uint32_t tag_stride = 0;      // records each of the four holds
+	TagArgs pending_tags;
+	hipEvent_t tag_ev[4] = {};  // around the counting pass, around the writing pass (urmapx_text_tag_ms)
+	bool tag_ev_ok = false, tag_timed = false;
+	bool tags_on() const { return tag_mask != 0 || have_rg; }
 };
 
 namespace {
@@ -666,6 +678,13 @@ int fetch_sam(urmapx_text *T, char *sam, size_t sam_cap, urmapx_text_report *rep
 	if (T->deferred && T->waiting && T->tail_ok) HIP_TRY(hipStreamWaitEvent(st, T->tail_ev[set ^ 1][2], 0));
 	if (T->bam) bam_launch(A, st);
 	else hipLaunchKernelGGL(sam_kernel, dim3(GRID), dim3(SAM_WAVES * 64), 0, st, A);
+	if (T->tags_on()) {  // the fields go where the record kernel left room behind every record
+		TagArgs G = T->pending_tags;
+		G.A = A;
+		if (T->tag_ev_ok) HIP_TRY(hipEventRecord(T->tag_ev[2], st));
+		tag_write_launch(G, st);
+		if (T->tag_ev_ok) { HIP_TRY(hipEventRecord(T->tag_ev[3], st)); T->tag_timed = true; }
+	}
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(T->h_hdr + 2 + set, T->hdr.p, sizeof(TextHdr), hipMemcpyDeviceToHost, st));  // (on the main stream: the next chunk clears the header there)
 	const uint8_t *d_src = T->sam.p;
@@ -715,6 +734,10 @@ int map_text(urmapx_text *T, const char *fastq1, size_t nbytes1, const char *fas
 	const size_t rec_cap = (size_t)ends_cap[0] / 4 + (size_t)ends_cap[1] / 4 + 2;
 	if ((rc = T->lens.ensure(rec_cap))) return rc;
 	if ((rc = T->qn.ensure(rec_cap))) return rc;
+	if (T->tags_on()) {
+		if ((rc = T->tag_arrays.ensure(4 * rec_cap))) return rc;
+		T->tag_stride = (uint32_t)(T->tag_arrays.cap / 4);
+	}
 	if ((rc = T->rec_offs.ensure(rec_cap + 1))) return rc;
 	if ((rc = T->offs.ensure(rec_cap + 1))) return rc;
 	if ((rc = T->sums.ensure(rec_cap / SC_TILE + 2))) return rc;
@@ -766,9 +789,22 @@ int map_text(urmapx_text *T, const char *fastq1, size_t nbytes1, const char *fas
 	A.lens = T->lens.p; A.qn = T->qn.p; A.rec_offs = T->rec_offs.p; A.sam = nullptr;
 	if (T->bam) bam_len_launch(A, st);
 	else hipLaunchKernelGGL(sam_len_kernel, dim3(GRID), dim3(256), 0, st, A);
-	hipLaunchKernelGGL(scan_sums_kernel, dim3(GRID), dim3(SC_THREADS), 0, st, T->lens.p, &hdr->n_reads, T->sums.p);
+	// with optional fields a record's place is its length plus its fields' bytes (tags_gpu.hip); the record kernels keep reading lens
+	const uint32_t *slot_lens = T->lens.p;
+	if (T->tags_on()) {
+		const IndexStore S = index_store(ctx_index(C));  // (resident: urmapx_text_set_tags has looked)
+		TagArgs &G = T->pending_tags;
+		G.A = A; G.store = S.d_seq; G.seq_offs = S.d_seq_offsets; G.store_size = S.seq_data_size; G.mask = T->tag_mask;
+		G.rg_id = T->have_rg ? T->rg_id.p : nullptr; G.rg_len = T->rg_len; G.bam = T->bam ? 1u : 0u;
+		G.nm = T->tag_arrays.p; G.md_len = G.nm + T->tag_stride; G.tag_len = G.md_len + T->tag_stride; G.slots = G.tag_len + T->tag_stride;
+		if (T->tag_ev_ok) HIP_TRY(hipEventRecord(T->tag_ev[0], st));
+		tag_len_launch(G, st);
+		if (T->tag_ev_ok) HIP_TRY(hipEventRecord(T->tag_ev[1], st));
+		slot_lens = G.slots;
+	}
+	hipLaunchKernelGGL(scan_sums_kernel, dim3(GRID), dim3(SC_THREADS), 0, st, slot_lens, &hdr->n_reads, T->sums.p);
 	hipLaunchKernelGGL(scan_small_kernel, dim3(1), dim3(1024), 0, st, T->sums.p, &hdr->n_reads, (uint32_t)SC_TILE, 0u, &hdr->sam_total, &hdr->flags);
-	hipLaunchKernelGGL(scan_apply_kernel<uint32_t>, dim3(GRID), dim3(SC_THREADS), 0, st, T->lens.p, &hdr->n_reads, T->sums.p, T->rec_offs.p);
+	hipLaunchKernelGGL(scan_apply_kernel<uint32_t>, dim3(GRID), dim3(SC_THREADS), 0, st, slot_lens, &hdr->n_reads, T->sums.p, T->rec_offs.p);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(T->h_hdr, hdr, sizeof(TextHdr), hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
@@ -852,6 +888,9 @@ void urmapx_text_destroy(urmapx_text *T) {
 	T->sums.release(); T->lens.release(); T->qn.release(); T->rec_offs.release();
 	T->used.release(); T->tname_offs.release(); T->offs.release(); T->tnames.release(); T->results.release(); T->pathops.release();
 	T->hdr.release();
+	T->rg_id.release(); T->tag_arrays.release();
+	for (hipEvent_t x : T->tag_ev)
+		if (x) (void)hipEventDestroy(x);
 	if (T->h_hdr) (void)hipHostFree(T->h_hdr);
 	for (hipEvent_t x : T->ev)
 		if (x) (void)hipEventDestroy(x);
@@ -892,6 +931,44 @@ int urmapx_text_set_bgzf(urmapx_text *T, int on) {
 int urmapx_text_set_bam(urmapx_text *T, int on) {
 	if (!T || T->waiting || T->pending) return URMAPX_E_ARG;
 	T->bam = on != 0;
+	return URMAPX_OK;
+}
+
+int urmapx_text_set_tags(urmapx_text *T, unsigned mask, const char *rg_id) {
+	if (!T || T->waiting || T->pending || (mask & ~URMAPX_TAG_ALL)) return URMAPX_E_ARG;
+	HIP_TRY(hipSetDevice(ctx_device(T->C)));
+	if (mask || rg_id) {  // the tag passes read the sequence store where the context's index has it on the device
+		const IndexStore S = index_store(ctx_index(T->C));
+		if (!S.d_seq || !S.d_seq_offsets) return URMAPX_E_ARG;
+	}
+	if (rg_id) {
+		const size_t n = strlen(rg_id);
+		if (n == 0 || n > (1u << 20)) return URMAPX_E_ARG;
+		HIP_TRY(hipStreamSynchronize(ctx_stream(T->C)));  // (the array may be replaced: nothing reads the old one any more)
+		int rc = T->rg_id.ensure(n + 1);
+		if (rc) return rc;
+		HIP_TRY(hipMemcpy(T->rg_id.p, rg_id, n, hipMemcpyHostToDevice));
+		T->rg_len = (uint32_t)n;
+	}
+	T->have_rg = rg_id != nullptr;
+	T->tag_mask = mask;
+	if (T->tags_on() && !T->tag_ev_ok && !T->tag_ev[0]) {
+		T->tag_ev_ok = true;
+		for (hipEvent_t &x : T->tag_ev)
+			if (hipEventCreate(&x) != hipSuccess) { T->tag_ev_ok = false; x = nullptr; }
+	}
+	T->tag_timed = false;
+	return URMAPX_OK;
+}
+
+int urmapx_text_tag_ms(urmapx_text *T, float ms[2]) {
+	if (!T || !ms) return URMAPX_E_ARG;
+	ms[0] = ms[1] = 0;
+	if (!T->tag_ev_ok || !T->tag_timed || !T->tags_on()) return URMAPX_OK;
+	HIP_TRY(hipSetDevice(ctx_device(T->C)));
+	HIP_TRY(hipEventSynchronize(T->tag_ev[3]));
+	(void)hipEventElapsedTime(&ms[0], T->tag_ev[0], T->tag_ev[1]);
+	(void)hipEventElapsedTime(&ms[1], T->tag_ev[2], T->tag_ev[3]);
 	return URMAPX_OK;
 }
 

@@ -64,6 +64,8 @@ struct Opts {
 	std::string bamout; // -bamout: a BAM file in -samout's place, records encoded and deflated on the device
 	bool veryfast = false, quiet = false, minq_given = false, host_build = false, notrunclabels = false;
 	bool sort = false;  // -sort: the -bamout file in coordinate order, with its .bai index
+	std::string tags, rg;  // -tags NM,MD,AS and -rg '@RG\tID:..': optional fields of the records, the read group's header line
+	bool tags_given = false, rg_given = false;
 	bool trunclabels = false, wordlength_given = false;
 	double load_factor = 0.6;  // myopts.h: FLT_OPT(load_factor, 0.6, ...)
 	unsigned threads = 0, wordlength = 24, maxix = 0, minq = 10;
@@ -108,6 +110,8 @@ static Opts parse(int argc, char **argv) {
 		else if (a == "-bamout") o.bamout = val();
 		else if (a == "-host") o.host_build = true;
 		else if (a == "-sort") o.sort = true;
+		else if (a == "-tags") { o.tags = val(); o.tags_given = true; }
+		else if (a == "-rg") { o.rg = val(); o.rg_given = true; }
 		else if (a == "-quiet") o.quiet = true;
 		else if (a == "-log") o.log = val();
 		else if (a == "-load_factor") o.load_factor = atof(val());
@@ -173,6 +177,24 @@ static void check(int rc, const char *what) {
 	if (rc != URMAPX_OK && rc != URMAPX_E_UNSUPPORTED) die("%s: %s", what, urmapx_strerror(rc));
 }
 
+// -tags LIST: a comma-separated non-empty subset of NM, MD, AS in any order; anything else is refused by the word that is wrong
+static unsigned parse_tags(const std::string &list) {
+	unsigned mask = 0;
+	for (size_t at = 0;;) {
+		size_t e = list.find(',', at);
+		if (e == std::string::npos) e = list.size();
+		const std::string w = list.substr(at, e - at);
+		const unsigned bit = w == "NM" ? URMAPX_TAG_NM : w == "MD" ? URMAPX_TAG_MD : w == "AS" ? URMAPX_TAG_AS : 0u;
+		if (w.empty()) die("-tags %s: empty element '' (a comma-separated list of NM, MD, AS)", list.c_str());
+		if (!bit) die("-tags %s: unknown tag '%s' (a comma-separated list of NM, MD, AS)", list.c_str(), w.c_str());
+		if (mask & bit) die("-tags %s: tag '%s' is named twice", list.c_str(), w.c_str());
+		mask |= bit;
+		if (e == list.size()) break;
+		at = e + 1;
+	}
+	return mask;
+}
+
 static int cmd_map(const Opts &o, int argc, char **argv) {
 	const bool paired = !o.map2.empty();
 	const unsigned minq = paired ? o.minq : 10;  // only cmd_map2 reads -minq (map2.cpp:76); -map keeps State1::m_Minq = 10
@@ -192,6 +214,15 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 		if (stat(o.bamout.c_str(), &st) == 0 && !S_ISREG(st.st_mode)) die("-sort needs a file name for -bamout, not a pipe or %s: the index %s.bai sits beside it", o.bamout.c_str(), o.bamout.c_str());
 		if (o.host_build) setenv("URMAPX_HOST_SORT", "1", 1);  // -host: the sort too runs on the host (urmapx_bam_sort_host)
 	}
+	// -tags / -rg: refused here, before the index is loaded
+	unsigned tag_mask = 0;
+	std::vector<char> rg_line(o.rg.size() + 1);
+	if (o.tags_given) tag_mask = parse_tags(o.tags);
+	if (o.rg_given) {
+		char why[512];
+		if (urmapx_read_group_id(o.rg.c_str(), rg_line.data(), rg_line.size(), nullptr, 0, why, sizeof why)) die("%s", why);
+	}
+	if ((o.tags_given || o.rg_given) && samout.empty()) die("-tags and -rg go with -samout or -bamout: they are fields of its records");
 	const auto t0 = std::chrono::steady_clock::now();
 	urmapx_index *I = nullptr;
 	// the file streams to the first device (urmapx_index_open_device); URMAPX_HOST_INDEX=1: through host arrays as before (measurement)
@@ -213,6 +244,8 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 	mo.bgzf = o.bgzf ? 1 : 0;
 	mo.bam = bam ? 1 : 0;
 	mo.bam_sort = o.sort ? 1 : 0;
+	mo.tags = tag_mask;
+	mo.read_group = o.rg_given ? rg_line.data() : nullptr;
 	urmapx_map_report rep;
 	memset(&rep, 0, sizeof rep);
 	char err[1024];
@@ -558,9 +591,11 @@ int main(int argc, char **argv) {
 	fprintf(stderr, "urmap (MI355X build)\n  urmap -map reads.fq -ufi index.ufi -samout out.sam [-veryfast] [-gpu D] [-gpus N] [-streams K] [-samshards N] [-bgzf]\n"
 	                "  urmap -map2 R1.fq -reverse R2.fq -ufi index.ufi -samout out.sam [-tabbedout out.tab] [-gpu D] [-gpus N] [-bgzf]\n"
 	                "      -bgzf: the file named by -samout is BGZF (gzip members of 64 KB of text, deflated on the GPU); `gzip -dc` gives the SAM text\n"
-	                "      -bamout out.bam: in place of -samout, a BAM file (records encoded and deflated on the GPU, unsorted, no optional fields);\n"
+	                "      -bamout out.bam: in place of -samout, a BAM file (records encoded and deflated on the GPU, unsorted);\n"
 	                "               with -samshards N every out.bam.0 .. out.bam.N-1 is a complete BAM file\n"
 	                "      -sort: with -bamout, the records in coordinate order (sorted on the GPU) and the index out.bam.bai beside the file\n"
+	                "      -tags NM,MD,AS: these optional fields behind QUAL of every mapped record (any subset; computed on the GPU), SAM and BAM\n"
+	                "      -rg '@RG\\tID:x\\tSM:y': that line in the header in front of @PG and RG:Z:x on every record\n"
 	                "  urmap -make_ufi genome.fa -output index.ufi [-slots N] [-wordlength W] [-maxix M]\n"
 	                "  urmap -ufi_validate index.ufi [-gpu D]\n"
 	                "  urmap -ufi_stats index.ufi [-log F] [-gpu D] [-quiet]\n"

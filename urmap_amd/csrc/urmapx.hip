@@ -115,6 +115,10 @@ __attribute__((constructor)) static void urx_more_hw_queues() { setenv("GPU_MAX_
 hipStream_t ctx_stream(urmapx_ctx *C) { return C->stream; }
 int ctx_device(const urmapx_ctx *C) { return C->device; }
 const urmapx_index *ctx_index(const urmapx_ctx *C) { return C->index; }
+IndexStore index_store(const urmapx_index *I) {
+	return IndexStore{I->d_seq, I->d_seqOffsets, I->h_seq, I->seqDataSize, (uint32_t)I->labels.size(), I->device};
+}
+const uint8_t *index_host_seq(const urmapx_index *I) { return I->h_seq; }
 }  // namespace urx
 
 // The work buffer (urmapx_ctx::dpbuf) of phase 6 and of phase 3 parked: its head (kernels.h: DpHead), then per DpWork, in this order, kidx, jobs,
