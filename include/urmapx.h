@@ -428,6 +428,10 @@ typedef struct urmapx_map_options {
 	const char *read_group; /* -rg: a complete @RG header line, tabs real, with an ID: field (urmapx_read_group_id); it goes into the header in
 	                     * front of the @PG line and every record gets RG:Z:<ID>.  NULL: neither.  URMAPX_E_ARG with the reason in err for a
 	                     * line urmapx_read_group_id refuses and for tag bits outside URMAPX_TAG_ALL */
+	int markdup;        /* -markdup (with bam_sort): flag 0x400 of every record says whether it is a duplicate (see "Duplicate marking" below),
+	                     * decided on first_gpu while the kept records lie there for the sort (urmapx_bam_sort_markdup; on the host road
+	                     * urmapx_bam_sort_markdup_host).  Only the flag half-words differ from the run without it: the order, the cuts and
+	                     * the index stay.  The counters go to the report.  URMAPX_E_ARG with the reason in err without bam_sort */
 } urmapx_map_options;
 typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:593-632) and where the time went */
 	uint64_t reads, mapped_q, mapped_lowq, unmapped, unsupported;
@@ -456,6 +460,8 @@ typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:59
 	uint32_t alloc_dev_calls, alloc_pinned_calls;
 	uint64_t sam_text_bytes, sam_file_bytes;         /* SAM text (bam: header block and records) made, bytes written to samout: equal unless bgzf / bam */
 	double sort_s;                                   /* bam_sort: last record mapped .. last byte of samout and samout.bai written; inside `seconds` */
+	uint64_t pairs_examined, pairs_duplicate, fragments_examined, fragments_duplicate;  /* markdup: urmapx_markdup_stats of the run's records */
+	double markdup_s;                                /* markdup: the marking's share of sort_s */
 } urmapx_map_report;
 /* fastq2 NULL: single-end (-map); else the mates' file (-map2 ... -reverse).  samout / tabout may be NULL.  The index
  * needs its host arrays, or to be resident on first_gpu already (the other devices' replicas are then copied from there).  Batch b is mapped on device
@@ -745,6 +751,46 @@ int urmapx_bam_sort_host(const void *records, size_t n_bytes, uint32_t n_ref, ui
 void urmapx_bam_sort_free(urmapx_bam_sort_result *);
 /* device memory urmapx_bam_sort takes for n_bytes of records in n_records records (slice and compressor scratch included) */
 uint64_t urmapx_bam_sort_device_bytes(size_t n_bytes, uint64_t n_records);
+
+/* ---- Duplicate marking (-bamout ... -sort -markdup): flag 0x400, decided while the records lie on the device for the sort ----
+ * urmapx_bam_sort_markdup / _host: urmapx_bam_sort / _host with one step more.  Order, cuts and index are those of the plain call;
+ * only bit 0x400 of the records' flag half-words may differ.  The rule is Picard's and samtools', without libraries and without
+ * optical duplicates.  The input is the records in input order; all arithmetic on positions is signed and 64 bits wide.
+ *  1. Eligible: a record with none of the flags 0x4, 0x100, 0x800.  Every other record is copied untouched, with whatever 0x400 it
+ *     carries.  An eligible record's 0x400 on output is set exactly when the rules below make it a duplicate (an incoming 0x400 is
+ *     overwritten).
+ *  2. The end of a record: E = (refID, u5, rev).  rev is flag 0x10.  Forward: u5 = pos - (the S and H lengths in front of the first
+ *     reference-consuming op).  Reverse: u5 = pos + refspan - 1 + (the S and H lengths behind the last reference-consuming op).
+ *     refspan is the sum over M, D, N, =, X (not cut off at 2^31), 1 for a record without such an op; for that record every S and H op
+ *     counts as in front and as behind.  u5 may be negative.  Ends are ordered by refID (as unsigned), then u5 (signed), then rev.
+ *  3. Pair: records i and i + 1 of the input, both eligible, i with flags 0x1 and 0x40 and without 0x80, i + 1 with 0x1 and 0x80, their
+ *     read_names equal byte for byte (equal l_read_name included).  A record is in at most one pair: scanning from the front, a record
+ *     taken as a second mate is not tried as a first mate.  Every other eligible record is a fragment: single-end reads, mates whose
+ *     partner is unmapped, mates that are not adjacent.
+ *  4. Score of a record: the sum of its QUAL bytes q with 15 <= q and q != 0xFF, at most 2^31 - 1 (it saturates there: over eight
+ *     million bases).  Score of a pair: the sum over its two records.
+ *  5. Pairs: the key of a pair is (min(E1, E2), max(E1, E2)).  Among the pairs of one key the one with the largest score stays, ties
+ *     going to the pair whose first record comes first in the input; both records of every other pair are duplicates.
+ *  6. Fragments: all eligible records grouped by E, members of pairs included.  If the group holds a member of a pair, every fragment
+ *     in it is a duplicate; otherwise the fragment with the largest score stays (ties: first in the input) and the others are
+ *     duplicates.  Members of pairs are decided by rule 5 alone.
+ *  7. pairs_examined counts pairs, pairs_duplicate flagged pairs (not records), fragments_examined fragments, fragments_duplicate
+ *     flagged fragments.
+ * The result is a function of the records in input order.  The device version (markdup.hip) and the host version (markdup_host.cpp,
+ * written apart from it: std::stable_sort on a tuple and a walk over the groups) give the same inflated stream and counters.
+ * URMAPX_E_FORMAT in addition to urmapx_bam_sort's: an eligible record whose SEQ and QUAL (l_seq) do not lie inside its block_size;
+ * device version only: ends whose packed form -- bits for n_ref, for the span of u5 seen, one for rev -- exceeds 64 bits (more
+ * references and longer clips than any file has). */
+typedef struct urmapx_markdup_stats {
+	uint64_t pairs_examined, pairs_duplicate, fragments_examined, fragments_duplicate;
+	double markdup_s;        /* seconds of the calling thread in the marking (device: its launches and copies; inside no part of the result's times) */
+} urmapx_markdup_stats;
+int urmapx_bam_sort_markdup(int device, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
+                            size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out);
+int urmapx_bam_sort_markdup_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
+                                 size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out);
+/* device memory urmapx_bam_sort_markdup takes: urmapx_bam_sort_device_bytes and 24 bytes a record for ends, best words and roles */
+uint64_t urmapx_bam_sort_markdup_device_bytes(size_t n_bytes, uint64_t n_records);
 
 const char *urmapx_strerror(int code);
 /* "gfx950" etc. of the ctx's device; NULL without a device */

@@ -43,6 +43,7 @@ EXPORTS = (
     "urmapx_bgzf_destroy", "urmapx_bgzf_compress_device", "urmapx_text_set_bgzf",
     "urmapx_text_set_bam", "urmapx_bam_header", "urmapx_bam_se", "urmapx_bam_pe",
     "urmapx_bam_sort", "urmapx_bam_sort_host", "urmapx_bam_sort_free", "urmapx_bam_sort_device_bytes",
+    "urmapx_bam_sort_markdup", "urmapx_bam_sort_markdup_host", "urmapx_bam_sort_markdup_device_bytes",
     "urmapx_calmd", "urmapx_ref_span", "urmapx_sam_se_tags", "urmapx_sam_pe_tags", "urmapx_bam_se_tags", "urmapx_bam_pe_tags",
     "urmapx_read_group_id", "urmapx_sam_header_rg", "urmapx_bam_header_rg", "urmapx_index_fetch_spans", "urmapx_text_set_tags",
     "urmapx_text_tag_ms", "urmapx_tags_batch",
@@ -74,6 +75,12 @@ class MapOptions(C.Structure):
                 ("bam", C.c_int), ("bam_sort", C.c_int), ("tags", C.c_uint), ("read_group", C.c_char_p)]
 
 
+class MapOptionsMarkdup(C.Structure):
+    """urmapx_map_options as urmapx_map_files reads it: MapOptions (the struct up to read_group, whose layout tests/test_tags_cpu.py
+    pins) with the field appended behind it.  map_files always passes this one."""
+    _fields_ = MapOptions._fields_ + [("markdup", C.c_int)]
+
+
 class TagOptions(C.Structure):
     _fields_ = [("tags", C.c_uint), ("rg_id", C.c_char_p), ("ref", C.c_void_p * 2)]
 
@@ -87,7 +94,9 @@ class MapReport(C.Structure):
                 ("dev_d2h_s", C.c_double), ("shards", C.c_int), ("placement", C.c_char * 256), ("shard_scan_s", C.c_double),
                 ("dev_map_search_s", C.c_double), ("dev_map_dp_s", C.c_double), ("map_enqueue_s", C.c_double),
                 ("alloc_dev_s", C.c_double), ("alloc_pinned_s", C.c_double), ("alloc_dev_calls", C.c_uint32), ("alloc_pinned_calls", C.c_uint32),
-                ("sam_text_bytes", C.c_uint64), ("sam_file_bytes", C.c_uint64), ("sort_s", C.c_double)]
+                ("sam_text_bytes", C.c_uint64), ("sam_file_bytes", C.c_uint64), ("sort_s", C.c_double),
+                ("pairs_examined", C.c_uint64), ("pairs_duplicate", C.c_uint64), ("fragments_examined", C.c_uint64),
+                ("fragments_duplicate", C.c_uint64), ("markdup_s", C.c_double)]
 
 
 class BamSortResult(C.Structure):
@@ -95,6 +104,11 @@ class BamSortResult(C.Structure):
                 ("stream_bytes", C.c_uint64), ("records", C.c_uint64), ("no_coor", C.c_uint64), ("sort_passes", C.c_uint32),
                 ("slices", C.c_uint32), ("scan_s", C.c_double), ("alloc_s", C.c_double), ("upload_s", C.c_double), ("sort_s", C.c_double),
                 ("gather_s", C.c_double), ("deflate_s", C.c_double), ("copy_s", C.c_double), ("index_s", C.c_double)]
+
+
+class MarkdupStats(C.Structure):
+    _fields_ = [("pairs_examined", C.c_uint64), ("pairs_duplicate", C.c_uint64), ("fragments_examined", C.c_uint64),
+                ("fragments_duplicate", C.c_uint64), ("markdup_s", C.c_double)]
 
 
 class ValidateReport(C.Structure):
@@ -205,7 +219,7 @@ def lib():
     L.urmapx_ctx_get_pair_info.argtypes = [vp, vp, u32]
     L.urmapx_tab_pe.restype = C.c_size_t
     L.urmapx_tab_pe.argtypes = [vp, vp, vp, vp, cp, u32, u32, i32, vp, C.c_size_t]
-    L.urmapx_map_files.argtypes = [vp, C.POINTER(MapOptions), cp, cp, cp, cp, C.POINTER(MapReport), cp, C.c_size_t]
+    L.urmapx_map_files.argtypes = [vp, C.POINTER(MapOptionsMarkdup), cp, cp, cp, cp, C.POINTER(MapReport), cp, C.c_size_t]
     L.urmapx_host_pool_trim.argtypes = []
     L.urmapx_host_pool_trim.restype = None
     L.urmapx_text_create.argtypes = [vp, C.POINTER(vp)]
@@ -626,14 +640,15 @@ def gunzip_file(gz_path, out_path, threads=0):
 
 def map_files(index: "Index", fastq1, fastq2=None, samout=None, tabout=None, first_gpu=0, gpus=1, streams=2, host_threads=0,
               batch=0, veryfast=False, minq=10, cmdline=None, allow_unsupported=False, sam_shards=0, discard_sam=False, bgzf=False, bam=False,
-              bam_sort=False, tags=0, read_group=None):
+              bam_sort=False, tags=0, read_group=None, markdup=False):
     """urmap -map / -map2 file to file (cmd_map / cmd_map2) on an index that has its host arrays or is resident on
     first_gpu.  bgzf: samout is a BGZF file (-bgzf).  bam: samout is a BAM file (-bamout).  bam_sort (with bam):
     its records in coordinate order, with the index samout + ".bai" beside it (-sort).  tags: TAG_* bits (-tags), read_group: an @RG line
-    with real tabs (-rg): the optional fields of the records.  -> dict of State1::HitStats' counters and stage times."""
-    o = MapOptions(first_gpu, gpus, streams, host_threads, batch, int(veryfast), minq, cmdline.encode() if cmdline else None,
+    with real tabs (-rg): the optional fields of the records.  markdup (with bam_sort): flag 0x400 on duplicate records (-markdup),
+    the counters in the report.  -> dict of State1::HitStats' counters and stage times."""
+    o = MapOptionsMarkdup(first_gpu, gpus, streams, host_threads, batch, int(veryfast), minq, cmdline.encode() if cmdline else None,
                    int(sam_shards), int(discard_sam), int(bgzf), int(bam), int(bam_sort), int(tags),
-                   (read_group.encode("latin-1") if isinstance(read_group, str) else read_group))
+                   (read_group.encode("latin-1") if isinstance(read_group, str) else read_group), int(markdup))
     rep = MapReport()
     err = C.create_string_buffer(1024)
     enc = lambda p: os.fsencode(p) if p else None
@@ -680,36 +695,45 @@ def read_group_id(line):
     return out.value.decode("latin-1"), ident.value.decode("latin-1")
 
 
-def _bam_sort(fn_name, head, records, n_ref, in_front, report, starts=None):
+def _bam_sort(fn_name, head, records, n_ref, in_front, report, starts=None, markdup=False):
     src = np.frombuffer(bytes(records), dtype=np.uint8)
     res = BamSortResult()
+    md = MarkdupStats()
     L = lib()
+    if markdup:
+        fn_name = fn_name.replace("urmapx_bam_sort", "urmapx_bam_sort_markdup")
     fn = getattr(L, fn_name)
-    fn.argtypes = [C.c_int] * len(head) + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(BamSortResult)]
+    fn.argtypes = ([C.c_int] * len(head) + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t] +
+                   ([C.POINTER(MarkdupStats)] if markdup else []) + [C.POINTER(BamSortResult)])
     L.urmapx_bam_sort_free.argtypes = [C.POINTER(BamSortResult)]
     L.urmapx_bam_sort_free.restype = None
     st = np.ascontiguousarray(starts if starts is not None else [], dtype=np.uint64)
+    tail = (C.byref(md), C.byref(res)) if markdup else (C.byref(res),)
     _check(fn(*head, src.ctypes.data if len(src) else None, len(src), int(n_ref), int(in_front), st.ctypes.data if len(st) else None, len(st),
-              C.byref(res)), fn_name)
+              *tail), fn_name)
     try:
         out = (C.string_at(res.bgzf, res.bgzf_bytes) if res.bgzf_bytes else b"", C.string_at(res.bai, res.bai_bytes))
         rep = {k: getattr(res, k) for k, _ in BamSortResult._fields_ if k not in ("bgzf", "bai")}
+        if markdup:
+            rep.update({k: getattr(md, k) for k, _ in MarkdupStats._fields_})
     finally:
         L.urmapx_bam_sort_free(C.byref(res))
     return out + (rep,) if report else out
 
 
-def bam_sort(records: bytes, n_ref, device=0, bytes_in_front=0, report=False, starts=None):
+def bam_sort(records: bytes, n_ref, device=0, bytes_in_front=0, report=False, starts=None, markdup=False):
     """BAM alignment records back to back -> (the records in coordinate order as BGZF members, the bytes of their .bai index), sorted on
     the device (urmapx_bam_sort; bam_sort.hip).  bytes_in_front: what the file holds in front of the first member, for the index's
     virtual offsets.  report: a third item, the call's counters and step times.  starts: offsets at which records are known to begin (the
-    chain is then walked from all of them at once)."""
-    return _bam_sort("urmapx_bam_sort", (int(device),), records, n_ref, bytes_in_front, report, starts)
+    chain is then walked from all of them at once).  markdup: flag 0x400 of the records says whether they are duplicates
+    (urmapx_bam_sort_markdup; markdup.hip), and the report holds the counters and markdup_s."""
+    return _bam_sort("urmapx_bam_sort", (int(device),), records, n_ref, bytes_in_front, report, starts, markdup)
 
 
-def bam_sort_host(records: bytes, n_ref, bytes_in_front=0, report=False, starts=None):
-    """the same contract on the host, no device (urmapx_bam_sort_host): std::stable_sort and zlib inside the BGZF framing"""
-    return _bam_sort("urmapx_bam_sort_host", (), records, n_ref, bytes_in_front, report, starts)
+def bam_sort_host(records: bytes, n_ref, bytes_in_front=0, report=False, starts=None, markdup=False):
+    """the same contract on the host, no device (urmapx_bam_sort_host, urmapx_bam_sort_markdup_host): std::stable_sort and zlib inside
+    the BGZF framing"""
+    return _bam_sort("urmapx_bam_sort_host", (), records, n_ref, bytes_in_front, report, starts, markdup)
 
 
 BGZF_PIECE = 65280

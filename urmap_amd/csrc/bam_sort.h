@@ -117,5 +117,14 @@ std::vector<uint8_t> write_bai(const IndexArrays &X, uint32_t n_ref, const std::
 int finish_result(urmapx_bam_sort_result *out, uint8_t *bgzf, size_t bgzf_bytes, uint64_t stream_bytes, uint64_t in_front,
                   const IndexArrays &X, uint32_t n_ref);
 
+// ---- duplicate marking (include/urmapx.h "Duplicate marking") ----
+constexpr uint32_t FLAG_BYTE = 19;     // the byte of a record that holds bit 0x400 of its flag, as its bit 0x04
+constexpr uint8_t FLAG_DUP_BIT = 0x04;
+constexpr uint32_t MAX_SCORE = 0x7FFFFFFFu;  // where a record's score saturates
+enum : uint8_t { MD_KEEP = 0, MD_SET = 1, MD_CLEAR = 2 };  // what becomes of a record's bit 0x400
+// the host version (markdup_host.cpp): action[i] for every record of `rec` in input order, and the counters.  URMAPX_E_FORMAT for an
+// eligible record whose SEQ and QUAL do not lie inside it
+int markdup_host(const uint8_t *rec, const std::vector<uint64_t> &offs, std::vector<uint8_t> &action, urmapx_markdup_stats *md);
+
 }  // namespace bamsort
 }  // namespace urx

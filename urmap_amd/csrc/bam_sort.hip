@@ -18,8 +18,7 @@
 //   bounds / extent / lin / bin_key / chunk_*   the index: first and last record of every reference and its largest end, the smallest
 //                    stream offset per 16 384-base window (atomicMin), a second sort of the record numbers by (reference, bin) with
 //                    the same two sort kernels, a flag where a chunk begins, a scan of the flags, the chunks
-#include "bam_sort.h"
-#include "internal.h"
+#include "bam_sort_dev.h"
 
 #include <chrono>
 #include <cstdlib>
@@ -30,11 +29,7 @@ using namespace urx::bamsort;
 
 namespace {
 
-constexpr int NT = 256;                   // threads of a sort workgroup: four wavefronts
-constexpr uint32_t TILE = 4 * NT;         // records a workgroup takes when every workgroup takes the least
-constexpr uint32_t MAX_BLOCKS = 512;      // workgroups of a sort pass: beyond MAX_BLOCKS * TILE records each takes several tiles
-constexpr uint32_t SCAN_NT = 1024;
-constexpr uint32_t MAX_RUNS = 65536;      // threads of a large scan
+// (the sizes of the sort's grids -- NT, TILE, MAX_BLOCKS, SCAN_NT, MAX_RUNS -- are in bam_sort_dev.h: markdup.hip sorts with them too)
 constexpr uint32_t DEFAULT_SLICE = 2048;  // members of 65 280 bytes in one slice of the sorted stream
 
 __device__ __forceinline__ uint32_t load4(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
@@ -275,38 +270,19 @@ __global__ __launch_bounds__(NT) void chunk_write_kernel(const uint64_t *key2, c
 using Clock = std::chrono::steady_clock;
 double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::now() - t).count(); }
 
-// device array of exactly the size asked for
-thread_local double t_alloc_s = 0;  // what this thread's call has spent in hipMalloc and hipFree (urmapx_bam_sort_result.alloc_s)
-template <class T>
-struct Dev {
-	T *p = nullptr;
-	int alloc(size_t n) {
-		urx::AllocTimer at(0);
-		const auto t0 = Clock::now();
-		const hipError_t e = hipMalloc((void **)&p, (n ? n : 1) * sizeof(T));
-		t_alloc_s += since(t0);
-		if (e != hipSuccess) { p = nullptr; (void)hipGetLastError(); return urx::hip_rc(e); }
-		return URMAPX_OK;
-	}
-	~Dev() {
-		if (!p) return;
-		urx::AllocTimer at(0);
-		const auto t0 = Clock::now();
-		(void)hipFree(p);
-		t_alloc_s += since(t0);
-	}
-};
-
-uint32_t grid_for(uint64_t n, uint32_t most = 4096) {
-	const uint64_t g = (n + NT - 1) / NT;
-	return (uint32_t)(g < 1 ? 1 : g > most ? most : g);
-}
-
 uint32_t slice_members() {
 	const char *e = getenv("URMAPX_TEST_SORT_SLICE");
 	const long v = e ? atol(e) : 0;
 	return v >= 1 && v <= (long)DEFAULT_SLICE ? (uint32_t)v : DEFAULT_SLICE;
 }
+
+}  // namespace
+
+// ---- what markdup.hip uses too (declared in bam_sort_dev.h) ----
+namespace urx {
+namespace bamsort {
+
+thread_local double t_alloc_s = 0;
 
 // out[0 .. n] = exclusive sums of in[0 .. n), the total in out[n]; sums: MAX_RUNS + 1 entries of scratch
 template <class TI, class TO>
@@ -321,11 +297,6 @@ void scan_launch(const TI *in, uint32_t n, TO *out, uint64_t *sums) {
 }
 
 // stable sort of (key, val)[0 .. n) by the low `bits` bits of the key, between two pairs of arrays; `in` says where the result is
-struct SortArrays {
-	uint64_t *key[2];
-	uint32_t *val[2];
-	int in = 0;
-};
 uint32_t radix_sort(SortArrays &S, uint32_t n, uint32_t bits, uint32_t *hist) {
 	if (n == 0) return 0;
 	const uint32_t tiles = (n + TILE - 1) / TILE, blocks = tiles < MAX_BLOCKS ? tiles : MAX_BLOCKS;
@@ -341,6 +312,13 @@ uint32_t radix_sort(SortArrays &S, uint32_t n, uint32_t bits, uint32_t *hist) {
 	}
 	return passes;
 }
+template void scan_launch<uint32_t, uint64_t>(const uint32_t *, uint32_t, uint64_t *, uint64_t *);
+template void scan_launch<uint32_t, uint32_t>(const uint32_t *, uint32_t, uint32_t *, uint64_t *);
+
+}  // namespace bamsort
+}  // namespace urx
+
+namespace {
 
 size_t slice_scratch_bytes(size_t slice_bytes) {
 	// the slice, its members at their worst, the compressor's staging slot per member and its token arenas (bgzf_gpu.hip)
@@ -348,7 +326,7 @@ size_t slice_scratch_bytes(size_t slice_bytes) {
 }
 
 int sort_device(int device, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts,
-                urmapx_bam_sort_result *out) {
+                urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
 	auto t = Clock::now();
 	std::vector<uint64_t> offs;
 	uint32_t max_pos = 0;
@@ -458,6 +436,15 @@ int sort_device(int device, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, 
 	}
 	out->index_s = since(t);
 
+	// markdup: bit 0x400 of the resident records, before the first of them is copied into order.  The two key arrays, the sorted
+	// lengths, the second sort's record numbers and the ends are used up by now; val_s, d_dst, d_off and d_rec are not
+	if (md) {
+		t = Clock::now();
+		const MarkdupArrays A{d_rec.p, d_off.p, n, n_ref, {key_s, key_f}, {val_f, d_val[2].p}, d_end.p, d_hist.p, d_sums.p};
+		if ((rc = markdup_device(A, md))) return rc;
+		md->markdup_s = since(t);
+	}
+
 	// the sorted stream, a slice at a time: gather, deflate, copy back
 	const size_t slice_bytes = (size_t)slice_members() * MEMBER;
 	const size_t slice_cap = slice_bytes < n_bytes ? slice_bytes : n_bytes, z_cap = urmapx_bgzf_bound(slice_cap);
@@ -515,22 +502,39 @@ uint64_t urmapx_bam_sort_device_bytes(size_t n_bytes, uint64_t n_records) {
 	return (uint64_t)n_bytes + 48u * n_records + slice_scratch_bytes(slice < n_bytes ? slice : n_bytes) + ((uint64_t)1 << 20);
 }
 
-int urmapx_bam_sort(int device, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
-                    size_t n_starts, urmapx_bam_sort_result *out) {
+uint64_t urmapx_bam_sort_markdup_device_bytes(size_t n_bytes, uint64_t n_records) {
+	// ends and best words: 8 bytes each; what a record is and where a pair begins: 4 bytes each (markdup.hip)
+	return urmapx_bam_sort_device_bytes(n_bytes, n_records) + 24u * n_records + 4096u;
+}
+
+static int sort_entry(int device, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
+                      size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
 	if (!out || (n_bytes && !records) || (n_starts && !starts)) return URMAPX_E_ARG;
 	memset(out, 0, sizeof *out);
+	if (md) memset(md, 0, sizeof *md);
 	int count = 0;
 	if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) { (void)hipGetLastError(); return URMAPX_E_NODEVICE; }
 	int rc;
 	try {
 		t_alloc_s = 0;
-		rc = sort_device(device, (const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, out);
+		rc = sort_device(device, (const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
 	} catch (const std::bad_alloc &) {
 		rc = URMAPX_E_NOMEM;
 	}
 	out->alloc_s = t_alloc_s;  // (the arrays are freed by now)
 	if (rc) urmapx_bam_sort_free(out);
 	return rc;
+}
+
+int urmapx_bam_sort(int device, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
+                    size_t n_starts, urmapx_bam_sort_result *out) {
+	return sort_entry(device, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, nullptr, out);
+}
+
+int urmapx_bam_sort_markdup(int device, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
+                            size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
+	if (!md) return URMAPX_E_ARG;
+	return sort_entry(device, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
 }
 
 }  // extern "C"

@@ -165,7 +165,8 @@ namespace {
 using Clock = std::chrono::steady_clock;
 double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::now() - t).count(); }
 
-int sort_host(const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts, urmapx_bam_sort_result *out) {
+int sort_host(const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts, urmapx_markdup_stats *md,
+              urmapx_bam_sort_result *out) {
 	auto t = Clock::now();
 	std::vector<uint64_t> offs;
 	uint32_t max_pos = 0;
@@ -186,6 +187,14 @@ int sort_host(const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_fr
 	std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
 	out->sort_s = since(t);
 
+	// markdup: what becomes of every record's bit 0x400, applied to the copy below (the caller's records stay as they are)
+	std::vector<uint8_t> action;
+	if (md) {
+		t = Clock::now();
+		if ((rc = markdup_host(rec, offs, action, md))) return rc;
+		md->markdup_s = since(t);
+	}
+
 	t = Clock::now();
 	std::vector<uint8_t> stream(n_bytes);
 	std::vector<uint64_t> dst(n + 1);
@@ -194,6 +203,8 @@ int sort_host(const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_fr
 		const uint64_t a = offs[perm[k]], len = offs[perm[k] + 1] - a;
 		dst[k] = at;
 		if (len) memcpy(stream.data() + at, rec + a, (size_t)len);
+		if (md && action[perm[k]] == MD_SET) stream[(size_t)at + FLAG_BYTE] |= FLAG_DUP_BIT;
+		else if (md && action[perm[k]] == MD_CLEAR) stream[(size_t)at + FLAG_BYTE] &= (uint8_t)~FLAG_DUP_BIT;
 		at += len;
 	}
 	dst[n] = at;
@@ -255,18 +266,30 @@ int sort_host(const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_fr
 
 extern "C" {
 
-int urmapx_bam_sort_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts, size_t n_starts,
-                         urmapx_bam_sort_result *out) {
+static int sort_host_entry(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts, size_t n_starts,
+                           urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
 	if (!out || (n_bytes && !records) || (n_starts && !starts)) return URMAPX_E_ARG;
 	memset(out, 0, sizeof *out);
+	if (md) memset(md, 0, sizeof *md);
 	int rc;
 	try {
-		rc = sort_host((const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, out);
+		rc = sort_host((const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
 	} catch (const std::bad_alloc &) {
 		rc = URMAPX_E_NOMEM;
 	}
 	if (rc) urmapx_bam_sort_free(out);
 	return rc;
+}
+
+int urmapx_bam_sort_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts, size_t n_starts,
+                         urmapx_bam_sort_result *out) {
+	return sort_host_entry(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, nullptr, out);
+}
+
+int urmapx_bam_sort_markdup_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
+                                 size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
+	if (!md) return URMAPX_E_ARG;
+	return sort_host_entry(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
 }
 
 void urmapx_bam_sort_free(urmapx_bam_sort_result *R) {

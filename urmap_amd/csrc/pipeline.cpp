@@ -1108,22 +1108,31 @@ struct Run {
 		rep.sam_text_bytes += hdr.size();
 		if (!bgzf_members(hdr)) { fail.raise(URMAPX_E_NOMEM, "out of memory"); return; }
 		urmapx_bam_sort_result S;
+		urmapx_markdup_stats M;
+		memset(&M, 0, sizeof M);
 		int rc;
 		const std::vector<uint64_t> starts = sink.kept_starts();
+		const bool markdup = opt.markdup != 0;
+		auto on_device = [&]() {
+			return markdup ? urmapx_bam_sort_markdup(phys(0), sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &M, &S)
+			               : urmapx_bam_sort(phys(0), sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &S);
+		};
 		if (getenv("URMAPX_HOST_TEXT") || getenv("URMAPX_HOST_SORT"))
-			rc = urmapx_bam_sort_host(sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &S);
+			rc = markdup ? urmapx_bam_sort_markdup_host(sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &M, &S)
+			             : urmapx_bam_sort_host(sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &S);
 		else {
-			rc = urmapx_bam_sort(phys(0), sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &S);
+			rc = on_device();
 			if (rc == URMAPX_E_NOMEM) {  // the device is full of lanes: this run's and the pool's go first (the mapping is over)
 				close();
 				LanePool::get().purge(nullptr);
-				rc = urmapx_bam_sort(phys(0), sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &S);
+				rc = on_device();
 			}
 			if (rc == URMAPX_E_NOMEM) {
 				size_t free_b = 0, total_b = 0;
 				(void)hipSetDevice(phys(0));
 				if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-				fail.raise(rc, "bam_sort: the records and the sort's arrays need " + std::to_string(urmapx_bam_sort_device_bytes((size_t)n_bytes, rep.reads)) +
+				const uint64_t need = markdup ? urmapx_bam_sort_markdup_device_bytes((size_t)n_bytes, rep.reads) : urmapx_bam_sort_device_bytes((size_t)n_bytes, rep.reads);
+				fail.raise(rc, "bam_sort: the records and the sort's arrays need " + std::to_string(need) +
 				                   " bytes on the device, " + std::to_string(free_b) + " are free");
 				return;
 			}
@@ -1150,6 +1159,14 @@ struct Run {
 			                "records %llu bytes %llu passes %u slices %u\n",
 			        rep.sort_s, S.scan_s, S.alloc_s, S.upload_s, S.sort_s, S.gather_s, S.deflate_s, S.copy_s, S.index_s, secs(tw0, now()),
 			        (unsigned long long)S.records, (unsigned long long)S.stream_bytes, S.sort_passes, S.slices);
+		if (markdup) {
+			rep.pairs_examined = M.pairs_examined; rep.pairs_duplicate = M.pairs_duplicate;
+			rep.fragments_examined = M.fragments_examined; rep.fragments_duplicate = M.fragments_duplicate;
+			rep.markdup_s = M.markdup_s;
+			if (getenv("URMAPX_VERBOSE"))  // (scripts/markdup_bench.py reads this line)
+				fprintf(stderr, "markdup seconds: %.4f; pairs %llu duplicate %llu fragments %llu duplicate %llu\n", M.markdup_s, (unsigned long long)M.pairs_examined,
+				        (unsigned long long)M.pairs_duplicate, (unsigned long long)M.fragments_examined, (unsigned long long)M.fragments_duplicate);
+		}
 		urmapx_bam_sort_free(&S);
 		trace.add("sort", -1, 0, t0);
 	}
@@ -1956,6 +1973,7 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
 		                  opt->discard_sam ? "bam_sort with discard_sam: there is nothing to sort" : nullptr;
 		if (why) { say(err, errcap, why); return URMAPX_E_ARG; }
 	}
+	if (opt->markdup && !opt->bam_sort) { say(err, errcap, "markdup needs bam_sort: the duplicates are marked while the records are sorted"); return URMAPX_E_ARG; }
 	const int shards = opt->sam_shards > 1 ? opt->sam_shards : 1;
 	if (shards == 1) return map_files_impl(I, opt, InputRange(), fastq1, fastq2, samout, tabout, report, err, errcap);
 	const bool paired = fastq2 != nullptr;

@@ -392,5 +392,10 @@ int urmapx_bam_sort(int, const void *records, size_t n_bytes, uint32_t n_ref, ui
                     urmapx_bam_sort_result *out) {
 	return urmapx_bam_sort_host(records, n_bytes, n_ref, in_front, starts, n_starts, out);
 }
+int urmapx_bam_sort_markdup(int, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts,
+                            urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
+	return urmapx_bam_sort_markdup_host(records, n_bytes, n_ref, in_front, starts, n_starts, md, out);
+}
 uint64_t urmapx_bam_sort_device_bytes(size_t n_bytes, uint64_t n_records) { return n_bytes + 48u * n_records; }
+uint64_t urmapx_bam_sort_markdup_device_bytes(size_t n_bytes, uint64_t n_records) { return n_bytes + 72u * n_records; }
 }

@@ -64,6 +64,7 @@ struct Opts {
 	std::string bamout; // -bamout: a BAM file in -samout's place, records encoded and deflated on the device
 	bool veryfast = false, quiet = false, minq_given = false, host_build = false, notrunclabels = false;
 	bool sort = false;  // -sort: the -bamout file in coordinate order, with its .bai index
+	bool markdup = false;  // -markdup: with -sort, flag 0x400 on the duplicates
 	std::string tags, rg;  // -tags NM,MD,AS and -rg '@RG\tID:..': optional fields of the records, the read group's header line
 	bool tags_given = false, rg_given = false;
 	bool trunclabels = false, wordlength_given = false;
@@ -110,6 +111,7 @@ static Opts parse(int argc, char **argv) {
 		else if (a == "-bamout") o.bamout = val();
 		else if (a == "-host") o.host_build = true;
 		else if (a == "-sort") o.sort = true;
+		else if (a == "-markdup") o.markdup = true;
 		else if (a == "-tags") { o.tags = val(); o.tags_given = true; }
 		else if (a == "-rg") { o.rg = val(); o.rg_given = true; }
 		else if (a == "-quiet") o.quiet = true;
@@ -207,6 +209,7 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 	if (bam && !o.samout.empty()) die("-bamout replaces -samout: give one of the two");
 	if (bam && o.bgzf) die("-bgzf goes with -samout: a -bamout file is always BGZF");
 	const std::string &samout = bam ? o.bamout : o.samout;
+	if (o.markdup && !o.sort) die("-markdup needs -sort: the duplicates are marked while the records of the -bamout file are sorted");
 	if (o.sort) {
 		struct stat st;
 		if (!bam) die("-sort needs -bamout: it sorts the records of a BAM file");
@@ -246,6 +249,7 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 	mo.bam_sort = o.sort ? 1 : 0;
 	mo.tags = tag_mask;
 	mo.read_group = o.rg_given ? rg_line.data() : nullptr;
+	mo.markdup = o.markdup ? 1 : 0;
 	urmapx_map_report rep;
 	memset(&rep, 0, sizeof rep);
 	char err[1024];
@@ -288,6 +292,9 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 			progress_log(q, bam ? "%16s  Bytes of BAM records, %s written as BGZF (%.3f)\n\n" : "%16s  Bytes of SAM text, %s written as BGZF (%.3f)\n\n", commas(rep.sam_text_bytes).c_str(), commas(rep.sam_file_bytes).c_str(),
 			             rep.sam_text_bytes ? (double)rep.sam_file_bytes / (double)rep.sam_text_bytes : 0.0);
 		if (o.sort) progress_log(q, "%16.3f  Seconds to sort the records and write %s.bai\n\n", rep.sort_s, samout.c_str());
+		if (o.markdup)
+			progress_log(q, "%16.3f  Seconds to mark duplicates: %llu of %llu pairs, %llu of %llu fragments\n\n", rep.markdup_s, (unsigned long long)rep.pairs_duplicate,
+			             (unsigned long long)rep.pairs_examined, (unsigned long long)rep.fragments_duplicate, (unsigned long long)rep.fragments_examined);
 		if (o.minq_given && !paired) progress_log(q, "\nWARNING: Option -minq not used\n\n");
 	}
 	urmapx_index_close(I);
@@ -594,6 +601,7 @@ int main(int argc, char **argv) {
 	                "      -bamout out.bam: in place of -samout, a BAM file (records encoded and deflated on the GPU, unsorted);\n"
 	                "               with -samshards N every out.bam.0 .. out.bam.N-1 is a complete BAM file\n"
 	                "      -sort: with -bamout, the records in coordinate order (sorted on the GPU) and the index out.bam.bai beside the file\n"
+                "      -markdup: with -sort, flag 0x400 on duplicate reads (Picard's rule: same ends, the best qualities stay), marked on the GPU\n"
 	                "      -tags NM,MD,AS: these optional fields behind QUAL of every mapped record (any subset; computed on the GPU), SAM and BAM\n"
 	                "      -rg '@RG\\tID:x\\tSM:y': that line in the header in front of @PG and RG:Z:x on every record\n"
 	                "  urmap -make_ufi genome.fa -output index.ufi [-slots N] [-wordlength W] [-maxix M]\n"
