@@ -422,7 +422,9 @@ typedef struct urmapx_map_options {
 	                     * no chunk took the device road, urmapx_bam_sort_host) and the file and its index are written: header block in a
 	                     * member of its own, the sorted stream cut every 65 280 bytes, the end-of-file member.  The inflated bytes do not
 	                     * depend on gpus, streams, batch or host_threads.  If the device has no room (urmapx_bam_sort_device_bytes) the kept
-	                     * lanes are let go first; then URMAPX_E_NOMEM with the bytes needed and free in err.  URMAPX_E_ARG without bam, with
+	                     * lanes are let go first; then the records are streamed through the device with the memory that is free
+	                     * (urmapx_bam_sort_external), and only where the per-record arrays and one slice do not fit either the run ends
+	                     * with URMAPX_E_NOMEM, the least bytes needed and the bytes free in err.  URMAPX_E_ARG without bam, with
 	                     * sam_shards > 1 or with discard_sam; samout must be a regular file.  A failed run removes both files */
 	unsigned tags;      /* -tags: URMAPX_TAG_NM | _MD | _AS, the optional fields of every mapped record (see "Optional fields" below); 0: none */
 	const char *read_group; /* -rg: a complete @RG header line, tabs real, with an ID: field (urmapx_read_group_id); it goes into the header in
@@ -432,6 +434,11 @@ typedef struct urmapx_map_options {
 	                     * decided on first_gpu while the kept records lie there for the sort (urmapx_bam_sort_markdup; on the host road
 	                     * urmapx_bam_sort_markdup_host).  Only the flag half-words differ from the run without it: the order, the cuts and
 	                     * the index stay.  The counters go to the report.  URMAPX_E_ARG with the reason in err without bam_sort */
+	uint64_t sort_mem;  /* -sortmem (with bam_sort): the device memory the sort may take, in bytes.  The sort is planned from it directly
+	                     * (urmapx_bam_sort_plan_for): in core where that fits, else streamed through the device in as few partitions as
+	                     * fit (urmapx_bam_sort_external); URMAPX_E_NOMEM naming the least it takes where even one slice does not.  0: in
+	                     * core when the device has room, else streamed with what is free.  No effect on the host road.  URMAPX_E_ARG
+	                     * without bam_sort */
 } urmapx_map_options;
 typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:593-632) and where the time went */
 	uint64_t reads, mapped_q, mapped_lowq, unmapped, unsupported;
@@ -462,6 +469,7 @@ typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:59
 	double sort_s;                                   /* bam_sort: last record mapped .. last byte of samout and samout.bai written; inside `seconds` */
 	uint64_t pairs_examined, pairs_duplicate, fragments_examined, fragments_duplicate;  /* markdup: urmapx_markdup_stats of the run's records */
 	double markdup_s;                                /* markdup: the marking's share of sort_s */
+	uint32_t sort_partitions;                        /* bam_sort: partitions the sorted stream was made in on the external road; 0: in core (or the host) */
 } urmapx_map_report;
 /* fastq2 NULL: single-end (-map); else the mates' file (-map2 ... -reverse).  samout / tabout may be NULL.  The index
  * needs its host arrays, or to be resident on first_gpu already (the other devices' replicas are then copied from there).  Batch b is mapped on device
@@ -725,6 +733,15 @@ int urmapx_tags_batch(urmapx_ctx *, const uint8_t *bases, const uint64_t *offs, 
  * and the largest pos need, the gather of the records into sorted order, the index arrays and the deflate are kernels.  The sorted
  * stream is made, compressed and copied back in slices of a multiple of 65 280 bytes (URMAPX_TEST_SORT_SLICE=N: of N members), so the
  * device holds the unsorted records, the per-record arrays (urmapx_bam_sort_device_bytes says how much in all) and one slice.
+ * urmapx_bam_sort_external lifts "the records must fit": it plans from a budget of device bytes (urmapx_bam_sort_plan_for) and takes
+ * the road the plan names.  In core: the call above.  External: only the per-record arrays stay on the device -- 48 bytes a record,
+ * under marking 25 more -- and the records stream through two staging buffers in input order, 1 + P times: once for the keys, the ends,
+ * the flag-4 bits and what the marking reads, then once per partition of the sorted stream (P partitions, each a whole number of
+ * slices), where place_kernel copies the part of every staged record that falls into the partition to its place and sets or clears
+ * bit 0x400 on the way.  A filled partition is deflated slice by slice as in core, so the members, the stream and the index are the
+ * in-core call's.  budget_bytes 0: what hipMemGetInfo reports free less URMAPX_SORT_HEADROOM.  md NULL: no marking.  The per-record
+ * arrays must still fit the device, the result still lies in host memory.  URMAPX_TEST_SORT_PARTITION=N: external with partitions of N
+ * slices whatever the budget; URMAPX_TEST_SORT_STAGE=B: staged chunks of B bytes (whole records, one at the least).
  * urmapx_bam_sort_host: the same contract by std::stable_sort, plain loops and urmapx_bgzf_compress_host; no device.  The two give the
  * same inflated stream and, expressed in places of the stream, the same index; their compressed bytes differ.
  * starts[n_starts] (optional, NULL / 0: none): offsets in `records`, ascending, at which the caller knows a record to begin (the pieces
@@ -743,6 +760,12 @@ typedef struct urmapx_bam_sort_result {
 	double upload_s, sort_s, gather_s, deflate_s, copy_s, index_s;  /* records to the device; key + sort launches; gather launches; the
 	                          * compressor; members back to the host; index kernels and the .bai bytes.  Host version: sort_s (the sort),
 	                          * gather_s (the copy into order), deflate_s, index_s */
+	uint32_t external;       /* 1: the records were streamed through the device (urmapx_bam_sort_external's external road) */
+	uint32_t partitions;     /* external: pieces of the sorted stream that were filled one after the other; 0 in core */
+	uint64_t stage_chunks;   /* external: staged chunks of one pass over the input */
+	double stage_s;          /* external: the 1 + partitions passes over the input -- copies to the staging buffers, keys_kernel and the
+	                          * marking's record kernels in the first, place_kernel in the others (upload_s: the record starts alone;
+	                          * gather_s: 0) */
 } urmapx_bam_sort_result;
 int urmapx_bam_sort(int device, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
                     size_t n_starts, urmapx_bam_sort_result *out);
@@ -751,6 +774,18 @@ int urmapx_bam_sort_host(const void *records, size_t n_bytes, uint32_t n_ref, ui
 void urmapx_bam_sort_free(urmapx_bam_sort_result *);
 /* device memory urmapx_bam_sort takes for n_bytes of records in n_records records (slice and compressor scratch included) */
 uint64_t urmapx_bam_sort_device_bytes(size_t n_bytes, uint64_t n_records);
+/* The road urmapx_bam_sort_external takes for a budget of device bytes (host arithmetic).  In core (external 0; device_bytes =
+ * urmapx_bam_sort[_markdup]_device_bytes, the other fields 0) when that fits the budget.  Otherwise external: staged chunks of stage_bytes
+ * (a tuning value, n_bytes / 16 at the most), partitions of partition_bytes -- the largest whole number of slices with which
+ * device_bytes, the sum the allocations follow, stays within the budget -- and partitions = ceil(n_bytes / partition_bytes).
+ * URMAPX_E_NOMEM when even one slice does not fit: device_bytes is then the least budget that does. */
+typedef struct urmapx_bam_sort_plan {
+	int external;            /* 0: the in-core road */
+	uint64_t partition_bytes, partitions, stage_bytes, device_bytes;
+} urmapx_bam_sort_plan;
+int urmapx_bam_sort_plan_for(size_t n_bytes, uint64_t n_records, int markdup, uint64_t budget_bytes, urmapx_bam_sort_plan *plan);
+#define URMAPX_SORT_HEADROOM ((uint64_t)256 << 20)  /* device bytes left alone when the budget is taken from hipMemGetInfo */
+/* (urmapx_bam_sort_external itself is declared behind urmapx_markdup_stats, below) */
 
 /* ---- Duplicate marking (-bamout ... -sort -markdup): flag 0x400, decided while the records lie on the device for the sort ----
  * urmapx_bam_sort_markdup / _host: urmapx_bam_sort / _host with one step more.  Order, cuts and index are those of the plain call;
@@ -789,8 +824,12 @@ int urmapx_bam_sort_markdup(int device, const void *records, size_t n_bytes, uin
                             size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out);
 int urmapx_bam_sort_markdup_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
                                  size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out);
-/* device memory urmapx_bam_sort_markdup takes: urmapx_bam_sort_device_bytes and 24 bytes a record for ends, best words and roles */
+/* device memory urmapx_bam_sort_markdup takes: urmapx_bam_sort_device_bytes and 24 bytes a record for ends, best words and roles
+ * (urmapx_bam_sort_external with md on its external road: 25 a record, the record bytes not among them) */
 uint64_t urmapx_bam_sort_markdup_device_bytes(size_t n_bytes, uint64_t n_records);
+/* the planned sort ("Sorted BAM output" above): in core or streamed, as urmapx_bam_sort_plan_for says for budget_bytes; md NULL: no marking */
+int urmapx_bam_sort_external(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
+                             const uint64_t *starts, size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out);
 
 const char *urmapx_strerror(int code);
 /* "gfx950" etc. of the ctx's device; NULL without a device */

@@ -44,6 +44,7 @@ EXPORTS = (
     "urmapx_text_set_bam", "urmapx_bam_header", "urmapx_bam_se", "urmapx_bam_pe",
     "urmapx_bam_sort", "urmapx_bam_sort_host", "urmapx_bam_sort_free", "urmapx_bam_sort_device_bytes",
     "urmapx_bam_sort_markdup", "urmapx_bam_sort_markdup_host", "urmapx_bam_sort_markdup_device_bytes",
+    "urmapx_bam_sort_plan_for", "urmapx_bam_sort_external",
     "urmapx_calmd", "urmapx_ref_span", "urmapx_sam_se_tags", "urmapx_sam_pe_tags", "urmapx_bam_se_tags", "urmapx_bam_pe_tags",
     "urmapx_read_group_id", "urmapx_sam_header_rg", "urmapx_bam_header_rg", "urmapx_index_fetch_spans", "urmapx_text_set_tags",
     "urmapx_text_tag_ms", "urmapx_tags_batch",
@@ -81,6 +82,11 @@ class MapOptionsMarkdup(C.Structure):
     _fields_ = MapOptions._fields_ + [("markdup", C.c_int)]
 
 
+class MapOptionsSortMem(C.Structure):
+    """urmapx_map_options in full: MapOptionsMarkdup with sort_mem appended (the earlier layouts stay pinned by their tests)"""
+    _fields_ = MapOptionsMarkdup._fields_ + [("sort_mem", C.c_uint64)]
+
+
 class TagOptions(C.Structure):
     _fields_ = [("tags", C.c_uint), ("rg_id", C.c_char_p), ("ref", C.c_void_p * 2)]
 
@@ -99,11 +105,22 @@ class MapReport(C.Structure):
                 ("fragments_duplicate", C.c_uint64), ("markdup_s", C.c_double)]
 
 
+class MapReportSort(C.Structure):
+    """urmapx_map_report in full: MapReport with sort_partitions appended.  map_files passes this one."""
+    _fields_ = MapReport._fields_ + [("sort_partitions", C.c_uint32)]
+
+
 class BamSortResult(C.Structure):
     _fields_ = [("bgzf", C.c_void_p), ("bai", C.c_void_p), ("bgzf_bytes", C.c_size_t), ("bai_bytes", C.c_size_t),
                 ("stream_bytes", C.c_uint64), ("records", C.c_uint64), ("no_coor", C.c_uint64), ("sort_passes", C.c_uint32),
                 ("slices", C.c_uint32), ("scan_s", C.c_double), ("alloc_s", C.c_double), ("upload_s", C.c_double), ("sort_s", C.c_double),
-                ("gather_s", C.c_double), ("deflate_s", C.c_double), ("copy_s", C.c_double), ("index_s", C.c_double)]
+                ("gather_s", C.c_double), ("deflate_s", C.c_double), ("copy_s", C.c_double), ("index_s", C.c_double),
+                ("external", C.c_uint32), ("partitions", C.c_uint32), ("stage_chunks", C.c_uint64), ("stage_s", C.c_double)]
+
+
+class BamSortPlan(C.Structure):
+    _fields_ = [("external", C.c_int), ("partition_bytes", C.c_uint64), ("partitions", C.c_uint64), ("stage_bytes", C.c_uint64),
+                ("device_bytes", C.c_uint64)]
 
 
 class MarkdupStats(C.Structure):
@@ -219,7 +236,7 @@ def lib():
     L.urmapx_ctx_get_pair_info.argtypes = [vp, vp, u32]
     L.urmapx_tab_pe.restype = C.c_size_t
     L.urmapx_tab_pe.argtypes = [vp, vp, vp, vp, cp, u32, u32, i32, vp, C.c_size_t]
-    L.urmapx_map_files.argtypes = [vp, C.POINTER(MapOptionsMarkdup), cp, cp, cp, cp, C.POINTER(MapReport), cp, C.c_size_t]
+    L.urmapx_map_files.argtypes = [vp, C.POINTER(MapOptionsSortMem), cp, cp, cp, cp, C.POINTER(MapReportSort), cp, C.c_size_t]
     L.urmapx_host_pool_trim.argtypes = []
     L.urmapx_host_pool_trim.restype = None
     L.urmapx_text_create.argtypes = [vp, C.POINTER(vp)]
@@ -640,22 +657,24 @@ def gunzip_file(gz_path, out_path, threads=0):
 
 def map_files(index: "Index", fastq1, fastq2=None, samout=None, tabout=None, first_gpu=0, gpus=1, streams=2, host_threads=0,
               batch=0, veryfast=False, minq=10, cmdline=None, allow_unsupported=False, sam_shards=0, discard_sam=False, bgzf=False, bam=False,
-              bam_sort=False, tags=0, read_group=None, markdup=False):
+              bam_sort=False, tags=0, read_group=None, markdup=False, sort_mem=0):
     """urmap -map / -map2 file to file (cmd_map / cmd_map2) on an index that has its host arrays or is resident on
     first_gpu.  bgzf: samout is a BGZF file (-bgzf).  bam: samout is a BAM file (-bamout).  bam_sort (with bam):
     its records in coordinate order, with the index samout + ".bai" beside it (-sort).  tags: TAG_* bits (-tags), read_group: an @RG line
     with real tabs (-rg): the optional fields of the records.  markdup (with bam_sort): flag 0x400 on duplicate records (-markdup),
-    the counters in the report.  -> dict of State1::HitStats' counters and stage times."""
-    o = MapOptionsMarkdup(first_gpu, gpus, streams, host_threads, batch, int(veryfast), minq, cmdline.encode() if cmdline else None,
+    the counters in the report.  sort_mem (with bam_sort): the device bytes the sort may take (-sortmem); records that do not fit them
+    stream through the device, and the report's sort_partitions says in how many partitions.  -> dict of State1::HitStats' counters
+    and stage times."""
+    o = MapOptionsSortMem(first_gpu, gpus, streams, host_threads, batch, int(veryfast), minq, cmdline.encode() if cmdline else None,
                    int(sam_shards), int(discard_sam), int(bgzf), int(bam), int(bam_sort), int(tags),
-                   (read_group.encode("latin-1") if isinstance(read_group, str) else read_group), int(markdup))
-    rep = MapReport()
+                   (read_group.encode("latin-1") if isinstance(read_group, str) else read_group), int(markdup), int(sort_mem))
+    rep = MapReportSort()
     err = C.create_string_buffer(1024)
     enc = lambda p: os.fsencode(p) if p else None
     rc = lib().urmapx_map_files(index.h, C.byref(o), enc(fastq1), enc(fastq2), enc(samout), enc(tabout), C.byref(rep), err, len(err))
     if rc != 0 and not (rc == E_UNSUPPORTED and allow_unsupported):
         raise UrmapxError(rc, "urmapx_map_files: " + err.value.decode("latin-1"))
-    return {k: getattr(rep, k) for k, _ in MapReport._fields_}
+    return {k: getattr(rep, k) for k, _ in MapReportSort._fields_}
 
 
 def calmd(ref: bytes, cigar, seq: bytes):
@@ -695,20 +714,23 @@ def read_group_id(line):
     return out.value.decode("latin-1"), ident.value.decode("latin-1")
 
 
-def _bam_sort(fn_name, head, records, n_ref, in_front, report, starts=None, markdup=False):
+def _bam_sort(fn_name, head, records, n_ref, in_front, report, starts=None, markdup=False, budget=None):
     src = np.frombuffer(bytes(records), dtype=np.uint8)
     res = BamSortResult()
     md = MarkdupStats()
     L = lib()
-    if markdup:
+    if budget is not None:  # the planned call: one entry with or without marking (md NULL), the budget behind the device
+        fn_name, head = "urmapx_bam_sort_external", head + (int(budget),)
+    elif markdup:
         fn_name = fn_name.replace("urmapx_bam_sort", "urmapx_bam_sort_markdup")
     fn = getattr(L, fn_name)
-    fn.argtypes = ([C.c_int] * len(head) + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t] +
-                   ([C.POINTER(MarkdupStats)] if markdup else []) + [C.POINTER(BamSortResult)])
+    fn.argtypes = ([C.c_int] * (len(head) - (budget is not None)) + [C.c_uint64] * (budget is not None) +
+                   [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t] +
+                   ([C.POINTER(MarkdupStats)] if markdup or budget is not None else []) + [C.POINTER(BamSortResult)])
     L.urmapx_bam_sort_free.argtypes = [C.POINTER(BamSortResult)]
     L.urmapx_bam_sort_free.restype = None
     st = np.ascontiguousarray(starts if starts is not None else [], dtype=np.uint64)
-    tail = (C.byref(md), C.byref(res)) if markdup else (C.byref(res),)
+    tail = (C.byref(md), C.byref(res)) if markdup else (None, C.byref(res)) if budget is not None else (C.byref(res),)
     _check(fn(*head, src.ctypes.data if len(src) else None, len(src), int(n_ref), int(in_front), st.ctypes.data if len(st) else None, len(st),
               *tail), fn_name)
     try:
@@ -721,13 +743,31 @@ def _bam_sort(fn_name, head, records, n_ref, in_front, report, starts=None, mark
     return out + (rep,) if report else out
 
 
-def bam_sort(records: bytes, n_ref, device=0, bytes_in_front=0, report=False, starts=None, markdup=False):
+def bam_sort_plan(n_bytes, n_records, budget, markdup=False):
+    """the road urmapx_bam_sort_external takes for `budget` device bytes (urmapx_bam_sort_plan_for; host arithmetic, no device) -> dict of
+    external, partition_bytes, partitions, stage_bytes, device_bytes.  UrmapxError (E_NOMEM) where not even one slice fits: its `plan`
+    attribute is the dict, device_bytes the least budget that does."""
+    L = lib()
+    L.urmapx_bam_sort_plan_for.argtypes = [C.c_size_t, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(BamSortPlan)]
+    p = BamSortPlan()
+    rc = L.urmapx_bam_sort_plan_for(int(n_bytes), int(n_records), int(markdup), int(budget), C.byref(p))
+    plan = {k: int(getattr(p, k)) for k, _ in BamSortPlan._fields_}
+    if rc != 0:
+        e = UrmapxError(rc, "urmapx_bam_sort_plan_for: %d bytes are needed at the least" % plan["device_bytes"])
+        e.plan = plan
+        raise e
+    return plan
+
+
+def bam_sort(records: bytes, n_ref, device=0, bytes_in_front=0, report=False, starts=None, markdup=False, budget=None):
     """BAM alignment records back to back -> (the records in coordinate order as BGZF members, the bytes of their .bai index), sorted on
     the device (urmapx_bam_sort; bam_sort.hip).  bytes_in_front: what the file holds in front of the first member, for the index's
     virtual offsets.  report: a third item, the call's counters and step times.  starts: offsets at which records are known to begin (the
     chain is then walked from all of them at once).  markdup: flag 0x400 of the records says whether they are duplicates
-    (urmapx_bam_sort_markdup; markdup.hip), and the report holds the counters and markdup_s."""
-    return _bam_sort("urmapx_bam_sort", (int(device),), records, n_ref, bytes_in_front, report, starts, markdup)
+    (urmapx_bam_sort_markdup; markdup.hip), and the report holds the counters and markdup_s.  budget: device bytes the sort may take
+    (0: what is free): the call is urmapx_bam_sort_external, which streams the records through the device where they do not fit the
+    budget; the report's external, partitions, stage_chunks and stage_s say what it did."""
+    return _bam_sort("urmapx_bam_sort", (int(device),), records, n_ref, bytes_in_front, report, starts, markdup, budget)
 
 
 def bam_sort_host(records: bytes, n_ref, bytes_in_front=0, report=False, starts=None, markdup=False):

@@ -117,6 +117,35 @@ std::vector<uint8_t> write_bai(const IndexArrays &X, uint32_t n_ref, const std::
 int finish_result(urmapx_bam_sort_result *out, uint8_t *bgzf, size_t bgzf_bytes, uint64_t stream_bytes, uint64_t in_front,
                   const IndexArrays &X, uint32_t n_ref);
 
+// ---- the device sort's memory, as the plan (urmapx_bam_sort_plan_for, bam_sort_host.cpp) and the allocations (bam_sort.hip) count it ----
+constexpr uint32_t DEFAULT_SLICE = 2048;           // members of 65 280 bytes in one slice of the sorted stream
+constexpr uint64_t DEFAULT_STAGE = 16u << 20;      // bytes of one staged chunk on the external road (4, 16 and 64 MiB measured)
+constexpr uint64_t SORT_PER_RECORD = 48;           // off, dst, two keys: 8 bytes each; three record-number arrays and the ends: 4 bytes each
+constexpr uint64_t MARKDUP_PER_RECORD = 24;        // ends and best words: 8 bytes each; what a record is and where a pair begins: 4 bytes each
+constexpr uint64_t ACTION_PER_RECORD = 1;          // external road under markdup: what becomes of a record's bit 0x400
+constexpr uint64_t SORT_SLACK = (uint64_t)1 << 20; // the arrays per reference, the histograms, the scans' sums, the paddings
+
+// URMAPX_TEST_SORT_SLICE=N: slices of N members; _PARTITION=N: the external road with partitions of N slices; _STAGE=B: staged chunks of B bytes
+uint32_t slice_members();
+uint64_t test_partition_slices();  // 0: not set
+uint64_t test_stage_bytes();       // 0: not set
+// beside a slice of the stream: its members at their worst, the compressor's staging slot per member and its token arenas (bgzf_gpu.hip)
+size_t slice_scratch_bytes(size_t slice_bytes);
+// Device bytes of the external road: the per-record arrays, two staging buffers, one partition, one slice's members, the compressor's
+// scratch.  The one sum the plan and sort_device (which allocates these pieces, a partition no larger than the stream) both use.
+uint64_t external_device_bytes(size_t n_bytes, uint64_t n_records, bool markdup, uint64_t stage_bytes, uint64_t partition_bytes);
+// the plan for staged chunks of stage_bytes (the public function passes the default; the sort, a larger one where a record needs it)
+int plan_with_stage(size_t n_bytes, uint64_t n_records, bool markdup, uint64_t budget, uint64_t stage_bytes, urmapx_bam_sort_plan *plan);
+uint64_t default_stage_bytes(size_t n_bytes);
+// A staged chunk is a run of whole records [i0, i1) of at most stage_bytes, one record at the least; with `lookahead` record i1 (the
+// first of the next chunk) is staged behind it and counts.  -> i1
+inline uint64_t chunk_end(const uint64_t *offs, uint64_t n, uint64_t i0, uint64_t stage_bytes, bool lookahead) {
+	uint64_t i1 = i0 + 1;
+	const uint64_t la = lookahead ? 1u : 0u;
+	while (i1 < n && offs[i1 + 1 + la < n ? i1 + 1 + la : n] - offs[i0] <= stage_bytes) ++i1;
+	return i1;
+}
+
 // ---- duplicate marking (include/urmapx.h "Duplicate marking") ----
 constexpr uint32_t FLAG_BYTE = 19;     // the byte of a record that holds bit 0x400 of its flag, as its bit 0x04
 constexpr uint8_t FLAG_DUP_BIT = 0x04;

@@ -18,8 +18,13 @@
 //   bounds / extent / lin / bin_key / chunk_*   the index: first and last record of every reference and its largest end, the smallest
 //                    stream offset per 16 384-base window (atomicMin), a second sort of the record numbers by (reference, bin) with
 //                    the same two sort kernels, a flag where a chunk begins, a scan of the flags, the chunks
+//   place_fill / place_kernel   the external road (urmapx_bam_sort_external, where the records do not fit the device): only the
+//                    per-record arrays are resident, the records pass through two staging buffers in input order -- once for
+//                    keys_kernel (and what the marking reads), then once per partition of the sorted stream, where place_kernel
+//                    copies the part of every staged record that falls into the partition to its place, as gather_kernel copies
 #include "bam_sort_dev.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -29,22 +34,25 @@ using namespace urx::bamsort;
 
 namespace {
 
-// (the sizes of the sort's grids -- NT, TILE, MAX_BLOCKS, SCAN_NT, MAX_RUNS -- are in bam_sort_dev.h: markdup.hip sorts with them too)
-constexpr uint32_t DEFAULT_SLICE = 2048;  // members of 65 280 bytes in one slice of the sorted stream
+// (the sizes of the sort's grids -- NT, TILE, MAX_BLOCKS, SCAN_NT, MAX_RUNS -- are in bam_sort_dev.h: markdup.hip sorts with them too;
+// the slice, the staged chunk and the bytes per record in bam_sort.h: the plan counts with them on the host)
 
 __device__ __forceinline__ uint32_t load4(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 __device__ __forceinline__ uint64_t bcast64(uint64_t v, uint32_t from) {  // lane `from`'s value, in every lane
 	return (uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)from, 64) << 32 | (uint32_t)__shfl((int)(uint32_t)v, (int)from, 64);
 }
 
-__global__ __launch_bounds__(NT) void keys_kernel(const uint8_t *rec, const uint64_t *off, uint32_t n, KeyLayout K, uint64_t *key, uint32_t *val,
-                                                  uint32_t *end) {
-	for (uint32_t i = blockIdx.x * NT + threadIdx.x; i < n; i += gridDim.x * NT) {
-		const uint8_t *r = rec + off[i];
+// Records i0 .. i1 - 1 lie at rec + (off[i] - base): a staged chunk whose first byte is byte `base` of the input, or (base 0, all
+// records) the whole input.  flag4[i]: does the record carry flag 0x4 -- all bounds_kernel wants of a record's bytes
+__global__ __launch_bounds__(NT) void keys_kernel(const uint8_t *rec, uint64_t base, const uint64_t *off, uint32_t i0, uint32_t i1, KeyLayout K, uint64_t *key,
+                                                  uint32_t *val, uint32_t *end, uint32_t *flag4) {
+	for (uint64_t i = (uint64_t)i0 + blockIdx.x * NT + threadIdx.x; i < i1; i += gridDim.x * NT) {
+		const uint8_t *r = rec + (off[i] - base);
 		const uint32_t ref_id = load_u32(r + 4), pos = load_u32(r + 8);
 		key[i] = K.key(ref_id, pos);
-		val[i] = i;
+		val[i] = (uint32_t)i;
 		end[i] = ref_id == 0xFFFFFFFFu ? 0u : (uint32_t)ref_end(r, (uint32_t)(off[i + 1] - off[i]), pos);
+		flag4[i] = load_u32(r + 16) >> 16 & 4u;
 	}
 }
 
@@ -198,10 +206,73 @@ __global__ __launch_bounds__(NT) void gather_kernel(const uint8_t *rec, const ui
 	}
 }
 
+// ---- the external road: the records are not resident, they pass through a staging buffer in input order ----
+// where every record of the input goes in the sorted stream
+__global__ __launch_bounds__(NT) void place_fill_kernel(const uint32_t *val, const uint64_t *dst, uint32_t n, uint64_t *place) {
+	for (uint32_t k = blockIdx.x * NT + threadIdx.x; k < n; k += gridDim.x * NT) place[val[k]] = dst[k];
+}
+
+// Records i0 .. i1 - 1 lie in `stage` from byte `base` of the input on; `part` is the partition [s0, s1) of the sorted stream.  As in
+// gather_kernel a wavefront takes 64 records at a time, every LANE fetching where one of them goes, how long it is and what becomes of
+// its bit 0x400; then the wavefront copies, with all lanes, the part of each that lies inside the partition -- a record may begin in
+// front of it, end behind it or cover it whole -- in gather_kernel's form: bytes up to the destination's next word, whole words from
+// an unaligned source, bytes.  A record outside the partition is dropped on what the lanes fetched: its bytes are not read.  Byte 19
+// of a record (FLAG_BYTE) takes its bit from the action in the one lane that copies it, in whichever partition holds that byte.
+__global__ __launch_bounds__(NT) void place_kernel(const uint8_t *stage, uint64_t base, const uint64_t *off, uint32_t i0, uint32_t i1, const uint64_t *place,
+                                                   const uint8_t *action, uint64_t s0, uint64_t s1, uint8_t *part) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint64_t wave = ((uint64_t)blockIdx.x * NT + threadIdx.x) >> 6, n_waves = (uint64_t)gridDim.x * (NT / 64);
+	for (uint64_t first = i0 + wave * 64u; first < i1; first += n_waves * 64u) {
+		const uint64_t i = first + lane;
+		uint64_t my_d0 = 0, my_src = 0;
+		uint32_t my_len = 0, my_act = MD_KEEP;
+		if (i < i1) {
+			my_d0 = place[i];
+			my_src = off[i] - base;
+			my_len = (uint32_t)(off[i + 1] - off[i]);
+			if (action) my_act = action[i];
+		}
+		const uint32_t cnt = (uint32_t)(i1 - first < 64u ? i1 - first : 64u);
+		for (uint32_t t = 0; t < cnt; ++t) {
+			const uint64_t d0 = bcast64(my_d0, t), d1 = d0 + (uint32_t)__shfl((int)my_len, (int)t, 64);
+			const uint64_t lo = d0 > s0 ? d0 : s0, hi = d1 < s1 ? d1 : s1;
+			if (hi <= lo) continue;  // (the same in all lanes)
+			const uint32_t act = (uint32_t)__shfl((int)my_act, (int)t, 64);
+			const uint8_t *src = stage + bcast64(my_src, t) + (lo - d0);
+			uint8_t *to = part + (lo - s0);
+			const uint32_t len = (uint32_t)(hi - lo);
+			// the flag byte's place among the bytes copied here; none: beyond every index
+			const uint64_t fb64 = d0 + FLAG_BYTE;
+			const uint32_t fb = act != MD_KEEP && fb64 >= lo && fb64 < hi ? (uint32_t)(fb64 - lo) : 0xFFFFFFFFu;
+			const uint32_t set = act == MD_SET ? FLAG_DUP_BIT : 0u;
+			const uint32_t to_word = (uint32_t)((4u - ((uintptr_t)to & 3u)) & 3u), head = len < to_word ? len : to_word;
+			if (lane < head) {
+				const uint32_t b = src[lane];
+				to[lane] = (uint8_t)(lane == fb ? (b & ~(uint32_t)FLAG_DUP_BIT) | set : b);
+			}
+			const uint32_t words = (len - head) >> 2;
+			uint32_t *tw = (uint32_t *)(to + head);
+			const uint8_t *sw = src + head;
+			const uint32_t fw = fb != 0xFFFFFFFFu && fb >= head ? (fb - head) >> 2 : 0xFFFFFFFFu, fs = 8u * ((fb - head) & 3u);
+			for (uint32_t w = lane; w < words; w += 64u) {
+				uint32_t v = load4(sw + 4u * w);
+				if (w == fw) v = (v & ~((uint32_t)FLAG_DUP_BIT << fs)) | set << fs;
+				tw[w] = v;
+			}
+			const uint32_t done = head + 4u * words;
+			if (lane < len - done) {
+				const uint32_t b = src[done + lane];
+				to[done + lane] = (uint8_t)(done + lane == fb ? (b & ~(uint32_t)FLAG_DUP_BIT) | set : b);
+			}
+		}
+	}
+}
+
 // ---- the index ----
 // per sorted record: where its reference's records begin and end; the reference's largest end (one atomic per wavefront where its 64
-// records share the reference, which in sorted order is nearly everywhere); its records with flag 4
-__global__ __launch_bounds__(NT) void bounds_kernel(const uint8_t *rec, const uint64_t *off, const uint64_t *key, const uint32_t *val, const uint32_t *end,
+// records share the reference, which in sorted order is nearly everywhere); its records with flag 4 (has4[i]: keys_kernel's note of
+// record i, so no record's bytes are read here)
+__global__ __launch_bounds__(NT) void bounds_kernel(const uint32_t *has4, const uint64_t *key, const uint32_t *val, const uint32_t *end,
                                                     uint32_t n, KeyLayout K, uint32_t *first, uint32_t *last, uint32_t *max_end, uint32_t *flag4) {
 	const uint32_t rounds = (n + gridDim.x * NT - 1) / (gridDim.x * NT);
 	for (uint32_t it = 0; it < rounds; ++it) {  // (whole wavefronts stay together for the shuffles)
@@ -214,7 +285,7 @@ __global__ __launch_bounds__(NT) void bounds_kernel(const uint8_t *rec, const ui
 			if (k == n - 1 || K.ref_of(key[k + 1]) != r) last[r] = k;
 			if (r < K.n_ref) {
 				e = end[val[k]];
-				if (load_u32(rec + off[val[k]] + 16) >> 16 & 4u) atomicAdd(&flag4[r], 1u);
+				if (has4[val[k]]) atomicAdd(&flag4[r], 1u);
 			}
 		}
 		const uint32_t r0 = __shfl(r, 0, 64);
@@ -270,12 +341,6 @@ __global__ __launch_bounds__(NT) void chunk_write_kernel(const uint64_t *key2, c
 using Clock = std::chrono::steady_clock;
 double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::now() - t).count(); }
 
-uint32_t slice_members() {
-	const char *e = getenv("URMAPX_TEST_SORT_SLICE");
-	const long v = e ? atol(e) : 0;
-	return v >= 1 && v <= (long)DEFAULT_SLICE ? (uint32_t)v : DEFAULT_SLICE;
-}
-
 }  // namespace
 
 // ---- what markdup.hip uses too (declared in bam_sort_dev.h) ----
@@ -320,12 +385,28 @@ template void scan_launch<uint32_t, uint32_t>(const uint32_t *, uint32_t, uint32
 
 namespace {
 
-size_t slice_scratch_bytes(size_t slice_bytes) {
-	// the slice, its members at their worst, the compressor's staging slot per member and its token arenas (bgzf_gpu.hip)
-	return slice_bytes + urmapx_bgzf_bound(slice_bytes) + slice_bytes + slice_bytes / 64 + ((size_t)1024 * 255 << 10);
-}
+// the two streams of the external road: a staging buffer's copy and the kernels that read it go to the buffer's own stream, so the
+// kernels of one chunk run while the next chunk is copied
+struct StageStreams {
+	hipStream_t s[2] = {nullptr, nullptr};
+	int create() {
+		for (int b = 0; b < 2; ++b) HIP_TRY(hipStreamCreateWithFlags(&s[b], hipStreamNonBlocking));
+		return URMAPX_OK;
+	}
+	int wait() {
+		for (int b = 0; b < 2; ++b)
+			if (s[b]) HIP_TRY(hipStreamSynchronize(s[b]));
+		return URMAPX_OK;
+	}
+	~StageStreams() {
+		for (int b = 0; b < 2; ++b)
+			if (s[b]) (void)hipStreamDestroy(s[b]);
+	}
+};
 
-int sort_device(int device, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts,
+// budget == nullptr: the in-core road, whatever it takes (urmapx_bam_sort, urmapx_bam_sort_markdup).  Else the road the plan names for
+// *budget device bytes (urmapx_bam_sort_external).
+int sort_device(int device, const uint64_t *budget, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts,
                 urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
 	auto t = Clock::now();
 	std::vector<uint64_t> offs;
@@ -339,12 +420,48 @@ int sort_device(int device, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, 
 	const uint32_t bin_bits = max_pos < (1u << 29) ? 16u : 18u;  // (reg2bin's largest value: 37 448 below 2^29, 4681 + 2^17 in all)
 	const size_t n_ref1 = (size_t)n_ref + 1;
 
+	// the road; on the external one the staged chunks: chunk c is records cut[c] .. cut[c + 1] - 1, under marking with record cut[c + 1]
+	// behind it (first_kernel compares neighbours).  A staging buffer holds the largest of them: a record longer than the staged chunk
+	// asked for, or its successor, makes the buffers grow, and the partition is planned again around them
+	urmapx_bam_sort_plan P;
+	memset(&P, 0, sizeof P);
+	std::vector<uint32_t> cut;
+	const bool look = md != nullptr;
+	if (budget) {
+		if ((rc = plan_with_stage(n_bytes, n, md != nullptr, *budget, default_stage_bytes(n_bytes), &P))) return rc;
+		if (P.external) {
+			uint64_t need = 0;
+			for (uint64_t i0 = 0; i0 < n;) {
+				const uint64_t i1 = chunk_end(offs.data(), n, i0, P.stage_bytes, look), seen = look && i1 < n ? i1 + 1 : i1;
+				cut.push_back((uint32_t)i0);
+				need = std::max(need, offs[seen] - offs[i0]);
+				i0 = i1;
+			}
+			cut.push_back(n);
+			if (need > P.stage_bytes && (rc = plan_with_stage(n_bytes, n, md != nullptr, *budget, need, &P))) return rc;
+		}
+	}
+	const bool ext = P.external != 0;
+	out->external = ext;
+	out->partitions = (uint32_t)P.partitions;
+	out->stage_chunks = ext ? cut.size() - 1 : 0;
+
 	HIP_TRY(hipSetDevice(device));
-	Dev<uint8_t> d_rec;
+	Dev<uint8_t> d_rec, d_stage[2], d_part, d_action;
 	Dev<uint64_t> d_off, d_dst, d_key[2], d_sums, d_ext[2], d_win, d_lin;
 	Dev<uint32_t> d_val[3], d_end, d_hist, d_range, d_ref[4];
 	Dev<Chunk> d_chunks;
-	if ((rc = d_rec.alloc(n_bytes + 16)) || (rc = d_off.alloc((size_t)n + 1)) || (rc = d_dst.alloc((size_t)n + 1)) || (rc = d_key[0].alloc((size_t)n + 2)) ||
+	MarkdupOwn W;
+	StageStreams st;
+	if (ext) {  // (the pieces external_device_bytes counts, in its order; the partition is not larger than the stream)
+		const size_t part_cap = (size_t)std::min<uint64_t>(P.partition_bytes, n_bytes);
+		if ((md && ((rc = W.begin(n)) || (rc = d_action.alloc(n)))) || (rc = d_stage[0].alloc((size_t)P.stage_bytes + 16)) ||
+		    (rc = d_stage[1].alloc((size_t)P.stage_bytes + 16)) || (rc = d_part.alloc(part_cap + 16)) || (rc = st.create()))
+			return rc;
+		if (md) HIP_TRY(hipMemset(d_action.p, MD_KEEP, n ? n : 1));
+	} else if ((rc = d_rec.alloc(n_bytes + 16)))
+		return rc;
+	if ((rc = d_off.alloc((size_t)n + 1)) || (rc = d_dst.alloc((size_t)n + 1)) || (rc = d_key[0].alloc((size_t)n + 2)) ||
 	    (rc = d_key[1].alloc((size_t)n + 2)) || (rc = d_val[0].alloc((size_t)n + 1)) || (rc = d_val[1].alloc((size_t)n + 1)) ||
 	    (rc = d_val[2].alloc((size_t)n + 1)) || (rc = d_end.alloc(n)) || (rc = d_hist.alloc((size_t)256 * MAX_BLOCKS)) || (rc = d_sums.alloc(MAX_RUNS + 1)) ||
 	    (rc = d_range.alloc(2)) || (rc = d_ext[0].alloc(n_ref1)) || (rc = d_ext[1].alloc(n_ref1)) || (rc = d_win.alloc(n_ref1 + 1)))
@@ -353,14 +470,43 @@ int sort_device(int device, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, 
 		if ((rc = d_ref[k].alloc(n_ref1))) return rc;
 
 	t = Clock::now();
-	if (n_bytes) HIP_TRY(hipMemcpy(d_rec.p, rec, n_bytes, hipMemcpyHostToDevice));
+	if (!ext && n_bytes) HIP_TRY(hipMemcpy(d_rec.p, rec, n_bytes, hipMemcpyHostToDevice));
 	HIP_TRY(hipMemcpy(d_off.p, offs.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
 	out->upload_s = since(t);
 
-	// keys and the coordinate sort
+	// One pass over the input on the external road: chunk c goes to staging buffer c & 1 on that buffer's stream (a plain copy from the
+	// caller's pageable memory: the call returns when the bytes have left it), `launch` queues the chunk's kernels behind it, and the
+	// next chunk's copy runs while they do.  Before a buffer is written again its stream is waited for.
+	auto pass = [&](bool with_successor, auto &&launch) -> int {
+		const auto t0 = Clock::now();
+		HIP_TRY(hipStreamSynchronize(nullptr));
+		for (size_t c = 0; c + 1 < cut.size(); ++c) {
+			const int b = (int)(c & 1u);
+			const uint32_t i0 = cut[c], i1 = cut[c + 1], seen = with_successor && i1 < n ? i1 + 1u : i1;
+			const uint64_t bytes = offs[seen] - offs[i0];
+			if (bytes > P.stage_bytes) return URMAPX_E_NODEVICE;  // (never: the buffers were sized by these very chunks)
+			HIP_TRY(hipStreamSynchronize(st.s[b]));
+			if (bytes) HIP_TRY(hipMemcpyAsync(d_stage[b].p, rec + offs[i0], (size_t)bytes, hipMemcpyHostToDevice, st.s[b]));
+			int r = launch((const uint8_t *)d_stage[b].p, offs[i0], i0, i1, st.s[b]);
+			if (r) return r;
+		}
+		HIP_TRY(hipGetLastError());
+		int r = st.wait();
+		out->stage_s += since(t0);
+		return r;
+	};
+
+	// keys and the coordinate sort.  (d_val[2] is free until the second sort: the flag-4 notes live there up to bounds_kernel)
 	t = Clock::now();
 	SortArrays S{{d_key[0].p, d_key[1].p}, {d_val[0].p, d_val[1].p}, 0};
-	if (n) hipLaunchKernelGGL(keys_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, (const uint8_t *)d_rec.p, (const uint64_t *)d_off.p, n, K, S.key[0], S.val[0], d_end.p);
+	auto keys = [&](const uint8_t *at, uint64_t base, uint32_t i0, uint32_t i1, hipStream_t s) -> int {
+		hipLaunchKernelGGL(keys_kernel, dim3(grid_for(i1 - i0)), dim3(NT), 0, s, at, base, (const uint64_t *)d_off.p, i0, i1, K, S.key[0], S.val[0], d_end.p, d_val[2].p);
+		return md && ext ? markdup_chunk(W, at, base, d_off.p, i0, i1, n, s) : URMAPX_OK;
+	};
+	if (ext) {
+		if ((rc = pass(look, keys))) return rc;
+		t = Clock::now();
+	} else if (n) (void)keys(d_rec.p, 0, 0, n, nullptr);
 	out->sort_passes = radix_sort(S, n, K.bits(), d_hist.p);
 	uint64_t *const key_s = S.key[S.in], *const key_f = S.key[1 - S.in];
 	uint32_t *const val_s = S.val[S.in], *const val_f = S.val[1 - S.in];
@@ -381,7 +527,7 @@ int sort_device(int device, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, 
 	HIP_TRY(hipMemset(d_ref[0].p, 0xFF, n_ref1 * 4));
 	for (int k = 1; k < 4; ++k) HIP_TRY(hipMemset(d_ref[k].p, 0, n_ref1 * 4));
 	if (n) {
-		hipLaunchKernelGGL(bounds_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, (const uint8_t *)d_rec.p, (const uint64_t *)d_off.p, (const uint64_t *)key_s,
+		hipLaunchKernelGGL(bounds_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, (const uint32_t *)d_val[2].p, (const uint64_t *)key_s,
 		                   (const uint32_t *)val_s, (const uint32_t *)d_end.p, n, K, d_ref[0].p, d_ref[1].p, d_ref[2].p, d_ref[3].p);
 		hipLaunchKernelGGL(extent_kernel, dim3(grid_for(n_ref1, 1u << 22)), dim3(NT), 0, nullptr, (const uint32_t *)d_ref[0].p, (const uint32_t *)d_ref[1].p,
 		                   (const uint64_t *)d_dst.p, (uint32_t)n_ref1, d_ext[0].p, d_ext[1].p);
@@ -438,10 +584,13 @@ int sort_device(int device, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, 
 
 	// markdup: bit 0x400 of the resident records, before the first of them is copied into order.  The two key arrays, the sorted
 	// lengths, the second sort's record numbers and the ends are used up by now; val_s, d_dst, d_off and d_rec are not
+	// On the external road what it reads of the records was taken as they passed (markdup_chunk in the first pass) and the decisions go
+	// to d_action, for place_kernel
 	if (md) {
 		t = Clock::now();
-		const MarkdupArrays A{d_rec.p, d_off.p, n, n_ref, {key_s, key_f}, {val_f, d_val[2].p}, d_end.p, d_hist.p, d_sums.p};
-		if ((rc = markdup_device(A, md))) return rc;
+		if (!ext && ((rc = W.begin(n)) || (rc = markdup_chunk(W, d_rec.p, 0, d_off.p, 0, n, n, nullptr)))) return rc;
+		const MarkdupArrays A{d_rec.p, d_off.p, n, n_ref, {key_s, key_f}, {val_f, d_val[2].p}, d_end.p, d_hist.p, d_sums.p, ext ? d_action.p : nullptr};
+		if ((rc = markdup_device(A, W, md))) return rc;
 		md->markdup_s = since(t);
 	}
 
@@ -450,12 +599,28 @@ int sort_device(int device, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, 
 	const size_t slice_cap = slice_bytes < n_bytes ? slice_bytes : n_bytes, z_cap = urmapx_bgzf_bound(slice_cap);
 	Dev<uint8_t> d_slice, d_z;
 	Dev<uint64_t> d_used;
-	if ((rc = d_slice.alloc(slice_cap + 16)) || (rc = d_z.alloc(z_cap + 16)) || (rc = d_used.alloc(1))) return rc;
+	if ((!ext && (rc = d_slice.alloc(slice_cap + 16))) || (rc = d_z.alloc(z_cap + 16)) || (rc = d_used.alloc(1))) return rc;
 	urmapx_bgzf *Z = nullptr;
 	if ((rc = urmapx_bgzf_create(device, nullptr, &Z))) return rc;
 	const size_t host_cap = urmapx_bgzf_bound(n_bytes);
 	uint8_t *z = (uint8_t *)malloc(host_cap ? host_cap : 1);
 	size_t z_bytes = 0;
+	// a slice that lies on the device: deflate, copy back
+	auto members = [&](const uint8_t *d_in, size_t bytes) -> int {
+		auto t0 = Clock::now();
+		int r = urmapx_bgzf_compress_device(device, d_in, bytes, d_z.p, z_cap, d_used.p, 0, Z);
+		if (r) return r;
+		uint64_t used = 0;
+		HIP_TRY(hipMemcpy(&used, d_used.p, 8, hipMemcpyDeviceToHost));
+		out->deflate_s += since(t0);
+		if (used > z_cap || z_bytes + used > host_cap) return URMAPX_E_NODEVICE;
+		t0 = Clock::now();
+		if (used) HIP_TRY(hipMemcpy(z + z_bytes, d_z.p, (size_t)used, hipMemcpyDeviceToHost));
+		out->copy_s += since(t0);
+		z_bytes += (size_t)used;
+		++out->slices;
+		return URMAPX_OK;
+	};
 	auto slices = [&]() -> int {
 		if (!z) return URMAPX_E_NOMEM;
 		for (uint64_t s0 = 0; s0 < n_bytes; s0 += slice_bytes) {
@@ -467,22 +632,35 @@ int sort_device(int device, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, 
 			HIP_TRY(hipGetLastError());
 			HIP_TRY(hipStreamSynchronize(nullptr));
 			out->gather_s += since(t0);
-			t0 = Clock::now();
-			int r = urmapx_bgzf_compress_device(device, d_slice.p, (size_t)(s1 - s0), d_z.p, z_cap, d_used.p, 0, Z);
+			int r = members(d_slice.p, (size_t)(s1 - s0));
 			if (r) return r;
-			uint64_t used = 0;
-			HIP_TRY(hipMemcpy(&used, d_used.p, 8, hipMemcpyDeviceToHost));
-			out->deflate_s += since(t0);
-			if (used > z_cap || z_bytes + used > host_cap) return URMAPX_E_NODEVICE;
-			t0 = Clock::now();
-			if (used) HIP_TRY(hipMemcpy(z + z_bytes, d_z.p, (size_t)used, hipMemcpyDeviceToHost));
-			out->copy_s += since(t0);
-			z_bytes += (size_t)used;
-			++out->slices;
 		}
 		return URMAPX_OK;
 	};
-	rc = slices();
+	// The external road: where every record of the input goes (into key_f: both key arrays are used up), then partition after partition:
+	// the input passes through the staging buffers once more, place_kernel fills the partition, and its slices -- partitions end on
+	// slice ends, so they are the in-core road's slices -- are deflated and copied back
+	auto partitions = [&]() -> int {
+		if (!z) return URMAPX_E_NOMEM;
+		uint64_t *const place = key_f;
+		if (n) hipLaunchKernelGGL(place_fill_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, (const uint32_t *)val_s, (const uint64_t *)d_dst.p, n, place);
+		HIP_TRY(hipGetLastError());
+		for (uint64_t p0 = 0; p0 < n_bytes; p0 += P.partition_bytes) {
+			const uint64_t p1 = p0 + P.partition_bytes < n_bytes ? p0 + P.partition_bytes : n_bytes;
+			int r = pass(false, [&](const uint8_t *at, uint64_t base, uint32_t i0, uint32_t i1, hipStream_t s) -> int {
+				hipLaunchKernelGGL(place_kernel, dim3(grid_for(i1 - i0)), dim3(NT), 0, s, at, base, (const uint64_t *)d_off.p, i0, i1, (const uint64_t *)place,
+				                   (const uint8_t *)(md ? d_action.p : nullptr), p0, p1, d_part.p);
+				return URMAPX_OK;
+			});
+			if (r) return r;
+			for (uint64_t s0 = p0; s0 < p1; s0 += slice_bytes) {
+				const uint64_t s1 = s0 + slice_bytes < p1 ? s0 + slice_bytes : p1;
+				if ((r = members(d_part.p + (s0 - p0), (size_t)(s1 - s0)))) return r;
+			}
+		}
+		return URMAPX_OK;
+	};
+	rc = ext ? partitions() : slices();
 	urmapx_bgzf_destroy(Z);
 	if (rc) { free(z); return rc; }
 	if (uint8_t *fit = (uint8_t *)realloc(z, z_bytes ? z_bytes : 1)) z = fit;
@@ -498,16 +676,14 @@ extern "C" {
 
 uint64_t urmapx_bam_sort_device_bytes(size_t n_bytes, uint64_t n_records) {
 	const size_t slice = (size_t)slice_members() * MEMBER;
-	// off, dst, two keys: 8 bytes each; three record-number arrays and the ends: 4 bytes each
-	return (uint64_t)n_bytes + 48u * n_records + slice_scratch_bytes(slice < n_bytes ? slice : n_bytes) + ((uint64_t)1 << 20);
+	return (uint64_t)n_bytes + SORT_PER_RECORD * n_records + slice_scratch_bytes(slice < n_bytes ? slice : n_bytes) + SORT_SLACK;
 }
 
 uint64_t urmapx_bam_sort_markdup_device_bytes(size_t n_bytes, uint64_t n_records) {
-	// ends and best words: 8 bytes each; what a record is and where a pair begins: 4 bytes each (markdup.hip)
-	return urmapx_bam_sort_device_bytes(n_bytes, n_records) + 24u * n_records + 4096u;
+	return urmapx_bam_sort_device_bytes(n_bytes, n_records) + MARKDUP_PER_RECORD * n_records + 4096u;
 }
 
-static int sort_entry(int device, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
+static int sort_entry(int device, const uint64_t *budget, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
                       size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
 	if (!out || (n_bytes && !records) || (n_starts && !starts)) return URMAPX_E_ARG;
 	memset(out, 0, sizeof *out);
@@ -517,7 +693,14 @@ static int sort_entry(int device, const void *records, size_t n_bytes, uint32_t 
 	int rc;
 	try {
 		t_alloc_s = 0;
-		rc = sort_device(device, (const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
+		uint64_t have = budget ? *budget : 0;
+		if (budget && have == 0) {  // what is free, less the headroom
+			size_t free_b = 0, total_b = 0;
+			HIP_TRY(hipSetDevice(device));
+			HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+			have = free_b > URMAPX_SORT_HEADROOM ? (uint64_t)free_b - URMAPX_SORT_HEADROOM : 1u;
+		}
+		rc = sort_device(device, budget ? &have : nullptr, (const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
 	} catch (const std::bad_alloc &) {
 		rc = URMAPX_E_NOMEM;
 	}
@@ -528,13 +711,18 @@ static int sort_entry(int device, const void *records, size_t n_bytes, uint32_t 
 
 int urmapx_bam_sort(int device, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
                     size_t n_starts, urmapx_bam_sort_result *out) {
-	return sort_entry(device, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, nullptr, out);
+	return sort_entry(device, nullptr, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, nullptr, out);
 }
 
 int urmapx_bam_sort_markdup(int device, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
                             size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
 	if (!md) return URMAPX_E_ARG;
-	return sort_entry(device, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
+	return sort_entry(device, nullptr, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
+}
+
+int urmapx_bam_sort_external(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
+                             const uint64_t *starts, size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
+	return sort_entry(device, &budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
 }
 
 }  // extern "C"

@@ -59,10 +59,23 @@ struct SortArrays {
 };
 uint32_t radix_sort(SortArrays &S, uint32_t n, uint32_t bits, uint32_t *hist);
 
-// The marking (markdup.hip), inside the device sort once the index arrays are made and before the first slice is gathered: bit 0x400 of
-// the eligible records in `rec` (n records at off[0 .. n], as they came) is set or cleared, the counters go to md.  key / val: the
-// sort's two key arrays (n + 2 entries each) and two of its record-number arrays (n + 1), free by then; score: n entries (the sort's
-// array of ends); hist, sums: as above.  It allocates 24 bytes a record of its own.
+// The marking (markdup.hip) in two steps.
+// 1. What it reads of the records' bytes -- ends, scores, refIDs, which neighbours are pairs -- goes into its own arrays (24 bytes a
+//    record: MarkdupOwn), a chunk of records at a time: records i0 .. i1 - 1 lie at rec + (off[i] - base), and unless i1 is n record i1
+//    lies behind them.  In core that is one chunk of all records (base 0) just before step 2; on the external road every staged chunk of
+//    the first pass, so begin() comes before that pass.
+// 2. Inside the device sort once the index arrays are made and before the first record is copied into order: the groups and the
+//    decisions, from the arrays alone.  Bit 0x400 of the eligible records is set or cleared in `rec` (n records at off[0 .. n], as they
+//    came), or, with `action` (n bytes, MD_KEEP at first; rec unused), the decision is stored there.  The counters go to md.  key / val:
+//    the sort's two key arrays (n + 2 entries each) and two of its record-number arrays (n + 1), free by then; score: n entries (the
+//    sort's array of ends); hist, sums: as above.
+struct MarkdupOwn {
+	Dev<uint64_t> end, best;
+	Dev<uint32_t> what, first;
+	Dev<unsigned long long> stat;
+	int begin(uint32_t n);  // the arrays and the statistics block
+};
+int markdup_chunk(const MarkdupOwn &W, const uint8_t *rec, uint64_t base, const uint64_t *off, uint32_t i0, uint32_t i1, uint32_t n, hipStream_t stream);
 struct MarkdupArrays {
 	uint8_t *rec;
 	const uint64_t *off;
@@ -71,8 +84,9 @@ struct MarkdupArrays {
 	uint32_t *val[2];
 	uint32_t *score, *hist;
 	uint64_t *sums;
+	uint8_t *action;
 };
-int markdup_device(const MarkdupArrays &A, urmapx_markdup_stats *md);
+int markdup_device(const MarkdupArrays &A, const MarkdupOwn &W, urmapx_markdup_stats *md);
 
 }  // namespace bamsort
 }  // namespace urx

@@ -156,6 +156,66 @@ int finish_result(urmapx_bam_sort_result *out, uint8_t *bgzf, size_t bgzf_bytes,
 	return URMAPX_OK;
 }
 
+// ---- the device sort's plan: host arithmetic, shared with bam_sort.hip ----
+namespace {
+uint64_t env_number(const char *name, uint64_t most) {
+	const char *e = getenv(name);
+	const long long v = e ? atoll(e) : 0;
+	return v >= 1 && (uint64_t)v <= most ? (uint64_t)v : 0;
+}
+}  // namespace
+uint32_t slice_members() {
+	const uint64_t v = env_number("URMAPX_TEST_SORT_SLICE", DEFAULT_SLICE);
+	return v ? (uint32_t)v : DEFAULT_SLICE;
+}
+uint64_t test_partition_slices() { return env_number("URMAPX_TEST_SORT_PARTITION", (uint64_t)1 << 32); }
+uint64_t test_stage_bytes() { return env_number("URMAPX_TEST_SORT_STAGE", (uint64_t)1 << 40); }
+
+size_t slice_scratch_bytes(size_t slice_bytes) {
+	return slice_bytes + urmapx_bgzf_bound(slice_bytes) + slice_bytes + slice_bytes / 64 + ((size_t)1024 * 255 << 10);
+}
+
+uint64_t external_device_bytes(size_t n_bytes, uint64_t n_records, bool markdup, uint64_t stage_bytes, uint64_t partition_bytes) {
+	const size_t slice = (size_t)slice_members() * MEMBER, slice_cap = slice < n_bytes ? slice : n_bytes;
+	const uint64_t per_record = SORT_PER_RECORD + (markdup ? MARKDUP_PER_RECORD + ACTION_PER_RECORD : 0u);
+	// (a partition is not larger than the stream; the slice itself lies inside it: slice_scratch_bytes counts it, so it goes off again)
+	const uint64_t part = partition_bytes < n_bytes ? partition_bytes : (uint64_t)n_bytes;
+	return per_record * n_records + 2u * stage_bytes + part + (slice_scratch_bytes(slice_cap) - slice_cap) + SORT_SLACK + (markdup ? 4096u : 0u);
+}
+
+uint64_t default_stage_bytes(size_t n_bytes) {
+	if (const uint64_t t = test_stage_bytes()) return t;
+	const uint64_t cap = (uint64_t)n_bytes / 16u;  // (small inputs plan sensibly: two buffers are an eighth of them at the most)
+	return DEFAULT_STAGE < cap ? DEFAULT_STAGE : cap;
+}
+
+int plan_with_stage(size_t n_bytes, uint64_t n_records, bool markdup, uint64_t budget, uint64_t stage_bytes, urmapx_bam_sort_plan *plan) {
+	memset(plan, 0, sizeof *plan);
+	const uint64_t forced = test_partition_slices();
+	const uint64_t in_core = markdup ? urmapx_bam_sort_markdup_device_bytes(n_bytes, n_records) : urmapx_bam_sort_device_bytes(n_bytes, n_records);
+	if (!forced && in_core <= budget) {
+		plan->device_bytes = in_core;
+		return URMAPX_OK;
+	}
+	const uint64_t slice = (uint64_t)slice_members() * MEMBER;
+	const uint64_t whole = ((uint64_t)n_bytes + slice - 1) / slice;  // slices of the whole stream: a partition is never larger
+	const uint64_t least = whole ? 1u : 0u;
+	const uint64_t fixed = external_device_bytes(n_bytes, n_records, markdup, stage_bytes, 0);
+	plan->external = 1;
+	plan->stage_bytes = stage_bytes;
+	// the most slices that fit: all of them where the whole stream does (the last slice may be a short one), else whole slices only
+	uint64_t slices = forced ? forced : budget >= fixed + n_bytes ? whole : budget > fixed ? (budget - fixed) / slice : 0u;
+	if (slices > whole) slices = whole;
+	if (slices < least) {
+		plan->device_bytes = external_device_bytes(n_bytes, n_records, markdup, stage_bytes, slice);
+		return URMAPX_E_NOMEM;
+	}
+	plan->partition_bytes = slices * slice;
+	plan->partitions = slices ? ((uint64_t)n_bytes + plan->partition_bytes - 1) / plan->partition_bytes : 0u;
+	plan->device_bytes = external_device_bytes(n_bytes, n_records, markdup, stage_bytes, plan->partition_bytes);
+	return URMAPX_OK;
+}
+
 }  // namespace bamsort
 }  // namespace urx
 
@@ -290,6 +350,11 @@ int urmapx_bam_sort_markdup_host(const void *records, size_t n_bytes, uint32_t n
                                  size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
 	if (!md) return URMAPX_E_ARG;
 	return sort_host_entry(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
+}
+
+int urmapx_bam_sort_plan_for(size_t n_bytes, uint64_t n_records, int markdup, uint64_t budget_bytes, urmapx_bam_sort_plan *plan) {
+	if (!plan) return URMAPX_E_ARG;
+	return plan_with_stage(n_bytes, n_records, markdup != 0, budget_bytes, default_stage_bytes(n_bytes), plan);
 }
 
 void urmapx_bam_sort_free(urmapx_bam_sort_result *R) {

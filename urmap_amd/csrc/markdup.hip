@@ -16,6 +16,8 @@
 //                     into its group, a fragment its (score, ~record): a fragment that is not its group's best is a duplicate
 // A maximum does not depend on the order the atomics arrive in, so nothing here depends on scheduling.  Flag bytes are written with
 // byte stores (a record starts at any address), each by the one thread that owns the record.
+// Only ends_kernel and first_kernel read a record's bytes.  They take a chunk of records (markdup_chunk): the whole input where it
+// is resident, a staged chunk of it on the sort's external road, where the decisions go to an action array instead of the records.
 #include "bam_sort_dev.h"
 
 #include <cstdio>
@@ -47,27 +49,34 @@ __device__ __forceinline__ void count_block(uint32_t mine, uint32_t *s_sum, unsi
 	__syncthreads();
 	if (threadIdx.x == 0 && *s_sum) atomicAdd(to, (unsigned long long)*s_sum);
 }
-__device__ __forceinline__ void write_dup(uint8_t *r, bool dup) {
+// what becomes of record v's bit 0x400: into the resident record, or -- where the records are not resident (action != nullptr) -- the same
+// decision into the action array, which place_kernel (bam_sort.hip) applies as it copies the record
+__device__ __forceinline__ void write_dup(uint8_t *rec, const uint64_t *off, uint8_t *action, uint32_t v, bool dup) {
+	if (action) { action[v] = dup ? MD_SET : MD_CLEAR; return; }
+	uint8_t *r = rec + off[v];
 	const uint8_t b = r[FLAG_BYTE];
 	r[FLAG_BYTE] = dup ? (uint8_t)(b | FLAG_DUP_BIT) : (uint8_t)(b & ~FLAG_DUP_BIT);
 }
 
-__global__ __launch_bounds__(NT) void ends_kernel(const uint8_t *rec, const uint64_t *off, uint32_t n, int64_t *u5, uint32_t *score, uint32_t *what,
-                                                  unsigned long long *stat) {
+// The records i0 .. i1 - 1 lie at rec + (off[i] - base): a staged chunk whose first byte is byte `base` of the input, or (base 0, all
+// records) the whole input.  word[i]: the score in the high half, refID in the low one -- what pack_kernel needs of a record's bytes
+__global__ __launch_bounds__(NT) void ends_kernel(const uint8_t *rec, uint64_t base, const uint64_t *off, uint32_t i0, uint32_t i1, int64_t *u5, uint64_t *word,
+                                                  uint32_t *what, unsigned long long *stat) {
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint64_t wave = ((uint64_t)blockIdx.x * NT + threadIdx.x) >> 6, n_waves = (uint64_t)gridDim.x * (NT / 64);
-	for (uint64_t i = wave; i < n; i += n_waves) {  // (i is the same in all lanes of a wave)
-		const uint8_t *r = rec + off[i];
+	for (uint64_t i = i0 + wave; i < i1; i += n_waves) {  // (i is the same in all lanes of a wave)
+		const uint8_t *r = rec + (off[i] - base);
 		const uint64_t len = off[i + 1] - off[i];
+		const uint32_t ref_id = load_u32(r + 4);
 		const uint32_t w3 = load_u32(r + 12), w4 = load_u32(r + 16), l_seq = load_u32(r + 20);
 		const uint32_t l_name = w3 & 0xFFu, n_cigar = w4 & 0xFFFFu, flag = w4 >> 16;
 		if (flag & (0x4u | 0x100u | 0x800u)) {
-			if (lane == 0) { what[i] = 0; score[i] = 0; u5[i] = 0; }
+			if (lane == 0) { what[i] = 0; word[i] = ref_id; u5[i] = 0; }
 			continue;
 		}
 		const uint64_t qual_at = (uint64_t)CORE + l_name + 4ull * n_cigar + ((uint64_t)l_seq + 1u) / 2u;
 		if (qual_at + l_seq > len) {  // SEQ and QUAL do not lie inside the record: the call is refused
-			if (lane == 0) { what[i] = 0; score[i] = 0; u5[i] = 0; atomicOr(&stat[ST_BAD], 1ull); }
+			if (lane == 0) { what[i] = 0; word[i] = ref_id; u5[i] = 0; atomicOr(&stat[ST_BAD], 1ull); }
 			continue;
 		}
 		const uint8_t *q = r + qual_at;
@@ -89,7 +98,7 @@ __global__ __launch_bounds__(NT) void ends_kernel(const uint8_t *rec, const uint
 			}
 			const int64_t pos = (int32_t)load_u32(r + 8);
 			u5[i] = rev ? pos + (span ? span : 1) - 1 + behind : pos - front;
-			score[i] = sum < MAX_SCORE ? (uint32_t)sum : MAX_SCORE;
+			word[i] = (uint64_t)(sum < MAX_SCORE ? (uint32_t)sum : MAX_SCORE) << 32 | ref_id;
 			what[i] = ELIGIBLE | (rev ? REVERSE : 0u);
 		}
 	}
@@ -109,12 +118,14 @@ __global__ __launch_bounds__(NT) void range_kernel(const int64_t *u5, const uint
 	}
 }
 
-// in place: u5 becomes the packed end (an ineligible record's stays unread)
-__global__ __launch_bounds__(NT) void pack_kernel(const uint8_t *rec, const uint64_t *off, const uint32_t *what, uint32_t n, uint32_t n_ref, int64_t u5_min,
-                                                  uint32_t u5_bits, uint64_t *end) {
+// in place: u5 becomes the packed end (an ineligible record's stays unread); ends_kernel's words come apart: the scores to their array,
+// refID into the end.  No record bytes are read here
+__global__ __launch_bounds__(NT) void pack_kernel(const uint64_t *word, const uint32_t *what, uint32_t n, uint32_t n_ref, int64_t u5_min, uint32_t u5_bits,
+                                                  uint64_t *end, uint32_t *score) {
 	for (uint32_t i = blockIdx.x * NT + threadIdx.x; i < n; i += gridDim.x * NT) {
+		score[i] = (uint32_t)(word[i] >> 32);
 		if (!(what[i] & ELIGIBLE)) continue;
-		const uint32_t ref_id = load_u32(rec + off[i] + 4);
+		const uint32_t ref_id = (uint32_t)word[i];
 		const uint64_t r = ref_id == 0xFFFFFFFFu ? n_ref : ref_id;
 		end[i] = (r << u5_bits | (uint64_t)((int64_t)end[i] - u5_min)) << 1 | (what[i] & REVERSE ? 1u : 0u);
 	}
@@ -124,11 +135,14 @@ __global__ __launch_bounds__(NT) void pack_kernel(const uint8_t *rec, const uint
 // its own.  The two agree: a first mate has 0x40 and not 0x80, a second mate has 0x80, so no record can be both -- the record i of a
 // candidate (i, i + 1) is never the second mate of (i - 1, i), and its record i + 1 never the first mate of (i + 1, i + 2).  In
 // 0x40 0x80 0x80 only (0, 1) is a candidate, in 0x40 0x40 0x80 only (1, 2), as in the scan.
-__global__ __launch_bounds__(NT) void first_kernel(const uint8_t *rec, const uint64_t *off, const uint32_t *what, uint32_t n, uint32_t *first) {
-	for (uint32_t i = blockIdx.x * NT + threadIdx.x; i < n; i += gridDim.x * NT) {
+// Records i0 .. i1 - 1 of a chunk as in ends_kernel, which has run on them and on record i1: a chunk that is not the last has its
+// successor's first record staged behind it, so every adjacent pair of the input is tested once, by the chunk that holds its first record.
+__global__ __launch_bounds__(NT) void first_kernel(const uint8_t *rec, uint64_t base, const uint64_t *off, const uint32_t *what, uint32_t i0, uint32_t i1, uint32_t n,
+                                                   uint32_t *first) {
+	for (uint64_t i = (uint64_t)i0 + blockIdx.x * NT + threadIdx.x; i < i1; i += gridDim.x * NT) {
 		bool pair = false;
 		if (i + 1u < n && (what[i] & ELIGIBLE) && (what[i + 1] & ELIGIBLE)) {
-			const uint8_t *a = rec + off[i], *b = rec + off[i + 1];
+			const uint8_t *a = rec + (off[i] - base), *b = rec + (off[i + 1] - base);
 			const uint32_t fa = load_u32(a + 16) >> 16, fb = load_u32(b + 16) >> 16;
 			const uint32_t la = a[12], lb = b[12];
 			if ((fa & 0xC1u) == 0x41u && (fb & 0x81u) == 0x81u && la == lb) {
@@ -168,7 +182,7 @@ __global__ __launch_bounds__(NT) void pair_best_kernel(const uint32_t *val, cons
 	}
 }
 __global__ __launch_bounds__(NT) void pair_write_kernel(const uint32_t *val, const uint32_t *flag, const uint32_t *index, const uint32_t *score, uint32_t n_pairs,
-                                                        const unsigned long long *best, const uint64_t *off, uint8_t *rec, unsigned long long *stat) {
+                                                        const unsigned long long *best, const uint64_t *off, uint8_t *rec, uint8_t *action, unsigned long long *stat) {
 	__shared__ uint32_t s_dups;
 	if (threadIdx.x == 0) s_dups = 0;
 	__syncthreads();
@@ -176,8 +190,8 @@ __global__ __launch_bounds__(NT) void pair_write_kernel(const uint32_t *val, con
 	for (uint32_t j = blockIdx.x * NT + threadIdx.x; j < n_pairs; j += gridDim.x * NT) {
 		const uint32_t g = index[j] + flag[j] - 1u, v = val[j];
 		const bool dup = g < n_pairs && best[g] != word_of(score[v] + score[v + 1], v);
-		write_dup(rec + off[v], dup);
-		write_dup(rec + off[v + 1], dup);
+		write_dup(rec, off, action, v, dup);
+		write_dup(rec, off, action, v + 1u, dup);
 		dups += dup;
 	}
 	count_block(dups, &s_dups, &stat[ST_PAIR_DUP]);
@@ -204,7 +218,8 @@ __global__ __launch_bounds__(NT) void frag_best_kernel(const uint32_t *val, cons
 	}
 }
 __global__ __launch_bounds__(NT) void frag_write_kernel(const uint32_t *val, const uint32_t *flag, const uint32_t *index, const uint32_t *score, const uint32_t *first,
-                                                        uint32_t n_elig, const unsigned long long *best, const uint64_t *off, uint8_t *rec, unsigned long long *stat) {
+                                                        uint32_t n_elig, const unsigned long long *best, const uint64_t *off, uint8_t *rec, uint8_t *action,
+                                                        unsigned long long *stat) {
 	__shared__ uint32_t s_frags, s_dups;
 	if (threadIdx.x == 0) s_frags = s_dups = 0;
 	__syncthreads();
@@ -213,7 +228,7 @@ __global__ __launch_bounds__(NT) void frag_write_kernel(const uint32_t *val, con
 		const uint32_t g = index[j] + flag[j] - 1u, v = val[j];
 		if (in_pair(first, v)) continue;
 		const bool dup = g < n_elig && best[g] != word_of(score[v], v);
-		write_dup(rec + off[v], dup);
+		write_dup(rec, off, action, v, dup);
 		++frags;
 		dups += dup;
 	}
@@ -226,14 +241,32 @@ __global__ __launch_bounds__(NT) void frag_write_kernel(const uint32_t *val, con
 namespace urx {
 namespace bamsort {
 
-int markdup_device(const MarkdupArrays &A, urmapx_markdup_stats *md) {
+int MarkdupOwn::begin(uint32_t n) {
+	int rc;
+	if ((rc = end.alloc(n)) || (rc = best.alloc((size_t)n + 1)) || (rc = what.alloc(n)) || (rc = first.alloc(n)) || (rc = stat.alloc(ST_WORDS))) return rc;
+	unsigned long long s[ST_WORDS] = {0};
+	s[ST_MIN] = (unsigned long long)INT64_MAX;
+	s[ST_MAX] = (unsigned long long)INT64_MIN;
+	HIP_TRY(hipMemcpy(stat.p, s, sizeof s, hipMemcpyHostToDevice));
+	return URMAPX_OK;
+}
+
+int markdup_chunk(const MarkdupOwn &W, const uint8_t *rec, uint64_t base, const uint64_t *off, uint32_t i0, uint32_t i1, uint32_t n, hipStream_t stream) {
+	if (i1 <= i0) return URMAPX_OK;
+	const uint32_t seen = i1 < n ? i1 + 1u : n;  // (the successor's first record is staged behind the chunk: first_kernel looks at it)
+	hipLaunchKernelGGL(ends_kernel, dim3(grid_for((uint64_t)(seen - i0) * 64u)), dim3(NT), 0, stream, rec, base, off, i0, seen, (int64_t *)W.end.p, W.best.p, W.what.p,
+	                   W.stat.p);
+	hipLaunchKernelGGL(first_kernel, dim3(grid_for(i1 - i0)), dim3(NT), 0, stream, rec, base, off, (const uint32_t *)W.what.p, i0, i1, n, W.first.p);
+	HIP_TRY(hipGetLastError());
+	return URMAPX_OK;
+}
+
+int markdup_device(const MarkdupArrays &A, const MarkdupOwn &W, urmapx_markdup_stats *md) {
 	const uint32_t n = A.n;
 	if (n == 0) return URMAPX_OK;
-	int rc;
-	Dev<uint64_t> d_end, d_best;
-	Dev<uint32_t> d_what, d_first;
-	Dev<unsigned long long> d_stat;
-	if ((rc = d_end.alloc(n)) || (rc = d_best.alloc((size_t)n + 1)) || (rc = d_what.alloc(n)) || (rc = d_first.alloc(n)) || (rc = d_stat.alloc(ST_WORDS))) return rc;
+	const Dev<uint64_t> &d_end = W.end, &d_best = W.best;
+	const Dev<uint32_t> &d_what = W.what, &d_first = W.first;
+	const Dev<unsigned long long> &d_stat = W.stat;
 	// URMAPX_VERBOSE: where the time goes, a line on stderr (scripts/markdup_bench.py reads it); the stream is waited for after each part
 	const bool verbose = getenv("URMAPX_VERBOSE") != nullptr;
 	double part_s[3] = {0, 0, 0};
@@ -246,12 +279,8 @@ int markdup_device(const MarkdupArrays &A, urmapx_markdup_stats *md) {
 		t0 = t1;
 	};
 	unsigned long long stat[ST_WORDS] = {0};
-	stat[ST_MIN] = (unsigned long long)INT64_MAX;
-	stat[ST_MAX] = (unsigned long long)INT64_MIN;
-	HIP_TRY(hipMemcpy(d_stat.p, stat, sizeof stat, hipMemcpyHostToDevice));
 
-	// ends and scores; the width of the packed end
-	hipLaunchKernelGGL(ends_kernel, dim3(grid_for((uint64_t)n * 64u)), dim3(NT), 0, nullptr, (const uint8_t *)A.rec, A.off, n, (int64_t *)d_end.p, A.score, d_what.p, d_stat.p);
+	// ends, scores and pairs are there (markdup_chunk); the width of the packed end
 	hipLaunchKernelGGL(range_kernel, dim3(grid_for(n, 1024)), dim3(NT), 0, nullptr, (const int64_t *)d_end.p, (const uint32_t *)d_what.p, n, d_stat.p);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpy(stat, d_stat.p, sizeof stat, hipMemcpyDeviceToHost));
@@ -260,9 +289,8 @@ int markdup_device(const MarkdupArrays &A, urmapx_markdup_stats *md) {
 	if (u5_min > u5_max) return URMAPX_OK;  // no eligible record: nothing is written
 	const uint32_t u5_bits = bits_for((uint64_t)u5_max - (uint64_t)u5_min), end_bits = bits_for(A.n_ref) + u5_bits + 1u;
 	if (end_bits > 64u) return URMAPX_E_FORMAT;
-	hipLaunchKernelGGL(pack_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, (const uint8_t *)A.rec, A.off, (const uint32_t *)d_what.p, n, A.n_ref, u5_min, u5_bits,
-	                   d_end.p);
-	hipLaunchKernelGGL(first_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, (const uint8_t *)A.rec, A.off, (const uint32_t *)d_what.p, n, d_first.p);
+	hipLaunchKernelGGL(pack_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, (const uint64_t *)d_best.p, (const uint32_t *)d_what.p, n, A.n_ref, u5_min, u5_bits, d_end.p,
+	                   A.score);
 
 	lap(0);
 
@@ -287,7 +315,7 @@ int markdup_device(const MarkdupArrays &A, urmapx_markdup_stats *md) {
 		hipLaunchKernelGGL(pair_best_kernel, dim3(grid_for(n_pairs)), dim3(NT), 0, nullptr, val, (const uint32_t *)flag, (const uint32_t *)index, (const uint32_t *)A.score,
 		                   n_pairs, (unsigned long long *)d_best.p);
 		hipLaunchKernelGGL(pair_write_kernel, dim3(grid_for(n_pairs)), dim3(NT), 0, nullptr, val, (const uint32_t *)flag, (const uint32_t *)index, (const uint32_t *)A.score,
-		                   n_pairs, (const unsigned long long *)d_best.p, A.off, A.rec, d_stat.p);
+		                   n_pairs, (const unsigned long long *)d_best.p, A.off, A.rec, A.action, d_stat.p);
 		HIP_TRY(hipGetLastError());
 	}
 
@@ -316,7 +344,7 @@ int markdup_device(const MarkdupArrays &A, urmapx_markdup_stats *md) {
 		hipLaunchKernelGGL(frag_best_kernel, dim3(grid_for(n_elig)), dim3(NT), 0, nullptr, val, (const uint32_t *)flag, (const uint32_t *)index, (const uint32_t *)A.score,
 		                   (const uint32_t *)d_first.p, n_elig, (unsigned long long *)d_best.p);
 		hipLaunchKernelGGL(frag_write_kernel, dim3(grid_for(n_elig)), dim3(NT), 0, nullptr, val, (const uint32_t *)flag, (const uint32_t *)index, (const uint32_t *)A.score,
-		                   (const uint32_t *)d_first.p, n_elig, (const unsigned long long *)d_best.p, A.off, A.rec, d_stat.p);
+		                   (const uint32_t *)d_first.p, n_elig, (const unsigned long long *)d_best.p, A.off, A.rec, A.action, d_stat.p);
 		HIP_TRY(hipGetLastError());
 	}
 	HIP_TRY(hipMemcpy(stat, d_stat.p, sizeof stat, hipMemcpyDeviceToHost));

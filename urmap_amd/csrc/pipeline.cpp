@@ -1121,19 +1121,29 @@ struct Run {
 			rc = markdup ? urmapx_bam_sort_markdup_host(sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &M, &S)
 			             : urmapx_bam_sort_host(sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &S);
 		else {
-			rc = on_device();
+			// sort_mem (or the test knob that forces partitions): the sort is planned from that budget and nothing else is tried
+			const bool planned = opt.sort_mem != 0 || getenv("URMAPX_TEST_SORT_PARTITION");
+			auto streamed = [&]() {
+				return urmapx_bam_sort_external(phys(0), opt.sort_mem, sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), markdup ? &M : nullptr, &S);
+			};
+			rc = planned ? streamed() : on_device();
 			if (rc == URMAPX_E_NOMEM) {  // the device is full of lanes: this run's and the pool's go first (the mapping is over)
 				close();
 				LanePool::get().purge(nullptr);
-				rc = on_device();
+				rc = planned ? streamed() : on_device();
 			}
+			if (rc == URMAPX_E_NOMEM && !planned) rc = streamed();  // the records do not fit: they stream through the device, with the memory that is free
 			if (rc == URMAPX_E_NOMEM) {
 				size_t free_b = 0, total_b = 0;
 				(void)hipSetDevice(phys(0));
 				if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-				const uint64_t need = markdup ? urmapx_bam_sort_markdup_device_bytes((size_t)n_bytes, rep.reads) : urmapx_bam_sort_device_bytes((size_t)n_bytes, rep.reads);
-				fail.raise(rc, "bam_sort: the records and the sort's arrays need " + std::to_string(need) +
-				                   " bytes on the device, " + std::to_string(free_b) + " are free");
+				const uint64_t have = opt.sort_mem ? opt.sort_mem : free_b > URMAPX_SORT_HEADROOM ? (uint64_t)free_b - URMAPX_SORT_HEADROOM : 1u;
+				urmapx_bam_sort_plan plan;
+				if (urmapx_bam_sort_plan_for((size_t)n_bytes, rep.reads, markdup, have, &plan) == URMAPX_E_NOMEM)
+					fail.raise(rc, "bam_sort: the sort's arrays, its staging buffers and one slice need at least " + std::to_string(plan.device_bytes) +
+					                   " bytes on the device, " + std::to_string(have) + (opt.sort_mem ? " were given (sort_mem)" : " are free"));
+				else
+					fail.raise(rc, "bam_sort: out of device memory: the plan takes " + std::to_string(plan.device_bytes) + " bytes, " + std::to_string(free_b) + " are free");
 				return;
 			}
 		}
@@ -1159,6 +1169,9 @@ struct Run {
 			                "records %llu bytes %llu passes %u slices %u\n",
 			        rep.sort_s, S.scan_s, S.alloc_s, S.upload_s, S.sort_s, S.gather_s, S.deflate_s, S.copy_s, S.index_s, secs(tw0, now()),
 			        (unsigned long long)S.records, (unsigned long long)S.stream_bytes, S.sort_passes, S.slices);
+		rep.sort_partitions = S.external ? S.partitions : 0;
+		if (S.external && getenv("URMAPX_VERBOSE"))  // (scripts/bam_sort_external_bench.py reads this line)
+			fprintf(stderr, "bam_sort external: partitions %u chunks %llu passes %u stage %.4f\n", S.partitions, (unsigned long long)S.stage_chunks, S.partitions + 1u, S.stage_s);
 		if (markdup) {
 			rep.pairs_examined = M.pairs_examined; rep.pairs_duplicate = M.pairs_duplicate;
 			rep.fragments_examined = M.fragments_examined; rep.fragments_duplicate = M.fragments_duplicate;
@@ -1974,6 +1987,7 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
 		if (why) { say(err, errcap, why); return URMAPX_E_ARG; }
 	}
 	if (opt->markdup && !opt->bam_sort) { say(err, errcap, "markdup needs bam_sort: the duplicates are marked while the records are sorted"); return URMAPX_E_ARG; }
+	if (opt->sort_mem && !opt->bam_sort) { say(err, errcap, "sort_mem needs bam_sort: it is the device memory the sort may take"); return URMAPX_E_ARG; }
 	const int shards = opt->sam_shards > 1 ? opt->sam_shards : 1;
 	if (shards == 1) return map_files_impl(I, opt, InputRange(), fastq1, fastq2, samout, tabout, report, err, errcap);
 	const bool paired = fastq2 != nullptr;

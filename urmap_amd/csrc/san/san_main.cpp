@@ -1,12 +1,13 @@
 // san_main.cpp -- driver of the sanitizer builds (make san): the host side of the drop-in path run from the command line, with the
 // device side replaced by san/stub_device.cpp.  tests/test_sanitizers_cpu.py runs it on well-formed and on damaged input; a
 // sanitizer report ends the process with exit code 99 (ASAN_OPTIONS / UBSAN_OPTIONS / TSAN_OPTIONS exitcode, set by the tests).
-//   urmap_san map <fastq1> [-2 fastq2] -o out.sam [-tab out.tab] [-batch N] [-streams K] [-gpus N] [-shards N] [-threads T] [-null] [-bgzf] [-bam] [-sort] [-markdup] [-biglen N] [-tags MASK] [-rg LINE]
+//   urmap_san map <fastq1> [-2 fastq2] -o out.sam [-tab out.tab] [-batch N] [-streams K] [-gpus N] [-shards N] [-threads T] [-null] [-bgzf] [-bam] [-sort] [-markdup] [-sortmem N[G]] [-biglen N] [-tags MASK] [-rg LINE]
 //       (-tags: URMAPX_TAG_* bits, -rg: an @RG line with real tabs; both need the stand-in store, which exists with -biglen up to 60 000 000)
 //       (-biglen: bases of the stand-in index's third sequence, 4 000 000 000 unless given; a BAM position holds 2^31 - 1)
 //   urmap_san gunzip <in.gz> <out> [threads]
 //   urmap_san fastq <file> <batch>
 //   urmap_san makeufi <fasta> <out.ufi> <slots>
+//   urmap_san plan <n_bytes> <n_records> <markdup 0|1>     (urmapx_bam_sort_plan_for over a sweep of budgets)
 // Exit code: 0 = the call succeeded, 1 = it refused its input with an error code (printed), 2 = usage.
 #include <cstdio>
 #include <cstdlib>
@@ -39,6 +40,11 @@ static int cmd_map(int argc, char **argv) {
 		else if (a == "-bam") o.bam = 1;
 		else if (a == "-sort") o.bam_sort = 1;
 		else if (a == "-markdup") o.markdup = 1;
+		else if (a == "-sortmem") {  // bytes, with G for 2^30
+			char *end = nullptr;
+			o.sort_mem = strtoull(val(), &end, 10);
+			if (end && *end == 'G') o.sort_mem <<= 30;
+		}
 		else if (a == "-tags") o.tags = (unsigned)atoi(val());
 		else if (a == "-rg") o.read_group = val();
 		else if (a == "-biglen") biglen = (uint32_t)strtoul(val(), nullptr, 10);
@@ -102,9 +108,26 @@ static int cmd_makeufi(int argc, char **argv) {
 	return rc == URMAPX_OK ? 0 : 1;
 }
 
+// the sort's plan over a sweep of budgets: host arithmetic, so whole-genome sizes cost nothing
+static int cmd_plan(int argc, char **argv) {
+	if (argc < 3) return 2;
+	const uint64_t n_bytes = strtoull(argv[0], nullptr, 10), n_records = strtoull(argv[1], nullptr, 10);
+	const int markdup = atoi(argv[2]);
+	uint64_t before = ~(uint64_t)0;
+	for (uint64_t budget = 1; budget < (uint64_t)1 << 40; budget += budget / 3 + 1) {
+		urmapx_bam_sort_plan p;
+		const int rc = urmapx_bam_sort_plan_for((size_t)n_bytes, n_records, markdup, budget, &p);
+		if (rc == URMAPX_OK && (p.device_bytes > budget || p.partitions > before)) { printf("rc=%d budget=%llu: a plan beyond its budget\n", rc, (unsigned long long)budget); return 1; }
+		if (rc == URMAPX_OK) before = p.partitions;
+	}
+	printf("rc=0 partitions=%llu\n", (unsigned long long)before);
+	return 0;
+}
+
 int main(int argc, char **argv) {
 	if (argc < 3) return 2;
 	const std::string cmd = argv[1];
+	if (cmd == "plan") return cmd_plan(argc - 2, argv + 2);
 	if (cmd == "map") return cmd_map(argc - 2, argv + 2);
 	if (cmd == "gunzip") return cmd_gunzip(argc - 2, argv + 2);
 	if (cmd == "fastq") return cmd_fastq(argc - 2, argv + 2);

@@ -396,6 +396,17 @@ int urmapx_bam_sort_markdup(int, const void *records, size_t n_bytes, uint32_t n
                             urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
 	return urmapx_bam_sort_markdup_host(records, n_bytes, n_ref, in_front, starts, n_starts, md, out);
 }
+// the planned sort's stand-in: the plan is made (host arithmetic, bam_sort_host.cpp) and its refusal kept; the sort itself is the host's
+int urmapx_bam_sort_external(int, uint64_t budget, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts,
+                             urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
+	if (budget == 0) budget = ((uint64_t)200 << 30) - URMAPX_SORT_HEADROOM;  // (hipMemGetInfo above)
+	urmapx_bam_sort_plan plan;
+	if (const int rc = urmapx_bam_sort_plan_for(n_bytes, n_bytes / 200 + 1, md != nullptr, budget, &plan)) return rc;
+	const int rc = md ? urmapx_bam_sort_markdup_host(records, n_bytes, n_ref, in_front, starts, n_starts, md, out)
+	                  : urmapx_bam_sort_host(records, n_bytes, n_ref, in_front, starts, n_starts, out);
+	if (rc == URMAPX_OK) { out->external = (uint32_t)plan.external; out->partitions = (uint32_t)plan.partitions; }
+	return rc;
+}
 uint64_t urmapx_bam_sort_device_bytes(size_t n_bytes, uint64_t n_records) { return n_bytes + 48u * n_records; }
 uint64_t urmapx_bam_sort_markdup_device_bytes(size_t n_bytes, uint64_t n_records) { return n_bytes + 72u * n_records; }
 }

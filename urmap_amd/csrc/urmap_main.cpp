@@ -65,6 +65,8 @@ struct Opts {
 	bool veryfast = false, quiet = false, minq_given = false, host_build = false, notrunclabels = false;
 	bool sort = false;  // -sort: the -bamout file in coordinate order, with its .bai index
 	bool markdup = false;  // -markdup: with -sort, flag 0x400 on the duplicates
+	std::string sortmem;   // -sortmem N[K|M|G]: with -sort, the device memory the sort may take
+	bool sortmem_given = false;
 	std::string tags, rg;  // -tags NM,MD,AS and -rg '@RG\tID:..': optional fields of the records, the read group's header line
 	bool tags_given = false, rg_given = false;
 	bool trunclabels = false, wordlength_given = false;
@@ -74,6 +76,24 @@ struct Opts {
 	int gpu = 0, gpus = 1, streams = 2, samshards = 0;
 	unsigned batch = 1u << 18;
 };
+
+// -sortmem's value: digits, then nothing or one of K M G (either case) for powers of 1024.  0: not such a value (or 0, or beyond 64 bits)
+static unsigned long long parse_bytes(const std::string &s) {
+	size_t k = 0;
+	unsigned long long v = 0;
+	for (; k < s.size() && s[k] >= '0' && s[k] <= '9'; ++k) {
+		if (v > (~0ull - 9u) / 10u) return 0;
+		v = v * 10u + (unsigned)(s[k] - '0');
+	}
+	if (k == 0 || s.size() > k + 1) return 0;
+	if (k < s.size()) {
+		const char c = (char)(s[k] | 0x20);
+		const int shift = c == 'k' ? 10 : c == 'm' ? 20 : c == 'g' ? 30 : -1;
+		if (shift < 0 || v > ~0ull >> shift) return 0;
+		v <<= shift;
+	}
+	return v;
+}
 
 static Opts parse(int argc, char **argv) {
 	Opts o;
@@ -112,6 +132,7 @@ static Opts parse(int argc, char **argv) {
 		else if (a == "-host") o.host_build = true;
 		else if (a == "-sort") o.sort = true;
 		else if (a == "-markdup") o.markdup = true;
+		else if (a == "-sortmem") { o.sortmem = val(); o.sortmem_given = true; }
 		else if (a == "-tags") { o.tags = val(); o.tags_given = true; }
 		else if (a == "-rg") { o.rg = val(); o.rg_given = true; }
 		else if (a == "-quiet") o.quiet = true;
@@ -210,6 +231,12 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 	if (bam && o.bgzf) die("-bgzf goes with -samout: a -bamout file is always BGZF");
 	const std::string &samout = bam ? o.bamout : o.samout;
 	if (o.markdup && !o.sort) die("-markdup needs -sort: the duplicates are marked while the records of the -bamout file are sorted");
+	unsigned long long sort_mem = 0;
+	if (o.sortmem_given) {
+		if (!o.sort) die("-sortmem needs -sort: it is the device memory the sort of the -bamout file may take");
+		sort_mem = parse_bytes(o.sortmem);
+		if (!sort_mem) die("-sortmem %s: a number of bytes from 1 on, with K, M or G behind it for powers of 1024", o.sortmem.c_str());
+	}
 	if (o.sort) {
 		struct stat st;
 		if (!bam) die("-sort needs -bamout: it sorts the records of a BAM file");
@@ -250,6 +277,7 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 	mo.tags = tag_mask;
 	mo.read_group = o.rg_given ? rg_line.data() : nullptr;
 	mo.markdup = o.markdup ? 1 : 0;
+	mo.sort_mem = sort_mem;
 	urmapx_map_report rep;
 	memset(&rep, 0, sizeof rep);
 	char err[1024];
@@ -602,6 +630,7 @@ int main(int argc, char **argv) {
 	                "               with -samshards N every out.bam.0 .. out.bam.N-1 is a complete BAM file\n"
 	                "      -sort: with -bamout, the records in coordinate order (sorted on the GPU) and the index out.bam.bai beside the file\n"
                 "      -markdup: with -sort, flag 0x400 on duplicate reads (Picard's rule: same ends, the best qualities stay), marked on the GPU\n"
+                "      -sortmem N[K|M|G]: with -sort, the GPU memory the sort may take; records that do not fit it stream through the GPU in partitions\n"
 	                "      -tags NM,MD,AS: these optional fields behind QUAL of every mapped record (any subset; computed on the GPU), SAM and BAM\n"
 	                "      -rg '@RG\\tID:x\\tSM:y': that line in the header in front of @PG and RG:Z:x on every record\n"
 	                "  urmap -make_ufi genome.fa -output index.ufi [-slots N] [-wordlength W] [-maxix M]\n"
