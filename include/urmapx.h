@@ -439,6 +439,14 @@ typedef struct urmapx_map_options {
 	                     * fit (urmapx_bam_sort_external); URMAPX_E_NOMEM naming the least it takes where even one slice does not.  0: in
 	                     * core when the device has room, else streamed with what is free.  No effect on the host road.  URMAPX_E_ARG
 	                     * without bam_sort */
+	const char *depth_out; /* -depth (with bam_sort): a bedGraph file of the per-base depth of the records as the BAM file holds them --
+	                     * under markdup without the duplicates --, taken on first_gpu while the records lie there for the sort (see "Depth"
+	                     * below; urmapx_bam_sort_depth, on the host road urmapx_bam_sort_depth_host).  The BAM file and its index are those
+	                     * of the run without it but for the @PG line.  The depth arrays come off sort_mem (or off what is free) before the
+	                     * sort is planned; URMAPX_E_NOMEM naming the least budget where they do not fit.  The totals go to the report, the
+	                     * table per reference to urmapx_map_depth_summary.  NULL: none.  URMAPX_E_ARG without bam_sort, and for a name
+	                     * that is samout's or its index's.  A failed run removes the file with the other two */
+	uint32_t depth_mapq; /* -depth_mapq (with depth_out): records with a MAPQ below it do not count; 0 .. 255 */
 } urmapx_map_options;
 typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:593-632) and where the time went */
 	uint64_t reads, mapped_q, mapped_lowq, unmapped, unsupported;
@@ -470,6 +478,8 @@ typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:59
 	uint64_t pairs_examined, pairs_duplicate, fragments_examined, fragments_duplicate;  /* markdup: urmapx_markdup_stats of the run's records */
 	double markdup_s;                                /* markdup: the marking's share of sort_s */
 	uint32_t sort_partitions;                        /* bam_sort: partitions the sorted stream was made in on the external road; 0: in core (or the host) */
+	double depth_s;                                  /* depth_out: the depth's share of sort_s (its arrays, the counting, scan, runs, text and the file) */
+	uint64_t depth_runs, depth_covered, depth_bases; /* depth_out: lines of the file; columns with depth >= 1 and the sum of all depths, over all references */
 } urmapx_map_report;
 /* fastq2 NULL: single-end (-map); else the mates' file (-map2 ... -reverse).  samout / tabout may be NULL.  The index
  * needs its host arrays, or to be resident on first_gpu already (the other devices' replicas are then copied from there).  Batch b is mapped on device
@@ -486,6 +496,11 @@ int urmapx_map_files(urmapx_index *, const urmapx_map_options *, const char *fas
  *     sees at most that much held back.
  * urmapx_host_pool_trim() frees both; urmapx_index_close() destroys the lanes of its index; URMAPX_NO_LANE_POOL=1 keeps no lanes. */
 void urmapx_host_pool_trim(void);
+/* The table of the calling thread's last urmapx_map_files run with depth_out: one line per reference --
+ * "name\tlength\treads\tcovered\tpercent covered\tmean depth\tmean MAPQ\n", the percentage and the means with two decimals (0.00 for a
+ * reference without columns or reads) -- under a header line that names the columns.  "" after a run without depth_out.  The text
+ * is the library's until the thread's next run. */
+const char *urmapx_map_depth_summary(void);
 
 /* ---- FASTQ bytes in, SAM bytes out (both text stages of -map on the device) ---- */
 /* One chunk of a FASTQ file, cut after a record's last '\n', goes to the device as it lies in the file; line ends,
@@ -830,6 +845,75 @@ uint64_t urmapx_bam_sort_markdup_device_bytes(size_t n_bytes, uint64_t n_records
 /* the planned sort ("Sorted BAM output" above): in core or streamed, as urmapx_bam_sort_plan_for says for budget_bytes; md NULL: no marking */
 int urmapx_bam_sort_external(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
                              const uint64_t *starts, size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out);
+
+/* ---- Depth (per-base coverage of BAM records, as a bedGraph text and a summary per reference) ----
+ * The input is BAM records as above, in any order, n_ref reference names (C strings of 1 .. 255 bytes: the names of the @SQ lines) and
+ * their lengths l_ref.  The rule is `samtools depth` without -J, -s and base-quality filters; the result is exact.
+ *  1. Eligible: a record with 0 <= refID < n_ref, pos >= 0, (flag & 0x704) == 0 -- not unmapped, secondary, QC-fail or duplicate -- and
+ *     MAPQ >= min_mapq.  The flag is the one the record carries; inside urmapx_bam_sort_depth it is the one the record carries in the
+ *     sorted stream, so under marking bit 0x400 is the marking's decision, not the incoming bit.  Supplementary records (0x800) count.
+ *  2. Covered columns: the CIGAR is walked with a reference cursor c that starts at pos.  M, = and X of length L cover the columns
+ *     [c, c + L) that lie in [0, l_ref) and advance c by L; D and N advance c and cover nothing; I, S, H and P do nothing.  Columns
+ *     beyond the reference's length are dropped, which is no error.  Overlapping mates count twice.  A record without a CIGAR covers
+ *     nothing (one whose CIGAR does not lie inside its block_size is refused with the chain: URMAPX_E_FORMAT).
+ *  3. d(r, x), the depth of column x of reference r, is the number of covering ops.  All arithmetic on positions is 64 bits wide: the
+ *     concatenated space of the counters, the sum over the references of l_ref + 1, may exceed 2^32.  The counters are 32 bits wide: a
+ *     call with 2^31 records or more is URMAPX_E_ARG.
+ *  4. Text: for every reference with l_ref > 0, in index order, [0, l_ref) is cut into maximal runs of equal depth and each run is one
+ *     line "name\tbeg\tend\tdepth\n", 0-based and half-open, the numbers in decimal.  Runs of depth 0 are lines too, so the lines of a
+ *     reference tile it exactly; a reference without reads is the one line "name\t0\tl_ref\t0".  No header line.
+ *  5. Summary per reference: reads = the eligible records on it, whatever they cover; covered = its columns with d >= 1; bases = the
+ *     sum of d over its columns; mapq_sum = the sum of MAPQ over its eligible records.
+ * urmapx_bam_depth runs on `device` (depth.hip): the records pass through two staging buffers in input order (chunks of whole records,
+ * URMAPX_TEST_SORT_STAGE=B: of B bytes), so its memory does not grow with n_bytes; depth_count_kernel adds +1 and -1 into a difference
+ * array in which reference r owns l_ref + 1 entries -- an end that was clipped lands in the extra one, so every reference's entries
+ * sum to zero and one inclusive scan of the whole array gives every reference's depths --, the runs are found and compacted a segment
+ * of the array at a time, and their lines are made in slices of 65 536 runs (URMAPX_TEST_DEPTH_SLICE=N: of N) that are copied back
+ * while the next one is formatted.  urmapx_bam_depth_host (depth_host.cpp, written apart from it: a difference array and a running
+ * sum in plain loops) gives the same bytes and numbers.  starts / n_starts: as for the sort.
+ * urmapx_bam_sort_depth is urmapx_bam_sort_external with the depth taken while the records are on the device: in core by one launch
+ * over the unsorted records once the marking has decided, on the external road on the chunks of the first placing pass, where the
+ * marking's decisions lie complete beside the records.  The depth arrays (urmapx_bam_depth_resident_bytes) come off the budget before the
+ * sort is planned; a budget that does not hold them is URMAPX_E_NOMEM, and depth->least_budget then names the least budget that does.
+ * depth NULL: urmapx_bam_sort_external itself (dopts, names and lens unused).  urmapx_bam_sort_depth_host: the host sort (with marking
+ * when md is given) and urmapx_bam_depth_host of its stream.
+ * URMAPX_E_ARG: a name that is empty or longer than 255 bytes, 2^31 records or more; else the sort's codes. */
+typedef struct urmapx_depth_opts {
+	uint32_t min_mapq;
+} urmapx_depth_opts;
+typedef struct urmapx_depth_summary {
+	uint64_t reads, covered, bases, mapq_sum;
+} urmapx_depth_summary;
+typedef struct urmapx_depth_result {
+	char *text;              /* the bedGraph lines (malloc; not terminated) */
+	size_t text_bytes;
+	uint64_t runs;           /* lines of the text */
+	urmapx_depth_summary *refs;  /* n_ref of them */
+	uint32_t n_ref;
+	uint32_t text_slices;    /* device: pieces the text was formatted and copied back in */
+	uint64_t records;        /* records seen, eligible or not */
+	uint64_t stage_chunks;   /* urmapx_bam_depth: staged chunks of its pass over the input */
+	uint64_t least_budget;   /* urmapx_bam_sort_depth under URMAPX_E_NOMEM from the budget: the least budget_bytes that holds the call */
+	double alloc_s, count_s, scan_s, runs_s, format_s, copy_s;  /* device arrays; staging and depth_count_kernel (host: the CIGAR walk);
+	                          * the scan (host: the running sum and the runs); boundary flags, compaction and the summaries; the lines;
+	                          * the lines back to the host (inside no other part) */
+} urmapx_depth_result;
+int urmapx_bam_depth(int device, const void *records, size_t n_bytes, uint32_t n_ref, const char *const *names, const uint32_t *lens,
+                     const uint64_t *starts, size_t n_starts, const urmapx_depth_opts *opts, urmapx_depth_result *out);
+int urmapx_bam_depth_host(const void *records, size_t n_bytes, uint32_t n_ref, const char *const *names, const uint32_t *lens,
+                          const uint64_t *starts, size_t n_starts, const urmapx_depth_opts *opts, urmapx_depth_result *out);
+void urmapx_depth_free(urmapx_depth_result *);
+/* device memory urmapx_bam_depth takes for references of total_columns columns in all and n_records records, with staged chunks of
+ * the default size (the sum its allocations follow: depth.h) */
+uint64_t urmapx_bam_depth_device_bytes(uint64_t total_columns, uint32_t n_ref, uint64_t n_records);
+/* what of that urmapx_bam_sort_depth adds to the sort: no staging buffers and no record starts of its own */
+uint64_t urmapx_bam_depth_resident_bytes(uint64_t total_columns, uint32_t n_ref);
+int urmapx_bam_sort_depth(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
+                          const uint64_t *starts, size_t n_starts, urmapx_markdup_stats *md, const urmapx_depth_opts *dopts,
+                          const char *const *names, const uint32_t *lens, urmapx_depth_result *depth, urmapx_bam_sort_result *out);
+int urmapx_bam_sort_depth_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
+                               size_t n_starts, urmapx_markdup_stats *md, const urmapx_depth_opts *dopts, const char *const *names,
+                               const uint32_t *lens, urmapx_depth_result *depth, urmapx_bam_sort_result *out);
 
 const char *urmapx_strerror(int code);
 /* "gfx950" etc. of the ctx's device; NULL without a device */

@@ -45,6 +45,8 @@ EXPORTS = (
     "urmapx_bam_sort", "urmapx_bam_sort_host", "urmapx_bam_sort_free", "urmapx_bam_sort_device_bytes",
     "urmapx_bam_sort_markdup", "urmapx_bam_sort_markdup_host", "urmapx_bam_sort_markdup_device_bytes",
     "urmapx_bam_sort_plan_for", "urmapx_bam_sort_external",
+    "urmapx_bam_depth", "urmapx_bam_depth_host", "urmapx_depth_free", "urmapx_bam_depth_device_bytes", "urmapx_bam_depth_resident_bytes",
+    "urmapx_bam_sort_depth", "urmapx_bam_sort_depth_host", "urmapx_map_depth_summary",
     "urmapx_calmd", "urmapx_ref_span", "urmapx_sam_se_tags", "urmapx_sam_pe_tags", "urmapx_bam_se_tags", "urmapx_bam_pe_tags",
     "urmapx_read_group_id", "urmapx_sam_header_rg", "urmapx_bam_header_rg", "urmapx_index_fetch_spans", "urmapx_text_set_tags",
     "urmapx_text_tag_ms", "urmapx_tags_batch",
@@ -87,6 +89,11 @@ class MapOptionsSortMem(C.Structure):
     _fields_ = MapOptionsMarkdup._fields_ + [("sort_mem", C.c_uint64)]
 
 
+class MapOptionsDepth(C.Structure):
+    """urmapx_map_options in full: MapOptionsSortMem with depth_out and depth_mapq appended.  map_files passes this one."""
+    _fields_ = MapOptionsSortMem._fields_ + [("depth_out", C.c_char_p), ("depth_mapq", C.c_uint32)]
+
+
 class TagOptions(C.Structure):
     _fields_ = [("tags", C.c_uint), ("rg_id", C.c_char_p), ("ref", C.c_void_p * 2)]
 
@@ -110,6 +117,11 @@ class MapReportSort(C.Structure):
     _fields_ = MapReport._fields_ + [("sort_partitions", C.c_uint32)]
 
 
+class MapReportDepth(C.Structure):
+    """urmapx_map_report in full: MapReportSort with the depth's seconds and totals appended.  map_files passes this one."""
+    _fields_ = MapReportSort._fields_ + [("depth_s", C.c_double), ("depth_runs", C.c_uint64), ("depth_covered", C.c_uint64), ("depth_bases", C.c_uint64)]
+
+
 class BamSortResult(C.Structure):
     _fields_ = [("bgzf", C.c_void_p), ("bai", C.c_void_p), ("bgzf_bytes", C.c_size_t), ("bai_bytes", C.c_size_t),
                 ("stream_bytes", C.c_uint64), ("records", C.c_uint64), ("no_coor", C.c_uint64), ("sort_passes", C.c_uint32),
@@ -126,6 +138,21 @@ class BamSortPlan(C.Structure):
 class MarkdupStats(C.Structure):
     _fields_ = [("pairs_examined", C.c_uint64), ("pairs_duplicate", C.c_uint64), ("fragments_examined", C.c_uint64),
                 ("fragments_duplicate", C.c_uint64), ("markdup_s", C.c_double)]
+
+
+class DepthOpts(C.Structure):
+    _fields_ = [("min_mapq", C.c_uint32)]
+
+
+class DepthSummary(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("covered", C.c_uint64), ("bases", C.c_uint64), ("mapq_sum", C.c_uint64)]
+
+
+class DepthResult(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("text_bytes", C.c_size_t), ("runs", C.c_uint64), ("refs", C.POINTER(DepthSummary)),
+                ("n_ref", C.c_uint32), ("text_slices", C.c_uint32), ("records", C.c_uint64), ("stage_chunks", C.c_uint64),
+                ("least_budget", C.c_uint64), ("alloc_s", C.c_double), ("count_s", C.c_double), ("scan_s", C.c_double),
+                ("runs_s", C.c_double), ("format_s", C.c_double), ("copy_s", C.c_double)]
 
 
 class ValidateReport(C.Structure):
@@ -236,7 +263,9 @@ def lib():
     L.urmapx_ctx_get_pair_info.argtypes = [vp, vp, u32]
     L.urmapx_tab_pe.restype = C.c_size_t
     L.urmapx_tab_pe.argtypes = [vp, vp, vp, vp, cp, u32, u32, i32, vp, C.c_size_t]
-    L.urmapx_map_files.argtypes = [vp, C.POINTER(MapOptionsSortMem), cp, cp, cp, cp, C.POINTER(MapReportSort), cp, C.c_size_t]
+    L.urmapx_map_files.argtypes = [vp, C.POINTER(MapOptionsDepth), cp, cp, cp, cp, C.POINTER(MapReportDepth), cp, C.c_size_t]
+    L.urmapx_map_depth_summary.argtypes = []
+    L.urmapx_map_depth_summary.restype = C.c_char_p
     L.urmapx_host_pool_trim.argtypes = []
     L.urmapx_host_pool_trim.restype = None
     L.urmapx_text_create.argtypes = [vp, C.POINTER(vp)]
@@ -657,24 +686,30 @@ def gunzip_file(gz_path, out_path, threads=0):
 
 def map_files(index: "Index", fastq1, fastq2=None, samout=None, tabout=None, first_gpu=0, gpus=1, streams=2, host_threads=0,
               batch=0, veryfast=False, minq=10, cmdline=None, allow_unsupported=False, sam_shards=0, discard_sam=False, bgzf=False, bam=False,
-              bam_sort=False, tags=0, read_group=None, markdup=False, sort_mem=0):
+              bam_sort=False, tags=0, read_group=None, markdup=False, sort_mem=0, depth_out=None, depth_mapq=0):
     """urmap -map / -map2 file to file (cmd_map / cmd_map2) on an index that has its host arrays or is resident on
     first_gpu.  bgzf: samout is a BGZF file (-bgzf).  bam: samout is a BAM file (-bamout).  bam_sort (with bam):
     its records in coordinate order, with the index samout + ".bai" beside it (-sort).  tags: TAG_* bits (-tags), read_group: an @RG line
     with real tabs (-rg): the optional fields of the records.  markdup (with bam_sort): flag 0x400 on duplicate records (-markdup),
     the counters in the report.  sort_mem (with bam_sort): the device bytes the sort may take (-sortmem); records that do not fit them
-    stream through the device, and the report's sort_partitions says in how many partitions.  -> dict of State1::HitStats' counters
-    and stage times."""
-    o = MapOptionsSortMem(first_gpu, gpus, streams, host_threads, batch, int(veryfast), minq, cmdline.encode() if cmdline else None,
+    stream through the device, and the report's sort_partitions says in how many partitions.  depth_out (with bam_sort): a bedGraph
+    file of the per-base depth of the records as written (-depth), depth_mapq: its least MAPQ (-depth_mapq); the report then holds
+    depth_s, depth_runs, depth_covered, depth_bases and, as depth_summary, the table per reference.  -> dict of State1::HitStats'
+    counters and stage times."""
+    o = MapOptionsDepth(first_gpu, gpus, streams, host_threads, batch, int(veryfast), minq, cmdline.encode() if cmdline else None,
                    int(sam_shards), int(discard_sam), int(bgzf), int(bam), int(bam_sort), int(tags),
-                   (read_group.encode("latin-1") if isinstance(read_group, str) else read_group), int(markdup), int(sort_mem))
-    rep = MapReportSort()
+                   (read_group.encode("latin-1") if isinstance(read_group, str) else read_group), int(markdup), int(sort_mem),
+                   os.fsencode(depth_out) if depth_out else None, int(depth_mapq))
+    rep = MapReportDepth()
     err = C.create_string_buffer(1024)
     enc = lambda p: os.fsencode(p) if p else None
     rc = lib().urmapx_map_files(index.h, C.byref(o), enc(fastq1), enc(fastq2), enc(samout), enc(tabout), C.byref(rep), err, len(err))
     if rc != 0 and not (rc == E_UNSUPPORTED and allow_unsupported):
         raise UrmapxError(rc, "urmapx_map_files: " + err.value.decode("latin-1"))
-    return {k: getattr(rep, k) for k, _ in MapReportSort._fields_}
+    out = {k: getattr(rep, k) for k, _ in MapReportDepth._fields_}
+    if depth_out:
+        out["depth_summary"] = lib().urmapx_map_depth_summary().decode("latin-1")
+    return out
 
 
 def calmd(ref: bytes, cigar, seq: bytes):
@@ -712,6 +747,103 @@ def read_group_id(line):
     if L.urmapx_read_group_id(raw, out, len(out), ident, len(ident), err, len(err)) != 0:
         raise ValueError(err.value.decode("latin-1"))
     return out.value.decode("latin-1"), ident.value.decode("latin-1")
+
+
+def _depth_refs(n_ref, names, lens):
+    """the names and lengths of n_ref references as the depth calls take them -> (char ** array, uint32 array)"""
+    names = [n.encode("latin-1") if isinstance(n, str) else bytes(n) for n in names]
+    if len(names) != int(n_ref) or len(lens) != int(n_ref):
+        raise ValueError("n_ref names and lengths are needed")
+    return (C.c_char_p * max(1, len(names)))(*names), np.ascontiguousarray(lens, dtype=np.uint32)
+
+
+def _depth_out(res, report):
+    """(text, runs, summaries[, report]) of a filled DepthResult; summaries: one dict of reads, covered, bases, mapq_sum per reference"""
+    text = C.string_at(res.text, res.text_bytes) if res.text_bytes else b""
+    refs = [{k: int(getattr(res.refs[r], k)) for k, _ in DepthSummary._fields_} for r in range(res.n_ref)]
+    out = (text, int(res.runs), refs)
+    return out + ({k: getattr(res, k) for k, _ in DepthResult._fields_ if k not in ("text", "refs")},) if report else out
+
+
+def _bam_depth(fn_name, head, records, n_ref, names, lens, min_mapq, report, starts):
+    src = np.frombuffer(bytes(records), dtype=np.uint8)
+    L = lib()
+    fn = getattr(L, fn_name)
+    fn.argtypes = ([C.c_int] * len(head) + [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.POINTER(DepthOpts), C.POINTER(DepthResult)])
+    L.urmapx_depth_free.argtypes = [C.POINTER(DepthResult)]
+    L.urmapx_depth_free.restype = None
+    nm, ln = _depth_refs(n_ref, names, lens)
+    st = np.ascontiguousarray(starts if starts is not None else [], dtype=np.uint64)
+    res, opts = DepthResult(), DepthOpts(int(min_mapq))
+    _check(fn(*head, src.ctypes.data if len(src) else None, len(src), int(n_ref), nm, ln.ctypes.data if len(ln) else None,
+              st.ctypes.data if len(st) else None, len(st), C.byref(opts), C.byref(res)), fn_name)
+    try:
+        return _depth_out(res, report)
+    finally:
+        L.urmapx_depth_free(C.byref(res))
+
+
+def bam_depth(records: bytes, n_ref, names, lens, device=0, min_mapq=0, report=False, starts=None):
+    """BAM alignment records back to back, in any order, and the references' names and lengths -> (the bedGraph text of the per-base
+    depth, its number of lines, one dict of reads / covered / bases / mapq_sum per reference), computed on the device
+    (urmapx_bam_depth; depth.hip; the rule is in include/urmapx.h "Depth").  min_mapq: records below it do not count.  report: a
+    fourth item, the call's counters and step times."""
+    return _bam_depth("urmapx_bam_depth", (int(device),), records, n_ref, names, lens, min_mapq, report, starts)
+
+
+def bam_depth_host(records: bytes, n_ref, names, lens, min_mapq=0, report=False, starts=None):
+    """the same contract on the host, no device (urmapx_bam_depth_host; depth_host.cpp)"""
+    return _bam_depth("urmapx_bam_depth_host", (), records, n_ref, names, lens, min_mapq, report, starts)
+
+
+def bam_depth_device_bytes(total_columns, n_ref, n_records):
+    """device bytes urmapx_bam_depth takes (host arithmetic)"""
+    L = lib()
+    L.urmapx_bam_depth_device_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64]
+    L.urmapx_bam_depth_device_bytes.restype = C.c_uint64
+    return int(L.urmapx_bam_depth_device_bytes(int(total_columns), int(n_ref), int(n_records)))
+
+
+def bam_depth_resident_bytes(total_columns, n_ref):
+    """device bytes the depth adds to the planned sort (host arithmetic)"""
+    L = lib()
+    L.urmapx_bam_depth_resident_bytes.argtypes = [C.c_uint64, C.c_uint32]
+    L.urmapx_bam_depth_resident_bytes.restype = C.c_uint64
+    return int(L.urmapx_bam_depth_resident_bytes(int(total_columns), int(n_ref)))
+
+
+def _bam_sort_depth(fn_name, head, records, n_ref, in_front, report, starts, markdup, depth, depth_mapq):
+    """the planned sort with the depth taken on the way (urmapx_bam_sort_depth, urmapx_bam_sort_depth_host) -> (members, bai, depth
+    result[, report]); the depth result is (text, runs, summaries) and the report holds its fields as depth_*"""
+    src = np.frombuffer(bytes(records), dtype=np.uint8)
+    L = lib()
+    fn = getattr(L, fn_name)
+    fn.argtypes = ([C.c_int, C.c_uint64][:len(head)] + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(MarkdupStats),
+                                                       C.POINTER(DepthOpts), C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(DepthResult), C.POINTER(BamSortResult)])
+    L.urmapx_bam_sort_free.argtypes = [C.POINTER(BamSortResult)]
+    L.urmapx_bam_sort_free.restype = None
+    L.urmapx_depth_free.argtypes = [C.POINTER(DepthResult)]
+    L.urmapx_depth_free.restype = None
+    nm, ln = _depth_refs(n_ref, *depth)
+    st = np.ascontiguousarray(starts if starts is not None else [], dtype=np.uint64)
+    res, md, dres, opts = BamSortResult(), MarkdupStats(), DepthResult(), DepthOpts(int(depth_mapq))
+    rc = fn(*head, src.ctypes.data if len(src) else None, len(src), int(n_ref), int(in_front), st.ctypes.data if len(st) else None, len(st),
+            C.byref(md) if markdup else None, C.byref(opts), nm, ln.ctypes.data if len(ln) else None, C.byref(dres), C.byref(res))
+    if rc != 0:
+        e = UrmapxError(rc, fn_name + (": %d bytes are needed at the least" % dres.least_budget if dres.least_budget else ""))
+        e.least_budget = int(dres.least_budget)
+        raise e
+    try:
+        out = (C.string_at(res.bgzf, res.bgzf_bytes) if res.bgzf_bytes else b"", C.string_at(res.bai, res.bai_bytes), _depth_out(dres, False))
+        rep = {k: getattr(res, k) for k, _ in BamSortResult._fields_ if k not in ("bgzf", "bai")}
+        if markdup:
+            rep.update({k: getattr(md, k) for k, _ in MarkdupStats._fields_})
+        rep.update({"depth_" + k: getattr(dres, k) for k, _ in DepthResult._fields_ if k not in ("text", "refs")})
+    finally:
+        L.urmapx_bam_sort_free(C.byref(res))
+        L.urmapx_depth_free(C.byref(dres))
+    return out + (rep,) if report else out
 
 
 def _bam_sort(fn_name, head, records, n_ref, in_front, report, starts=None, markdup=False, budget=None):
@@ -759,20 +891,28 @@ def bam_sort_plan(n_bytes, n_records, budget, markdup=False):
     return plan
 
 
-def bam_sort(records: bytes, n_ref, device=0, bytes_in_front=0, report=False, starts=None, markdup=False, budget=None):
+def bam_sort(records: bytes, n_ref, device=0, bytes_in_front=0, report=False, starts=None, markdup=False, budget=None, depth=None, depth_mapq=0):
     """BAM alignment records back to back -> (the records in coordinate order as BGZF members, the bytes of their .bai index), sorted on
     the device (urmapx_bam_sort; bam_sort.hip).  bytes_in_front: what the file holds in front of the first member, for the index's
     virtual offsets.  report: a third item, the call's counters and step times.  starts: offsets at which records are known to begin (the
     chain is then walked from all of them at once).  markdup: flag 0x400 of the records says whether they are duplicates
     (urmapx_bam_sort_markdup; markdup.hip), and the report holds the counters and markdup_s.  budget: device bytes the sort may take
     (0: what is free): the call is urmapx_bam_sort_external, which streams the records through the device where they do not fit the
-    budget; the report's external, partitions, stage_chunks and stage_s say what it did."""
+    budget; the report's external, partitions, stage_chunks and stage_s say what it did.  depth=(names, lens) of the n_ref references:
+    the call is urmapx_bam_sort_depth (budget None: 0), the per-base depth of the records as written -- under markdup without the
+    duplicates -- is taken while they are on the device, and a third item (text, runs, summaries) comes back, as from bam_depth;
+    depth_mapq: its least MAPQ."""
+    if depth is not None:
+        return _bam_sort_depth("urmapx_bam_sort_depth", (int(device), int(budget or 0)), records, n_ref, bytes_in_front, report, starts, markdup, depth,
+                               depth_mapq)
     return _bam_sort("urmapx_bam_sort", (int(device),), records, n_ref, bytes_in_front, report, starts, markdup, budget)
 
 
-def bam_sort_host(records: bytes, n_ref, bytes_in_front=0, report=False, starts=None, markdup=False):
+def bam_sort_host(records: bytes, n_ref, bytes_in_front=0, report=False, starts=None, markdup=False, depth=None, depth_mapq=0):
     """the same contract on the host, no device (urmapx_bam_sort_host, urmapx_bam_sort_markdup_host): std::stable_sort and zlib inside
-    the BGZF framing"""
+    the BGZF framing.  depth: as for bam_sort (urmapx_bam_sort_depth_host)"""
+    if depth is not None:
+        return _bam_sort_depth("urmapx_bam_sort_depth_host", (), records, n_ref, bytes_in_front, report, starts, markdup, depth, depth_mapq)
     return _bam_sort("urmapx_bam_sort_host", (), records, n_ref, bytes_in_front, report, starts, markdup)
 
 

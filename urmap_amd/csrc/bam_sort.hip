@@ -23,6 +23,7 @@
 //                    keys_kernel (and what the marking reads), then once per partition of the sorted stream, where place_kernel
 //                    copies the part of every staged record that falls into the partition to its place, as gather_kernel copies
 #include "bam_sort_dev.h"
+#include "depth_dev.h"
 
 #include <algorithm>
 #include <chrono>
@@ -404,10 +405,19 @@ struct StageStreams {
 	}
 };
 
+// what urmapx_bam_sort_depth adds to the planned sort (include/urmapx.h "Depth"); names and lens are checked (check_refs: entries)
+struct DepthAsk {
+	uint32_t min_mapq;
+	const char *const *names;
+	const uint32_t *lens;
+	uint64_t entries;
+	urmapx_depth_result *out;
+};
+
 // budget == nullptr: the in-core road, whatever it takes (urmapx_bam_sort, urmapx_bam_sort_markdup).  Else the road the plan names for
-// *budget device bytes (urmapx_bam_sort_external).
+// *budget device bytes (urmapx_bam_sort_external), with `dep` for what the depth arrays leave of them (urmapx_bam_sort_depth).
 int sort_device(int device, const uint64_t *budget, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts,
-                urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
+                urmapx_markdup_stats *md, const DepthAsk *dep, urmapx_bam_sort_result *out) {
 	auto t = Clock::now();
 	std::vector<uint64_t> offs;
 	uint32_t max_pos = 0;
@@ -427,8 +437,16 @@ int sort_device(int device, const uint64_t *budget, const uint8_t *rec, size_t n
 	memset(&P, 0, sizeof P);
 	std::vector<uint32_t> cut;
 	const bool look = md != nullptr;
+	// the depth arrays come off the budget before the sort is planned; where that fails, the least budget is theirs and the plan's
+	const uint64_t depth_bytes = dep ? urx::depth::resident_bytes(dep->entries, n_ref, urx::depth::text_runs()) : 0u;
+	const uint64_t sort_budget = budget ? (*budget > depth_bytes ? *budget - depth_bytes : 0u) : 0u;
+	auto plan = [&](uint64_t stage) -> int {
+		const int r = plan_with_stage(n_bytes, n, md != nullptr, sort_budget, stage, &P);
+		if (r == URMAPX_E_NOMEM && dep) dep->out->least_budget = depth_bytes + P.device_bytes;
+		return r;
+	};
 	if (budget) {
-		if ((rc = plan_with_stage(n_bytes, n, md != nullptr, *budget, default_stage_bytes(n_bytes), &P))) return rc;
+		if ((rc = plan(default_stage_bytes(n_bytes)))) return rc;
 		if (P.external) {
 			uint64_t need = 0;
 			for (uint64_t i0 = 0; i0 < n;) {
@@ -438,7 +456,7 @@ int sort_device(int device, const uint64_t *budget, const uint8_t *rec, size_t n
 				i0 = i1;
 			}
 			cut.push_back(n);
-			if (need > P.stage_bytes && (rc = plan_with_stage(n_bytes, n, md != nullptr, *budget, need, &P))) return rc;
+			if (need > P.stage_bytes && (rc = plan(need))) return rc;
 		}
 	}
 	const bool ext = P.external != 0;
@@ -452,7 +470,15 @@ int sort_device(int device, const uint64_t *budget, const uint8_t *rec, size_t n
 	Dev<uint32_t> d_val[3], d_end, d_hist, d_range, d_ref[4];
 	Dev<Chunk> d_chunks;
 	MarkdupOwn W;
+	urx::depth::DepthOwn DW;
 	StageStreams st;
+	if (dep) {
+		if (n >= 0x7FFFFFFFu) return URMAPX_E_ARG;
+		dep->out->records = n;
+		const double a0 = t_alloc_s;
+		if ((rc = DW.begin(n_ref, dep->names, dep->lens, dep->entries))) return rc;
+		dep->out->alloc_s = t_alloc_s - a0;
+	}
 	if (ext) {  // (the pieces external_device_bytes counts, in its order; the partition is not larger than the stream)
 		const size_t part_cap = (size_t)std::min<uint64_t>(P.partition_bytes, n_bytes);
 		if ((md && ((rc = W.begin(n)) || (rc = d_action.alloc(n)))) || (rc = d_stage[0].alloc((size_t)P.stage_bytes + 16)) ||
@@ -594,6 +620,16 @@ int sort_device(int device, const uint64_t *budget, const uint8_t *rec, size_t n
 		md->markdup_s = since(t);
 	}
 
+	// depth, in core: one launch over the records as they came, now that every bit 0x400 is what the file will hold.  (On the external
+	// road the decisions wait in d_action until the records pass again: the first placing pass counts, below)
+	if (dep && !ext) {
+		t = Clock::now();
+		if ((rc = urx::depth::depth_count(DW, d_rec.p, 0, d_off.p, 0, n, nullptr, dep->min_mapq, nullptr))) return rc;
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(nullptr));
+		dep->out->count_s = since(t);
+	}
+
 	// the sorted stream, a slice at a time: gather, deflate, copy back
 	const size_t slice_bytes = (size_t)slice_members() * MEMBER;
 	const size_t slice_cap = slice_bytes < n_bytes ? slice_bytes : n_bytes, z_cap = urmapx_bgzf_bound(slice_cap);
@@ -647,10 +683,12 @@ int sort_device(int device, const uint64_t *budget, const uint8_t *rec, size_t n
 		HIP_TRY(hipGetLastError());
 		for (uint64_t p0 = 0; p0 < n_bytes; p0 += P.partition_bytes) {
 			const uint64_t p1 = p0 + P.partition_bytes < n_bytes ? p0 + P.partition_bytes : n_bytes;
+			// (every record crosses the device in each of these passes: the depth is taken in the first one only)
+			const bool count = dep && p0 == 0;
 			int r = pass(false, [&](const uint8_t *at, uint64_t base, uint32_t i0, uint32_t i1, hipStream_t s) -> int {
 				hipLaunchKernelGGL(place_kernel, dim3(grid_for(i1 - i0)), dim3(NT), 0, s, at, base, (const uint64_t *)d_off.p, i0, i1, (const uint64_t *)place,
 				                   (const uint8_t *)(md ? d_action.p : nullptr), p0, p1, d_part.p);
-				return URMAPX_OK;
+				return count ? urx::depth::depth_count(DW, at, base, d_off.p, i0, i1, md ? d_action.p : nullptr, dep->min_mapq, s) : URMAPX_OK;
 			});
 			if (r) return r;
 			for (uint64_t s0 = p0; s0 < p1; s0 += slice_bytes) {
@@ -662,6 +700,7 @@ int sort_device(int device, const uint64_t *budget, const uint8_t *rec, size_t n
 	};
 	rc = ext ? partitions() : slices();
 	urmapx_bgzf_destroy(Z);
+	if (!rc && dep) rc = urx::depth::depth_finish(DW, dep->out);
 	if (rc) { free(z); return rc; }
 	if (uint8_t *fit = (uint8_t *)realloc(z, z_bytes ? z_bytes : 1)) z = fit;
 	t = Clock::now();
@@ -684,7 +723,7 @@ uint64_t urmapx_bam_sort_markdup_device_bytes(size_t n_bytes, uint64_t n_records
 }
 
 static int sort_entry(int device, const uint64_t *budget, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
-                      size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
+                      size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out, const DepthAsk *dep = nullptr) {
 	if (!out || (n_bytes && !records) || (n_starts && !starts)) return URMAPX_E_ARG;
 	memset(out, 0, sizeof *out);
 	if (md) memset(md, 0, sizeof *md);
@@ -700,12 +739,13 @@ static int sort_entry(int device, const uint64_t *budget, const void *records, s
 			HIP_TRY(hipMemGetInfo(&free_b, &total_b));
 			have = free_b > URMAPX_SORT_HEADROOM ? (uint64_t)free_b - URMAPX_SORT_HEADROOM : 1u;
 		}
-		rc = sort_device(device, budget ? &have : nullptr, (const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
+		rc = sort_device(device, budget ? &have : nullptr, (const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, dep, out);
 	} catch (const std::bad_alloc &) {
 		rc = URMAPX_E_NOMEM;
 	}
 	out->alloc_s = t_alloc_s;  // (the arrays are freed by now)
 	if (rc) urmapx_bam_sort_free(out);
+	if (rc && dep) urmapx_depth_free(dep->out);
 	return rc;
 }
 
@@ -723,6 +763,16 @@ int urmapx_bam_sort_markdup(int device, const void *records, size_t n_bytes, uin
 int urmapx_bam_sort_external(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
                              const uint64_t *starts, size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
 	return sort_entry(device, &budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
+}
+
+int urmapx_bam_sort_depth(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
+                          const uint64_t *starts, size_t n_starts, urmapx_markdup_stats *md, const urmapx_depth_opts *dopts,
+                          const char *const *names, const uint32_t *lens, urmapx_depth_result *depth, urmapx_bam_sort_result *out) {
+	if (!depth) return sort_entry(device, &budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
+	memset(depth, 0, sizeof *depth);
+	DepthAsk ask{dopts ? dopts->min_mapq : 0u, names, lens, 0, depth};
+	if (const int rc = urx::depth::check_refs(n_ref, names, lens, &ask.entries)) return rc;
+	return sort_entry(device, &budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out, &ask);
 }
 
 }  // extern "C"

@@ -226,7 +226,7 @@ using Clock = std::chrono::steady_clock;
 double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::now() - t).count(); }
 
 int sort_host(const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts, urmapx_markdup_stats *md,
-              urmapx_bam_sort_result *out) {
+              urmapx_bam_sort_result *out, const AfterMark *hook) {
 	auto t = Clock::now();
 	std::vector<uint64_t> offs;
 	uint32_t max_pos = 0;
@@ -254,6 +254,7 @@ int sort_host(const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_fr
 		if ((rc = markdup_host(rec, offs, action, md))) return rc;
 		md->markdup_s = since(t);
 	}
+	if (hook && (rc = (*hook)(rec, offs, md ? action.data() : nullptr))) return rc;
 
 	t = Clock::now();
 	std::vector<uint8_t> stream(n_bytes);
@@ -327,13 +328,13 @@ int sort_host(const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_fr
 extern "C" {
 
 static int sort_host_entry(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts, size_t n_starts,
-                           urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
+                           urmapx_markdup_stats *md, urmapx_bam_sort_result *out, const AfterMark *hook = nullptr) {
 	if (!out || (n_bytes && !records) || (n_starts && !starts)) return URMAPX_E_ARG;
 	memset(out, 0, sizeof *out);
 	if (md) memset(md, 0, sizeof *md);
 	int rc;
 	try {
-		rc = sort_host((const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
+		rc = sort_host((const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out, hook);
 	} catch (const std::bad_alloc &) {
 		rc = URMAPX_E_NOMEM;
 	}
@@ -366,3 +367,12 @@ void urmapx_bam_sort_free(urmapx_bam_sort_result *R) {
 }
 
 }  // extern "C"
+
+namespace urx {
+namespace bamsort {
+int sort_host_hooked(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts, size_t n_starts,
+                     urmapx_markdup_stats *md, urmapx_bam_sort_result *out, const AfterMark &hook) {
+	return sort_host_entry(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out, &hook);
+}
+}  // namespace bamsort
+}  // namespace urx

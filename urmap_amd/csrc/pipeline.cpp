@@ -862,6 +862,11 @@ void omp_team(int n) { omp_workers_sleep_when_idle(); omp_set_num_threads(n); }
 void say(char *err, size_t errcap, const std::string &s) {
 	if (err && errcap) snprintf(err, errcap, "%s", s.c_str());
 }
+// the table per reference of this thread's last run with depth_out (urmapx_map_depth_summary)
+std::string &depth_summary() {
+	static thread_local std::string table;
+	return table;
+}
 // host threads for FASTQ parsing and SAM formatting (the mapping itself runs on the GPU)
 int host_threads_of(const urmapx_map_options &o) {
 	return o.host_threads > 0 ? o.host_threads : std::min(16, std::max(1, (int)std::thread::hardware_concurrency()));
@@ -1113,11 +1118,50 @@ struct Run {
 		int rc;
 		const std::vector<uint64_t> starts = sink.kept_starts();
 		const bool markdup = opt.markdup != 0;
+		// depth_out: the planned sort with the depth taken on the way (include/urmapx.h "Depth"); the names are those of the @SQ lines
+		const bool depth = opt.depth_out != nullptr;
+		urmapx_depth_result D;
+		memset(&D, 0, sizeof D);
+		const urmapx_depth_opts dopts{opt.depth_mapq};
+		std::vector<const char *> ref_names;
+		std::vector<uint32_t> ref_lens;
+		for (uint32_t r = 0; depth && r < n_ref; ++r) {
+			ref_names.push_back(urmapx_index_label(I, r));
+			ref_lens.push_back(urmapx_index_seq_length(I, r));
+		}
+		if (depth) {
+			auto with_depth = [&]() {
+				return urmapx_bam_sort_depth(phys(0), opt.sort_mem, sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), markdup ? &M : nullptr,
+				                             &dopts, ref_names.data(), ref_lens.data(), &D, &S);
+			};
+			if (getenv("URMAPX_HOST_TEXT") || getenv("URMAPX_HOST_SORT"))
+				rc = urmapx_bam_sort_depth_host(sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), markdup ? &M : nullptr, &dopts,
+				                                ref_names.data(), ref_lens.data(), &D, &S);
+			else {
+				rc = with_depth();
+				if (rc == URMAPX_E_NOMEM) {  // the same ladder as below: the lanes go first; the planned call itself streams where it must
+					close();
+					LanePool::get().purge(nullptr);
+					rc = with_depth();
+				}
+				if (rc == URMAPX_E_NOMEM) {
+					if (D.least_budget)
+						fail.raise(rc, "bam_sort with depth: the depth's counters, the sort's arrays, its staging buffers and one slice need at least " +
+						                   std::to_string(D.least_budget) + " bytes on the device" +
+						                   (opt.sort_mem ? ", " + std::to_string(opt.sort_mem) + " were given (sort_mem)" : std::string(", fewer are free")));
+					else
+						fail.raise(rc, "bam_sort with depth: out of device memory");
+					return;
+				}
+			}
+			if (rc == URMAPX_E_ARG) { fail.raise(rc, "depth: a reference name that is empty or longer than 255 bytes"); return; }
+		}
 		auto on_device = [&]() {
 			return markdup ? urmapx_bam_sort_markdup(phys(0), sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &M, &S)
 			               : urmapx_bam_sort(phys(0), sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &S);
 		};
-		if (getenv("URMAPX_HOST_TEXT") || getenv("URMAPX_HOST_SORT"))
+		if (depth) {  // (done above)
+		} else if (getenv("URMAPX_HOST_TEXT") || getenv("URMAPX_HOST_SORT"))
 			rc = markdup ? urmapx_bam_sort_markdup_host(sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &M, &S)
 			             : urmapx_bam_sort_host(sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &S);
 		else {
@@ -1169,6 +1213,35 @@ struct Run {
 			                "records %llu bytes %llu passes %u slices %u\n",
 			        rep.sort_s, S.scan_s, S.alloc_s, S.upload_s, S.sort_s, S.gather_s, S.deflate_s, S.copy_s, S.index_s, secs(tw0, now()),
 			        (unsigned long long)S.records, (unsigned long long)S.stream_bytes, S.sort_passes, S.slices);
+		if (depth) {  // the bedGraph file, with the writer threads a file of the sink's kind gets; then the table
+			const auto td0 = now();
+			FileSink dsink;
+			if (!dsink.open(opt.depth_out) || !dsink.write_at(D.text, D.text_bytes, 0, dsink.writer_threads(host_threads)) || !dsink.finish(D.text_bytes))
+				fail.raise(URMAPX_E_IO, std::string("Error writing ") + opt.depth_out);
+			const double file_s = secs(td0, now());
+			rep.write_s += file_s;
+			rep.sort_s = secs(t0, now());
+			rep.depth_runs = D.runs;
+			std::string &table = depth_summary();
+			table = "reference\tlength\treads\tcovered\tpercent\tmean_depth\tmean_mapq\n";
+			for (uint32_t r = 0; r < n_ref; ++r) {
+				const urmapx_depth_summary &s = D.refs[r];
+				rep.depth_covered += s.covered;
+				rep.depth_bases += s.bases;
+				char line[160];
+				snprintf(line, sizeof line, "\t%u\t%llu\t%llu\t%.2f\t%.2f\t%.2f\n", ref_lens[r], (unsigned long long)s.reads, (unsigned long long)s.covered,
+				         ref_lens[r] ? 100.0 * (double)s.covered / ref_lens[r] : 0.0, ref_lens[r] ? (double)s.bases / ref_lens[r] : 0.0,
+				         s.reads ? (double)s.mapq_sum / (double)s.reads : 0.0);
+				table += ref_names[r];
+				table += line;
+			}
+			rep.depth_s = D.alloc_s + D.count_s + D.scan_s + D.runs_s + D.format_s + D.copy_s + file_s;
+			if (getenv("URMAPX_VERBOSE"))  // (scripts/depth_bench.py reads this line)
+				fprintf(stderr, "depth seconds: total %.4f alloc %.4f count %.4f scan %.4f runs %.4f format %.4f copy %.4f write %.4f; runs %llu bytes %llu slices %u\n",
+				        rep.depth_s, D.alloc_s, D.count_s, D.scan_s, D.runs_s, D.format_s, D.copy_s, file_s, (unsigned long long)D.runs, (unsigned long long)D.text_bytes,
+				        D.text_slices);
+			urmapx_depth_free(&D);
+		}
 		rep.sort_partitions = S.external ? S.partitions : 0;
 		if (S.external && getenv("URMAPX_VERBOSE"))  // (scripts/bam_sort_external_bench.py reads this line)
 			fprintf(stderr, "bam_sort external: partitions %u chunks %llu passes %u stage %.4f\n", S.partitions, (unsigned long long)S.stage_chunks, S.partitions + 1u, S.stage_s);
@@ -1195,6 +1268,7 @@ struct Run {
 		if (sort && fail.set.load()) {  // a failed sorted run leaves neither file
 			remove(samout);
 			remove((std::string(samout) + ".bai").c_str());
+			if (opt.depth_out) remove(opt.depth_out);
 		}
 		ftab.reset();  // (inside the run's clock; the lanes are let go outside it)
 		const auto t2 = now();
@@ -1988,6 +2062,14 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
 	}
 	if (opt->markdup && !opt->bam_sort) { say(err, errcap, "markdup needs bam_sort: the duplicates are marked while the records are sorted"); return URMAPX_E_ARG; }
 	if (opt->sort_mem && !opt->bam_sort) { say(err, errcap, "sort_mem needs bam_sort: it is the device memory the sort may take"); return URMAPX_E_ARG; }
+	depth_summary().clear();
+	if (opt->depth_out && !opt->bam_sort) { say(err, errcap, "depth_out needs bam_sort: the depth is taken while the records are sorted"); return URMAPX_E_ARG; }
+	if (opt->depth_mapq && !opt->depth_out) { say(err, errcap, "depth_mapq needs depth_out: it is the least MAPQ of a record the depth counts"); return URMAPX_E_ARG; }
+	if (opt->depth_mapq > 255) { say(err, errcap, "depth_mapq: a MAPQ is 0 .. 255"); return URMAPX_E_ARG; }
+	if (opt->depth_out && samout && (!strcmp(opt->depth_out, samout) || std::string(opt->depth_out) == std::string(samout) + ".bai")) {
+		say(err, errcap, "depth_out names the BAM file or its index: the depth needs a file of its own");
+		return URMAPX_E_ARG;
+	}
 	const int shards = opt->sam_shards > 1 ? opt->sam_shards : 1;
 	if (shards == 1) return map_files_impl(I, opt, InputRange(), fastq1, fastq2, samout, tabout, report, err, errcap);
 	const bool paired = fastq2 != nullptr;
@@ -2155,6 +2237,7 @@ extern "C" int urmapx_map_files(urmapx_index *I, const urmapx_map_options *opt, 
 	}
 	return rc;
 }
+extern "C" const char *urmapx_map_depth_summary(void) { return depth_summary().c_str(); }
 extern "C" void urmapx_host_pool_trim(void) {
 	LanePool::get().purge(nullptr);
 	HostPool::get().trim();

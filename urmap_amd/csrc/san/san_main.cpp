@@ -1,7 +1,7 @@
 // san_main.cpp -- driver of the sanitizer builds (make san): the host side of the drop-in path run from the command line, with the
 // device side replaced by san/stub_device.cpp.  tests/test_sanitizers_cpu.py runs it on well-formed and on damaged input; a
 // sanitizer report ends the process with exit code 99 (ASAN_OPTIONS / UBSAN_OPTIONS / TSAN_OPTIONS exitcode, set by the tests).
-//   urmap_san map <fastq1> [-2 fastq2] -o out.sam [-tab out.tab] [-batch N] [-streams K] [-gpus N] [-shards N] [-threads T] [-null] [-bgzf] [-bam] [-sort] [-markdup] [-sortmem N[G]] [-biglen N] [-tags MASK] [-rg LINE]
+//   urmap_san map <fastq1> [-2 fastq2] -o out.sam [-tab out.tab] [-batch N] [-streams K] [-gpus N] [-shards N] [-threads T] [-null] [-bgzf] [-bam] [-sort] [-markdup] [-sortmem N[G]] [-depth FILE [-depthq N]] [-biglen N] [-tags MASK] [-rg LINE]
 //       (-tags: URMAPX_TAG_* bits, -rg: an @RG line with real tabs; both need the stand-in store, which exists with -biglen up to 60 000 000)
 //       (-biglen: bases of the stand-in index's third sequence, 4 000 000 000 unless given; a BAM position holds 2^31 - 1)
 //   urmap_san gunzip <in.gz> <out> [threads]
@@ -45,6 +45,8 @@ static int cmd_map(int argc, char **argv) {
 			o.sort_mem = strtoull(val(), &end, 10);
 			if (end && *end == 'G') o.sort_mem <<= 30;
 		}
+		else if (a == "-depth") o.depth_out = val();
+		else if (a == "-depthq") o.depth_mapq = (uint32_t)atoi(val());
 		else if (a == "-tags") o.tags = (unsigned)atoi(val());
 		else if (a == "-rg") o.read_group = val();
 		else if (a == "-biglen") biglen = (uint32_t)strtoul(val(), nullptr, 10);
@@ -59,6 +61,9 @@ static int cmd_map(int argc, char **argv) {
 	if (o.markdup && rc == URMAPX_OK)
 		printf("markdup pairs=%llu pair_dups=%llu fragments=%llu fragment_dups=%llu\n", (unsigned long long)rep.pairs_examined, (unsigned long long)rep.pairs_duplicate,
 		       (unsigned long long)rep.fragments_examined, (unsigned long long)rep.fragments_duplicate);
+	if (o.depth_out && rc == URMAPX_OK)
+		printf("depth runs=%llu covered=%llu bases=%llu\n%s", (unsigned long long)rep.depth_runs, (unsigned long long)rep.depth_covered, (unsigned long long)rep.depth_bases,
+		       urmapx_map_depth_summary());
 	printf("rc=%d reads=%llu mapped_q=%llu mapped_lowq=%llu unmapped=%llu text_on_device=%d input_bytes=%llu shards=%d lanes=%d err=%s\n", rc, (unsigned long long)rep.reads,
 	       (unsigned long long)rep.mapped_q, (unsigned long long)rep.mapped_lowq, (unsigned long long)rep.unmapped, rep.text_on_device, (unsigned long long)rep.input_bytes, rep.shards,
 	       rep.lanes, err);

@@ -407,6 +407,30 @@ int urmapx_bam_sort_external(int, uint64_t budget, const void *records, size_t n
 	if (rc == URMAPX_OK) { out->external = (uint32_t)plan.external; out->partitions = (uint32_t)plan.partitions; }
 	return rc;
 }
+// the depth's stand-ins: the host version (depth_host.cpp); the planned sort with depth keeps the refusal of a budget that does not
+// hold the depth arrays
+int urmapx_bam_depth(int, const void *records, size_t n_bytes, uint32_t n_ref, const char *const *names, const uint32_t *lens, const uint64_t *starts,
+                     size_t n_starts, const urmapx_depth_opts *opts, urmapx_depth_result *out) {
+	return urmapx_bam_depth_host(records, n_bytes, n_ref, names, lens, starts, n_starts, opts, out);
+}
+int urmapx_bam_sort_depth(int device, uint64_t budget, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts,
+                          size_t n_starts, urmapx_markdup_stats *md, const urmapx_depth_opts *dopts, const char *const *names, const uint32_t *lens,
+                          urmapx_depth_result *depth, urmapx_bam_sort_result *out) {
+	if (!depth) return urmapx_bam_sort_external(device, budget, records, n_bytes, n_ref, in_front, starts, n_starts, md, out);
+	memset(depth, 0, sizeof *depth);
+	if (budget == 0) budget = ((uint64_t)200 << 30) - URMAPX_SORT_HEADROOM;  // (hipMemGetInfo above)
+	uint64_t columns = 0;
+	for (uint32_t r = 0; r < n_ref && lens; ++r) columns += lens[r];
+	const uint64_t own = urmapx_bam_depth_resident_bytes(columns, n_ref);
+	urmapx_bam_sort_plan plan;
+	if (const int rc = urmapx_bam_sort_plan_for(n_bytes, n_bytes / 200 + 1, md != nullptr, budget > own ? budget - own : 0u, &plan)) {
+		if (rc == URMAPX_E_NOMEM) depth->least_budget = own + plan.device_bytes;
+		return rc;
+	}
+	const int rc = urmapx_bam_sort_depth_host(records, n_bytes, n_ref, in_front, starts, n_starts, md, dopts, names, lens, depth, out);
+	if (rc == URMAPX_OK) { out->external = (uint32_t)plan.external; out->partitions = (uint32_t)plan.partitions; }
+	return rc;
+}
 uint64_t urmapx_bam_sort_device_bytes(size_t n_bytes, uint64_t n_records) { return n_bytes + 48u * n_records; }
 uint64_t urmapx_bam_sort_markdup_device_bytes(size_t n_bytes, uint64_t n_records) { return n_bytes + 72u * n_records; }
 }

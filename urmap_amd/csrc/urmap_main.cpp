@@ -67,6 +67,9 @@ struct Opts {
 	bool markdup = false;  // -markdup: with -sort, flag 0x400 on the duplicates
 	std::string sortmem;   // -sortmem N[K|M|G]: with -sort, the device memory the sort may take
 	bool sortmem_given = false;
+	std::string depth;     // -depth FILE: with -sort, a bedGraph file of the per-base depth of the records of the -bamout file
+	std::string depth_mapq;  // -depth_mapq N: with -depth, the least MAPQ of a record that counts
+	bool depth_given = false, depth_mapq_given = false;
 	std::string tags, rg;  // -tags NM,MD,AS and -rg '@RG\tID:..': optional fields of the records, the read group's header line
 	bool tags_given = false, rg_given = false;
 	bool trunclabels = false, wordlength_given = false;
@@ -133,6 +136,8 @@ static Opts parse(int argc, char **argv) {
 		else if (a == "-sort") o.sort = true;
 		else if (a == "-markdup") o.markdup = true;
 		else if (a == "-sortmem") { o.sortmem = val(); o.sortmem_given = true; }
+		else if (a == "-depth") { o.depth = val(); o.depth_given = true; }
+		else if (a == "-depth_mapq") { o.depth_mapq = val(); o.depth_mapq_given = true; }
 		else if (a == "-tags") { o.tags = val(); o.tags_given = true; }
 		else if (a == "-rg") { o.rg = val(); o.rg_given = true; }
 		else if (a == "-quiet") o.quiet = true;
@@ -237,6 +242,21 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 		sort_mem = parse_bytes(o.sortmem);
 		if (!sort_mem) die("-sortmem %s: a number of bytes from 1 on, with K, M or G behind it for powers of 1024", o.sortmem.c_str());
 	}
+	unsigned depth_mapq = 0;
+	if (o.depth_mapq_given) {
+		if (!o.depth_given) die("-depth_mapq needs -depth: it is the least MAPQ of a record that the depth file counts");
+		char *end = nullptr;
+		const unsigned long v = strtoul(o.depth_mapq.c_str(), &end, 10);
+		if (o.depth_mapq.empty() || *end || o.depth_mapq[0] == '-' || v > 255) die("-depth_mapq %s: a MAPQ from 0 to 255", o.depth_mapq.c_str());
+		depth_mapq = (unsigned)v;
+	}
+	if (o.depth_given) {
+		struct stat st;
+		if (!o.sort) die("-depth needs -sort: the depth is taken while the records of the -bamout file are sorted");
+		if (o.depth.empty()) die("-depth needs a file name");
+		if (o.depth == o.bamout || o.depth == o.bamout + ".bai") die("-depth %s: that is the -bamout file or its index; the depth needs a file of its own", o.depth.c_str());
+		if (stat(o.depth.c_str(), &st) == 0 && !S_ISREG(st.st_mode)) die("-depth needs a file name, not a pipe or %s: the file is written at the end of the run, in pieces", o.depth.c_str());
+	}
 	if (o.sort) {
 		struct stat st;
 		if (!bam) die("-sort needs -bamout: it sorts the records of a BAM file");
@@ -278,6 +298,8 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 	mo.read_group = o.rg_given ? rg_line.data() : nullptr;
 	mo.markdup = o.markdup ? 1 : 0;
 	mo.sort_mem = sort_mem;
+	mo.depth_out = o.depth_given ? o.depth.c_str() : nullptr;
+	mo.depth_mapq = depth_mapq;
 	urmapx_map_report rep;
 	memset(&rep, 0, sizeof rep);
 	char err[1024];
@@ -320,6 +342,11 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 			progress_log(q, bam ? "%16s  Bytes of BAM records, %s written as BGZF (%.3f)\n\n" : "%16s  Bytes of SAM text, %s written as BGZF (%.3f)\n\n", commas(rep.sam_text_bytes).c_str(), commas(rep.sam_file_bytes).c_str(),
 			             rep.sam_text_bytes ? (double)rep.sam_file_bytes / (double)rep.sam_text_bytes : 0.0);
 		if (o.sort) progress_log(q, "%16.3f  Seconds to sort the records and write %s.bai\n\n", rep.sort_s, samout.c_str());
+		if (o.depth_given) {
+			progress_log(q, "%16.3f  Seconds for the depth: %llu lines in %s, %llu columns covered, %llu bases on them\n", rep.depth_s, (unsigned long long)rep.depth_runs,
+			             o.depth.c_str(), (unsigned long long)rep.depth_covered, (unsigned long long)rep.depth_bases);
+			progress_log(q, "%s\n", urmapx_map_depth_summary());
+		}
 		if (o.markdup)
 			progress_log(q, "%16.3f  Seconds to mark duplicates: %llu of %llu pairs, %llu of %llu fragments\n\n", rep.markdup_s, (unsigned long long)rep.pairs_duplicate,
 			             (unsigned long long)rep.pairs_examined, (unsigned long long)rep.fragments_duplicate, (unsigned long long)rep.fragments_examined);
@@ -630,6 +657,9 @@ int main(int argc, char **argv) {
 	                "               with -samshards N every out.bam.0 .. out.bam.N-1 is a complete BAM file\n"
 	                "      -sort: with -bamout, the records in coordinate order (sorted on the GPU) and the index out.bam.bai beside the file\n"
                 "      -markdup: with -sort, flag 0x400 on duplicate reads (Picard's rule: same ends, the best qualities stay), marked on the GPU\n"
+                "      -depth FILE: with -sort, the per-base depth of the records as written (with -markdup: without the duplicates) as a\n"
+                "          bedGraph file, runs of depth 0 included, computed on the GPU beside the sort; a table per reference goes to the log\n"
+                "      -depth_mapq N: with -depth, records with a MAPQ below N do not count (0..255; default 0)\n"
                 "      -sortmem N[K|M|G]: with -sort, the GPU memory the sort may take; records that do not fit it stream through the GPU in partitions\n"
 	                "      -tags NM,MD,AS: these optional fields behind QUAL of every mapped record (any subset; computed on the GPU), SAM and BAM\n"
 	                "      -rg '@RG\\tID:x\\tSM:y': that line in the header in front of @PG and RG:Z:x on every record\n"
