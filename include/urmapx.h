@@ -771,7 +771,9 @@ typedef struct urmapx_bam_sort_result {
 	uint32_t sort_passes;    /* histogram-scan-scatter rounds of the coordinate sort (device) */
 	uint32_t slices;         /* pieces the sorted stream was made in (device) */
 	double scan_s;           /* the walk along the block_size chain (host, both versions) */
-	double alloc_s;          /* device: hipMalloc and hipFree of the call's arrays (inside no other part) */
+	double alloc_s;          /* device: hipMalloc and hipFree of the call's arrays.  Inside no other part, but for the arrays that are
+	                          * allocated once their sizes are known: the linear index and the chunks (also inside index_s) and, in
+	                          * core, the marking's own (also inside markdup_s) */
 	double upload_s, sort_s, gather_s, deflate_s, copy_s, index_s;  /* records to the device; key + sort launches; gather launches; the
 	                          * compressor; members back to the host; index kernels and the .bai bytes.  Host version: sort_s (the sort),
 	                          * gather_s (the copy into order), deflate_s, index_s */

@@ -138,6 +138,50 @@ def test_sort_mem_through_the_pipeline_under_the_sanitizers(san, tmp_path):  # n
     assert rc == 1 and "sort_mem needs bam_sort" in text
 
 
+IN_CORE, MARKING, PLANNED, DEPTH = "urmapx_bam_sort", "urmapx_bam_sort_markdup", "urmapx_bam_sort_external", "urmapx_bam_sort_depth"
+G = 1 << 30
+# options, the device-sort calls the stand-in refuses, the calls it then sees (entry, budget; None: an in-core entry), does the run end well
+LADDER = [
+    ([], 0, [(IN_CORE, None)], True),
+    ([], 1, [(IN_CORE, None)] * 2, True),
+    ([], 2, [(IN_CORE, None)] * 2 + [(PLANNED, 0)], True),
+    (["-markdup"], 0, [(MARKING, None)], True),
+    (["-markdup"], 2, [(MARKING, None)] * 2 + [(PLANNED, 0)], True),
+    (["-sortmem", "1G"], 1, [(PLANNED, G)] * 2, True),
+    (["-sortmem", "1G"], 2, [(PLANNED, G)] * 2, False),
+    (["-depth"], 0, [(DEPTH, 0)], True),
+    (["-depth"], 1, [(DEPTH, 0)] * 2, True),
+]
+
+
+def test_the_order_in_which_the_device_sorts_are_tried(san, tmp_path):  # noqa: F811
+    """the ladder of Run::write_sorted's sort (pipeline.cpp) through the stand-in device, which finds the device full K times
+    (URX_STUB_SORT_NOMEM) and says which entry was called with what budget: in core twice, then planned from what is free; a planned
+    sort (sort_mem, depth_out) twice and nothing else; then the refusal, which leaves no file.  Whatever the rung, the files are those
+    of the run that was never refused."""
+    fq = tmp_path / "r.fq"
+    fq.write_bytes(b"".join(b"@r%d\n%s\n+\n%s\n" % (i, b"ACGT"[i % 4:] + b"ACGT" * 9, b"I" * (40 - i % 4)) for i in range(300)))
+    want = {}
+    for n, (extra, k, calls, ok) in enumerate(LADDER):
+        out, bed = tmp_path / f"{n}.bam", tmp_path / f"{n}.bedgraph"
+        args = ["map", fq, "-o", out, "-biglen", "300000", "-bam", "-sort"] + [a for e in extra for a in ([e, bed] if e == "-depth" else [e])]
+        rc, text = san_run(san["asan"], args, env={"URX_STUB_MAP": "1", "URX_STUB_SORT_NOMEM": str(k)})
+        seen = [l.split() for l in text.splitlines() if l.startswith("stub sort: ")]
+        assert [(w[2], int(w[4]) if len(w) > 3 else None) for w in seen] == calls, text
+        bai = tmp_path / f"{n}.bam.bai"
+        if not ok:
+            assert rc == 1 and "rc=-3" in text and "bam_sort: out of device memory: the plan takes " in text, text
+            assert not out.exists() and not bai.exists()
+            continue
+        assert rc == 0, text
+        files = (out.read_bytes(), bai.read_bytes(), bed.read_bytes() if "-depth" in extra else None)
+        assert len(files[0]) > 1000 and len(files[1]) > 8
+        # (marking changes the records' flags; the budget and the depth change nothing of the BAM file)
+        assert files == want.setdefault(("-markdup" in extra, "-depth" in extra), files), (extra, k)
+    assert want[False, False][:2] == want[False, True][:2] and want[False, True][2]
+    assert want[False, False] != want[True, False]
+
+
 def test_an_empty_input_plans_no_partition():
     p = api.bam_sort_plan(0, 0, 1 << 40)
     assert p["external"] == 0 and p["partitions"] == 0

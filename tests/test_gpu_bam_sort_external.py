@@ -123,6 +123,27 @@ def test_partitions_and_chunks(monkeypatch, four_thousand, partition, stage):
     assert all(any(o < c < o + len(r) for o, r in recs) for c in cuts), "no record straddles a partition's end"
 
 
+# ---- what the report says of each road ----
+@pytest.mark.parametrize("markdup", [False, True])
+def test_the_report_of_each_road(monkeypatch, four_thousand, markdup):
+    """the counters and step times that only one road fills: slices of one member on both; gather_s in core, where nothing is staged;
+    partitions, staged chunks (bam_sort.h's chunk_end over the records' lengths) and stage_s on the external road, where nothing is
+    gathered; the same coordinate sort on both; under marking its time on both"""
+    from urmap_amd import api
+    records, _ = four_thousand
+    slices = -(-len(records) // sl.MEMBER)
+    core = api.bam_sort(records, 1, device=0, report=True, markdup=markdup)[2]
+    assert core["slices"] == slices and core["partitions"] == 0 and core["stage_chunks"] == 0
+    assert core["stage_s"] == 0 and core["gather_s"] > 0
+    ext = external(monkeypatch, records, 1, 2, 4096, markdup=markdup)[2]
+    assert ext["slices"] == slices and ext["partitions"] == -(-slices // 2)
+    assert ext["stage_chunks"] == len(chunk_starts(lengths(records), 4096, look=markdup))
+    assert ext["gather_s"] == 0 and ext["stage_s"] > 0
+    assert ext["sort_passes"] == core["sort_passes"] > 0
+    if markdup:
+        assert core["markdup_s"] > 0 and ext["markdup_s"] > 0
+
+
 # ---- a record longer than a partition ----
 @pytest.mark.parametrize("pushed", [False, True])
 def test_a_record_longer_than_a_partition(monkeypatch, pushed):

@@ -133,7 +133,8 @@ uint64_t test_stage_bytes();       // 0: not set
 // beside a slice of the stream: its members at their worst, the compressor's staging slot per member and its token arenas (bgzf_gpu.hip)
 size_t slice_scratch_bytes(size_t slice_bytes);
 // Device bytes of the external road: the per-record arrays, two staging buffers, one partition, one slice's members, the compressor's
-// scratch.  The one sum the plan and sort_device (which allocates these pieces, a partition no larger than the stream) both use.
+// scratch.  The one sum the plan and DeviceSort (whose allocate and sorted_stream stages allocate these pieces, a partition no larger
+// than the stream) both use.
 uint64_t external_device_bytes(size_t n_bytes, uint64_t n_records, bool markdup, uint64_t stage_bytes, uint64_t partition_bytes);
 // the plan for staged chunks of stage_bytes (the public function passes the default; the sort, a larger one where a record needs it)
 int plan_with_stage(size_t n_bytes, uint64_t n_records, bool markdup, uint64_t budget, uint64_t stage_bytes, urmapx_bam_sort_plan *plan);

@@ -29,6 +29,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 
 using namespace urx::bamsort;
@@ -414,57 +415,68 @@ struct DepthAsk {
 	urmapx_depth_result *out;
 };
 
-// budget == nullptr: the in-core road, whatever it takes (urmapx_bam_sort, urmapx_bam_sort_markdup).  Else the road the plan names for
-// *budget device bytes (urmapx_bam_sort_external), with `dep` for what the depth arrays leave of them (urmapx_bam_sort_depth).
-int sort_device(int device, const uint64_t *budget, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts,
-                urmapx_markdup_stats *md, const DepthAsk *dep, urmapx_bam_sort_result *out) {
-	auto t = Clock::now();
+// adds the time from where it is made to the end of its scope
+struct Span {
+	double &to;
+	const Clock::time_point t0 = Clock::now();
+	explicit Span(double &sum) : to(sum) {}
+	~Span() { to += since(t0); }
+};
+struct BgzfDestroy { void operator()(urmapx_bgzf *z) const { urmapx_bgzf_destroy(z); } };
+struct Free { void operator()(void *p) const { free(p); } };
+struct KeyVal { uint64_t *key; uint32_t *val; };  // a key array and the record-number array that moves with it
+struct ChunkMarks { uint32_t *flag, *index; };    // per placed record: does a chunk begin here; behind the flags their sums, one more
+
+// One device sort, from the caller's records to the result.  budget == nullptr: the in-core road, whatever it takes (urmapx_bam_sort,
+// urmapx_bam_sort_markdup).  Else the road the plan names for *budget device bytes (urmapx_bam_sort_external), with `dep` for what the
+// depth arrays leave of them (urmapx_bam_sort_depth).  run() lists the stages; a stage returns a code, and the first that is not 0 ends
+// the run: every member lets go of what it holds.
+struct DeviceSort {
+	// ---- what the caller gave (sort_entry) ----
+	const int device;
+	const uint64_t *const budget;
+	const uint8_t *const rec;
+	const size_t n_bytes;
+	const uint32_t n_ref;
+	const uint64_t in_front;
+	const uint64_t *const starts;
+	const size_t n_starts;
+	urmapx_markdup_stats *const md;
+	const DepthAsk *const dep;
+	urmapx_bam_sort_result *const out;
+	size_t n_ref1() const { return (size_t)n_ref + 1; }
+	bool look() const { return md != nullptr; }  // the marking compares neighbours: a staged chunk is followed by its successor
+
+	// ---- what the scan gives ----
 	std::vector<uint64_t> offs;
-	uint32_t max_pos = 0;
-	int rc = scan_records(rec, n_bytes, n_ref, starts, n_starts, offs, max_pos);
-	if (rc) return rc;
-	out->scan_s = since(t);
-	const uint32_t n = (uint32_t)(offs.size() - 1);
-	out->records = n;
-	const KeyLayout K = key_layout(n_ref, max_pos);
-	const uint32_t bin_bits = max_pos < (1u << 29) ? 16u : 18u;  // (reg2bin's largest value: 37 448 below 2^29, 4681 + 2^17 in all)
-	const size_t n_ref1 = (size_t)n_ref + 1;
+	uint32_t n = 0;
+	KeyLayout K;
+	uint32_t bin_bits = 16;
 
-	// the road; on the external one the staged chunks: chunk c is records cut[c] .. cut[c + 1] - 1, under marking with record cut[c + 1]
-	// behind it (first_kernel compares neighbours).  A staging buffer holds the largest of them: a record longer than the staged chunk
-	// asked for, or its successor, makes the buffers grow, and the partition is planned again around them
-	urmapx_bam_sort_plan P;
-	memset(&P, 0, sizeof P);
+	// ---- the road; on the external one the staged chunks: chunk c is records cut[c] .. cut[c + 1] - 1 ----
+	urmapx_bam_sort_plan P{};
 	std::vector<uint32_t> cut;
-	const bool look = md != nullptr;
-	// the depth arrays come off the budget before the sort is planned; where that fails, the least budget is theirs and the plan's
-	const uint64_t depth_bytes = dep ? urx::depth::resident_bytes(dep->entries, n_ref, urx::depth::text_runs()) : 0u;
-	const uint64_t sort_budget = budget ? (*budget > depth_bytes ? *budget - depth_bytes : 0u) : 0u;
-	auto plan = [&](uint64_t stage) -> int {
-		const int r = plan_with_stage(n_bytes, n, md != nullptr, sort_budget, stage, &P);
-		if (r == URMAPX_E_NOMEM && dep) dep->out->least_budget = depth_bytes + P.device_bytes;
-		return r;
-	};
-	if (budget) {
-		if ((rc = plan(default_stage_bytes(n_bytes)))) return rc;
-		if (P.external) {
-			uint64_t need = 0;
-			for (uint64_t i0 = 0; i0 < n;) {
-				const uint64_t i1 = chunk_end(offs.data(), n, i0, P.stage_bytes, look), seen = look && i1 < n ? i1 + 1 : i1;
-				cut.push_back((uint32_t)i0);
-				need = std::max(need, offs[seen] - offs[i0]);
-				i0 = i1;
-			}
-			cut.push_back(n);
-			if (need > P.stage_bytes && (rc = plan(need))) return rc;
-		}
-	}
-	const bool ext = P.external != 0;
-	out->external = ext;
-	out->partitions = (uint32_t)P.partitions;
-	out->stage_chunks = ext ? cut.size() - 1 : 0;
+	bool ext = false;
+	uint64_t depth_bytes = 0, sort_budget = 0;
 
-	HIP_TRY(hipSetDevice(device));
+	// ---- the device arrays, in the order they are allocated (external_device_bytes counts them in this order) ----
+	// What each holds, stage by stage; "free" means any later stage may take it.
+	//                    keys+sort        destinations   index arrays                      marking       stream
+	//   d_rec (in core)  records          .              .                                 bit 0x400     gather reads
+	//   d_off            starts           read           .                                 read          read
+	//   d_key[0], [1]    keys, ping-pong  .              by_coor.key read; then the        key[0], [1]   spare.key = place (external)
+	//                    -> by_coor.key,                 second sort's keys, and flag and
+	//                       spare.key                    index in the one it leaves free
+	//   d_val[0], [1]    numbers          spare.val =    by_coor.val read; spare.val the   spare.val =   by_coor.val read
+	//                    -> by_coor.val,  lengths        second sort's other numbers       val[0]
+	//                       spare.val
+	//   d_val[2]         notes4           .              notes4 read (bounds_kernel);      val[1]        free
+	//                                                    then the second sort's numbers
+	//   d_end            ends             .              read (lin, bin_key)               score         free
+	//   d_dst            .                written        read                              .             read
+	//   d_hist, d_sums   scratch of every sort and scan, the marking's too
+	//   d_ref, d_ext, d_win, d_lin, d_chunks   the index arrays' own, read back by the index stage
+	//   d_stage, d_part, d_action (external)   staging buffers: both passes; the partition: stream; the decisions: marking -> stream
 	Dev<uint8_t> d_rec, d_stage[2], d_part, d_action;
 	Dev<uint64_t> d_off, d_dst, d_key[2], d_sums, d_ext[2], d_win, d_lin;
 	Dev<uint32_t> d_val[3], d_end, d_hist, d_range, d_ref[4];
@@ -472,38 +484,117 @@ int sort_device(int device, const uint64_t *budget, const uint8_t *rec, size_t n
 	MarkdupOwn W;
 	urx::depth::DepthOwn DW;
 	StageStreams st;
-	if (dep) {
-		if (n >= 0x7FFFFFFFu) return URMAPX_E_ARG;
-		dep->out->records = n;
-		const double a0 = t_alloc_s;
-		if ((rc = DW.begin(n_ref, dep->names, dep->lens, dep->entries))) return rc;
-		dep->out->alloc_s = t_alloc_s - a0;
-	}
-	if (ext) {  // (the pieces external_device_bytes counts, in its order; the partition is not larger than the stream)
-		const size_t part_cap = (size_t)std::min<uint64_t>(P.partition_bytes, n_bytes);
-		if ((md && ((rc = W.begin(n)) || (rc = d_action.alloc(n)))) || (rc = d_stage[0].alloc((size_t)P.stage_bytes + 16)) ||
-		    (rc = d_stage[1].alloc((size_t)P.stage_bytes + 16)) || (rc = d_part.alloc(part_cap + 16)) || (rc = st.create()))
-			return rc;
-		if (md) HIP_TRY(hipMemset(d_action.p, MD_KEEP, n ? n : 1));
-	} else if ((rc = d_rec.alloc(n_bytes + 16)))
-		return rc;
-	if ((rc = d_off.alloc((size_t)n + 1)) || (rc = d_dst.alloc((size_t)n + 1)) || (rc = d_key[0].alloc((size_t)n + 2)) ||
-	    (rc = d_key[1].alloc((size_t)n + 2)) || (rc = d_val[0].alloc((size_t)n + 1)) || (rc = d_val[1].alloc((size_t)n + 1)) ||
-	    (rc = d_val[2].alloc((size_t)n + 1)) || (rc = d_end.alloc(n)) || (rc = d_hist.alloc((size_t)256 * MAX_BLOCKS)) || (rc = d_sums.alloc(MAX_RUNS + 1)) ||
-	    (rc = d_range.alloc(2)) || (rc = d_ext[0].alloc(n_ref1)) || (rc = d_ext[1].alloc(n_ref1)) || (rc = d_win.alloc(n_ref1 + 1)))
-		return rc;
-	for (int k = 0; k < 4; ++k)
-		if ((rc = d_ref[k].alloc(n_ref1))) return rc;
+	IndexArrays X;
+	// ---- the arrays' later names; each is given in one place ----
+	uint32_t *notes4 = nullptr;  // does record i carry flag 0x4: from keys_kernel to bounds_kernel
+	KeyVal by_coor{}, spare{};   // after the coordinate sort: the sorted keys and record numbers, and the pair the sort left free
+	uint32_t *lengths = nullptr; // the records' lengths in sorted order
+	uint64_t *place = nullptr;   // external road: where record i of the input goes in the sorted stream
+	Clock::time_point t_sort;    // where sort_s begins
 
-	t = Clock::now();
-	if (!ext && n_bytes) HIP_TRY(hipMemcpy(d_rec.p, rec, n_bytes, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_off.p, offs.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-	out->upload_s = since(t);
+	// ---- the sorted stream: a slice, its members, the compressor, the members on the host ----
+	size_t slice_bytes = 0, z_cap = 0, host_cap = 0, z_bytes = 0;
+	Dev<uint8_t> d_slice, d_z;
+	Dev<uint64_t> d_used;
+	std::unique_ptr<urmapx_bgzf, BgzfDestroy> Z;
+	std::unique_ptr<uint8_t, Free> z;
+
+	int run() {
+		int rc;
+		if ((rc = scan_chain()) || (rc = choose_road()) || (rc = allocate()) || (rc = upload()) || (rc = sort_by_coordinate()) || (rc = destinations()) ||
+		    (rc = index_arrays()) || (rc = mark_duplicates()) || (rc = depth_in_core()) || (rc = sorted_stream()))
+			return rc;
+		return finish();
+	}
+
+	int scan_chain() {
+		uint32_t max_pos = 0;
+		{
+			Span span(out->scan_s);
+			if (const int rc = scan_records(rec, n_bytes, n_ref, starts, n_starts, offs, max_pos)) return rc;
+		}
+		n = (uint32_t)(offs.size() - 1);
+		out->records = n;
+		K = key_layout(n_ref, max_pos);
+		bin_bits = max_pos < (1u << 29) ? 16u : 18u;  // (reg2bin's largest value: 37 448 below 2^29, 4681 + 2^17 in all)
+		return URMAPX_OK;
+	}
+
+	// the plan for staged chunks of `stage` bytes; where nothing fits, the least budget is the depth arrays' and the plan's
+	int plan(uint64_t stage) {
+		const int r = plan_with_stage(n_bytes, n, md != nullptr, sort_budget, stage, &P);
+		if (r == URMAPX_E_NOMEM && dep) dep->out->least_budget = depth_bytes + P.device_bytes;
+		return r;
+	}
+	// The road.  On the external one the staged chunks, under marking each with the next chunk's first record behind it (first_kernel
+	// compares neighbours).  A staging buffer holds the largest of them: a record longer than the staged chunk asked for, or its
+	// successor, makes the buffers grow, and the partition is planned again around them
+	int choose_road() {
+		if (budget) {
+			// the depth arrays come off the budget before the sort is planned
+			depth_bytes = dep ? urx::depth::resident_bytes(dep->entries, n_ref, urx::depth::text_runs()) : 0u;
+			sort_budget = *budget > depth_bytes ? *budget - depth_bytes : 0u;
+			if (const int rc = plan(default_stage_bytes(n_bytes))) return rc;
+			if (P.external) {
+				uint64_t need = 0;
+				for (uint64_t i0 = 0; i0 < n;) {
+					const uint64_t i1 = chunk_end(offs.data(), n, i0, P.stage_bytes, look()), seen = look() && i1 < n ? i1 + 1 : i1;
+					cut.push_back((uint32_t)i0);
+					need = std::max(need, offs[seen] - offs[i0]);
+					i0 = i1;
+				}
+				cut.push_back(n);
+				if (need > P.stage_bytes)
+					if (const int rc = plan(need)) return rc;
+			}
+		}
+		ext = P.external != 0;
+		out->external = ext;
+		out->partitions = (uint32_t)P.partitions;
+		out->stage_chunks = ext ? cut.size() - 1 : 0;
+		return URMAPX_OK;
+	}
+
+	int allocate() {
+		int rc;
+		HIP_TRY(hipSetDevice(device));
+		if (dep) {
+			if (n >= 0x7FFFFFFFu) return URMAPX_E_ARG;
+			dep->out->records = n;
+			const double a0 = t_alloc_s;
+			if ((rc = DW.begin(n_ref, dep->names, dep->lens, dep->entries))) return rc;
+			dep->out->alloc_s = t_alloc_s - a0;
+		}
+		if (ext) {  // (the pieces external_device_bytes counts, in its order; the partition is not larger than the stream)
+			const size_t part_cap = (size_t)std::min<uint64_t>(P.partition_bytes, n_bytes);
+			if ((md && ((rc = W.begin(n)) || (rc = d_action.alloc(n)))) || (rc = d_stage[0].alloc((size_t)P.stage_bytes + 16)) ||
+			    (rc = d_stage[1].alloc((size_t)P.stage_bytes + 16)) || (rc = d_part.alloc(part_cap + 16)) || (rc = st.create()))
+				return rc;
+			if (md) HIP_TRY(hipMemset(d_action.p, MD_KEEP, n ? n : 1));
+		} else if ((rc = d_rec.alloc(n_bytes + 16)))
+			return rc;
+		if ((rc = d_off.alloc((size_t)n + 1)) || (rc = d_dst.alloc((size_t)n + 1)) || (rc = d_key[0].alloc((size_t)n + 2)) ||
+		    (rc = d_key[1].alloc((size_t)n + 2)) || (rc = d_val[0].alloc((size_t)n + 1)) || (rc = d_val[1].alloc((size_t)n + 1)) ||
+		    (rc = d_val[2].alloc((size_t)n + 1)) || (rc = d_end.alloc(n)) || (rc = d_hist.alloc((size_t)256 * MAX_BLOCKS)) || (rc = d_sums.alloc(MAX_RUNS + 1)) ||
+		    (rc = d_range.alloc(2)) || (rc = d_ext[0].alloc(n_ref1())) || (rc = d_ext[1].alloc(n_ref1())) || (rc = d_win.alloc(n_ref1() + 1)))
+			return rc;
+		for (int k = 0; k < 4; ++k)
+			if ((rc = d_ref[k].alloc(n_ref1()))) return rc;
+		return URMAPX_OK;
+	}
+
+	int upload() {
+		Span span(out->upload_s);
+		if (!ext && n_bytes) HIP_TRY(hipMemcpy(d_rec.p, rec, n_bytes, hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(d_off.p, offs.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+		return URMAPX_OK;
+	}
 
 	// One pass over the input on the external road: chunk c goes to staging buffer c & 1 on that buffer's stream (a plain copy from the
 	// caller's pageable memory: the call returns when the bytes have left it), `launch` queues the chunk's kernels behind it, and the
 	// next chunk's copy runs while they do.  Before a buffer is written again its stream is waited for.
-	auto pass = [&](bool with_successor, auto &&launch) -> int {
+	template <class Launch>
+	int pass(bool with_successor, Launch &&launch) {
 		const auto t0 = Clock::now();
 		HIP_TRY(hipStreamSynchronize(nullptr));
 		for (size_t c = 0; c + 1 < cut.size(); ++c) {
@@ -513,182 +604,202 @@ int sort_device(int device, const uint64_t *budget, const uint8_t *rec, size_t n
 			if (bytes > P.stage_bytes) return URMAPX_E_NODEVICE;  // (never: the buffers were sized by these very chunks)
 			HIP_TRY(hipStreamSynchronize(st.s[b]));
 			if (bytes) HIP_TRY(hipMemcpyAsync(d_stage[b].p, rec + offs[i0], (size_t)bytes, hipMemcpyHostToDevice, st.s[b]));
-			int r = launch((const uint8_t *)d_stage[b].p, offs[i0], i0, i1, st.s[b]);
-			if (r) return r;
+			if (const int r = launch((const uint8_t *)d_stage[b].p, offs[i0], i0, i1, st.s[b])) return r;
 		}
 		HIP_TRY(hipGetLastError());
-		int r = st.wait();
+		const int r = st.wait();
 		out->stage_s += since(t0);
 		return r;
-	};
+	}
 
-	// keys and the coordinate sort.  (d_val[2] is free until the second sort: the flag-4 notes live there up to bounds_kernel)
-	t = Clock::now();
-	SortArrays S{{d_key[0].p, d_key[1].p}, {d_val[0].p, d_val[1].p}, 0};
-	auto keys = [&](const uint8_t *at, uint64_t base, uint32_t i0, uint32_t i1, hipStream_t s) -> int {
-		hipLaunchKernelGGL(keys_kernel, dim3(grid_for(i1 - i0)), dim3(NT), 0, s, at, base, (const uint64_t *)d_off.p, i0, i1, K, S.key[0], S.val[0], d_end.p, d_val[2].p);
+	// keys, numbers, ends and notes of records i0 .. i1 - 1 at `at`; on the external road what the marking reads of them, as they pass
+	int keys_of(const uint8_t *at, uint64_t base, uint32_t i0, uint32_t i1, hipStream_t s) {
+		hipLaunchKernelGGL(keys_kernel, dim3(grid_for(i1 - i0)), dim3(NT), 0, s, at, base, d_off.p, i0, i1, K, d_key[0].p, d_val[0].p, d_end.p, notes4);
 		return md && ext ? markdup_chunk(W, at, base, d_off.p, i0, i1, n, s) : URMAPX_OK;
-	};
-	if (ext) {
-		if ((rc = pass(look, keys))) return rc;
-		t = Clock::now();
-	} else if (n) (void)keys(d_rec.p, 0, 0, n, nullptr);
-	out->sort_passes = radix_sort(S, n, K.bits(), d_hist.p);
-	uint64_t *const key_s = S.key[S.in], *const key_f = S.key[1 - S.in];
-	uint32_t *const val_s = S.val[S.in], *const val_f = S.val[1 - S.in];
-	// where every sorted record goes: the lengths in sorted order, scanned
-	if (n) hipLaunchKernelGGL(sorted_len_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, (const uint32_t *)val_s, (const uint64_t *)d_off.p, n, val_f);
-	scan_launch<uint32_t, uint64_t>(val_f, n, d_dst.p, d_sums.p);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	out->sort_s = since(t);
+	}
+	// Keys and the coordinate sort.  On the external road the keys are the first pass, which counts in stage_s and not in sort_s
+	int sort_by_coordinate() {
+		notes4 = d_val[2].p;  // (free until the second sort)
+		if (ext)
+			if (const int rc = pass(look(), [this](const uint8_t *at, uint64_t base, uint32_t i0, uint32_t i1, hipStream_t s) { return keys_of(at, base, i0, i1, s); })) return rc;
+		t_sort = Clock::now();
+		if (!ext && n) (void)keys_of(d_rec.p, 0, 0, n, nullptr);
+		SortArrays S{{d_key[0].p, d_key[1].p}, {d_val[0].p, d_val[1].p}, 0};
+		out->sort_passes = radix_sort(S, n, K.bits(), d_hist.p);
+		by_coor = KeyVal{S.key[S.in], S.val[S.in]};
+		spare = KeyVal{S.key[1 - S.in], S.val[1 - S.in]};  // (the sort's last pass read it: nothing in it is wanted any more)
+		return URMAPX_OK;
+	}
 
-	// the index arrays
-	t = Clock::now();
-	IndexArrays X;
-	X.refs.assign(n_ref, RefExtent());
-	X.win_base.assign(n_ref1, 0);
-	std::vector<uint32_t> first(n_ref1, 0xFFFFFFFFu), last(n_ref1, 0), max_end(n_ref1, 0), flag4(n_ref1, 0);
-	std::vector<uint64_t> ext_beg(n_ref1, 0), ext_end(n_ref1, 0);
-	HIP_TRY(hipMemset(d_ref[0].p, 0xFF, n_ref1 * 4));
-	for (int k = 1; k < 4; ++k) HIP_TRY(hipMemset(d_ref[k].p, 0, n_ref1 * 4));
-	if (n) {
-		hipLaunchKernelGGL(bounds_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, (const uint32_t *)d_val[2].p, (const uint64_t *)key_s,
-		                   (const uint32_t *)val_s, (const uint32_t *)d_end.p, n, K, d_ref[0].p, d_ref[1].p, d_ref[2].p, d_ref[3].p);
-		hipLaunchKernelGGL(extent_kernel, dim3(grid_for(n_ref1, 1u << 22)), dim3(NT), 0, nullptr, (const uint32_t *)d_ref[0].p, (const uint32_t *)d_ref[1].p,
-		                   (const uint64_t *)d_dst.p, (uint32_t)n_ref1, d_ext[0].p, d_ext[1].p);
+	// where every sorted record goes: the lengths in sorted order, scanned
+	int destinations() {
+		lengths = spare.val;
+		if (n) hipLaunchKernelGGL(sorted_len_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, by_coor.val, d_off.p, n, lengths);
+		scan_launch<uint32_t, uint64_t>(lengths, n, d_dst.p, d_sums.p);
 		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpy(first.data(), d_ref[0].p, n_ref1 * 4, hipMemcpyDeviceToHost));
-		HIP_TRY(hipMemcpy(last.data(), d_ref[1].p, n_ref1 * 4, hipMemcpyDeviceToHost));
-		HIP_TRY(hipMemcpy(max_end.data(), d_ref[2].p, n_ref1 * 4, hipMemcpyDeviceToHost));
-		HIP_TRY(hipMemcpy(flag4.data(), d_ref[3].p, n_ref1 * 4, hipMemcpyDeviceToHost));
-		HIP_TRY(hipMemcpy(ext_beg.data(), d_ext[0].p, n_ref1 * 8, hipMemcpyDeviceToHost));
-		HIP_TRY(hipMemcpy(ext_end.data(), d_ext[1].p, n_ref1 * 8, hipMemcpyDeviceToHost));
+		HIP_TRY(hipStreamSynchronize(nullptr));
+		out->sort_s = since(t_sort);
+		return URMAPX_OK;
 	}
-	for (uint32_t r = 0; r < n_ref; ++r) {
-		if (first[r] != 0xFFFFFFFFu) {
-			const uint64_t cnt = (uint64_t)last[r] - first[r] + 1u;
-			X.refs[r].beg = ext_beg[r]; X.refs[r].end = ext_end[r];
-			X.refs[r].n_unmapped = flag4[r]; X.refs[r].n_mapped = cnt - flag4[r];
+
+	int index_arrays() {
+		Span span(out->index_s);
+		if (const int rc = index_references()) return rc;
+		return index_bins();
+	}
+	// per reference: its first and last sorted record, its extent in the stream, its counts, its windows
+	int index_references() {
+		X.refs.assign(n_ref, RefExtent());
+		X.win_base.assign(n_ref1(), 0);
+		std::vector<uint32_t> first(n_ref1(), 0xFFFFFFFFu), last(n_ref1(), 0), max_end(n_ref1(), 0), flag4(n_ref1(), 0);
+		std::vector<uint64_t> ext_beg(n_ref1(), 0), ext_end(n_ref1(), 0);
+		HIP_TRY(hipMemset(d_ref[0].p, 0xFF, n_ref1() * 4));
+		for (int k = 1; k < 4; ++k) HIP_TRY(hipMemset(d_ref[k].p, 0, n_ref1() * 4));
+		if (n) {
+			hipLaunchKernelGGL(bounds_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, notes4, by_coor.key, by_coor.val, d_end.p, n, K, d_ref[0].p, d_ref[1].p,
+			                   d_ref[2].p, d_ref[3].p);
+			hipLaunchKernelGGL(extent_kernel, dim3(grid_for(n_ref1(), 1u << 22)), dim3(NT), 0, nullptr, d_ref[0].p, d_ref[1].p, d_dst.p, (uint32_t)n_ref1(), d_ext[0].p,
+			                   d_ext[1].p);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipMemcpy(first.data(), d_ref[0].p, n_ref1() * 4, hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(last.data(), d_ref[1].p, n_ref1() * 4, hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(max_end.data(), d_ref[2].p, n_ref1() * 4, hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(flag4.data(), d_ref[3].p, n_ref1() * 4, hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(ext_beg.data(), d_ext[0].p, n_ref1() * 8, hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(ext_end.data(), d_ext[1].p, n_ref1() * 8, hipMemcpyDeviceToHost));
 		}
-		X.win_base[r + 1] = X.win_base[r] + (max_end[r] ? (((uint64_t)max_end[r] - 1u) >> WINDOW_SHIFT) + 1u : 0u);
+		for (uint32_t r = 0; r < n_ref; ++r) {
+			if (first[r] != 0xFFFFFFFFu) {
+				const uint64_t cnt = (uint64_t)last[r] - first[r] + 1u;
+				X.refs[r].beg = ext_beg[r]; X.refs[r].end = ext_end[r];
+				X.refs[r].n_unmapped = flag4[r]; X.refs[r].n_mapped = cnt - flag4[r];
+			}
+			X.win_base[r + 1] = X.win_base[r] + (max_end[r] ? (((uint64_t)max_end[r] - 1u) >> WINDOW_SHIFT) + 1u : 0u);
+		}
+		X.n_no_coor = first[n_ref] != 0xFFFFFFFFu ? (uint64_t)last[n_ref] - first[n_ref] + 1u : 0u;
+		out->no_coor = X.n_no_coor;
+		return URMAPX_OK;
 	}
-	X.n_no_coor = first[n_ref] != 0xFFFFFFFFu ? (uint64_t)last[n_ref] - first[n_ref] + 1u : 0u;
-	out->no_coor = X.n_no_coor;
-	const uint32_t m = n - (uint32_t)X.n_no_coor;  // the placed records: the first m of the sorted ones
-	const size_t n_win = (size_t)X.win_base[n_ref];
-	X.lin.assign(n_win, NONE);
-	uint32_t n_chunks = 0;
-	if (m) {
+	// the linear index, then the chunks: the placed records' numbers sorted by (reference, bin), a flag where a chunk begins, the flags
+	// scanned.  (d_lin and d_chunks are allocated here, where their sizes are known)
+	int index_bins() {
+		const uint32_t m = n - (uint32_t)X.n_no_coor;  // the placed records: the first m of the sorted ones
+		const size_t n_win = (size_t)X.win_base[n_ref];
+		X.lin.assign(n_win, NONE);
+		if (!m) return URMAPX_OK;
+		int rc;
 		if ((rc = d_lin.alloc(n_win))) return rc;
 		HIP_TRY(hipMemset(d_lin.p, 0xFF, n_win * 8));
-		HIP_TRY(hipMemcpy(d_win.p, X.win_base.data(), n_ref1 * 8, hipMemcpyHostToDevice));
-		hipLaunchKernelGGL(lin_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, (const uint64_t *)key_s, (const uint32_t *)val_s, (const uint32_t *)d_end.p,
-		                   (const uint64_t *)d_dst.p, m, K, (const uint64_t *)d_win.p, (unsigned long long *)d_lin.p);
-		// the record numbers by (reference, bin): key_s is used up by then, val_f (the sorted lengths) too; val_s stays for the gather
-		SortArrays S2{{key_f, key_s}, {d_val[2].p, val_f}, 0};
-		hipLaunchKernelGGL(bin_key_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, (const uint64_t *)key_s, (const uint32_t *)val_s, (const uint32_t *)d_end.p, m, K,
-		                   bin_bits, S2.key[0], S2.val[0]);
+		HIP_TRY(hipMemcpy(d_win.p, X.win_base.data(), n_ref1() * 8, hipMemcpyHostToDevice));
+		hipLaunchKernelGGL(lin_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, by_coor.key, by_coor.val, d_end.p, d_dst.p, m, K, d_win.p, (unsigned long long *)d_lin.p);
+		// The second sort runs between the two key arrays: bin_key_kernel is the last reader of the coordinate keys.  Its numbers go to
+		// d_val[2] (the notes: bounds_kernel has read them) and the lengths (scanned into d_dst by destinations); by_coor.val stays
+		SortArrays S2{{spare.key, by_coor.key}, {d_val[2].p, lengths}, 0};
+		hipLaunchKernelGGL(bin_key_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, by_coor.key, by_coor.val, d_end.p, m, K, bin_bits, S2.key[0], S2.val[0]);
 		(void)radix_sort(S2, m, K.ref_bits + bin_bits, d_hist.p);
-		const uint64_t *key2 = S2.key[S2.in];
-		const uint32_t *val2 = S2.val[S2.in];
-		uint32_t *flag = (uint32_t *)S2.key[1 - S2.in], *index = flag + m;  // (2 m + 1 words in an array of 2 n + 4)
-		hipLaunchKernelGGL(chunk_flag_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, key2, val2, m, flag);
-		scan_launch<uint32_t, uint32_t>(flag, m, index, d_sums.p);
+		const uint64_t *const key2 = S2.key[S2.in];
+		const uint32_t *const val2 = S2.val[S2.in];
+		// in the key array the second sort left free, as words: 2 m + 1 of them in an array of 2 n + 4
+		const ChunkMarks C{(uint32_t *)S2.key[1 - S2.in], (uint32_t *)S2.key[1 - S2.in] + m};
+		hipLaunchKernelGGL(chunk_flag_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, key2, val2, m, C.flag);
+		scan_launch<uint32_t, uint32_t>(C.flag, m, C.index, d_sums.p);
 		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpy(&n_chunks, index + m, 4, hipMemcpyDeviceToHost));
+		uint32_t n_chunks = 0;
+		HIP_TRY(hipMemcpy(&n_chunks, C.index + m, 4, hipMemcpyDeviceToHost));
 		if (n_chunks > m) return URMAPX_E_NODEVICE;
 		if ((rc = d_chunks.alloc(n_chunks))) return rc;
-		hipLaunchKernelGGL(chunk_write_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, key2, val2, (const uint32_t *)flag, (const uint32_t *)index,
-		                   (const uint64_t *)d_dst.p, m, bin_bits, n_chunks, d_chunks.p);
+		hipLaunchKernelGGL(chunk_write_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, key2, val2, C.flag, C.index, d_dst.p, m, bin_bits, n_chunks, d_chunks.p);
 		HIP_TRY(hipGetLastError());
 		X.chunks.resize(n_chunks);
 		HIP_TRY(hipMemcpy(X.chunks.data(), d_chunks.p, (size_t)n_chunks * sizeof(Chunk), hipMemcpyDeviceToHost));
 		HIP_TRY(hipMemcpy(X.lin.data(), d_lin.p, n_win * 8, hipMemcpyDeviceToHost));
+		return URMAPX_OK;
 	}
-	out->index_s = since(t);
 
-	// markdup: bit 0x400 of the resident records, before the first of them is copied into order.  The two key arrays, the sorted
-	// lengths, the second sort's record numbers and the ends are used up by now; val_s, d_dst, d_off and d_rec are not
-	// On the external road what it reads of the records was taken as they passed (markdup_chunk in the first pass) and the decisions go
-	// to d_action, for place_kernel
-	if (md) {
-		t = Clock::now();
+	// markdup: bit 0x400 of the resident records, before the first of them is copied into order.  On the external road what it reads of
+	// the records was taken as they passed (keys_of in the first pass) and the decisions go to d_action, for place_kernel
+	int mark_duplicates() {
+		if (!md) return URMAPX_OK;
+		Span span(md->markdup_s);
+		int rc;
 		if (!ext && ((rc = W.begin(n)) || (rc = markdup_chunk(W, d_rec.p, 0, d_off.p, 0, n, n, nullptr)))) return rc;
-		const MarkdupArrays A{d_rec.p, d_off.p, n, n_ref, {key_s, key_f}, {val_f, d_val[2].p}, d_end.p, d_hist.p, d_sums.p, ext ? d_action.p : nullptr};
-		if ((rc = markdup_device(A, W, md))) return rc;
-		md->markdup_s = since(t);
+		// What the marking sorts and scores in is used up by now: both key arrays (the index stage's last reader was chunk_write_kernel),
+		// the lengths, the second sort's numbers in d_val[2], the ends (lin_kernel, bin_key_kernel).  by_coor.val, d_dst, d_off, d_rec are not
+		const MarkdupArrays A{d_rec.p, d_off.p, n, n_ref, {by_coor.key, spare.key}, {lengths, d_val[2].p}, d_end.p, d_hist.p, d_sums.p, ext ? d_action.p : nullptr};
+		return markdup_device(A, W, md);
 	}
 
 	// depth, in core: one launch over the records as they came, now that every bit 0x400 is what the file will hold.  (On the external
-	// road the decisions wait in d_action until the records pass again: the first placing pass counts, below)
-	if (dep && !ext) {
-		t = Clock::now();
-		if ((rc = urx::depth::depth_count(DW, d_rec.p, 0, d_off.p, 0, n, nullptr, dep->min_mapq, nullptr))) return rc;
+	// road the decisions wait in d_action until the records pass again: the first placing pass counts, in partitions)
+	int depth_in_core() {
+		if (!dep || ext) return URMAPX_OK;
+		Span span(dep->out->count_s);
+		if (const int rc = urx::depth::depth_count(DW, d_rec.p, 0, d_off.p, 0, n, nullptr, dep->min_mapq, nullptr)) return rc;
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipStreamSynchronize(nullptr));
-		dep->out->count_s = since(t);
+		return URMAPX_OK;
 	}
 
-	// the sorted stream, a slice at a time: gather, deflate, copy back
-	const size_t slice_bytes = (size_t)slice_members() * MEMBER;
-	const size_t slice_cap = slice_bytes < n_bytes ? slice_bytes : n_bytes, z_cap = urmapx_bgzf_bound(slice_cap);
-	Dev<uint8_t> d_slice, d_z;
-	Dev<uint64_t> d_used;
-	if ((!ext && (rc = d_slice.alloc(slice_cap + 16))) || (rc = d_z.alloc(z_cap + 16)) || (rc = d_used.alloc(1))) return rc;
-	urmapx_bgzf *Z = nullptr;
-	if ((rc = urmapx_bgzf_create(device, nullptr, &Z))) return rc;
-	const size_t host_cap = urmapx_bgzf_bound(n_bytes);
-	uint8_t *z = (uint8_t *)malloc(host_cap ? host_cap : 1);
-	size_t z_bytes = 0;
+	// the sorted stream, a slice at a time: into order, deflate, copy back
+	int sorted_stream() {
+		slice_bytes = (size_t)slice_members() * MEMBER;
+		const size_t slice_cap = slice_bytes < n_bytes ? slice_bytes : n_bytes;
+		z_cap = urmapx_bgzf_bound(slice_cap);
+		int rc;
+		if ((!ext && (rc = d_slice.alloc(slice_cap + 16))) || (rc = d_z.alloc(z_cap + 16)) || (rc = d_used.alloc(1))) return rc;
+		urmapx_bgzf *made = nullptr;
+		if ((rc = urmapx_bgzf_create(device, nullptr, &made))) return rc;
+		Z.reset(made);
+		host_cap = urmapx_bgzf_bound(n_bytes);
+		z.reset((uint8_t *)malloc(host_cap ? host_cap : 1));
+		rc = !z ? URMAPX_E_NOMEM : ext ? partitions() : slices();
+		Z.reset();  // (the compressor's device memory goes before depth_finish asks for its own)
+		return rc;
+	}
 	// a slice that lies on the device: deflate, copy back
-	auto members = [&](const uint8_t *d_in, size_t bytes) -> int {
-		auto t0 = Clock::now();
-		int r = urmapx_bgzf_compress_device(device, d_in, bytes, d_z.p, z_cap, d_used.p, 0, Z);
-		if (r) return r;
+	int members(const uint8_t *d_in, size_t bytes) {
 		uint64_t used = 0;
-		HIP_TRY(hipMemcpy(&used, d_used.p, 8, hipMemcpyDeviceToHost));
-		out->deflate_s += since(t0);
+		{
+			Span span(out->deflate_s);
+			if (const int r = urmapx_bgzf_compress_device(device, d_in, bytes, d_z.p, z_cap, d_used.p, 0, Z.get())) return r;
+			HIP_TRY(hipMemcpy(&used, d_used.p, 8, hipMemcpyDeviceToHost));
+		}
 		if (used > z_cap || z_bytes + used > host_cap) return URMAPX_E_NODEVICE;
-		t0 = Clock::now();
-		if (used) HIP_TRY(hipMemcpy(z + z_bytes, d_z.p, (size_t)used, hipMemcpyDeviceToHost));
-		out->copy_s += since(t0);
+		Span span(out->copy_s);
+		if (used) HIP_TRY(hipMemcpy(z.get() + z_bytes, d_z.p, (size_t)used, hipMemcpyDeviceToHost));
 		z_bytes += (size_t)used;
 		++out->slices;
 		return URMAPX_OK;
-	};
-	auto slices = [&]() -> int {
-		if (!z) return URMAPX_E_NOMEM;
+	}
+	int slices() {
 		for (uint64_t s0 = 0; s0 < n_bytes; s0 += slice_bytes) {
 			const uint64_t s1 = s0 + slice_bytes < n_bytes ? s0 + slice_bytes : n_bytes;
-			auto t0 = Clock::now();
-			hipLaunchKernelGGL(slice_range_kernel, dim3(1), dim3(1), 0, nullptr, (const uint64_t *)d_dst.p, n, s0, s1, d_range.p);
-			hipLaunchKernelGGL(gather_kernel, dim3(4096), dim3(NT), 0, nullptr, (const uint8_t *)d_rec.p, (const uint64_t *)d_off.p, (const uint32_t *)val_s,
-			                   (const uint64_t *)d_dst.p, (const uint32_t *)d_range.p, s0, s1, d_slice.p);
-			HIP_TRY(hipGetLastError());
-			HIP_TRY(hipStreamSynchronize(nullptr));
-			out->gather_s += since(t0);
-			int r = members(d_slice.p, (size_t)(s1 - s0));
-			if (r) return r;
+			{
+				Span span(out->gather_s);
+				hipLaunchKernelGGL(slice_range_kernel, dim3(1), dim3(1), 0, nullptr, d_dst.p, n, s0, s1, d_range.p);
+				hipLaunchKernelGGL(gather_kernel, dim3(4096), dim3(NT), 0, nullptr, d_rec.p, d_off.p, by_coor.val, d_dst.p, d_range.p, s0, s1, d_slice.p);
+				HIP_TRY(hipGetLastError());
+				HIP_TRY(hipStreamSynchronize(nullptr));
+			}
+			if (const int r = members(d_slice.p, (size_t)(s1 - s0))) return r;
 		}
 		return URMAPX_OK;
-	};
-	// The external road: where every record of the input goes (into key_f: both key arrays are used up), then partition after partition:
-	// the input passes through the staging buffers once more, place_kernel fills the partition, and its slices -- partitions end on
-	// slice ends, so they are the in-core road's slices -- are deflated and copied back
-	auto partitions = [&]() -> int {
-		if (!z) return URMAPX_E_NOMEM;
-		uint64_t *const place = key_f;
-		if (n) hipLaunchKernelGGL(place_fill_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, (const uint32_t *)val_s, (const uint64_t *)d_dst.p, n, place);
+	}
+	// The external road: where every record of the input goes, then partition after partition: the input passes through the staging
+	// buffers once more, place_kernel fills the partition, and its slices -- partitions end on slice ends, so they are the in-core
+	// road's slices -- are deflated and copied back
+	int partitions() {
+		place = spare.key;  // (both key arrays are used up: the index stage, then the marking)
+		if (n) hipLaunchKernelGGL(place_fill_kernel, dim3(grid_for(n)), dim3(NT), 0, nullptr, by_coor.val, d_dst.p, n, place);
 		HIP_TRY(hipGetLastError());
+		const uint8_t *const action = md ? d_action.p : nullptr;
 		for (uint64_t p0 = 0; p0 < n_bytes; p0 += P.partition_bytes) {
 			const uint64_t p1 = p0 + P.partition_bytes < n_bytes ? p0 + P.partition_bytes : n_bytes;
 			// (every record crosses the device in each of these passes: the depth is taken in the first one only)
 			const bool count = dep && p0 == 0;
 			int r = pass(false, [&](const uint8_t *at, uint64_t base, uint32_t i0, uint32_t i1, hipStream_t s) -> int {
-				hipLaunchKernelGGL(place_kernel, dim3(grid_for(i1 - i0)), dim3(NT), 0, s, at, base, (const uint64_t *)d_off.p, i0, i1, (const uint64_t *)place,
-				                   (const uint8_t *)(md ? d_action.p : nullptr), p0, p1, d_part.p);
-				return count ? urx::depth::depth_count(DW, at, base, d_off.p, i0, i1, md ? d_action.p : nullptr, dep->min_mapq, s) : URMAPX_OK;
+				hipLaunchKernelGGL(place_kernel, dim3(grid_for(i1 - i0)), dim3(NT), 0, s, at, base, d_off.p, i0, i1, place, action, p0, p1, d_part.p);
+				return count ? urx::depth::depth_count(DW, at, base, d_off.p, i0, i1, action, dep->min_mapq, s) : URMAPX_OK;
 			});
 			if (r) return r;
 			for (uint64_t s0 = p0; s0 < p1; s0 += slice_bytes) {
@@ -697,17 +808,20 @@ int sort_device(int device, const uint64_t *budget, const uint8_t *rec, size_t n
 			}
 		}
 		return URMAPX_OK;
-	};
-	rc = ext ? partitions() : slices();
-	urmapx_bgzf_destroy(Z);
-	if (!rc && dep) rc = urx::depth::depth_finish(DW, dep->out);
-	if (rc) { free(z); return rc; }
-	if (uint8_t *fit = (uint8_t *)realloc(z, z_bytes ? z_bytes : 1)) z = fit;
-	t = Clock::now();
-	rc = finish_result(out, z, z_bytes, n_bytes, in_front, X, n_ref);
-	out->index_s += since(t);
-	return rc;
-}
+	}
+
+	// the depth's result, then the sort's: the members trimmed to their size and handed to finish_result, which owns them from there
+	int finish() {
+		if (dep)
+			if (const int rc = urx::depth::depth_finish(DW, dep->out)) return rc;
+		if (uint8_t *fit = (uint8_t *)realloc(z.get(), z_bytes ? z_bytes : 1)) {
+			(void)z.release();
+			z.reset(fit);
+		}
+		Span span(out->index_s);
+		return finish_result(out, z.release(), z_bytes, n_bytes, in_front, X, n_ref);
+	}
+};
 
 }  // namespace
 
@@ -739,7 +853,7 @@ static int sort_entry(int device, const uint64_t *budget, const void *records, s
 			HIP_TRY(hipMemGetInfo(&free_b, &total_b));
 			have = free_b > URMAPX_SORT_HEADROOM ? (uint64_t)free_b - URMAPX_SORT_HEADROOM : 1u;
 		}
-		rc = sort_device(device, budget ? &have : nullptr, (const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, dep, out);
+		rc = DeviceSort{device, budget ? &have : nullptr, (const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, dep, out}.run();
 	} catch (const std::bad_alloc &) {
 		rc = URMAPX_E_NOMEM;
 	}

@@ -1,6 +1,6 @@
 // markdup.hip -- duplicate marking on the device (urmapx_bam_sort_markdup; the rule is in include/urmapx.h "Duplicate marking"): bit
 // 0x400 of the records that lie in HBM for the coordinate sort, written before gather_kernel copies them into order.  It runs inside
-// sort_device (bam_sort.hip) in arrays the sort has used up, and sorts with the sort's own radix_sort and scan_launch.
+// DeviceSort::mark_duplicates (bam_sort.hip) in arrays the sort has used up, and sorts with the sort's own radix_sort and scan_launch.
 //
 //   ends_kernel       one WAVEFRONT per record: the lanes sum the QUAL bytes 64 at a time and reduce across the wave, lane 0 walks the
 //                     CIGAR for u5.  Per record: u5 (signed), the score, what the record is (eligible, strand)

@@ -1102,159 +1102,184 @@ struct Run {
 		for (size_t g = 1; g < replicas.size(); ++g) urmapx_index_close(replicas[g]);
 		ctxs.clear(); texts.clear(); replicas.clear();  // (the destructor's pass finds nothing)
 	}
-	// bam_sort: the kept records (rep.sam_file_bytes of them, in input order) into coordinate order, then samout -- header block with the
-	// @HD line in a member of its own, the sorted stream, the end-of-file member -- and samout.bai
-	void write_sorted() {
-		const auto t0 = now();
-		const uint64_t n_bytes = rep.sam_file_bytes;
-		const uint32_t n_ref = urmapx_index_seq_count(I);
-		std::string hdr;
-		append_bam_header(hdr, I, opt.cmdline, true, rg_line);
-		rep.sam_text_bytes += hdr.size();
-		if (!bgzf_members(hdr)) { fail.raise(URMAPX_E_NOMEM, "out of memory"); return; }
+	// ---- bam_sort: the kept records (rep.sam_file_bytes of them, in input order) into coordinate order, then samout -- header block with
+	// the @HD line in a member of its own, the sorted stream, the end-of-file member -- and samout.bai; under depth_out the bedGraph file ----
+	// What the parts of write_sorted hand on.  Both results are freed on every way out; where the library has freed and zeroed them
+	// already (a call that failed) the frees find null pointers
+	struct Sorted {
+		std::string hdr;  // the header block, as BGZF members
+		uint64_t n_bytes = 0;  // of the kept records
+		uint32_t n_ref = 0;
 		urmapx_bam_sort_result S;
 		urmapx_markdup_stats M;
-		memset(&M, 0, sizeof M);
-		int rc;
-		const std::vector<uint64_t> starts = sink.kept_starts();
-		const bool markdup = opt.markdup != 0;
-		// depth_out: the planned sort with the depth taken on the way (include/urmapx.h "Depth"); the names are those of the @SQ lines
-		const bool depth = opt.depth_out != nullptr;
 		urmapx_depth_result D;
-		memset(&D, 0, sizeof D);
-		const urmapx_depth_opts dopts{opt.depth_mapq};
-		std::vector<const char *> ref_names;
+		std::vector<const char *> ref_names;  // depth_out: the names and lengths of the @SQ lines
 		std::vector<uint32_t> ref_lens;
-		for (uint32_t r = 0; depth && r < n_ref; ++r) {
-			ref_names.push_back(urmapx_index_label(I, r));
-			ref_lens.push_back(urmapx_index_seq_length(I, r));
-		}
-		if (depth) {
-			auto with_depth = [&]() {
-				return urmapx_bam_sort_depth(phys(0), opt.sort_mem, sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), markdup ? &M : nullptr,
-				                             &dopts, ref_names.data(), ref_lens.data(), &D, &S);
-			};
-			if (getenv("URMAPX_HOST_TEXT") || getenv("URMAPX_HOST_SORT"))
-				rc = urmapx_bam_sort_depth_host(sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), markdup ? &M : nullptr, &dopts,
-				                                ref_names.data(), ref_lens.data(), &D, &S);
-			else {
-				rc = with_depth();
-				if (rc == URMAPX_E_NOMEM) {  // the same ladder as below: the lanes go first; the planned call itself streams where it must
-					close();
-					LanePool::get().purge(nullptr);
-					rc = with_depth();
-				}
-				if (rc == URMAPX_E_NOMEM) {
-					if (D.least_budget)
-						fail.raise(rc, "bam_sort with depth: the depth's counters, the sort's arrays, its staging buffers and one slice need at least " +
-						                   std::to_string(D.least_budget) + " bytes on the device" +
-						                   (opt.sort_mem ? ", " + std::to_string(opt.sort_mem) + " were given (sort_mem)" : std::string(", fewer are free")));
-					else
-						fail.raise(rc, "bam_sort with depth: out of device memory");
-					return;
-				}
-			}
-			if (rc == URMAPX_E_ARG) { fail.raise(rc, "depth: a reference name that is empty or longer than 255 bytes"); return; }
-		}
-		auto on_device = [&]() {
-			return markdup ? urmapx_bam_sort_markdup(phys(0), sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &M, &S)
-			               : urmapx_bam_sort(phys(0), sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &S);
-		};
-		if (depth) {  // (done above)
-		} else if (getenv("URMAPX_HOST_TEXT") || getenv("URMAPX_HOST_SORT"))
-			rc = markdup ? urmapx_bam_sort_markdup_host(sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &M, &S)
-			             : urmapx_bam_sort_host(sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), &S);
-		else {
-			// sort_mem (or the test knob that forces partitions): the sort is planned from that budget and nothing else is tried
-			const bool planned = opt.sort_mem != 0 || getenv("URMAPX_TEST_SORT_PARTITION");
-			auto streamed = [&]() {
-				return urmapx_bam_sort_external(phys(0), opt.sort_mem, sink.kept(), (size_t)n_bytes, n_ref, hdr.size(), starts.data(), starts.size(), markdup ? &M : nullptr, &S);
-			};
-			rc = planned ? streamed() : on_device();
-			if (rc == URMAPX_E_NOMEM) {  // the device is full of lanes: this run's and the pool's go first (the mapping is over)
-				close();
-				LanePool::get().purge(nullptr);
-				rc = planned ? streamed() : on_device();
-			}
-			if (rc == URMAPX_E_NOMEM && !planned) rc = streamed();  // the records do not fit: they stream through the device, with the memory that is free
-			if (rc == URMAPX_E_NOMEM) {
-				size_t free_b = 0, total_b = 0;
-				(void)hipSetDevice(phys(0));
-				if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-				const uint64_t have = opt.sort_mem ? opt.sort_mem : free_b > URMAPX_SORT_HEADROOM ? (uint64_t)free_b - URMAPX_SORT_HEADROOM : 1u;
-				urmapx_bam_sort_plan plan;
-				if (urmapx_bam_sort_plan_for((size_t)n_bytes, rep.reads, markdup, have, &plan) == URMAPX_E_NOMEM)
-					fail.raise(rc, "bam_sort: the sort's arrays, its staging buffers and one slice need at least " + std::to_string(plan.device_bytes) +
-					                   " bytes on the device, " + std::to_string(have) + (opt.sort_mem ? " were given (sort_mem)" : " are free"));
-				else
-					fail.raise(rc, "bam_sort: out of device memory: the plan takes " + std::to_string(plan.device_bytes) + " bytes, " + std::to_string(free_b) + " are free");
-				return;
-			}
-		}
-		if (rc) { fail.raise(rc, std::string("bam_sort: ") + urmapx_strerror(rc)); return; }
+		Sorted() { memset(&S, 0, sizeof S); memset(&M, 0, sizeof M); memset(&D, 0, sizeof D); }
+		Sorted(const Sorted &) = delete;
+		~Sorted() { urmapx_bam_sort_free(&S); urmapx_depth_free(&D); }
+	};
+	static bool host_sort() { return getenv("URMAPX_HOST_TEXT") || getenv("URMAPX_HOST_SORT"); }
+	void write_sorted() {
+		const auto t0 = now();
+		Sorted W;
+		W.n_bytes = rep.sam_file_bytes;
+		W.n_ref = urmapx_index_seq_count(I);
+		if (!sorted_header(W.hdr)) return;
+		if (const int rc = sort_kept(W)) { refuse_sort(rc, W); return; }
 		sink.drop_kept();
 		sink.write_through();
+		const double bam_s = write_bam_and_bai(W);
+		const double sorted_s = rep.sort_s = secs(t0, now());
+		double bed_s = 0;
+		if (opt.depth_out) {
+			bed_s = write_depth(W);
+			rep.sort_s = secs(t0, now());
+		}
+		report_sorted(W, sorted_s, bam_s, bed_s);
+		trace.add("sort", -1, 0, t0);
+	}
+	bool sorted_header(std::string &hdr) {
+		append_bam_header(hdr, I, opt.cmdline, true, rg_line);
+		rep.sam_text_bytes += hdr.size();
+		if (!bgzf_members(hdr)) { fail.raise(URMAPX_E_NOMEM, "out of memory"); return false; }
+		return true;
+	}
+	// The sort, on the first device.  Planned -- sort_mem, depth_out (the depth is taken on the way: include/urmapx.h "Depth") or the
+	// test knob that forces partitions --: one call, which plans from the budget and streams where it must (urmapx_bam_sort_depth;
+	// without a depth result that is urmapx_bam_sort_external), and nothing else is tried.  Else in core, and if the records do not fit,
+	// planned from the memory that is free.  Where the device is full of lanes, this run's and the pool's go first (the mapping is over)
+	// and the same call is made once more.  Under URMAPX_HOST_TEXT / URMAPX_HOST_SORT the host's sort, once
+	int sort_kept(Sorted &W) {
+		const std::vector<uint64_t> starts = sink.kept_starts();
+		const void *const rec = sink.kept();
+		const size_t n_bytes = (size_t)W.n_bytes, in_front = W.hdr.size();
+		urmapx_markdup_stats *const md = opt.markdup ? &W.M : nullptr;
+		urmapx_depth_result *const depth = opt.depth_out ? &W.D : nullptr;
+		const urmapx_depth_opts dopts{opt.depth_mapq};
+		for (uint32_t r = 0; depth && r < W.n_ref; ++r) {
+			W.ref_names.push_back(urmapx_index_label(I, r));
+			W.ref_lens.push_back(urmapx_index_seq_length(I, r));
+		}
+		if (host_sort())
+			return urmapx_bam_sort_depth_host(rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), md, &dopts, W.ref_names.data(), W.ref_lens.data(), depth, &W.S);
+		auto planned_sort = [&]() {
+			return urmapx_bam_sort_depth(phys(0), opt.sort_mem, rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), md, &dopts, W.ref_names.data(),
+			                             W.ref_lens.data(), depth, &W.S);
+		};
+		auto in_core = [&]() {
+			return md ? urmapx_bam_sort_markdup(phys(0), rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), md, &W.S)
+			          : urmapx_bam_sort(phys(0), rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), &W.S);
+		};
+		const bool planned = depth || opt.sort_mem != 0 || getenv("URMAPX_TEST_SORT_PARTITION");
+		int rc = planned ? planned_sort() : in_core();
+		if (rc == URMAPX_E_NOMEM) {
+			close();
+			LanePool::get().purge(nullptr);
+			rc = planned ? planned_sort() : in_core();
+		}
+		if (rc == URMAPX_E_NOMEM && !planned) rc = planned_sort();
+		return rc;
+	}
+	// why the sort did not run: the device sorts' out-of-memory with the least budget that would do, the depth's references, or the code
+	void refuse_sort(int rc, const Sorted &W) {
+		if (rc == URMAPX_E_NOMEM && !host_sort() && opt.depth_out) {
+			if (W.D.least_budget)
+				fail.raise(rc, "bam_sort with depth: the depth's counters, the sort's arrays, its staging buffers and one slice need at least " +
+				                   std::to_string(W.D.least_budget) + " bytes on the device" +
+				                   (opt.sort_mem ? ", " + std::to_string(opt.sort_mem) + " were given (sort_mem)" : std::string(", fewer are free")));
+			else
+				fail.raise(rc, "bam_sort with depth: out of device memory");
+		} else if (rc == URMAPX_E_NOMEM && !host_sort()) {
+			size_t free_b = 0, total_b = 0;
+			(void)hipSetDevice(phys(0));
+			if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+			const uint64_t have = opt.sort_mem ? opt.sort_mem : free_b > URMAPX_SORT_HEADROOM ? (uint64_t)free_b - URMAPX_SORT_HEADROOM : 1u;
+			urmapx_bam_sort_plan plan;
+			if (urmapx_bam_sort_plan_for((size_t)W.n_bytes, rep.reads, opt.markdup != 0, have, &plan) == URMAPX_E_NOMEM)
+				fail.raise(rc, "bam_sort: the sort's arrays, its staging buffers and one slice need at least " + std::to_string(plan.device_bytes) +
+				                   " bytes on the device, " + std::to_string(have) + (opt.sort_mem ? " were given (sort_mem)" : " are free"));
+			else
+				fail.raise(rc, "bam_sort: out of device memory: the plan takes " + std::to_string(plan.device_bytes) + " bytes, " + std::to_string(free_b) + " are free");
+		} else if (rc == URMAPX_E_ARG && opt.depth_out)
+			fail.raise(rc, "depth: a reference name that is empty or longer than 255 bytes");
+		else
+			fail.raise(rc, std::string("bam_sort: ") + urmapx_strerror(rc));
+	}
+	// samout and samout.bai -> the seconds it took
+	double write_bam_and_bai(const Sorted &W) {
 		const auto tw0 = now();
+		const urmapx_bam_sort_result &S = W.S;
 		std::string eof;
 		(void)bgzf_members(eof, 1);
 		const int wt = sink.writer_threads(host_threads);
-		if (!sink.write_at(hdr.data(), hdr.size(), 0, 1) || !sink.write_at((const char *)S.bgzf, S.bgzf_bytes, hdr.size(), wt) ||
-		    !sink.write_at(eof.data(), eof.size(), hdr.size() + S.bgzf_bytes, 1))
+		if (!sink.write_at(W.hdr.data(), W.hdr.size(), 0, 1) || !sink.write_at((const char *)S.bgzf, S.bgzf_bytes, W.hdr.size(), wt) ||
+		    !sink.write_at(eof.data(), eof.size(), W.hdr.size() + S.bgzf_bytes, 1))
 			cannot_write_sam();
-		rep.sam_file_bytes = hdr.size() + S.bgzf_bytes + eof.size();
+		rep.sam_file_bytes = W.hdr.size() + S.bgzf_bytes + eof.size();
 		const std::string bai = std::string(samout) + ".bai";
 		FILE *f = fopen(bai.c_str(), "wb");
 		if (!f || fwrite(S.bai, 1, S.bai_bytes, f) != S.bai_bytes) fail.raise(URMAPX_E_IO, "Error writing " + bai);
 		if (f && fclose(f) != 0) fail.raise(URMAPX_E_IO, "Error writing " + bai);
-		rep.write_s += secs(tw0, now());
-		rep.sort_s = secs(t0, now());
-		if (getenv("URMAPX_VERBOSE"))  // the parts of sort_s (scripts/bam_sort_bench.py reads this line)
+		const double s = secs(tw0, now());
+		rep.write_s += s;
+		return s;
+	}
+	// the bedGraph file, with the writer threads a file of the sink's kind gets; then the summary table and its totals -> the file's seconds
+	double write_depth(const Sorted &W) {
+		const auto td0 = now();
+		const urmapx_depth_result &D = W.D;
+		FileSink dsink;
+		if (!dsink.open(opt.depth_out) || !dsink.write_at(D.text, D.text_bytes, 0, dsink.writer_threads(host_threads)) || !dsink.finish(D.text_bytes))
+			fail.raise(URMAPX_E_IO, std::string("Error writing ") + opt.depth_out);
+		const double file_s = secs(td0, now());
+		rep.write_s += file_s;
+		rep.depth_runs = D.runs;
+		std::string &table = depth_summary();
+		table = "reference\tlength\treads\tcovered\tpercent\tmean_depth\tmean_mapq\n";
+		for (uint32_t r = 0; r < W.n_ref; ++r) {
+			const urmapx_depth_summary &s = D.refs[r];
+			const uint32_t len = W.ref_lens[r];
+			rep.depth_covered += s.covered;
+			rep.depth_bases += s.bases;
+			char line[160];
+			snprintf(line, sizeof line, "\t%u\t%llu\t%llu\t%.2f\t%.2f\t%.2f\n", len, (unsigned long long)s.reads, (unsigned long long)s.covered,
+			         len ? 100.0 * (double)s.covered / len : 0.0, len ? (double)s.bases / len : 0.0, s.reads ? (double)s.mapq_sum / (double)s.reads : 0.0);
+			table += W.ref_names[r];
+			table += line;
+		}
+		return file_s;
+	}
+	// the report's fields of the sort, the marking and the depth, and under URMAPX_VERBOSE their lines, which the scripts read:
+	// scripts/bam_sort_bench.py, depth_bench.py, bam_sort_external_bench.py, markdup_bench.py, in this order
+	void report_sorted(const Sorted &W, double sorted_s, double bam_s, double bed_s) {
+		const urmapx_bam_sort_result &S = W.S;
+		const urmapx_markdup_stats &M = W.M;
+		const urmapx_depth_result &D = W.D;
+		const bool verbose = getenv("URMAPX_VERBOSE") != nullptr;
+		if (verbose)  // the parts of sort_s
 			fprintf(stderr, "bam_sort seconds: total %.4f scan %.4f alloc %.4f upload %.4f sort %.4f gather %.4f deflate %.4f copy %.4f index %.4f write %.4f; "
 			                "records %llu bytes %llu passes %u slices %u\n",
-			        rep.sort_s, S.scan_s, S.alloc_s, S.upload_s, S.sort_s, S.gather_s, S.deflate_s, S.copy_s, S.index_s, secs(tw0, now()),
+			        sorted_s, S.scan_s, S.alloc_s, S.upload_s, S.sort_s, S.gather_s, S.deflate_s, S.copy_s, S.index_s, bam_s,
 			        (unsigned long long)S.records, (unsigned long long)S.stream_bytes, S.sort_passes, S.slices);
-		if (depth) {  // the bedGraph file, with the writer threads a file of the sink's kind gets; then the table
-			const auto td0 = now();
-			FileSink dsink;
-			if (!dsink.open(opt.depth_out) || !dsink.write_at(D.text, D.text_bytes, 0, dsink.writer_threads(host_threads)) || !dsink.finish(D.text_bytes))
-				fail.raise(URMAPX_E_IO, std::string("Error writing ") + opt.depth_out);
-			const double file_s = secs(td0, now());
-			rep.write_s += file_s;
-			rep.sort_s = secs(t0, now());
-			rep.depth_runs = D.runs;
-			std::string &table = depth_summary();
-			table = "reference\tlength\treads\tcovered\tpercent\tmean_depth\tmean_mapq\n";
-			for (uint32_t r = 0; r < n_ref; ++r) {
-				const urmapx_depth_summary &s = D.refs[r];
-				rep.depth_covered += s.covered;
-				rep.depth_bases += s.bases;
-				char line[160];
-				snprintf(line, sizeof line, "\t%u\t%llu\t%llu\t%.2f\t%.2f\t%.2f\n", ref_lens[r], (unsigned long long)s.reads, (unsigned long long)s.covered,
-				         ref_lens[r] ? 100.0 * (double)s.covered / ref_lens[r] : 0.0, ref_lens[r] ? (double)s.bases / ref_lens[r] : 0.0,
-				         s.reads ? (double)s.mapq_sum / (double)s.reads : 0.0);
-				table += ref_names[r];
-				table += line;
-			}
-			rep.depth_s = D.alloc_s + D.count_s + D.scan_s + D.runs_s + D.format_s + D.copy_s + file_s;
-			if (getenv("URMAPX_VERBOSE"))  // (scripts/depth_bench.py reads this line)
+		if (opt.depth_out) {
+			rep.depth_s = D.alloc_s + D.count_s + D.scan_s + D.runs_s + D.format_s + D.copy_s + bed_s;
+			if (verbose)
 				fprintf(stderr, "depth seconds: total %.4f alloc %.4f count %.4f scan %.4f runs %.4f format %.4f copy %.4f write %.4f; runs %llu bytes %llu slices %u\n",
-				        rep.depth_s, D.alloc_s, D.count_s, D.scan_s, D.runs_s, D.format_s, D.copy_s, file_s, (unsigned long long)D.runs, (unsigned long long)D.text_bytes,
+				        rep.depth_s, D.alloc_s, D.count_s, D.scan_s, D.runs_s, D.format_s, D.copy_s, bed_s, (unsigned long long)D.runs, (unsigned long long)D.text_bytes,
 				        D.text_slices);
-			urmapx_depth_free(&D);
 		}
 		rep.sort_partitions = S.external ? S.partitions : 0;
-		if (S.external && getenv("URMAPX_VERBOSE"))  // (scripts/bam_sort_external_bench.py reads this line)
+		if (S.external && verbose)
 			fprintf(stderr, "bam_sort external: partitions %u chunks %llu passes %u stage %.4f\n", S.partitions, (unsigned long long)S.stage_chunks, S.partitions + 1u, S.stage_s);
-		if (markdup) {
+		if (opt.markdup) {
 			rep.pairs_examined = M.pairs_examined; rep.pairs_duplicate = M.pairs_duplicate;
 			rep.fragments_examined = M.fragments_examined; rep.fragments_duplicate = M.fragments_duplicate;
 			rep.markdup_s = M.markdup_s;
-			if (getenv("URMAPX_VERBOSE"))  // (scripts/markdup_bench.py reads this line)
+			if (verbose)
 				fprintf(stderr, "markdup seconds: %.4f; pairs %llu duplicate %llu fragments %llu duplicate %llu\n", M.markdup_s, (unsigned long long)M.pairs_examined,
 				        (unsigned long long)M.pairs_duplicate, (unsigned long long)M.fragments_examined, (unsigned long long)M.fragments_duplicate);
 		}
-		urmapx_bam_sort_free(&S);
-		trace.add("sort", -1, 0, t0);
 	}
 	int finish(urmapx_map_report *report, std::string &msg) {
 		if (sort && !fail.set.load()) write_sorted();

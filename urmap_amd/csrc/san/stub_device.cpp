@@ -13,6 +13,8 @@
 // function, so the SAM of a run must not depend on which road a chunk took, on the chunk size, the lane count or the shard count.
 #include <hip/hip_runtime_api.h>
 
+#include <atomic>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
@@ -387,18 +389,32 @@ int urmapx_text_fetch_pairs(urmapx_text *T, uint32_t npairs, urmapx_result *resu
 }
 // make_ufi.cpp's GPU-assisted builder has no device here
 int urmapx_build_slots_gpu(int, const uint8_t *, const void *, uint32_t, uint32_t, uint32_t, uint64_t, uint8_t *, uint32_t *) { return URMAPX_E_NODEVICE; }
+// URX_STUB_SORT_NOMEM=K: the first K device-sort calls of the process find the device full (URMAPX_E_NOMEM, nothing touched), and every
+// device-sort call says on stderr which entry it was and with what budget -- the order in which the pipeline tries them
+// (tests/test_bam_sort_plan_cpu.py).  budget null: an in-core entry, which takes none
+static bool stub_sort_refuses(const char *entry, const uint64_t *budget) {
+	static std::atomic<int> calls{0};
+	const char *k = getenv("URX_STUB_SORT_NOMEM");
+	if (!k) return false;
+	if (budget) fprintf(stderr, "stub sort: %s budget %llu\n", entry, (unsigned long long)*budget);
+	else fprintf(stderr, "stub sort: %s\n", entry);
+	return calls++ < atoi(k);
+}
 // the device sort's stand-in: the host sort (bam_sort_host.cpp), which keeps the same contract
 int urmapx_bam_sort(int, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts,
                     urmapx_bam_sort_result *out) {
+	if (stub_sort_refuses("urmapx_bam_sort", nullptr)) return URMAPX_E_NOMEM;
 	return urmapx_bam_sort_host(records, n_bytes, n_ref, in_front, starts, n_starts, out);
 }
 int urmapx_bam_sort_markdup(int, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts,
                             urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
+	if (stub_sort_refuses("urmapx_bam_sort_markdup", nullptr)) return URMAPX_E_NOMEM;
 	return urmapx_bam_sort_markdup_host(records, n_bytes, n_ref, in_front, starts, n_starts, md, out);
 }
 // the planned sort's stand-in: the plan is made (host arithmetic, bam_sort_host.cpp) and its refusal kept; the sort itself is the host's
 int urmapx_bam_sort_external(int, uint64_t budget, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts,
                              urmapx_markdup_stats *md, urmapx_bam_sort_result *out) {
+	if (stub_sort_refuses("urmapx_bam_sort_external", &budget)) return URMAPX_E_NOMEM;
 	if (budget == 0) budget = ((uint64_t)200 << 30) - URMAPX_SORT_HEADROOM;  // (hipMemGetInfo above)
 	urmapx_bam_sort_plan plan;
 	if (const int rc = urmapx_bam_sort_plan_for(n_bytes, n_bytes / 200 + 1, md != nullptr, budget, &plan)) return rc;
@@ -418,6 +434,7 @@ int urmapx_bam_sort_depth(int device, uint64_t budget, const void *records, size
                           urmapx_depth_result *depth, urmapx_bam_sort_result *out) {
 	if (!depth) return urmapx_bam_sort_external(device, budget, records, n_bytes, n_ref, in_front, starts, n_starts, md, out);
 	memset(depth, 0, sizeof *depth);
+	if (stub_sort_refuses("urmapx_bam_sort_depth", &budget)) return URMAPX_E_NOMEM;
 	if (budget == 0) budget = ((uint64_t)200 << 30) - URMAPX_SORT_HEADROOM;  // (hipMemGetInfo above)
 	uint64_t columns = 0;
 	for (uint32_t r = 0; r < n_ref && lens; ++r) columns += lens[r];
