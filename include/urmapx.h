@@ -740,8 +740,12 @@ int urmapx_tags_batch(urmapx_ctx *, const uint8_t *bases, const uint64_t *offs, 
  *                       of the CIGAR, at least one) --, then the pseudo-bin 37450 (where the reference's records begin and end; how many
  *                       there are without and with flag 4), then the linear index: for every 16 384-base window the smallest place of
  *                       a record that overlaps it, a window without one taking the next one's value, cut off behind the last window
- *                       that has one.  n_no_coor counts the records with refID -1.  The bins cover positions below 2^29: records
- *                       beyond are sorted like the others, but no reader finds them through the index.
+ *                       that has one.  n_no_coor counts the records with refID -1.  The scheme covers positions below 2^29 of a
+ *                       reference.  A record with pos >= 2^29 is sorted like the others and counted in its reference's pseudo-bin,
+ *                       between whose offsets it lies, but gets no chunk and no window.  A record that begins below 2^29 and ends
+ *                       beyond is indexed as [pos, 2^29): that region's bin, the windows pos >> 14 .. 32 767.  So no bin but the
+ *                       pseudo-bin exceeds 37 448, no linear index has more than 32 768 entries, and the index is well formed and
+ *                       answers every region below 2^29 whatever lies beyond.  The record's own bin field stays what it carries.
  * Both byte arrays are the result's until urmapx_bam_sort_free.  The times are seconds of the calling thread in the steps named.
  * urmapx_bam_sort runs on `device` (bam_sort.hip): the record starts come from one walk along the block_size chain on the host, which
  * also checks the chain; keys, a least-significant-digit radix sort of (key, record number) in 8-bit digits over as many digits as n_ref

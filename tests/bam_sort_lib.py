@@ -3,7 +3,7 @@ written from the SAM/BAM specification (SAMv1 sections 4.1, 5.2 and 5.3) and sha
 which reads and writes the records themselves.
 
     split_records(stream)               the records of an uncompressed record stream, each with its offset
-    fields(record)                      refID, pos, end on the reference, bin, flag
+    fields(record)                      refID, pos, end on the reference, the bin the index files it under, flag
     oracle_order(records)               the order the sort must give: Python's stable sort on (refID, pos) read as unsigned
     parse_bai(data)                     a .bai file -> Bai (bins with their chunks, pseudo-bins, linear indexes, n_no_coor)
     reg2bins(beg, end)                  the bins that may hold records overlapping [beg, end)
@@ -11,14 +11,21 @@ which reads and writes the records themselves.
     query(bai, f, ref, beg, end)        what a reader does with an index; brute(...) is the answer over all records
     check_sorted_bam(...)               every property the tests ask of a sorted stream and its index
 """
+import bisect
 import struct
 import zlib
+
+import numpy as np
 
 import bam_lib as bl
 
 MEMBER = 65280
 PSEUDO_BIN = 37450
 WINDOW = 1 << 14
+INDEX_END = 1 << 29   # the scheme of section 5.3 covers [0, 2^29) of a reference
+MAX_BIN = 37448       # its last bin: 4681 + 2^15 - 1
+MAX_WINDOWS = INDEX_END // WINDOW
+LEVELS = [(0, 0), (1, 8), (9, 72), (73, 584), (585, 4680), (4681, MAX_BIN)]  # first and last bin of each of the six levels
 
 
 def split_records(stream):
@@ -34,7 +41,9 @@ def split_records(stream):
 
 
 def fields(rec):
-    """(refID, pos, end, bin of [pos, end), flag) of one record; end = pos + the reference bases of the CIGAR, at least one"""
+    """(refID, pos, end, bin, flag) of one record; end = pos + the reference bases of the CIGAR, at least one.  bin is where the index
+    files the record: that of [pos, min(end, 2^29)); None for a record without a reference or with pos >= 2^29, which gets no chunk
+    and no window"""
     ref_id, pos, l_name, _mapq, _bin, n_cig, flag = struct.unpack_from("<iiBBHHH", rec, 4)
     span = 0
     for k in range(n_cig):
@@ -42,7 +51,7 @@ def fields(rec):
         if bl.CIGAR_LETTERS[w & 15] in bl.REF_CONSUMING:
             span += w >> 4
     end = pos + (span if span else 1)
-    return ref_id, pos, end, bl.reg2bin(pos, end) if ref_id >= 0 else None, flag
+    return ref_id, pos, end, bl.reg2bin(pos, min(end, INDEX_END)) if ref_id >= 0 and pos < INDEX_END else None, flag
 
 
 def sort_key(rec):
@@ -80,9 +89,10 @@ def parse_bai(data):
                 assert n_chunk == 2 and pseudo is None
                 pseudo = (chunks[0][0], chunks[0][1], chunks[1][0], chunks[1][1])
             else:
-                assert n_chunk >= 1
+                assert n_chunk >= 1 and bin_ <= MAX_BIN, (bin_, n_chunk)
                 bins.append((bin_, chunks))
         n_intv, = struct.unpack_from("<I", data, at)
+        assert n_intv <= MAX_WINDOWS, n_intv
         at += 4
         linear = list(struct.unpack_from(f"<{n_intv}Q", data, at))
         at += 8 * n_intv
@@ -232,7 +242,8 @@ def index_in_places(bai, table):
 
 
 def check_index(bai, recs, table, n_ref):
-    """recs: [(stream offset, record)] of the sorted stream; table: member_places of the file the index belongs to"""
+    """recs: [(stream offset, record)] of the sorted stream; table: member_places of the file the index belongs to.  A record with
+    pos >= 2^29 counts in its reference's pseudo-bin and nowhere else; one that ends beyond 2^29 has its windows up to 32 767"""
     assert len(bai.refs) == n_ref
     refs, n_no_coor = index_in_places(bai, table)
     by_ref = [[] for _ in range(n_ref)]
@@ -252,8 +263,15 @@ def check_index(bai, recs, table, n_ref):
             for (x, y), nxt in zip(cs, cs[1:] + [None]):
                 assert x < y and (nxt is None or y <= nxt[0]), (b, cs)
         for off, stop, pos, end, bin_, flag in mine:  # every record lies inside a chunk of its bin
-            assert any(x <= off and stop <= y for x, y in chunks_of.get(bin_, [])), (off, bin_)
-        assert set(chunks_of) == set(m[4] for m in mine)
+            assert bin_ is None or any(x <= off and stop <= y for x, y in chunks_of.get(bin_, [])), (off, bin_)
+        assert set(chunks_of) == set(m[4] for m in mine if m[4] is not None)
+        every = sorted((x, y, b) for b, cs in bins for x, y in cs)  # no record lies inside a chunk of another bin, or of any without one
+        assert all(a[1] <= c[0] for a, c in zip(every, every[1:])), "chunks of different bins overlap"
+        begins = [x for x, _, _ in every]
+        for off, stop, pos, end, bin_, flag in mine:
+            at = bisect.bisect_right(begins, off) - 1
+            holder = every[at][2] if at >= 0 and stop <= every[at][1] else None
+            assert holder == bin_, (off, bin_, holder)
         starts = set(m[0] for m in mine) | set(m[1] for m in mine)
         assert all(x in starts and y in starts for cs in chunks_of.values() for x, y in cs), "a chunk does not begin and end at a record"
         if not mine:
@@ -262,17 +280,23 @@ def check_index(bai, recs, table, n_ref):
         unm = sum(1 for m in mine if m[5] & 4)
         assert r["pseudo"] == (mine[0][0], mine[-1][1], len(mine) - unm, unm), r["pseudo"]
         lin = r["linear"]
+        mine = [(off, stop, pos, min(end, INDEX_END), bin_, flag) for off, stop, pos, end, bin_, flag in mine if bin_ is not None]
+        if not mine:
+            assert not lin
+            continue
         assert len(lin) == ((max(m[3] for m in mine) - 1) >> 14) + 1, "the linear index does not end behind the last non-empty window"
         assert all(a <= b for a, b in zip(lin, lin[1:])), "linear index not monotone"
-        smallest = {}
+        none = 1 << 63  # (no place of a stream is that large)
+        smallest = np.full(len(lin), none, dtype=np.uint64)  # per window: the smallest place of a record that overlaps it
         for off, stop, pos, end, bin_, flag in mine:
-            for w in range(pos >> 14, ((end - 1) >> 14) + 1):
-                smallest[w] = min(smallest.get(w, off), off)
-        for w, v in enumerate(lin):
-            if w in smallest:
-                assert v == smallest[w], (w, v, smallest[w])
-            else:  # an empty window: the next non-empty one's value
-                assert v == smallest[min(x for x in smallest if x > w)], w
+            a, b = pos >> 14, ((end - 1) >> 14) + 1
+            smallest[a:b] = np.minimum(smallest[a:b], np.uint64(off))
+        want = smallest.tolist()
+        assert want[-1] != none
+        for w in range(len(want) - 2, -1, -1):  # an empty window: the next non-empty one's value
+            if want[w] == none:
+                want[w] = want[w + 1]
+        assert lin == want, [(w, v, x) for w, (v, x) in enumerate(zip(lin, want)) if v != x][:5]
 
 
 def check_queries(bai, f, records, regions):
@@ -281,7 +305,7 @@ def check_queries(bai, f, records, regions):
 
 
 def edge_regions(ref_lengths, rng, n_random=200):
-    """the regions the issue names: seeded random ones, position 0, a reference's last base, across a 2^14 and a 2^26 boundary"""
+    """seeded random regions, position 0, a reference's last base, across the first boundary of every level: 2^14, 2^17, 2^20, 2^23, 2^26"""
     out = []
     for _ in range(n_random):
         ref = int(rng.integers(0, len(ref_lengths)))
@@ -290,7 +314,7 @@ def edge_regions(ref_lengths, rng, n_random=200):
         out.append((ref, beg, min(L, beg + int(rng.integers(1, 1 + max(1, L // 4))))))
     for ref, L in enumerate(ref_lengths):
         out += [(ref, 0, 1), (ref, 0, min(L, 100)), (ref, L - 1, L)]
-        for edge in (1 << 14, 1 << 26):
+        for edge in (1 << 14, 1 << 17, 1 << 20, 1 << 23, 1 << 26):
             if L > edge:
                 out += [(ref, edge - 1, edge + 1), (ref, edge - 10, min(L, edge + 300)), (ref, edge, edge + 1), (ref, edge - 1, edge)]
     return out

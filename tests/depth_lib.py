@@ -22,7 +22,7 @@ def with_mapq(rec, mapq):
 def model(records, names, lens, min_mapq=0):
     """records: bytes, the chain of BAM records -> (bedGraph text, number of lines, [dict of reads, covered, bases, mapq_sum])"""
     n_ref = len(lens)
-    depth = [np.zeros(int(l), dtype=np.int64) for l in lens]
+    depth = [np.zeros(int(l), dtype=np.int32) for l in lens]  # (four bytes a column: a chromosome's worth stays within a second or two)
     summary = [dict(reads=0, covered=0, bases=0, mapq_sum=0) for _ in lens]
     for _, r in sl.split_records(bytes(records)):
         ref_id, pos, l_name, mapq, _bin, n_cigar, flag = struct.unpack_from("<iiBBHHH", r, 4)
@@ -41,7 +41,7 @@ def model(records, names, lens, min_mapq=0):
     lines = []
     for r, d in enumerate(depth):
         summary[r]["covered"] = int(np.count_nonzero(d))
-        summary[r]["bases"] = int(d.sum())
+        summary[r]["bases"] = int(d.sum(dtype=np.int64))
         if not len(d):
             continue
         begs = np.concatenate(([0], np.flatnonzero(np.diff(d)) + 1))

@@ -22,12 +22,14 @@ REFS = [("big", (1 << 26) + 90000), ("mid", 40000), ("none", 5000), ("small", 20
 
 def synthetic_sam(seed=1, n=1500):
     """SAM lines whose positions crowd the places where an index goes wrong: position 0, a reference's last base, both sides of 2^14
-    multiples and of 2^26, long reference skips that cross many windows, ties, placed reads with flag 4, unplaced reads in between"""
+    multiples and of the first boundary of every bin level (2^17, 2^20, 2^23, 2^26), long reference skips that cross many windows, ties,
+    placed reads with flag 4, unplaced reads in between.  The last four records are fixed: a 30M20000N20M across each of 2^17, 2^20 and
+    2^23, and one 10M60000000N10M across 2^26, which sits in bin 0 and covers 3 663 windows"""
     rng = np.random.default_rng(seed)
     cigars = [("50M", 50), ("20M5D30M", 50), ("10M2I38M", 50), ("30M20000N20M", 50), ("1M", 1), ("25M40000N25M", 50), ("7M1D7M1I7M1D7M1I7M1D7M1I7M1D7M1I7M", 67)]
     span = {c: sum(k for k, op in bl.parse_cigar(c) if op in bl.REF_CONSUMING) for c, _ in cigars}
     lines = []
-    for i in range(n):
+    for i in range(n - 4):
         kind = int(rng.integers(0, 12))
         if kind == 0:
             lines.append(f"u{i}\t4\t*\t0\t0\t*\t*\t0\t0\tACGTA\tIIIII")
@@ -39,6 +41,7 @@ def synthetic_sam(seed=1, n=1500):
             cigar, qlen = cigars[0]
         room = L - span[cigar]
         hot = [0, 1, room, room - 1, (1 << 14) - 1, (1 << 14) - 30, 1 << 14, (1 << 15) - 10, (1 << 26) - 1, (1 << 26) - 40, 1 << 26, (1 << 26) + 16384]
+        hot += [(1 << s) + d for s in (17, 20, 23) for d in (-40, -1, 0, 16384)]
         pos = int(rng.choice(hot)) if kind < 5 else int(rng.integers(0, room + 1))
         if kind == 5:
             pos = 12345  # ties: many records with one key
@@ -47,6 +50,9 @@ def synthetic_sam(seed=1, n=1500):
         if flag == 4:
             cigar, qlen = "*", 7
         lines.append(f"r{i}\t{flag}\t{name}\t{pos + 1}\t30\t{cigar}\t*\t0\t0\t{'ACGTN'[i % 5] * qlen}\t{'I' * qlen}")
+    for s in (17, 20, 23):
+        lines.append(f"x{s}\t0\tbig\t{(1 << s) - 10000 + 1}\t30\t30M20000N20M\t*\t0\t0\t{'ACGTN' * 10}\t{'I' * 50}")
+    lines.append(f"wide\t0\tbig\t{7150000 + 1}\t30\t10M60000000N10M\t*\t0\t0\t{'ACGT' * 5}\t{'I' * 20}")
     return "\n".join(lines) + "\n"
 
 
@@ -78,6 +84,9 @@ def test_index_parses_and_holds_every_property(case):
     assert r[0]["pseudo"][3] > 0  # placed reads with flag 4 are counted apart
     levels = set(b for b, _ in r[0]["bins"])
     assert 0 in levels and any(b >= 4681 for b in levels) and any(585 <= b < 4681 for b in levels)
+    assert all(any(lo <= b <= hi for b in levels) for lo, hi in sl.LEVELS), sorted(levels)  # a bin on each of the six levels
+    wide = [r for _, r in case["recs"] if r[36:41] == b"wide\0"]
+    assert len(wide) == 1 and sl.fields(wide[0])[3] == 0 and ((sl.fields(wide[0])[2] - 1) >> 14) - (sl.fields(wide[0])[1] >> 14) + 1 == 3663
     assert len(r[0]["linear"]) > (1 << 26) >> 14
 
 

@@ -103,16 +103,16 @@ def test_keys(what):
         ref, pos, n_ref = np.full(n, -1), np.full(n, -1), 3
     elif what == "none_unmapped":
         ref, pos, n_ref = rng.integers(0, 3, n), rng.integers(0, 50000, n), 3
-    else:  # a position that needs bit 30: beyond what the bins cover, the order and the stream still hold
+    else:  # a position that needs bit 30: beyond what the bins cover; the order and the stream hold, and the index of what lies below 2^29
         ref, pos, n_ref = rng.integers(0, 2, n), np.where(rng.integers(0, 2, n) == 1, (1 << 30) + 5, rng.integers(0, 1 << 20, n)), 2
     stream, b, f, table, rep = both(tiny_records(ref, pos), n_ref)
     out = np.frombuffer(stream, TINY)
     assert (out["tlen"] == stable_order(ref, pos)).all()
     assert b.n_no_coor == (n if what == "only_unmapped" else 0) == rep["no_coor"]
-    if what != "high_pos":
-        sl.check_index(b, sl.split_records(stream), table, n_ref)
-    else:
+    sl.check_index(b, sl.split_records(stream), table, n_ref)
+    if what == "high_pos":
         assert rep["sort_passes"] == 5  # 2 bits of reference, 31 of position
+        assert all(0 < len(r["linear"]) <= (1 << 20) >> 14 for r in b.refs)  # (no window for the records beyond)
 
 
 @pytest.mark.parametrize("n_ref", [1, 255, 256, 257])

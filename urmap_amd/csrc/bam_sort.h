@@ -29,7 +29,16 @@ BAMSORT_HD uint32_t load_u32(const uint8_t *p) {
 	return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
 }
 
-// section 5.3 with 64-bit arithmetic; positions from 2^29 on have no bin of their own in this scheme (the index covers [0, 2^29))
+// The BAI scheme covers [0, INDEX_END) of a reference.  A placed record that begins at or beyond it gets no chunk and no window; one
+// that begins below and ends beyond is indexed as [pos, INDEX_END): the bin of that region, the windows pos >> 14 .. 32 767.  So no
+// ordinary bin exceeds NO_BIN - 1 = 37 448 and no linear index has more than 32 768 entries.  Both sorts index with these two.
+constexpr uint64_t INDEX_END = (uint64_t)1 << 29;
+constexpr uint32_t BIN_BITS = 16;         // bits of a bin in the second sort's key
+constexpr uint32_t NO_BIN = 0xFFFFu;      // there: a record without a chunk; sorts behind every bin of its reference
+BAMSORT_HD bool indexed(uint64_t pos) { return pos < INDEX_END; }
+BAMSORT_HD uint64_t index_end(uint64_t end) { return end < INDEX_END ? end : INDEX_END; }
+
+// section 5.3 with 64-bit arithmetic, for [beg, end) inside [0, INDEX_END)
 BAMSORT_HD uint32_t reg2bin(uint64_t beg, uint64_t end) {
 	--end;
 	if (beg >> 14 == end >> 14) return (uint32_t)(((1u << 15) - 1u) / 7u + (beg >> 14));

@@ -273,7 +273,8 @@ __global__ __launch_bounds__(NT) void place_kernel(const uint8_t *stage, uint64_
 // ---- the index ----
 // per sorted record: where its reference's records begin and end; the reference's largest end (one atomic per wavefront where its 64
 // records share the reference, which in sorted order is nearly everywhere); its records with flag 4 (has4[i]: keys_kernel's note of
-// record i, so no record's bytes are read here)
+// record i, so no record's bytes are read here).  The largest end is that of the index (bam_sort.h INDEX_END): a record that begins
+// beyond counts for nothing, one that ends beyond for 2^29
 __global__ __launch_bounds__(NT) void bounds_kernel(const uint32_t *has4, const uint64_t *key, const uint32_t *val, const uint32_t *end,
                                                     uint32_t n, KeyLayout K, uint32_t *first, uint32_t *last, uint32_t *max_end, uint32_t *flag4) {
 	const uint32_t rounds = (n + gridDim.x * NT - 1) / (gridDim.x * NT);
@@ -286,7 +287,7 @@ __global__ __launch_bounds__(NT) void bounds_kernel(const uint32_t *has4, const 
 			if (k == 0 || K.ref_of(key[k - 1]) != r) first[r] = k;
 			if (k == n - 1 || K.ref_of(key[k + 1]) != r) last[r] = k;
 			if (r < K.n_ref) {
-				e = end[val[k]];
+				e = indexed(K.pos_of(key[k])) ? (uint32_t)index_end(end[val[k]]) : 0u;
 				if (has4[val[k]]) atomicAdd(&flag4[r], 1u);
 			}
 		}
@@ -309,33 +310,39 @@ __global__ __launch_bounds__(NT) void lin_kernel(const uint64_t *key, const uint
 	for (uint32_t k = blockIdx.x * NT + threadIdx.x; k < m; k += gridDim.x * NT) {
 		const uint32_t r = K.ref_of(key[k]);
 		const uint64_t w0 = win_base[r], n_win = win_base[r + 1] - w0;
-		const uint64_t a = K.pos_of(key[k]) >> WINDOW_SHIFT, b = ((uint64_t)end[val[k]] - 1u) >> WINDOW_SHIFT;
+		const uint64_t pos = K.pos_of(key[k]);
+		if (!indexed(pos)) continue;
+		const uint64_t a = pos >> WINDOW_SHIFT, b = (index_end(end[val[k]]) - 1u) >> WINDOW_SHIFT;
 		for (uint64_t w = a; w <= b && w < n_win; ++w) atomicMin(&lin[w0 + w], (unsigned long long)dst[k]);
 	}
 }
-__global__ __launch_bounds__(NT) void bin_key_kernel(const uint64_t *key, const uint32_t *val, const uint32_t *end, uint32_t m, KeyLayout K, uint32_t bin_bits,
-                                                     uint64_t *key2, uint32_t *val2) {
+// (a record beyond the index gets NO_BIN: the second sort puts it behind its reference's bins, and no chunk is made of it)
+__global__ __launch_bounds__(NT) void bin_key_kernel(const uint64_t *key, const uint32_t *val, const uint32_t *end, uint32_t m, KeyLayout K, uint64_t *key2,
+                                                     uint32_t *val2) {
 	for (uint32_t k = blockIdx.x * NT + threadIdx.x; k < m; k += gridDim.x * NT) {
-		key2[k] = (uint64_t)K.ref_of(key[k]) << bin_bits | reg2bin(K.pos_of(key[k]), end[val[k]]);
+		const uint64_t pos = K.pos_of(key[k]);
+		key2[k] = (uint64_t)K.ref_of(key[k]) << BIN_BITS | (indexed(pos) ? reg2bin(pos, index_end(end[val[k]])) : NO_BIN);
 		val2[k] = k;
 	}
 }
-// a chunk begins where the (reference, bin) changes or the record is not the file's next one
+__device__ __forceinline__ bool no_bin(uint64_t key2) { return (key2 & NO_BIN) == NO_BIN; }
+// a chunk begins where the (reference, bin) changes or the record is not the file's next one; none at a record without a bin
 __global__ __launch_bounds__(NT) void chunk_flag_kernel(const uint64_t *key2, const uint32_t *val2, uint32_t m, uint32_t *flag) {
 	for (uint32_t j = blockIdx.x * NT + threadIdx.x; j < m; j += gridDim.x * NT)
-		flag[j] = j == 0 || key2[j] != key2[j - 1] || val2[j] != val2[j - 1] + 1u;
+		flag[j] = !no_bin(key2[j]) && (j == 0 || key2[j] != key2[j - 1] || val2[j] != val2[j - 1] + 1u);
 }
 __global__ __launch_bounds__(NT) void chunk_write_kernel(const uint64_t *key2, const uint32_t *val2, const uint32_t *flag, const uint32_t *index, const uint64_t *dst,
-                                                         uint32_t m, uint32_t bin_bits, uint32_t n_chunks, Chunk *chunks) {
+                                                         uint32_t m, uint32_t n_chunks, Chunk *chunks) {
 	for (uint32_t j = blockIdx.x * NT + threadIdx.x; j < m; j += gridDim.x * NT) {
+		if (no_bin(key2[j])) continue;
 		const uint32_t c = index[j] + flag[j] - 1u;  // (index: chunks that begin in front of j)
 		if (c >= n_chunks) continue;
 		if (flag[j]) {
-			chunks[c].ref = (uint32_t)(key2[j] >> bin_bits);
-			chunks[c].bin = (uint32_t)(key2[j] & (((uint64_t)1 << bin_bits) - 1u));
+			chunks[c].ref = (uint32_t)(key2[j] >> BIN_BITS);
+			chunks[c].bin = (uint32_t)(key2[j] & NO_BIN);
 			chunks[c].beg = dst[val2[j]];
 		}
-		if (j == m - 1 || flag[j + 1]) chunks[c].end = dst[val2[j] + 1];
+		if (j == m - 1 || flag[j + 1] || no_bin(key2[j + 1])) chunks[c].end = dst[val2[j] + 1];
 	}
 }
 
@@ -451,7 +458,6 @@ struct DeviceSort {
 	std::vector<uint64_t> offs;
 	uint32_t n = 0;
 	KeyLayout K;
-	uint32_t bin_bits = 16;
 
 	// ---- the road; on the external one the staged chunks: chunk c is records cut[c] .. cut[c + 1] - 1 ----
 	urmapx_bam_sort_plan P{};
@@ -516,7 +522,6 @@ struct DeviceSort {
 		n = (uint32_t)(offs.size() - 1);
 		out->records = n;
 		K = key_layout(n_ref, max_pos);
-		bin_bits = max_pos < (1u << 29) ? 16u : 18u;  // (reg2bin's largest value: 37 448 below 2^29, 4681 + 2^17 in all)
 		return URMAPX_OK;
 	}
 
@@ -695,8 +700,8 @@ struct DeviceSort {
 		// The second sort runs between the two key arrays: bin_key_kernel is the last reader of the coordinate keys.  Its numbers go to
 		// d_val[2] (the notes: bounds_kernel has read them) and the lengths (scanned into d_dst by destinations); by_coor.val stays
 		SortArrays S2{{spare.key, by_coor.key}, {d_val[2].p, lengths}, 0};
-		hipLaunchKernelGGL(bin_key_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, by_coor.key, by_coor.val, d_end.p, m, K, bin_bits, S2.key[0], S2.val[0]);
-		(void)radix_sort(S2, m, K.ref_bits + bin_bits, d_hist.p);
+		hipLaunchKernelGGL(bin_key_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, by_coor.key, by_coor.val, d_end.p, m, K, S2.key[0], S2.val[0]);
+		(void)radix_sort(S2, m, K.ref_bits + BIN_BITS, d_hist.p);
 		const uint64_t *const key2 = S2.key[S2.in];
 		const uint32_t *const val2 = S2.val[S2.in];
 		// in the key array the second sort left free, as words: 2 m + 1 of them in an array of 2 n + 4
@@ -708,7 +713,7 @@ struct DeviceSort {
 		HIP_TRY(hipMemcpy(&n_chunks, C.index + m, 4, hipMemcpyDeviceToHost));
 		if (n_chunks > m) return URMAPX_E_NODEVICE;
 		if ((rc = d_chunks.alloc(n_chunks))) return rc;
-		hipLaunchKernelGGL(chunk_write_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, key2, val2, C.flag, C.index, d_dst.p, m, bin_bits, n_chunks, d_chunks.p);
+		hipLaunchKernelGGL(chunk_write_kernel, dim3(grid_for(m)), dim3(NT), 0, nullptr, key2, val2, C.flag, C.index, d_dst.p, m, n_chunks, d_chunks.p);
 		HIP_TRY(hipGetLastError());
 		X.chunks.resize(n_chunks);
 		HIP_TRY(hipMemcpy(X.chunks.data(), d_chunks.p, (size_t)n_chunks * sizeof(Chunk), hipMemcpyDeviceToHost));

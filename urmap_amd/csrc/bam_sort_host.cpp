@@ -286,9 +286,10 @@ int sort_host(const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_fr
 		if (E.n_mapped + E.n_unmapped == 0) E.beg = dst[k];
 		E.end = dst[k + 1];
 		if (load_u32(p + 16) >> 16 & 4u) ++E.n_unmapped; else ++E.n_mapped;
-		max_end[r] = std::max(max_end[r], end);
-		end_of[k] = end;
-		bin_of[k] = reg2bin(beg, end);
+		if (!indexed(beg)) continue;  // (counted in the pseudo-bin, lying between its offsets; no chunk, no window)
+		end_of[k] = index_end(end);
+		max_end[r] = std::max(max_end[r], end_of[k]);
+		bin_of[k] = reg2bin(beg, end_of[k]);
 		placed.push_back((uint32_t)k);
 	}
 	for (uint32_t r = 0; r < n_ref; ++r) X.win_base[r + 1] = X.win_base[r] + (max_end[r] ? ((max_end[r] - 1) >> WINDOW_SHIFT) + 1 : 0);
