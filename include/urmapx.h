@@ -447,6 +447,13 @@ typedef struct urmapx_map_options {
 	                     * table per reference to urmapx_map_depth_summary.  NULL: none.  URMAPX_E_ARG without bam_sort, and for a name
 	                     * that is samout's or its index's.  A failed run removes the file with the other two */
 	uint32_t depth_mapq; /* -depth_mapq (with depth_out): records with a MAPQ below it do not count; 0 .. 255 */
+	const char *stats_out; /* -stats (with bam_sort): a text file of the alignment statistics of the records as the BAM file holds them -- under
+	                     * markdup with the marking's bit 0x400 --, counted on first_gpu where the depth is taken (see "Stats" below;
+	                     * urmapx_bam_sort_with, on the host road urmapx_bam_sort_with_host); its second line carries cmdline.  The BAM file
+	                     * and its index are those of the run without it but for the @PG line.  The tables come off sort_mem (or off
+	                     * what is free) with the depth's arrays before the sort is planned.  A few totals go to the report.  NULL: none.
+	                     * URMAPX_E_ARG without bam_sort, for an empty name and for a name that is samout's, its index's or depth_out's.
+	                     * A failed run removes the file with the others */
 } urmapx_map_options;
 typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:593-632) and where the time went */
 	uint64_t reads, mapped_q, mapped_lowq, unmapped, unsupported;
@@ -480,6 +487,8 @@ typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:59
 	uint32_t sort_partitions;                        /* bam_sort: partitions the sorted stream was made in on the external road; 0: in core (or the host) */
 	double depth_s;                                  /* depth_out: the depth's share of sort_s (its arrays, the counting, scan, runs, text and the file) */
 	uint64_t depth_runs, depth_covered, depth_bases; /* depth_out: lines of the file; columns with depth >= 1 and the sum of all depths, over all references */
+	double stats_s;                                  /* stats_out: the statistics' share of sort_s (their tables, the counting, the text and the file) */
+	uint64_t stats_reads, stats_mapped, stats_properly_paired, stats_duplicated, stats_insert_median;  /* stats_out: the SN lines of those names */
 } urmapx_map_report;
 /* fastq2 NULL: single-end (-map); else the mates' file (-map2 ... -reverse).  samout / tabout may be NULL.  The index
  * needs its host arrays, or to be resident on first_gpu already (the other devices' replicas are then copied from there).  Batch b is mapped on device
@@ -920,6 +929,96 @@ int urmapx_bam_sort_depth(int device, uint64_t budget_bytes, const void *records
 int urmapx_bam_sort_depth_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
                                size_t n_starts, urmapx_markdup_stats *md, const urmapx_depth_opts *dopts, const char *const *names,
                                const uint32_t *lens, urmapx_depth_result *depth, urmapx_bam_sort_result *out);
+
+/* ---- Stats (alignment QC tables of BAM records, as a tab-separated text) ----
+ * The input is BAM records as above, in any order, and the n_ref reference names and lengths (as for the depth).  Every counter is 64
+ * bits wide and exact, and no counter depends on the order of the records.
+ *  1. Flags are the ones the record carries; inside urmapx_bam_sort_with they are the ones it carries in the sorted stream, so under
+ *     marking bit 0x400 is the marking's decision.  A READ is a record with neither 0x100 nor 0x800.  The counters records, secondary
+ *     (0x100) and supplementary (0x800) count records; everything else counts reads only.  MAPPED: not 0x4.  LAST FRAGMENT: 0x80 set;
+ *     every other read is a FIRST FRAGMENT.
+ *  2. Fields.  l_seq, CIGAR, SEQ, QUAL and the aux area (from the end of QUAL to the end of block_size) are the record's.  A read whose
+ *     SEQ and QUAL do not lie inside its block_size counts with l_seq 0, no CIGAR op and no aux area.
+ *  3. Caps: CYCLES 1024, QUALS 94, IS_MAX 8000, RL_MAX 65535, ID_MAX 256; a value beyond a cap falls into the last bin (min(v, cap)).
+ *     Cycle of base i (0-based) of a read of l_seq bases: i, or l_seq - 1 - i where 0x10 is set.  Cycles >= CYCLES share one extra row.
+ *     Base classes from the 4-bit codes: A=1, C=2, G=4, T=8, N=15, every other code "other"; where 0x10 is set A<->T and C<->G swap.
+ *     A read HAS QUALITIES if l_seq > 0 and its first QUAL byte is not 0xFF; a quality value is min(QUAL byte, 93).
+ *  4. CIGAR sums, over mapped reads: bases mapped (cigar) = lengths of M, =, X, I; bases soft clipped = S; bases inserted = I; bases
+ *     deleted = D; insertions / deletions = the I / D ops of length >= 1.  ID bin of such an op: min(length, ID_MAX).
+ *  5. NM.  The aux area of a mapped read is walked field by field: tag (2 bytes), type (1), value -- A c C: 1 byte; s S: 2; i I f: 4;
+ *     Z H: up to and including a 0 byte; B: a subtype of c C s S i I f, a 32-bit count, count elements.  A field that would leave
+ *     block_size, an unknown type or subtype, or fewer than 3 bytes left end the walk.  The first field met with tag NM and a type of
+ *     c C s S i I gives the read's NM (signed for c s i; negative counts as 0) and ends the walk; the read is then a READ WITH NM.  An NM
+ *     field of another type is walked over.  mismatches = the sum of NM; error rate = mismatches / (the M, =, X, I lengths of the reads
+ *     with NM), six decimals.
+ *  6. Insert size.  A read contributes when 0x1 is set, it is mapped, 0x8 is not set, next_refID == refID and tlen > 0: one record per
+ *     pair, judged from the record alone.  Inward: 0x10 clear and 0x20 set.  Outward: 0x10 set and 0x20 clear.  Else "other".  The size
+ *     is min(tlen, IS_MAX).  insert size average: over the binned sizes, two decimals.  insert size median: the least size whose
+ *     cumulative count reaches ceil(pairs / 2); 0 without pairs.
+ *  7. Quotients: floor((10^d * num + den / 2) / den) in integers (den / 2 rounded down), printed with the point in front of the last d
+ *     digits; "0." and d zeros where den is 0.
+ *  8. The text: lines of tab-separated fields, each led by its section tag, in this order.
+ *       "# urmapx stats 1"  and  "# command: " followed by the command text (the @PG command of the run; empty for library calls)
+ *       SN <name> <value>, one line each, in this order: records; secondary; supplementary; reads; reads paired (0x1); first fragments;
+ *          last fragments; reads mapped; reads unmapped; reads properly paired (0x1, 0x2, mapped); reads mapped and paired (0x1, mapped,
+ *          not 0x8); singletons (0x1, mapped, 0x8); mate on another reference (mapped and paired, next_refID != refID); reads reverse
+ *          strand (mapped, 0x10); reads duplicated (0x400); reads QC failed (0x200); reads MQ0 (mapped, MAPQ 0); reads without qualities
+ *          (l_seq > 0, first QUAL byte 0xFF); total length (sum of l_seq); bases mapped (l_seq of mapped reads); bases mapped (cigar);
+ *          bases soft clipped; bases inserted; bases deleted; insertions; deletions; bases duplicated (l_seq of reads with 0x400); reads
+ *          with NM; mismatches; error rate; average length (total length / reads, two decimals); maximum length (of l_seq); average
+ *          quality (the quality values of the reads with qualities / their bases, two decimals); pairs with insert size; inward pairs;
+ *          outward pairs; other pairs; insert size average; insert size median
+ *       RL length first last      reads by min(l_seq, RL_MAX), first and last fragments; lengths with a count only
+ *       MQ mapq count             mapped reads; rows with a count only
+ *       IS size total inward outward other    rows with a count only
+ *       FFQ / LFQ cycle c0 .. c93 first / last fragments with qualities: per cycle (printed 1-based) the reads with each quality value;
+ *                                 rows 1 .. the largest cycle below CYCLES with a count in that table, then a row ">1024" if it has one
+ *       BC cycle A C G T N other  all reads; rows as for FFQ
+ *       GC percent count          reads with l_seq > 0 by floor(100 * (#C + #G) / l_seq), codes 2 and 4; rows with a count only
+ *       ID length insertions deletions        rows with a count only
+ *       RF name length mapped unmapped duplicated   reads by refID, one line per reference in index order, zeros included; a last
+ *                                 line with name "*" and length 0 for refID -1
+ * urmapx_bam_stats runs on `device` (stats.hip): the records pass through two staging buffers in input order, as for the depth
+ * (URMAPX_TEST_SORT_STAGE=B), and stats_count_kernel -- persistent workgroups, a wavefront per record, the hot low ends of the tables
+ * in LDS, added to the 64-bit tables once per workgroup and launch (URMAPX_TEST_STATS_BLOCKS=N: at most N workgroups) -- counts them;
+ * the tables (urmapx_bam_stats_resident_bytes) are copied back and one host formatter writes the text.  urmapx_bam_stats_host
+ * (stats_host.cpp): a plain loop on one thread and the same formatter; the same bytes.  starts / n_starts: as for the sort.  command:
+ * the text of the second line, NULL: empty.
+ * URMAPX_E_ARG: a name that is empty or longer than 255 bytes, 2^31 records or more; else the sort's codes. */
+typedef struct urmapx_stats_result {
+	char *text;              /* the text (malloc; not terminated) */
+	size_t text_bytes;
+	uint64_t records, reads, mapped, properly_paired, duplicated, insert_median;  /* the SN lines of those names */
+	uint64_t stage_chunks;   /* urmapx_bam_stats: staged chunks of its pass over the input */
+	uint64_t least_budget;   /* urmapx_bam_sort_with under URMAPX_E_NOMEM from the budget: the least budget_bytes that holds the call */
+	double alloc_s, count_s, format_s;  /* device tables; staging and stats_count_kernel (host: the loop); tables back and the text */
+} urmapx_stats_result;
+int urmapx_bam_stats(int device, const void *records, size_t n_bytes, uint32_t n_ref, const char *const *names, const uint32_t *lens,
+                     const uint64_t *starts, size_t n_starts, const char *command, urmapx_stats_result *out);
+int urmapx_bam_stats_host(const void *records, size_t n_bytes, uint32_t n_ref, const char *const *names, const uint32_t *lens,
+                          const uint64_t *starts, size_t n_starts, const char *command, urmapx_stats_result *out);
+void urmapx_stats_free(urmapx_stats_result *);
+/* device bytes of the statistics' tables: what they add to the planned sort (the sum the allocation follows: stats.h) */
+uint64_t urmapx_bam_stats_resident_bytes(uint32_t n_ref);
+/* The planned sort with what is taken on the way.  md NULL: no marking.  depth NULL: no depth (dopts unused).  stats NULL: no
+ * statistics (stats_command unused).  names and lens: needed with depth or stats.  With neither this is urmapx_bam_sort_external, with
+ * depth alone urmapx_bam_sort_depth.  The statistics are taken where the depth is -- in core by one launch over the unsorted records
+ * once the marking has decided, on the external road on the chunks of the first placing pass -- and their tables come off the budget
+ * with the depth's before the sort is planned; under URMAPX_E_NOMEM from the budget both results' least_budget name the least budget
+ * that holds the call.  _host: the host sort (with marking when md is given) and the host versions on its records. */
+typedef struct urmapx_bam_sort_extras {
+	urmapx_markdup_stats *md;
+	const urmapx_depth_opts *dopts;
+	const char *const *names;
+	const uint32_t *lens;
+	urmapx_depth_result *depth;
+	urmapx_stats_result *stats;
+	const char *stats_command;
+} urmapx_bam_sort_extras;
+int urmapx_bam_sort_with(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
+                         const uint64_t *starts, size_t n_starts, const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out);
+int urmapx_bam_sort_with_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
+                              size_t n_starts, const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out);
 
 const char *urmapx_strerror(int code);
 /* "gfx950" etc. of the ctx's device; NULL without a device */

@@ -47,6 +47,8 @@ EXPORTS = (
     "urmapx_bam_sort_plan_for", "urmapx_bam_sort_external",
     "urmapx_bam_depth", "urmapx_bam_depth_host", "urmapx_depth_free", "urmapx_bam_depth_device_bytes", "urmapx_bam_depth_resident_bytes",
     "urmapx_bam_sort_depth", "urmapx_bam_sort_depth_host", "urmapx_map_depth_summary",
+    "urmapx_bam_stats", "urmapx_bam_stats_host", "urmapx_stats_free", "urmapx_bam_stats_resident_bytes",
+    "urmapx_bam_sort_with", "urmapx_bam_sort_with_host",
     "urmapx_calmd", "urmapx_ref_span", "urmapx_sam_se_tags", "urmapx_sam_pe_tags", "urmapx_bam_se_tags", "urmapx_bam_pe_tags",
     "urmapx_read_group_id", "urmapx_sam_header_rg", "urmapx_bam_header_rg", "urmapx_index_fetch_spans", "urmapx_text_set_tags",
     "urmapx_text_tag_ms", "urmapx_tags_batch",
@@ -94,6 +96,11 @@ class MapOptionsDepth(C.Structure):
     _fields_ = MapOptionsSortMem._fields_ + [("depth_out", C.c_char_p), ("depth_mapq", C.c_uint32)]
 
 
+class MapOptionsStats(C.Structure):
+    """urmapx_map_options in full: MapOptionsDepth with stats_out appended.  map_files passes this one."""
+    _fields_ = MapOptionsDepth._fields_ + [("stats_out", C.c_char_p)]
+
+
 class TagOptions(C.Structure):
     _fields_ = [("tags", C.c_uint), ("rg_id", C.c_char_p), ("ref", C.c_void_p * 2)]
 
@@ -120,6 +127,12 @@ class MapReportSort(C.Structure):
 class MapReportDepth(C.Structure):
     """urmapx_map_report in full: MapReportSort with the depth's seconds and totals appended.  map_files passes this one."""
     _fields_ = MapReportSort._fields_ + [("depth_s", C.c_double), ("depth_runs", C.c_uint64), ("depth_covered", C.c_uint64), ("depth_bases", C.c_uint64)]
+
+
+class MapReportStats(C.Structure):
+    """urmapx_map_report in full: MapReportDepth with the statistics' seconds and totals appended.  map_files passes this one."""
+    _fields_ = MapReportDepth._fields_ + [("stats_s", C.c_double), ("stats_reads", C.c_uint64), ("stats_mapped", C.c_uint64),
+                                          ("stats_properly_paired", C.c_uint64), ("stats_duplicated", C.c_uint64), ("stats_insert_median", C.c_uint64)]
 
 
 class BamSortResult(C.Structure):
@@ -158,6 +171,18 @@ class DepthResult(C.Structure):
 class ValidateReport(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("slots", "heads", "positions", "used", "reached", "bad_hash", "bad_pos", "bad_link", "bad_len",
                                           "first_bad_slot")] + [("seconds", C.c_double)]
+
+
+class StatsResult(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("text_bytes", C.c_size_t), ("records", C.c_uint64), ("reads", C.c_uint64), ("mapped", C.c_uint64),
+                ("properly_paired", C.c_uint64), ("duplicated", C.c_uint64), ("insert_median", C.c_uint64), ("stage_chunks", C.c_uint64),
+                ("least_budget", C.c_uint64), ("alloc_s", C.c_double), ("count_s", C.c_double), ("format_s", C.c_double)]
+
+
+class BamSortExtras(C.Structure):
+    """urmapx_bam_sort_extras: what urmapx_bam_sort_with takes on the way"""
+    _fields_ = [("md", C.POINTER(MarkdupStats)), ("dopts", C.POINTER(DepthOpts)), ("names", C.POINTER(C.c_char_p)), ("lens", C.c_void_p),
+                ("depth", C.POINTER(DepthResult)), ("stats", C.POINTER(StatsResult)), ("stats_command", C.c_char_p)]
 
 
 STATS_FIELDS = ("word_length", "max_ix", "seqdata_size", "slots", "indexed", "not_indexed", "wildcard", "indexed2", "free", "collision",
@@ -263,7 +288,7 @@ def lib():
     L.urmapx_ctx_get_pair_info.argtypes = [vp, vp, u32]
     L.urmapx_tab_pe.restype = C.c_size_t
     L.urmapx_tab_pe.argtypes = [vp, vp, vp, vp, cp, u32, u32, i32, vp, C.c_size_t]
-    L.urmapx_map_files.argtypes = [vp, C.POINTER(MapOptionsDepth), cp, cp, cp, cp, C.POINTER(MapReportDepth), cp, C.c_size_t]
+    L.urmapx_map_files.argtypes = [vp, C.POINTER(MapOptionsStats), cp, cp, cp, cp, C.POINTER(MapReportStats), cp, C.c_size_t]
     L.urmapx_map_depth_summary.argtypes = []
     L.urmapx_map_depth_summary.restype = C.c_char_p
     L.urmapx_host_pool_trim.argtypes = []
@@ -686,7 +711,8 @@ def gunzip_file(gz_path, out_path, threads=0):
 
 def map_files(index: "Index", fastq1, fastq2=None, samout=None, tabout=None, first_gpu=0, gpus=1, streams=2, host_threads=0,
               batch=0, veryfast=False, minq=10, cmdline=None, allow_unsupported=False, sam_shards=0, discard_sam=False, bgzf=False, bam=False,
-              bam_sort=False, tags=0, read_group=None, markdup=False, sort_mem=0, depth_out=None, depth_mapq=0):
+              bam_sort=False, tags=0, read_group=None, markdup=False, sort_mem=0, depth_out=None, depth_mapq=0,
+              stats_out=None):
     """urmap -map / -map2 file to file (cmd_map / cmd_map2) on an index that has its host arrays or is resident on
     first_gpu.  bgzf: samout is a BGZF file (-bgzf).  bam: samout is a BAM file (-bamout).  bam_sort (with bam):
     its records in coordinate order, with the index samout + ".bai" beside it (-sort).  tags: TAG_* bits (-tags), read_group: an @RG line
@@ -694,19 +720,20 @@ def map_files(index: "Index", fastq1, fastq2=None, samout=None, tabout=None, fir
     the counters in the report.  sort_mem (with bam_sort): the device bytes the sort may take (-sortmem); records that do not fit them
     stream through the device, and the report's sort_partitions says in how many partitions.  depth_out (with bam_sort): a bedGraph
     file of the per-base depth of the records as written (-depth), depth_mapq: its least MAPQ (-depth_mapq); the report then holds
-    depth_s, depth_runs, depth_covered, depth_bases and, as depth_summary, the table per reference.  -> dict of State1::HitStats'
+    depth_s, depth_runs, depth_covered, depth_bases and, as depth_summary, the table per reference.  stats_out (with bam_sort): a text
+    file of the alignment statistics of the records as written (-stats); the report then holds stats_s and a few totals.  -> dict of State1::HitStats'
     counters and stage times."""
-    o = MapOptionsDepth(first_gpu, gpus, streams, host_threads, batch, int(veryfast), minq, cmdline.encode() if cmdline else None,
+    o = MapOptionsStats(first_gpu, gpus, streams, host_threads, batch, int(veryfast), minq, cmdline.encode() if cmdline else None,
                    int(sam_shards), int(discard_sam), int(bgzf), int(bam), int(bam_sort), int(tags),
                    (read_group.encode("latin-1") if isinstance(read_group, str) else read_group), int(markdup), int(sort_mem),
-                   os.fsencode(depth_out) if depth_out else None, int(depth_mapq))
-    rep = MapReportDepth()
+                   os.fsencode(depth_out) if depth_out else None, int(depth_mapq), os.fsencode(stats_out) if stats_out is not None else None)
+    rep = MapReportStats()
     err = C.create_string_buffer(1024)
     enc = lambda p: os.fsencode(p) if p else None
     rc = lib().urmapx_map_files(index.h, C.byref(o), enc(fastq1), enc(fastq2), enc(samout), enc(tabout), C.byref(rep), err, len(err))
     if rc != 0 and not (rc == E_UNSUPPORTED and allow_unsupported):
         raise UrmapxError(rc, "urmapx_map_files: " + err.value.decode("latin-1"))
-    out = {k: getattr(rep, k) for k, _ in MapReportDepth._fields_}
+    out = {k: getattr(rep, k) for k, _ in MapReportStats._fields_}
     if depth_out:
         out["depth_summary"] = lib().urmapx_map_depth_summary().decode("latin-1")
     return out
@@ -846,6 +873,88 @@ def _bam_sort_depth(fn_name, head, records, n_ref, in_front, report, starts, mar
     return out + (rep,) if report else out
 
 
+def _bam_stats(fn_name, head, records, n_ref, names, lens, command, report, starts):
+    src = np.frombuffer(bytes(records), dtype=np.uint8)
+    L = lib()
+    fn = getattr(L, fn_name)
+    fn.argtypes = ([C.c_int] * len(head) + [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.c_char_p, C.POINTER(StatsResult)])
+    L.urmapx_stats_free.argtypes = [C.POINTER(StatsResult)]
+    L.urmapx_stats_free.restype = None
+    nm, ln = _depth_refs(n_ref, names, lens)
+    st = np.ascontiguousarray(starts if starts is not None else [], dtype=np.uint64)
+    res = StatsResult()
+    cmd = command.encode("latin-1") if isinstance(command, str) else command
+    _check(fn(*head, src.ctypes.data if len(src) else None, len(src), int(n_ref), nm, ln.ctypes.data if len(ln) else None,
+              st.ctypes.data if len(st) else None, len(st), cmd, C.byref(res)), fn_name)
+    try:
+        text = C.string_at(res.text, res.text_bytes) if res.text_bytes else b""
+        return (text, {k: getattr(res, k) for k, _ in StatsResult._fields_ if k != "text"}) if report else text
+    finally:
+        L.urmapx_stats_free(C.byref(res))
+
+
+def bam_stats(records: bytes, n_ref, names, lens, device=0, command=None, report=False, starts=None):
+    """BAM alignment records back to back, in any order, and the references' names and lengths -> the text of their alignment
+    statistics (include/urmapx.h "Stats"), counted on the device (urmapx_bam_stats; stats.hip).  command: the text of the second
+    line.  report: (text, the call's totals and step times)."""
+    return _bam_stats("urmapx_bam_stats", (int(device),), records, n_ref, names, lens, command, report, starts)
+
+
+def bam_stats_host(records: bytes, n_ref, names, lens, command=None, report=False, starts=None):
+    """the same contract on the host, no device (urmapx_bam_stats_host; stats_host.cpp)"""
+    return _bam_stats("urmapx_bam_stats_host", (), records, n_ref, names, lens, command, report, starts)
+
+
+def bam_stats_resident_bytes(n_ref):
+    """device bytes the statistics add to the planned sort (host arithmetic)"""
+    L = lib()
+    L.urmapx_bam_stats_resident_bytes.argtypes = [C.c_uint32]
+    L.urmapx_bam_stats_resident_bytes.restype = C.c_uint64
+    return int(L.urmapx_bam_stats_resident_bytes(int(n_ref)))
+
+
+def _bam_sort_with(fn_name, head, records, n_ref, in_front, report, starts, markdup, depth, depth_mapq, stats):
+    """the planned sort with the depth and the statistics taken on the way (urmapx_bam_sort_with, urmapx_bam_sort_with_host) ->
+    (members, bai[, depth result], stats text[, report]); the report holds the depth's fields as depth_* and the statistics' as stats_*"""
+    src = np.frombuffer(bytes(records), dtype=np.uint8)
+    L = lib()
+    fn = getattr(L, fn_name)
+    fn.argtypes = ([C.c_int, C.c_uint64][:len(head)] + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(BamSortExtras),
+                                                       C.POINTER(BamSortResult)])
+    for free, kind in (("urmapx_bam_sort_free", BamSortResult), ("urmapx_depth_free", DepthResult), ("urmapx_stats_free", StatsResult)):
+        getattr(L, free).argtypes = [C.POINTER(kind)]
+        getattr(L, free).restype = None
+    nm, ln = _depth_refs(n_ref, *(depth if depth is not None else stats))
+    st = np.ascontiguousarray(starts if starts is not None else [], dtype=np.uint64)
+    res, md, dres, sres, opts = BamSortResult(), MarkdupStats(), DepthResult(), StatsResult(), DepthOpts(int(depth_mapq))
+    ex = BamSortExtras(C.pointer(md) if markdup else None, C.pointer(opts), nm, ln.ctypes.data if len(ln) else None,
+                       C.pointer(dres) if depth is not None else None, C.pointer(sres) if stats is not None else None, None)
+    rc = fn(*head, src.ctypes.data if len(src) else None, len(src), int(n_ref), int(in_front), st.ctypes.data if len(st) else None, len(st),
+            C.byref(ex), C.byref(res))
+    if rc != 0:
+        least = int(sres.least_budget or dres.least_budget)
+        e = UrmapxError(rc, fn_name + (": %d bytes are needed at the least" % least if least else ""))
+        e.least_budget = least
+        raise e
+    try:
+        out = (C.string_at(res.bgzf, res.bgzf_bytes) if res.bgzf_bytes else b"", C.string_at(res.bai, res.bai_bytes))
+        rep = {k: getattr(res, k) for k, _ in BamSortResult._fields_ if k not in ("bgzf", "bai")}
+        if markdup:
+            rep.update({k: getattr(md, k) for k, _ in MarkdupStats._fields_})
+        if depth is not None:
+            out += (_depth_out(dres, False),)
+            rep.update({"depth_" + k: getattr(dres, k) for k, _ in DepthResult._fields_ if k not in ("text", "refs")})
+        if stats is not None:
+            out += (C.string_at(sres.text, sres.text_bytes) if sres.text_bytes else b"",)
+            rep.update({"stats_" + k: getattr(sres, k) for k, _ in StatsResult._fields_ if k != "text"})
+    finally:
+        L.urmapx_bam_sort_free(C.byref(res))
+        L.urmapx_depth_free(C.byref(dres))
+        L.urmapx_stats_free(C.byref(sres))
+    return out + (rep,) if report else out
+
+
 def _bam_sort(fn_name, head, records, n_ref, in_front, report, starts=None, markdup=False, budget=None):
     src = np.frombuffer(bytes(records), dtype=np.uint8)
     res = BamSortResult()
@@ -891,7 +1000,8 @@ def bam_sort_plan(n_bytes, n_records, budget, markdup=False):
     return plan
 
 
-def bam_sort(records: bytes, n_ref, device=0, bytes_in_front=0, report=False, starts=None, markdup=False, budget=None, depth=None, depth_mapq=0):
+def bam_sort(records: bytes, n_ref, device=0, bytes_in_front=0, report=False, starts=None, markdup=False, budget=None, depth=None, depth_mapq=0,
+             stats=None):
     """BAM alignment records back to back -> (the records in coordinate order as BGZF members, the bytes of their .bai index), sorted on
     the device (urmapx_bam_sort; bam_sort.hip).  bytes_in_front: what the file holds in front of the first member, for the index's
     virtual offsets.  report: a third item, the call's counters and step times.  starts: offsets at which records are known to begin (the
@@ -901,16 +1011,22 @@ def bam_sort(records: bytes, n_ref, device=0, bytes_in_front=0, report=False, st
     budget; the report's external, partitions, stage_chunks and stage_s say what it did.  depth=(names, lens) of the n_ref references:
     the call is urmapx_bam_sort_depth (budget None: 0), the per-base depth of the records as written -- under markdup without the
     duplicates -- is taken while they are on the device, and a third item (text, runs, summaries) comes back, as from bam_depth;
-    depth_mapq: its least MAPQ."""
+    depth_mapq: its least MAPQ.  stats=(names, lens): the call is urmapx_bam_sort_with, the alignment statistics of the records as
+    written are counted where the depth is taken, and their text comes back as one more item behind the depth's (as from bam_stats)."""
+    if stats is not None:
+        return _bam_sort_with("urmapx_bam_sort_with", (int(device), int(budget or 0)), records, n_ref, bytes_in_front, report, starts, markdup, depth,
+                              depth_mapq, stats)
     if depth is not None:
         return _bam_sort_depth("urmapx_bam_sort_depth", (int(device), int(budget or 0)), records, n_ref, bytes_in_front, report, starts, markdup, depth,
                                depth_mapq)
     return _bam_sort("urmapx_bam_sort", (int(device),), records, n_ref, bytes_in_front, report, starts, markdup, budget)
 
 
-def bam_sort_host(records: bytes, n_ref, bytes_in_front=0, report=False, starts=None, markdup=False, depth=None, depth_mapq=0):
+def bam_sort_host(records: bytes, n_ref, bytes_in_front=0, report=False, starts=None, markdup=False, depth=None, depth_mapq=0, stats=None):
     """the same contract on the host, no device (urmapx_bam_sort_host, urmapx_bam_sort_markdup_host): std::stable_sort and zlib inside
-    the BGZF framing.  depth: as for bam_sort (urmapx_bam_sort_depth_host)"""
+    the BGZF framing.  depth, stats: as for bam_sort (urmapx_bam_sort_depth_host, urmapx_bam_sort_with_host)"""
+    if stats is not None:
+        return _bam_sort_with("urmapx_bam_sort_with_host", (), records, n_ref, bytes_in_front, report, starts, markdup, depth, depth_mapq, stats)
     if depth is not None:
         return _bam_sort_depth("urmapx_bam_sort_depth_host", (), records, n_ref, bytes_in_front, report, starts, markdup, depth, depth_mapq)
     return _bam_sort("urmapx_bam_sort_host", (), records, n_ref, bytes_in_front, report, starts, markdup)

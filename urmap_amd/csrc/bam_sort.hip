@@ -24,6 +24,7 @@
 //                    copies the part of every staged record that falls into the partition to its place, as gather_kernel copies
 #include "bam_sort_dev.h"
 #include "depth_dev.h"
+#include "stats_dev.h"
 
 #include <algorithm>
 #include <chrono>
@@ -422,6 +423,14 @@ struct DepthAsk {
 	urmapx_depth_result *out;
 };
 
+// what the statistics add to it (include/urmapx.h "Stats"); names and lens are checked
+struct StatsAsk {
+	const char *const *names;
+	const uint32_t *lens;
+	const char *command;
+	urmapx_stats_result *out;
+};
+
 // adds the time from where it is made to the end of its scope
 struct Span {
 	double &to;
@@ -450,6 +459,7 @@ struct DeviceSort {
 	const size_t n_starts;
 	urmapx_markdup_stats *const md;
 	const DepthAsk *const dep;
+	const StatsAsk *const sta;
 	urmapx_bam_sort_result *const out;
 	size_t n_ref1() const { return (size_t)n_ref + 1; }
 	bool look() const { return md != nullptr; }  // the marking compares neighbours: a staged chunk is followed by its successor
@@ -463,7 +473,7 @@ struct DeviceSort {
 	urmapx_bam_sort_plan P{};
 	std::vector<uint32_t> cut;
 	bool ext = false;
-	uint64_t depth_bytes = 0, sort_budget = 0;
+	uint64_t depth_bytes = 0, stats_bytes = 0, sort_budget = 0;
 
 	// ---- the device arrays, in the order they are allocated (external_device_bytes counts them in this order) ----
 	// What each holds, stage by stage; "free" means any later stage may take it.
@@ -489,6 +499,7 @@ struct DeviceSort {
 	Dev<Chunk> d_chunks;
 	MarkdupOwn W;
 	urx::depth::DepthOwn DW;
+	urx::stats::StatsOwn SW;
 	StageStreams st;
 	IndexArrays X;
 	// ---- the arrays' later names; each is given in one place ----
@@ -508,7 +519,8 @@ struct DeviceSort {
 	int run() {
 		int rc;
 		if ((rc = scan_chain()) || (rc = choose_road()) || (rc = allocate()) || (rc = upload()) || (rc = sort_by_coordinate()) || (rc = destinations()) ||
-		    (rc = index_arrays()) || (rc = mark_duplicates()) || (rc = depth_in_core()) || (rc = sorted_stream()))
+		    (rc = index_arrays()) || (rc = mark_duplicates()) || (rc = depth_in_core()) || (rc = stats_in_core()) ||
+		    (rc = sorted_stream()))
 			return rc;
 		return finish();
 	}
@@ -525,10 +537,12 @@ struct DeviceSort {
 		return URMAPX_OK;
 	}
 
-	// the plan for staged chunks of `stage` bytes; where nothing fits, the least budget is the depth arrays' and the plan's
+	// the plan for staged chunks of `stage` bytes; where nothing fits, the least budget is the depth arrays', the statistics' tables'
+	// and the plan's
 	int plan(uint64_t stage) {
 		const int r = plan_with_stage(n_bytes, n, md != nullptr, sort_budget, stage, &P);
-		if (r == URMAPX_E_NOMEM && dep) dep->out->least_budget = depth_bytes + P.device_bytes;
+		if (r == URMAPX_E_NOMEM && dep) dep->out->least_budget = depth_bytes + stats_bytes + P.device_bytes;
+		if (r == URMAPX_E_NOMEM && sta) sta->out->least_budget = depth_bytes + stats_bytes + P.device_bytes;
 		return r;
 	}
 	// The road.  On the external one the staged chunks, under marking each with the next chunk's first record behind it (first_kernel
@@ -536,9 +550,10 @@ struct DeviceSort {
 	// successor, makes the buffers grow, and the partition is planned again around them
 	int choose_road() {
 		if (budget) {
-			// the depth arrays come off the budget before the sort is planned
+			// the depth arrays and the statistics' tables come off the budget before the sort is planned
 			depth_bytes = dep ? urx::depth::resident_bytes(dep->entries, n_ref, urx::depth::text_runs()) : 0u;
-			sort_budget = *budget > depth_bytes ? *budget - depth_bytes : 0u;
+			stats_bytes = sta ? urx::stats::resident_bytes(n_ref) : 0u;
+			sort_budget = *budget > depth_bytes + stats_bytes ? *budget - depth_bytes - stats_bytes : 0u;
 			if (const int rc = plan(default_stage_bytes(n_bytes))) return rc;
 			if (P.external) {
 				uint64_t need = 0;
@@ -569,6 +584,12 @@ struct DeviceSort {
 			const double a0 = t_alloc_s;
 			if ((rc = DW.begin(n_ref, dep->names, dep->lens, dep->entries))) return rc;
 			dep->out->alloc_s = t_alloc_s - a0;
+		}
+		if (sta) {
+			if (n >= 0x7FFFFFFFu) return URMAPX_E_ARG;
+			const double a0 = t_alloc_s;
+			if ((rc = SW.begin(n_ref))) return rc;
+			sta->out->alloc_s = t_alloc_s - a0;
 		}
 		if (ext) {  // (the pieces external_device_bytes counts, in its order; the partition is not larger than the stream)
 			const size_t part_cap = (size_t)std::min<uint64_t>(P.partition_bytes, n_bytes);
@@ -745,6 +766,16 @@ struct DeviceSort {
 		return URMAPX_OK;
 	}
 
+	// the statistics, in core: beside the depth, on the same records
+	int stats_in_core() {
+		if (!sta || ext) return URMAPX_OK;
+		Span span(sta->out->count_s);
+		if (const int rc = urx::stats::stats_count(SW, d_rec.p, 0, d_off.p, 0, n, nullptr, nullptr)) return rc;
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(nullptr));
+		return URMAPX_OK;
+	}
+
 	// the sorted stream, a slice at a time: into order, deflate, copy back
 	int sorted_stream() {
 		slice_bytes = (size_t)slice_members() * MEMBER;
@@ -800,11 +831,13 @@ struct DeviceSort {
 		const uint8_t *const action = md ? d_action.p : nullptr;
 		for (uint64_t p0 = 0; p0 < n_bytes; p0 += P.partition_bytes) {
 			const uint64_t p1 = p0 + P.partition_bytes < n_bytes ? p0 + P.partition_bytes : n_bytes;
-			// (every record crosses the device in each of these passes: the depth is taken in the first one only)
-			const bool count = dep && p0 == 0;
+			// (every record crosses the device in each of these passes: the depth and the statistics are taken in the first one only)
+			const bool count = dep && p0 == 0, tally = sta && p0 == 0;
 			int r = pass(false, [&](const uint8_t *at, uint64_t base, uint32_t i0, uint32_t i1, hipStream_t s) -> int {
 				hipLaunchKernelGGL(place_kernel, dim3(grid_for(i1 - i0)), dim3(NT), 0, s, at, base, d_off.p, i0, i1, place, action, p0, p1, d_part.p);
-				return count ? urx::depth::depth_count(DW, at, base, d_off.p, i0, i1, action, dep->min_mapq, s) : URMAPX_OK;
+				if (count)
+					if (const int e = urx::depth::depth_count(DW, at, base, d_off.p, i0, i1, action, dep->min_mapq, s)) return e;
+				return tally ? urx::stats::stats_count(SW, at, base, d_off.p, i0, i1, action, s) : URMAPX_OK;
 			});
 			if (r) return r;
 			for (uint64_t s0 = p0; s0 < p1; s0 += slice_bytes) {
@@ -815,10 +848,14 @@ struct DeviceSort {
 		return URMAPX_OK;
 	}
 
-	// the depth's result, then the sort's: the members trimmed to their size and handed to finish_result, which owns them from there
+	// the depth's result and the statistics', then the sort's: the members trimmed to their size and handed to finish_result, which owns them from there
 	int finish() {
 		if (dep)
 			if (const int rc = urx::depth::depth_finish(DW, dep->out)) return rc;
+		if (sta) {
+			sta->out->records = n;
+			if (const int rc = urx::stats::stats_finish(SW, sta->names, sta->lens, sta->command, sta->out)) return rc;
+		}
 		if (uint8_t *fit = (uint8_t *)realloc(z.get(), z_bytes ? z_bytes : 1)) {
 			(void)z.release();
 			z.reset(fit);
@@ -842,7 +879,8 @@ uint64_t urmapx_bam_sort_markdup_device_bytes(size_t n_bytes, uint64_t n_records
 }
 
 static int sort_entry(int device, const uint64_t *budget, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
-                      size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out, const DepthAsk *dep = nullptr) {
+                      size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out, const DepthAsk *dep = nullptr,
+                      const StatsAsk *sta = nullptr) {
 	if (!out || (n_bytes && !records) || (n_starts && !starts)) return URMAPX_E_ARG;
 	memset(out, 0, sizeof *out);
 	if (md) memset(md, 0, sizeof *md);
@@ -858,13 +896,14 @@ static int sort_entry(int device, const uint64_t *budget, const void *records, s
 			HIP_TRY(hipMemGetInfo(&free_b, &total_b));
 			have = free_b > URMAPX_SORT_HEADROOM ? (uint64_t)free_b - URMAPX_SORT_HEADROOM : 1u;
 		}
-		rc = DeviceSort{device, budget ? &have : nullptr, (const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, dep, out}.run();
+		rc = DeviceSort{device, budget ? &have : nullptr, (const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, dep, sta, out}.run();
 	} catch (const std::bad_alloc &) {
 		rc = URMAPX_E_NOMEM;
 	}
 	out->alloc_s = t_alloc_s;  // (the arrays are freed by now)
 	if (rc) urmapx_bam_sort_free(out);
 	if (rc && dep) urmapx_depth_free(dep->out);
+	if (rc && sta) urmapx_stats_free(sta->out);
 	return rc;
 }
 
@@ -887,11 +926,22 @@ int urmapx_bam_sort_external(int device, uint64_t budget_bytes, const void *reco
 int urmapx_bam_sort_depth(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
                           const uint64_t *starts, size_t n_starts, urmapx_markdup_stats *md, const urmapx_depth_opts *dopts,
                           const char *const *names, const uint32_t *lens, urmapx_depth_result *depth, urmapx_bam_sort_result *out) {
-	if (!depth) return sort_entry(device, &budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
-	memset(depth, 0, sizeof *depth);
-	DepthAsk ask{dopts ? dopts->min_mapq : 0u, names, lens, 0, depth};
-	if (const int rc = urx::depth::check_refs(n_ref, names, lens, &ask.entries)) return rc;
-	return sort_entry(device, &budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out, &ask);
+	const urmapx_bam_sort_extras extras{md, dopts, names, lens, depth, nullptr, nullptr};
+	return urmapx_bam_sort_with(device, budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, &extras, out);
+}
+
+int urmapx_bam_sort_with(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
+                         const uint64_t *starts, size_t n_starts, const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out) {
+	const urmapx_bam_sort_extras none{};
+	const urmapx_bam_sort_extras &E = extras ? *extras : none;
+	if (!E.depth && !E.stats) return sort_entry(device, &budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, E.md, out);
+	if (E.depth) memset(E.depth, 0, sizeof *E.depth);
+	if (E.stats) memset(E.stats, 0, sizeof *E.stats);
+	DepthAsk dask{E.dopts ? E.dopts->min_mapq : 0u, E.names, E.lens, 0, E.depth};
+	const StatsAsk sask{E.names, E.lens, E.stats_command, E.stats};
+	if (const int rc = urx::depth::check_refs(n_ref, E.names, E.lens, &dask.entries)) return rc;
+	return sort_entry(device, &budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, E.md, out, E.depth ? &dask : nullptr,
+	                  E.stats ? &sask : nullptr);
 }
 
 }  // extern "C"

@@ -168,21 +168,8 @@ int urmapx_bam_depth_host(const void *records, size_t n_bytes, uint32_t n_ref, c
 int urmapx_bam_sort_depth_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts, size_t n_starts,
                                urmapx_markdup_stats *md, const urmapx_depth_opts *dopts, const char *const *names, const uint32_t *lens,
                                urmapx_depth_result *depth, urmapx_bam_sort_result *out) {
-	if (!depth) {
-		return md ? urmapx_bam_sort_markdup_host(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out)
-		          : urmapx_bam_sort_host(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, out);
-	}
-	memset(depth, 0, sizeof *depth);
-	uint64_t entries = 0;
-	int rc = check_refs(n_ref, names, lens, &entries);
-	if (rc) return rc;
-	// the flags as written: the marking's decisions beside the records as they came (order does not matter to the depth)
-	const urx::bamsort::AfterMark hook = [&](const uint8_t *rec, const std::vector<uint64_t> &offs, const uint8_t *action) {
-		return offs.size() - 1 >= 0x7FFFFFFFu ? URMAPX_E_ARG : depth_host(rec, offs, action, n_ref, names, lens, dopts ? dopts->min_mapq : 0u, depth);
-	};
-	rc = urx::bamsort::sort_host_hooked(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out, hook);
-	if (rc) urmapx_depth_free(depth);
-	return rc;
+	const urmapx_bam_sort_extras extras{md, dopts, names, lens, depth, nullptr, nullptr};
+	return urmapx_bam_sort_with_host(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, &extras, out);
 }
 
 }  // extern "C"

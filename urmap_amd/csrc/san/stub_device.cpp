@@ -448,6 +448,36 @@ int urmapx_bam_sort_depth(int device, uint64_t budget, const void *records, size
 	if (rc == URMAPX_OK) { out->external = (uint32_t)plan.external; out->partitions = (uint32_t)plan.partitions; }
 	return rc;
 }
+// the statistics' stand-ins: the host version (stats_host.cpp); the planned sort with them keeps the refusal of a budget that does not
+// hold the depth arrays and the tables
+int urmapx_bam_stats(int, const void *records, size_t n_bytes, uint32_t n_ref, const char *const *names, const uint32_t *lens, const uint64_t *starts,
+                     size_t n_starts, const char *command, urmapx_stats_result *out) {
+	return urmapx_bam_stats_host(records, n_bytes, n_ref, names, lens, starts, n_starts, command, out);
+}
+int urmapx_bam_sort_with(int device, uint64_t budget, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts,
+                         size_t n_starts, const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out) {
+	const urmapx_bam_sort_extras none{};
+	const urmapx_bam_sort_extras &E = extras ? *extras : none;
+	if (!E.stats) return urmapx_bam_sort_depth(device, budget, records, n_bytes, n_ref, in_front, starts, n_starts, E.md, E.dopts, E.names, E.lens, E.depth, out);
+	if (E.depth) memset(E.depth, 0, sizeof *E.depth);
+	memset(E.stats, 0, sizeof *E.stats);
+	if (stub_sort_refuses("urmapx_bam_sort_with", &budget)) return URMAPX_E_NOMEM;
+	if (budget == 0) budget = ((uint64_t)200 << 30) - URMAPX_SORT_HEADROOM;  // (hipMemGetInfo above)
+	uint64_t columns = 0;
+	for (uint32_t r = 0; r < n_ref && E.lens; ++r) columns += E.lens[r];
+	const uint64_t own = (E.depth ? urmapx_bam_depth_resident_bytes(columns, n_ref) : 0u) + urmapx_bam_stats_resident_bytes(n_ref);
+	urmapx_bam_sort_plan plan;
+	if (const int rc = urmapx_bam_sort_plan_for(n_bytes, n_bytes / 200 + 1, E.md != nullptr, budget > own ? budget - own : 0u, &plan)) {
+		if (rc == URMAPX_E_NOMEM) {
+			E.stats->least_budget = own + plan.device_bytes;
+			if (E.depth) E.depth->least_budget = own + plan.device_bytes;
+		}
+		return rc;
+	}
+	const int rc = urmapx_bam_sort_with_host(records, n_bytes, n_ref, in_front, starts, n_starts, &E, out);
+	if (rc == URMAPX_OK) { out->external = (uint32_t)plan.external; out->partitions = (uint32_t)plan.partitions; }
+	return rc;
+}
 uint64_t urmapx_bam_sort_device_bytes(size_t n_bytes, uint64_t n_records) { return n_bytes + 48u * n_records; }
 uint64_t urmapx_bam_sort_markdup_device_bytes(size_t n_bytes, uint64_t n_records) { return n_bytes + 72u * n_records; }
 }

@@ -70,6 +70,8 @@ struct Opts {
 	std::string depth;     // -depth FILE: with -sort, a bedGraph file of the per-base depth of the records of the -bamout file
 	std::string depth_mapq;  // -depth_mapq N: with -depth, the least MAPQ of a record that counts
 	bool depth_given = false, depth_mapq_given = false;
+	std::string stats;     // -stats FILE: with -sort, a text file of the alignment statistics of the records of the -bamout file
+	bool stats_given = false;
 	std::string tags, rg;  // -tags NM,MD,AS and -rg '@RG\tID:..': optional fields of the records, the read group's header line
 	bool tags_given = false, rg_given = false;
 	bool trunclabels = false, wordlength_given = false;
@@ -137,6 +139,7 @@ static Opts parse(int argc, char **argv) {
 		else if (a == "-markdup") o.markdup = true;
 		else if (a == "-sortmem") { o.sortmem = val(); o.sortmem_given = true; }
 		else if (a == "-depth") { o.depth = val(); o.depth_given = true; }
+		else if (a == "-stats") { o.stats = val(); o.stats_given = true; }
 		else if (a == "-depth_mapq") { o.depth_mapq = val(); o.depth_mapq_given = true; }
 		else if (a == "-tags") { o.tags = val(); o.tags_given = true; }
 		else if (a == "-rg") { o.rg = val(); o.rg_given = true; }
@@ -257,6 +260,14 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 		if (o.depth == o.bamout || o.depth == o.bamout + ".bai") die("-depth %s: that is the -bamout file or its index; the depth needs a file of its own", o.depth.c_str());
 		if (stat(o.depth.c_str(), &st) == 0 && !S_ISREG(st.st_mode)) die("-depth needs a file name, not a pipe or %s: the file is written at the end of the run, in pieces", o.depth.c_str());
 	}
+	if (o.stats_given) {
+		struct stat st;
+		if (!o.sort) die("-stats needs -sort: the statistics are counted while the records of the -bamout file are sorted");
+		if (o.stats.empty()) die("-stats needs a file name");
+		if (o.stats == o.bamout || o.stats == o.bamout + ".bai" || (o.depth_given && o.stats == o.depth))
+			die("-stats %s: that is the -bamout file, its index or the -depth file; the statistics need a file of their own", o.stats.c_str());
+		if (stat(o.stats.c_str(), &st) == 0 && !S_ISREG(st.st_mode)) die("-stats needs a file name, not a pipe or %s: the file is written at the end of the run", o.stats.c_str());
+	}
 	if (o.sort) {
 		struct stat st;
 		if (!bam) die("-sort needs -bamout: it sorts the records of a BAM file");
@@ -300,6 +311,7 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 	mo.sort_mem = sort_mem;
 	mo.depth_out = o.depth_given ? o.depth.c_str() : nullptr;
 	mo.depth_mapq = depth_mapq;
+	mo.stats_out = o.stats_given ? o.stats.c_str() : nullptr;
 	urmapx_map_report rep;
 	memset(&rep, 0, sizeof rep);
 	char err[1024];
@@ -347,6 +359,10 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 			             o.depth.c_str(), (unsigned long long)rep.depth_covered, (unsigned long long)rep.depth_bases);
 			progress_log(q, "%s\n", urmapx_map_depth_summary());
 		}
+		if (o.stats_given)
+			progress_log(q, "%16.3f  Seconds for the statistics in %s: %llu reads, %llu mapped, %llu properly paired, %llu duplicated, median insert size %llu\n\n", rep.stats_s,
+			             o.stats.c_str(), (unsigned long long)rep.stats_reads, (unsigned long long)rep.stats_mapped, (unsigned long long)rep.stats_properly_paired,
+			             (unsigned long long)rep.stats_duplicated, (unsigned long long)rep.stats_insert_median);
 		if (o.markdup)
 			progress_log(q, "%16.3f  Seconds to mark duplicates: %llu of %llu pairs, %llu of %llu fragments\n\n", rep.markdup_s, (unsigned long long)rep.pairs_duplicate,
 			             (unsigned long long)rep.pairs_examined, (unsigned long long)rep.fragments_duplicate, (unsigned long long)rep.fragments_examined);
@@ -660,6 +676,8 @@ int main(int argc, char **argv) {
                 "      -depth FILE: with -sort, the per-base depth of the records as written (with -markdup: without the duplicates) as a\n"
                 "          bedGraph file, runs of depth 0 included, computed on the GPU beside the sort; a table per reference goes to the log\n"
                 "      -depth_mapq N: with -depth, records with a MAPQ below N do not count (0..255; default 0)\n"
+                "      -stats FILE: with -sort, the alignment statistics of the records as written -- counts by flag, MAPQ, read lengths, insert\n"
+                "          sizes, qualities and bases per cycle, GC, indels, reads per reference -- as a text file, counted on the GPU beside the sort\n"
                 "      -sortmem N[K|M|G]: with -sort, the GPU memory the sort may take; records that do not fit it stream through the GPU in partitions\n"
 	                "      -tags NM,MD,AS: these optional fields behind QUAL of every mapped record (any subset; computed on the GPU), SAM and BAM\n"
 	                "      -rg '@RG\\tID:x\\tSM:y': that line in the header in front of @PG and RG:Z:x on every record\n"
