@@ -454,6 +454,20 @@ typedef struct urmapx_map_options {
 	                     * what is free) with the depth's arrays before the sort is planned.  A few totals go to the report.  NULL: none.
 	                     * URMAPX_E_ARG without bam_sort, for an empty name and for a name that is samout's, its index's or depth_out's.
 	                     * A failed run removes the file with the others */
+	const char *vcf_out;   /* -vcfout (with bam_sort): a sites-only VCF 4.2 file of the columns where the records as the BAM file holds them --
+	                     * under markdup without the marked duplicates -- show a base other than the reference's (see "Pileup" below),
+	                     * counted on first_gpu where the depth is taken (urmapx_bam_sort_with2, on the host road urmapx_bam_sort_with2_host).
+	                     * The reference bases are the index's sequence store, read in place where it is resident on first_gpu and fetched
+	                     * once (urmapx_index_fetch_spans) where it is not.  Its ##urmapCommand line carries cmdline.  The BAM file and its
+	                     * index are those of the run without it but for the @PG line.  The counters (16 bytes a reference base) come off
+	                     * sort_mem (or off what is free) with the depth's and the statistics' arrays before the sort is planned.  NULL: none.
+	                     * URMAPX_E_ARG without bam_sort, for an empty name and for a name that is samout's, its index's, depth_out's or
+	                     * stats_out's.  A failed run removes the file with the others */
+	uint32_t vcf_mapq;     /* -vcf_mapq (with vcf_out): records with a MAPQ below it do not count; 0 .. 255 */
+	uint32_t vcf_baseq;    /* -vcf_baseq: bases with a quality below it do not count; 0 .. 255 */
+	uint32_t vcf_min_alt;  /* -vcf_min_alt: the least count of an alternative allele; 1 or more (URMAPX_E_ARG for 0 with vcf_out) */
+	uint32_t vcf_min_pct;  /* -vcf_min_pct: its least share of DP in per cent; 0 .. 100.  All four are taken as they stand: the defaults
+	                     * (0, 13, 3, 10) are the command line's and api.py's */
 } urmapx_map_options;
 typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:593-632) and where the time went */
 	uint64_t reads, mapped_q, mapped_lowq, unmapped, unsupported;
@@ -489,6 +503,9 @@ typedef struct urmapx_map_report {  /* State1::HitStats' counters (state1.cpp:59
 	uint64_t depth_runs, depth_covered, depth_bases; /* depth_out: lines of the file; columns with depth >= 1 and the sum of all depths, over all references */
 	double stats_s;                                  /* stats_out: the statistics' share of sort_s (their tables, the counting, the text and the file) */
 	uint64_t stats_reads, stats_mapped, stats_properly_paired, stats_duplicated, stats_insert_median;  /* stats_out: the SN lines of those names */
+	double pileup_s;                                 /* vcf_out: the pileup's share of sort_s (its counters, the counting, the sites, the text and the file) */
+	uint64_t pileup_sites;                           /* vcf_out: lines of the file behind its header */
+	uint64_t pileup_records, pileup_alt_alleles;     /* vcf_out: records that counted (rule 1); ALT entries over all lines (the log line's numbers) */
 } urmapx_map_report;
 /* fastq2 NULL: single-end (-map); else the mates' file (-map2 ... -reverse).  samout / tabout may be NULL.  The index
  * needs its host arrays, or to be resident on first_gpu already (the other devices' replicas are then copied from there).  Batch b is mapped on device
@@ -1019,6 +1036,93 @@ int urmapx_bam_sort_with(int device, uint64_t budget_bytes, const void *records,
                          const uint64_t *starts, size_t n_starts, const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out);
 int urmapx_bam_sort_with_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
                               size_t n_starts, const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out);
+
+/* ---- Pileup (SNV candidate sites of BAM records against the reference bases, as a sites-only VCF 4.2 text) ----
+ * The input is BAM records as above, in any order, the n_ref reference names and lengths (as for the depth) and the reference bases,
+ * lens[r] ASCII letters per reference.  Every rule is exact integer arithmetic and no count depends on the order of the records.
+ *  1. Which records count: exactly the depth's (items 1-2 of "Depth").  The record has a reference (0 <= refID < n_ref) and a position
+ *     (pos >= 0), none of the flags 0x704 as the file carries them -- inside urmapx_bam_sort_with2 under marking bit 0x400 is the
+ *     marking's decision, not the incoming bit (on the external road the action byte stands in) --, and its MAPQ is at least min_mapq
+ *     (default 0).  Supplementary records (0x800) count.  A record whose CIGAR, SEQ and QUAL do not lie inside its block_size counts
+ *     as a record and adds no base.
+ *  2. Which bases count.  The walk over the CIGAR keeps a query cursor (from 0) and a reference cursor (from pos).  M, = and X cover:
+ *     query base q lies on column x, and both cursors advance.  I and S advance the query cursor, D and N the reference cursor, H, P
+ *     and the unused op codes neither.  A base counts when its column is below l_ref, its query offset is below l_seq, its 4-bit code
+ *     is 1, 2, 4 or 8 (A, C, G, T) and its quality is at least min_baseq (default 13).  Every other code (N, IUPAC, =) counts nowhere.
+ *     A record with l_seq > 0 whose first QUAL byte is 0xFF has no qualities: all its bases pass.  Overlapping mates count twice, as
+ *     in the depth.
+ *  3. Per column: four counters cnt[A], cnt[C], cnt[G], cnt[T]; DP is their sum.  The reference letter is the sequence's byte, case
+ *     folded.  A column whose reference letter is not one of A C G T is never a site.  A base b other than the reference's is an
+ *     alternative allele when cnt[b] >= min_alt (default 3; at least 1) and cnt[b] * 100 >= min_pct * DP (min_pct 0 .. 100, default
+ *     10), both in 64-bit integers.  A column with at least one alternative allele is a site.
+ *  4. The text.  The header: "##fileformat=VCFv4.2", "##source=urmap", "##urmapCommand=" followed by the command text (empty for NULL),
+ *     one "##contig=<ID=name,length=l_ref>" per reference in index order,
+ *     "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Bases counted on the column\">",
+ *     "##INFO=<ID=AD,Number=R,Type=Integer,Description=\"Bases counted per allele, the reference's first\">" and
+ *     "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO".  Then one line per site, by reference in index order, then by position:
+ *       name \t pos+1 \t . \t REF \t ALT[,ALT..] \t . \t . \t DP=n;AD=ref,alt1[,alt2..]
+ *     REF is the folded letter; the alternative alleles stand by count descending, ties in the order A, C, G, T; numbers are decimal.
+ * Limits: the counters are uint32; 2^31 records or more are URMAPX_E_ARG, so none wraps.  All column arithmetic is 64 bits wide.
+ * The defaults are choices, not measurements: 13 is samtools mpileup's base-quality floor; 3 reads and 10 % keep single sequencing
+ * errors out at 30-fold coverage.  With min_baseq 0 and reads without N a site's DP is the depth of its column for the same MAPQ floor.
+ *
+ * urmapx_bam_pileup runs on `device` (pileup.hip): the sequences are uploaded (a byte a base), the records pass through two staging
+ * buffers in input order (URMAPX_TEST_SORT_STAGE=B) and pileup_count_kernel -- a persistent grid, a wavefront per record, the CIGAR 64
+ * ops a step, the covered bases 64 a step with one atomic add a lane (URMAPX_TEST_PILEUP_BLOCKS=N: at most N workgroups) -- counts
+ * them into one 16-byte entry per reference column.  The sites are found a segment of columns at a time (URMAPX_TEST_PILEUP_SEGMENT=N
+ * columns), compacted into entries of 24 bytes and copied back a slice at a time (URMAPX_TEST_PILEUP_SLICE=N entries) through two
+ * page-locked buffers; one host formatter writes the text.  urmapx_bam_pileup_host (pileup_host.cpp): a plain walk on one thread and
+ * the same formatter; the same bytes.  seqs[r]: lens[r] letters (may be NULL where lens[r] is 0).  opts NULL: the defaults.
+ * URMAPX_E_ARG: a name that is empty or longer than 255 bytes, a missing sequence, min_mapq or min_baseq above 255, min_alt 0, min_pct
+ * above 100, 2^31 records or more; else the sort's codes. */
+typedef struct urmapx_pileup_opts {
+	uint32_t min_mapq, min_baseq, min_alt, min_pct;
+} urmapx_pileup_opts;
+typedef struct urmapx_pileup_result {
+	char *text;              /* the text (malloc; not terminated) */
+	size_t text_bytes;
+	uint64_t sites, alt_alleles, records;  /* lines behind the header; ALT entries over all lines; records that counted (rule 1) */
+	uint64_t stage_chunks;   /* urmapx_bam_pileup: staged chunks of its pass over the input */
+	uint64_t least_budget;   /* urmapx_bam_sort_with2 under URMAPX_E_NOMEM from the budget: the least budget_bytes that holds the call */
+	double alloc_s, count_s, sites_s, format_s, copy_s;  /* device arrays; staging and pileup_count_kernel (host: the walk); the site
+	                          * kernels (host: the scan of the columns); the text; waiting for the slices' copies */
+} urmapx_pileup_result;
+int urmapx_bam_pileup(int device, const void *records, size_t n_bytes, uint32_t n_ref, const char *const *names, const uint32_t *lens,
+                      const uint8_t *const *seqs, const uint64_t *starts, size_t n_starts, const urmapx_pileup_opts *opts, const char *command,
+                      urmapx_pileup_result *out);
+int urmapx_bam_pileup_host(const void *records, size_t n_bytes, uint32_t n_ref, const char *const *names, const uint32_t *lens,
+                           const uint8_t *const *seqs, const uint64_t *starts, size_t n_starts, const urmapx_pileup_opts *opts,
+                           const char *command, urmapx_pileup_result *out);
+void urmapx_pileup_free(urmapx_pileup_result *);
+/* device bytes of the pileup's arrays: what they add to the planned sort (the sum the allocation follows: pileup.h).  seq_resident
+ * not 0: the reference bases are read in place (an index resident on the sort's device); 0: a byte a base more for their upload */
+uint64_t urmapx_bam_pileup_resident_bytes(uint64_t total_columns, uint32_t n_ref, int seq_resident);
+/* what urmapx_bam_pileup takes: those with the upload, the record starts and two staging buffers */
+uint64_t urmapx_bam_pileup_device_bytes(uint64_t total_columns, uint32_t n_ref, uint64_t n_records);
+/* urmapx_bam_sort_with with the pileup: the seven fields of urmapx_bam_sort_extras in their order, then the pileup's.  pileup NULL: no
+ * pileup, and the call is urmapx_bam_sort_with.  The reference bases: seqs (as above), or, with seqs NULL, index: its sequence store,
+ * read in place where it is resident on `device`, else fetched once through urmapx_index_fetch_spans and uploaded; its sequence count
+ * and lengths must be n_ref and lens (URMAPX_E_ARG).  The pileup is taken where the depth and the statistics are, and its arrays come
+ * off the budget with theirs; under URMAPX_E_NOMEM from the budget every result's least_budget names the least budget that holds the
+ * call.  _host: the host sort and the host versions on its records. */
+typedef struct urmapx_bam_sort_extras2 {
+	urmapx_markdup_stats *md;
+	const urmapx_depth_opts *dopts;
+	const char *const *names;
+	const uint32_t *lens;
+	urmapx_depth_result *depth;
+	urmapx_stats_result *stats;
+	const char *stats_command;
+	const urmapx_pileup_opts *popts;
+	const uint8_t *const *seqs;
+	const urmapx_index *index;
+	urmapx_pileup_result *pileup;
+	const char *pileup_command;
+} urmapx_bam_sort_extras2;
+int urmapx_bam_sort_with2(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
+                          const uint64_t *starts, size_t n_starts, const urmapx_bam_sort_extras2 *extras, urmapx_bam_sort_result *out);
+int urmapx_bam_sort_with2_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
+                               size_t n_starts, const urmapx_bam_sort_extras2 *extras, urmapx_bam_sort_result *out);
 
 const char *urmapx_strerror(int code);
 /* "gfx950" etc. of the ctx's device; NULL without a device */

@@ -49,6 +49,8 @@ EXPORTS = (
     "urmapx_bam_sort_depth", "urmapx_bam_sort_depth_host", "urmapx_map_depth_summary",
     "urmapx_bam_stats", "urmapx_bam_stats_host", "urmapx_stats_free", "urmapx_bam_stats_resident_bytes",
     "urmapx_bam_sort_with", "urmapx_bam_sort_with_host",
+    "urmapx_bam_pileup", "urmapx_bam_pileup_host", "urmapx_pileup_free", "urmapx_bam_pileup_resident_bytes", "urmapx_bam_pileup_device_bytes",
+    "urmapx_bam_sort_with2", "urmapx_bam_sort_with2_host",
     "urmapx_calmd", "urmapx_ref_span", "urmapx_sam_se_tags", "urmapx_sam_pe_tags", "urmapx_bam_se_tags", "urmapx_bam_pe_tags",
     "urmapx_read_group_id", "urmapx_sam_header_rg", "urmapx_bam_header_rg", "urmapx_index_fetch_spans", "urmapx_text_set_tags",
     "urmapx_text_tag_ms", "urmapx_tags_batch",
@@ -101,6 +103,12 @@ class MapOptionsStats(C.Structure):
     _fields_ = MapOptionsDepth._fields_ + [("stats_out", C.c_char_p)]
 
 
+class MapOptionsPileup(C.Structure):
+    """urmapx_map_options in full: MapOptionsStats with vcf_out and its four thresholds appended.  map_files passes this one."""
+    _fields_ = MapOptionsStats._fields_ + [("vcf_out", C.c_char_p), ("vcf_mapq", C.c_uint32), ("vcf_baseq", C.c_uint32), ("vcf_min_alt", C.c_uint32),
+                                           ("vcf_min_pct", C.c_uint32)]
+
+
 class TagOptions(C.Structure):
     _fields_ = [("tags", C.c_uint), ("rg_id", C.c_char_p), ("ref", C.c_void_p * 2)]
 
@@ -133,6 +141,11 @@ class MapReportStats(C.Structure):
     """urmapx_map_report in full: MapReportDepth with the statistics' seconds and totals appended.  map_files passes this one."""
     _fields_ = MapReportDepth._fields_ + [("stats_s", C.c_double), ("stats_reads", C.c_uint64), ("stats_mapped", C.c_uint64),
                                           ("stats_properly_paired", C.c_uint64), ("stats_duplicated", C.c_uint64), ("stats_insert_median", C.c_uint64)]
+
+
+class MapReportPileup(C.Structure):
+    """urmapx_map_report in full: MapReportStats with the pileup's seconds and totals appended.  map_files passes this one."""
+    _fields_ = MapReportStats._fields_ + [("pileup_s", C.c_double), ("pileup_sites", C.c_uint64), ("pileup_records", C.c_uint64), ("pileup_alt_alleles", C.c_uint64)]
 
 
 class BamSortResult(C.Structure):
@@ -183,6 +196,22 @@ class BamSortExtras(C.Structure):
     """urmapx_bam_sort_extras: what urmapx_bam_sort_with takes on the way"""
     _fields_ = [("md", C.POINTER(MarkdupStats)), ("dopts", C.POINTER(DepthOpts)), ("names", C.POINTER(C.c_char_p)), ("lens", C.c_void_p),
                 ("depth", C.POINTER(DepthResult)), ("stats", C.POINTER(StatsResult)), ("stats_command", C.c_char_p)]
+
+
+class PileupOpts(C.Structure):
+    _fields_ = [("min_mapq", C.c_uint32), ("min_baseq", C.c_uint32), ("min_alt", C.c_uint32), ("min_pct", C.c_uint32)]
+
+
+class PileupResult(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("text_bytes", C.c_size_t), ("sites", C.c_uint64), ("alt_alleles", C.c_uint64), ("records", C.c_uint64),
+                ("stage_chunks", C.c_uint64), ("least_budget", C.c_uint64), ("alloc_s", C.c_double), ("count_s", C.c_double), ("sites_s", C.c_double),
+                ("format_s", C.c_double), ("copy_s", C.c_double)]
+
+
+class BamSortExtras2(C.Structure):
+    """urmapx_bam_sort_extras2: BamSortExtras' fields, then the pileup's"""
+    _fields_ = BamSortExtras._fields_ + [("popts", C.POINTER(PileupOpts)), ("seqs", C.POINTER(C.c_char_p)), ("index", C.c_void_p),
+                                         ("pileup", C.POINTER(PileupResult)), ("pileup_command", C.c_char_p)]
 
 
 STATS_FIELDS = ("word_length", "max_ix", "seqdata_size", "slots", "indexed", "not_indexed", "wildcard", "indexed2", "free", "collision",
@@ -288,7 +317,7 @@ def lib():
     L.urmapx_ctx_get_pair_info.argtypes = [vp, vp, u32]
     L.urmapx_tab_pe.restype = C.c_size_t
     L.urmapx_tab_pe.argtypes = [vp, vp, vp, vp, cp, u32, u32, i32, vp, C.c_size_t]
-    L.urmapx_map_files.argtypes = [vp, C.POINTER(MapOptionsStats), cp, cp, cp, cp, C.POINTER(MapReportStats), cp, C.c_size_t]
+    L.urmapx_map_files.argtypes = [vp, C.POINTER(MapOptionsPileup), cp, cp, cp, cp, C.POINTER(MapReportPileup), cp, C.c_size_t]
     L.urmapx_map_depth_summary.argtypes = []
     L.urmapx_map_depth_summary.restype = C.c_char_p
     L.urmapx_host_pool_trim.argtypes = []
@@ -712,7 +741,7 @@ def gunzip_file(gz_path, out_path, threads=0):
 def map_files(index: "Index", fastq1, fastq2=None, samout=None, tabout=None, first_gpu=0, gpus=1, streams=2, host_threads=0,
               batch=0, veryfast=False, minq=10, cmdline=None, allow_unsupported=False, sam_shards=0, discard_sam=False, bgzf=False, bam=False,
               bam_sort=False, tags=0, read_group=None, markdup=False, sort_mem=0, depth_out=None, depth_mapq=0,
-              stats_out=None):
+              stats_out=None, vcf_out=None, vcf_mapq=0, vcf_baseq=13, vcf_min_alt=3, vcf_min_pct=10):
     """urmap -map / -map2 file to file (cmd_map / cmd_map2) on an index that has its host arrays or is resident on
     first_gpu.  bgzf: samout is a BGZF file (-bgzf).  bam: samout is a BAM file (-bamout).  bam_sort (with bam):
     its records in coordinate order, with the index samout + ".bai" beside it (-sort).  tags: TAG_* bits (-tags), read_group: an @RG line
@@ -721,19 +750,22 @@ def map_files(index: "Index", fastq1, fastq2=None, samout=None, tabout=None, fir
     stream through the device, and the report's sort_partitions says in how many partitions.  depth_out (with bam_sort): a bedGraph
     file of the per-base depth of the records as written (-depth), depth_mapq: its least MAPQ (-depth_mapq); the report then holds
     depth_s, depth_runs, depth_covered, depth_bases and, as depth_summary, the table per reference.  stats_out (with bam_sort): a text
-    file of the alignment statistics of the records as written (-stats); the report then holds stats_s and a few totals.  -> dict of State1::HitStats'
-    counters and stage times."""
-    o = MapOptionsStats(first_gpu, gpus, streams, host_threads, batch, int(veryfast), minq, cmdline.encode() if cmdline else None,
+    file of the alignment statistics of the records as written (-stats); the report then holds stats_s and a few totals.  vcf_out (with
+    bam_sort): a sites-only VCF file of the columns where the records as written differ from the index's sequences (-vcfout; include/urmapx.h
+    "Pileup"), vcf_mapq, vcf_baseq, vcf_min_alt, vcf_min_pct: its thresholds; the report then holds pileup_s, pileup_sites, pileup_records
+    and pileup_alt_alleles.  -> dict of State1::HitStats' counters and stage times."""
+    o = MapOptionsPileup(first_gpu, gpus, streams, host_threads, batch, int(veryfast), minq, cmdline.encode() if cmdline else None,
                    int(sam_shards), int(discard_sam), int(bgzf), int(bam), int(bam_sort), int(tags),
                    (read_group.encode("latin-1") if isinstance(read_group, str) else read_group), int(markdup), int(sort_mem),
-                   os.fsencode(depth_out) if depth_out else None, int(depth_mapq), os.fsencode(stats_out) if stats_out is not None else None)
-    rep = MapReportStats()
+                   os.fsencode(depth_out) if depth_out else None, int(depth_mapq), os.fsencode(stats_out) if stats_out is not None else None,
+                   os.fsencode(vcf_out) if vcf_out is not None else None, int(vcf_mapq), int(vcf_baseq), int(vcf_min_alt), int(vcf_min_pct))
+    rep = MapReportPileup()
     err = C.create_string_buffer(1024)
     enc = lambda p: os.fsencode(p) if p else None
     rc = lib().urmapx_map_files(index.h, C.byref(o), enc(fastq1), enc(fastq2), enc(samout), enc(tabout), C.byref(rep), err, len(err))
     if rc != 0 and not (rc == E_UNSUPPORTED and allow_unsupported):
         raise UrmapxError(rc, "urmapx_map_files: " + err.value.decode("latin-1"))
-    out = {k: getattr(rep, k) for k, _ in MapReportStats._fields_}
+    out = {k: getattr(rep, k) for k, _ in MapReportPileup._fields_}
     if depth_out:
         out["depth_summary"] = lib().urmapx_map_depth_summary().decode("latin-1")
     return out
@@ -955,6 +987,124 @@ def _bam_sort_with(fn_name, head, records, n_ref, in_front, report, starts, mark
     return out + (rep,) if report else out
 
 
+def _pileup_opts(opts):
+    """None (the library's defaults), a dict of min_mapq / min_baseq / min_alt / min_pct (those left out: 0, 13, 3, 10) or the four numbers"""
+    if opts is None:
+        return None
+    if isinstance(opts, dict):
+        opts = (opts.get("min_mapq", 0), opts.get("min_baseq", 13), opts.get("min_alt", 3), opts.get("min_pct", 10))
+    return PileupOpts(*[int(v) for v in opts])
+
+
+def _pileup_seqs(n_ref, seqs):
+    """one bytes object per reference -> char ** array (the caller keeps it alive over the call)"""
+    seqs = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in seqs]
+    if len(seqs) != int(n_ref):
+        raise ValueError("a sequence per reference is needed")
+    return (C.c_char_p * max(1, len(seqs)))(*seqs)
+
+
+def _bam_pileup(fn_name, head, records, n_ref, names, lens, seqs, opts, command, report, starts):
+    src = np.frombuffer(bytes(records), dtype=np.uint8)
+    L = lib()
+    fn = getattr(L, fn_name)
+    fn.argtypes = ([C.c_int] * len(head) + [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_size_t,
+                                            C.POINTER(PileupOpts), C.c_char_p, C.POINTER(PileupResult)])
+    L.urmapx_pileup_free.argtypes = [C.POINTER(PileupResult)]
+    L.urmapx_pileup_free.restype = None
+    nm, ln = _depth_refs(n_ref, names, lens)
+    sq = _pileup_seqs(n_ref, seqs)
+    st = np.ascontiguousarray(starts if starts is not None else [], dtype=np.uint64)
+    res, po = PileupResult(), _pileup_opts(opts)
+    cmd = command.encode("latin-1") if isinstance(command, str) else command
+    _check(fn(*head, src.ctypes.data if len(src) else None, len(src), int(n_ref), nm, ln.ctypes.data if len(ln) else None, sq,
+              st.ctypes.data if len(st) else None, len(st), C.byref(po) if po is not None else None, cmd, C.byref(res)), fn_name)
+    try:
+        text = C.string_at(res.text, res.text_bytes) if res.text_bytes else b""
+        return (text, {k: getattr(res, k) for k, _ in PileupResult._fields_ if k != "text"}) if report else text
+    finally:
+        L.urmapx_pileup_free(C.byref(res))
+
+
+def bam_pileup(records: bytes, n_ref, names, lens, seqs, opts=None, device=0, command=None, report=False, starts=None):
+    """BAM alignment records back to back, in any order, the references' names and lengths and their bases (one bytes object of ASCII
+    letters per reference) -> the sites-only VCF text of the columns where the reads show a base other than the reference's
+    (include/urmapx.h "Pileup"), piled up on the device (urmapx_bam_pileup; pileup.hip).  opts: None for the defaults, or a dict of
+    min_mapq, min_baseq, min_alt, min_pct.  command: the text of the ##urmapCommand line.  report: (text, the call's totals and times)."""
+    return _bam_pileup("urmapx_bam_pileup", (int(device),), records, n_ref, names, lens, seqs, opts, command, report, starts)
+
+
+def bam_pileup_host(records: bytes, n_ref, names, lens, seqs, opts=None, command=None, report=False, starts=None):
+    """the same contract on the host, no device (urmapx_bam_pileup_host; pileup_host.cpp)"""
+    return _bam_pileup("urmapx_bam_pileup_host", (), records, n_ref, names, lens, seqs, opts, command, report, starts)
+
+
+def bam_pileup_resident_bytes(total_columns, n_ref, seq_resident=False):
+    """device bytes the pileup adds to the planned sort (host arithmetic); seq_resident: the bases are an index's resident store"""
+    L = lib()
+    L.urmapx_bam_pileup_resident_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_int]
+    L.urmapx_bam_pileup_resident_bytes.restype = C.c_uint64
+    return int(L.urmapx_bam_pileup_resident_bytes(int(total_columns), int(n_ref), int(seq_resident)))
+
+
+def bam_pileup_device_bytes(total_columns, n_ref, n_records):
+    """device bytes urmapx_bam_pileup takes (host arithmetic)"""
+    L = lib()
+    L.urmapx_bam_pileup_device_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64]
+    L.urmapx_bam_pileup_device_bytes.restype = C.c_uint64
+    return int(L.urmapx_bam_pileup_device_bytes(int(total_columns), int(n_ref), int(n_records)))
+
+
+def _bam_sort_with2(fn_name, head, records, n_ref, in_front, report, starts, markdup, depth, depth_mapq, stats, pileup):
+    """the planned sort with the depth, the statistics and the pileup taken on the way (urmapx_bam_sort_with2, urmapx_bam_sort_with2_host)
+    -> (members, bai[, depth result][, stats text], VCF text[, report]); the report holds the pileup's fields as pileup_*.  pileup:
+    (names, lens, seqs, opts); seqs may be an Index, whose sequence store then gives the bases"""
+    src = np.frombuffer(bytes(records), dtype=np.uint8)
+    L = lib()
+    fn = getattr(L, fn_name)
+    fn.argtypes = ([C.c_int, C.c_uint64][:len(head)] + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(BamSortExtras2),
+                                                       C.POINTER(BamSortResult)])
+    for free, kind in (("urmapx_bam_sort_free", BamSortResult), ("urmapx_depth_free", DepthResult), ("urmapx_stats_free", StatsResult),
+                       ("urmapx_pileup_free", PileupResult)):
+        getattr(L, free).argtypes = [C.POINTER(kind)]
+        getattr(L, free).restype = None
+    names, lens, seqs, popts = pileup
+    nm, ln = _depth_refs(n_ref, names, lens)
+    index = seqs.h if isinstance(seqs, Index) else None
+    sq = None if index is not None else _pileup_seqs(n_ref, seqs)
+    st = np.ascontiguousarray(starts if starts is not None else [], dtype=np.uint64)
+    res, md, dres, sres, pres, opts, po = BamSortResult(), MarkdupStats(), DepthResult(), StatsResult(), PileupResult(), DepthOpts(int(depth_mapq)), _pileup_opts(popts)
+    ex = BamSortExtras2(C.pointer(md) if markdup else None, C.pointer(opts), nm, ln.ctypes.data if len(ln) else None,
+                        C.pointer(dres) if depth is not None else None, C.pointer(sres) if stats is not None else None, None,
+                        C.pointer(po) if po is not None else None, sq, index, C.pointer(pres), None)
+    rc = fn(*head, src.ctypes.data if len(src) else None, len(src), int(n_ref), int(in_front), st.ctypes.data if len(st) else None, len(st),
+            C.byref(ex), C.byref(res))
+    if rc != 0:
+        least = int(pres.least_budget or sres.least_budget or dres.least_budget)
+        e = UrmapxError(rc, fn_name + (": %d bytes are needed at the least" % least if least else ""))
+        e.least_budget = least
+        raise e
+    try:
+        out = (C.string_at(res.bgzf, res.bgzf_bytes) if res.bgzf_bytes else b"", C.string_at(res.bai, res.bai_bytes))
+        rep = {k: getattr(res, k) for k, _ in BamSortResult._fields_ if k not in ("bgzf", "bai")}
+        if markdup:
+            rep.update({k: getattr(md, k) for k, _ in MarkdupStats._fields_})
+        if depth is not None:
+            out += (_depth_out(dres, False),)
+            rep.update({"depth_" + k: getattr(dres, k) for k, _ in DepthResult._fields_ if k not in ("text", "refs")})
+        if stats is not None:
+            out += (C.string_at(sres.text, sres.text_bytes) if sres.text_bytes else b"",)
+            rep.update({"stats_" + k: getattr(sres, k) for k, _ in StatsResult._fields_ if k != "text"})
+        out += (C.string_at(pres.text, pres.text_bytes) if pres.text_bytes else b"",)
+        rep.update({"pileup_" + k: getattr(pres, k) for k, _ in PileupResult._fields_ if k != "text"})
+    finally:
+        L.urmapx_bam_sort_free(C.byref(res))
+        L.urmapx_depth_free(C.byref(dres))
+        L.urmapx_stats_free(C.byref(sres))
+        L.urmapx_pileup_free(C.byref(pres))
+    return out + (rep,) if report else out
+
+
 def _bam_sort(fn_name, head, records, n_ref, in_front, report, starts=None, markdup=False, budget=None):
     src = np.frombuffer(bytes(records), dtype=np.uint8)
     res = BamSortResult()
@@ -1001,7 +1151,7 @@ def bam_sort_plan(n_bytes, n_records, budget, markdup=False):
 
 
 def bam_sort(records: bytes, n_ref, device=0, bytes_in_front=0, report=False, starts=None, markdup=False, budget=None, depth=None, depth_mapq=0,
-             stats=None):
+             stats=None, pileup=None):
     """BAM alignment records back to back -> (the records in coordinate order as BGZF members, the bytes of their .bai index), sorted on
     the device (urmapx_bam_sort; bam_sort.hip).  bytes_in_front: what the file holds in front of the first member, for the index's
     virtual offsets.  report: a third item, the call's counters and step times.  starts: offsets at which records are known to begin (the
@@ -1012,7 +1162,13 @@ def bam_sort(records: bytes, n_ref, device=0, bytes_in_front=0, report=False, st
     the call is urmapx_bam_sort_depth (budget None: 0), the per-base depth of the records as written -- under markdup without the
     duplicates -- is taken while they are on the device, and a third item (text, runs, summaries) comes back, as from bam_depth;
     depth_mapq: its least MAPQ.  stats=(names, lens): the call is urmapx_bam_sort_with, the alignment statistics of the records as
-    written are counted where the depth is taken, and their text comes back as one more item behind the depth's (as from bam_stats)."""
+    written are counted where the depth is taken, and their text comes back as one more item behind the depth's (as from bam_stats).
+    pileup=(names, lens, seqs, opts): the call is urmapx_bam_sort_with2, the SNV candidate sites of the records as written are piled up
+    there too, and their VCF text comes back as the last item in front of the report (as from bam_pileup); seqs: a bytes object per
+    reference, or an Index, whose sequence store then gives the bases."""
+    if pileup is not None:
+        return _bam_sort_with2("urmapx_bam_sort_with2", (int(device), int(budget or 0)), records, n_ref, bytes_in_front, report, starts, markdup, depth,
+                               depth_mapq, stats, pileup)
     if stats is not None:
         return _bam_sort_with("urmapx_bam_sort_with", (int(device), int(budget or 0)), records, n_ref, bytes_in_front, report, starts, markdup, depth,
                               depth_mapq, stats)
@@ -1022,9 +1178,11 @@ def bam_sort(records: bytes, n_ref, device=0, bytes_in_front=0, report=False, st
     return _bam_sort("urmapx_bam_sort", (int(device),), records, n_ref, bytes_in_front, report, starts, markdup, budget)
 
 
-def bam_sort_host(records: bytes, n_ref, bytes_in_front=0, report=False, starts=None, markdup=False, depth=None, depth_mapq=0, stats=None):
+def bam_sort_host(records: bytes, n_ref, bytes_in_front=0, report=False, starts=None, markdup=False, depth=None, depth_mapq=0, stats=None, pileup=None):
     """the same contract on the host, no device (urmapx_bam_sort_host, urmapx_bam_sort_markdup_host): std::stable_sort and zlib inside
-    the BGZF framing.  depth, stats: as for bam_sort (urmapx_bam_sort_depth_host, urmapx_bam_sort_with_host)"""
+    the BGZF framing.  depth, stats, pileup: as for bam_sort (urmapx_bam_sort_depth_host, urmapx_bam_sort_with_host, urmapx_bam_sort_with2_host)"""
+    if pileup is not None:
+        return _bam_sort_with2("urmapx_bam_sort_with2_host", (), records, n_ref, bytes_in_front, report, starts, markdup, depth, depth_mapq, stats, pileup)
     if stats is not None:
         return _bam_sort_with("urmapx_bam_sort_with_host", (), records, n_ref, bytes_in_front, report, starts, markdup, depth, depth_mapq, stats)
     if depth is not None:

@@ -25,6 +25,7 @@
 #include "bam_sort_dev.h"
 #include "depth_dev.h"
 #include "stats_dev.h"
+#include "pileup_dev.h"
 
 #include <algorithm>
 #include <chrono>
@@ -431,6 +432,20 @@ struct StatsAsk {
 	urmapx_stats_result *out;
 };
 
+// what the pileup adds to it (include/urmapx.h "Pileup"); names, lens and the rule are checked.  The bases: seqs on the host, or, with
+// seqs null, d_store on the sort's device with reference r's letters from store_at[r] on
+struct PileupAsk {
+	urx::pileup::Rule R;
+	const char *const *names;
+	const uint32_t *lens;
+	uint64_t columns;
+	const uint8_t *const *seqs;
+	const uint8_t *d_store;
+	const uint64_t *store_at;
+	const char *command;
+	urmapx_pileup_result *out;
+};
+
 // adds the time from where it is made to the end of its scope
 struct Span {
 	double &to;
@@ -460,6 +475,7 @@ struct DeviceSort {
 	urmapx_markdup_stats *const md;
 	const DepthAsk *const dep;
 	const StatsAsk *const sta;
+	const PileupAsk *const pil;
 	urmapx_bam_sort_result *const out;
 	size_t n_ref1() const { return (size_t)n_ref + 1; }
 	bool look() const { return md != nullptr; }  // the marking compares neighbours: a staged chunk is followed by its successor
@@ -473,7 +489,7 @@ struct DeviceSort {
 	urmapx_bam_sort_plan P{};
 	std::vector<uint32_t> cut;
 	bool ext = false;
-	uint64_t depth_bytes = 0, stats_bytes = 0, sort_budget = 0;
+	uint64_t depth_bytes = 0, stats_bytes = 0, pileup_bytes = 0, sort_budget = 0;
 
 	// ---- the device arrays, in the order they are allocated (external_device_bytes counts them in this order) ----
 	// What each holds, stage by stage; "free" means any later stage may take it.
@@ -500,6 +516,7 @@ struct DeviceSort {
 	MarkdupOwn W;
 	urx::depth::DepthOwn DW;
 	urx::stats::StatsOwn SW;
+	urx::pileup::PileupOwn PW;
 	StageStreams st;
 	IndexArrays X;
 	// ---- the arrays' later names; each is given in one place ----
@@ -520,7 +537,7 @@ struct DeviceSort {
 		int rc;
 		if ((rc = scan_chain()) || (rc = choose_road()) || (rc = allocate()) || (rc = upload()) || (rc = sort_by_coordinate()) || (rc = destinations()) ||
 		    (rc = index_arrays()) || (rc = mark_duplicates()) || (rc = depth_in_core()) || (rc = stats_in_core()) ||
-		    (rc = sorted_stream()))
+		    (rc = pileup_in_core()) || (rc = sorted_stream()))
 			return rc;
 		return finish();
 	}
@@ -537,12 +554,14 @@ struct DeviceSort {
 		return URMAPX_OK;
 	}
 
-	// the plan for staged chunks of `stage` bytes; where nothing fits, the least budget is the depth arrays', the statistics' tables'
-	// and the plan's
+	// the plan for staged chunks of `stage` bytes; where nothing fits, the least budget is the depth arrays', the statistics' tables',
+	// the pileup's arrays' and the plan's
 	int plan(uint64_t stage) {
 		const int r = plan_with_stage(n_bytes, n, md != nullptr, sort_budget, stage, &P);
-		if (r == URMAPX_E_NOMEM && dep) dep->out->least_budget = depth_bytes + stats_bytes + P.device_bytes;
-		if (r == URMAPX_E_NOMEM && sta) sta->out->least_budget = depth_bytes + stats_bytes + P.device_bytes;
+		const uint64_t least = depth_bytes + stats_bytes + pileup_bytes + P.device_bytes;
+		if (r == URMAPX_E_NOMEM && dep) dep->out->least_budget = least;
+		if (r == URMAPX_E_NOMEM && sta) sta->out->least_budget = least;
+		if (r == URMAPX_E_NOMEM && pil) pil->out->least_budget = least;
 		return r;
 	}
 	// The road.  On the external one the staged chunks, under marking each with the next chunk's first record behind it (first_kernel
@@ -550,10 +569,12 @@ struct DeviceSort {
 	// successor, makes the buffers grow, and the partition is planned again around them
 	int choose_road() {
 		if (budget) {
-			// the depth arrays and the statistics' tables come off the budget before the sort is planned
+			// the depth arrays, the statistics' tables and the pileup's arrays come off the budget before the sort is planned
 			depth_bytes = dep ? urx::depth::resident_bytes(dep->entries, n_ref, urx::depth::text_runs()) : 0u;
 			stats_bytes = sta ? urx::stats::resident_bytes(n_ref) : 0u;
-			sort_budget = *budget > depth_bytes + stats_bytes ? *budget - depth_bytes - stats_bytes : 0u;
+			pileup_bytes = pil ? urx::pileup::resident_bytes(pil->columns, n_ref, urx::pileup::segment_columns(), urx::pileup::slice_sites(), !pil->seqs) : 0u;
+			const uint64_t own = depth_bytes + stats_bytes + pileup_bytes;
+			sort_budget = *budget > own ? *budget - own : 0u;
 			if (const int rc = plan(default_stage_bytes(n_bytes))) return rc;
 			if (P.external) {
 				uint64_t need = 0;
@@ -590,6 +611,12 @@ struct DeviceSort {
 			const double a0 = t_alloc_s;
 			if ((rc = SW.begin(n_ref))) return rc;
 			sta->out->alloc_s = t_alloc_s - a0;
+		}
+		if (pil) {
+			if (n >= 0x7FFFFFFFu) return URMAPX_E_ARG;
+			const double a0 = t_alloc_s;
+			if ((rc = PW.begin(n_ref, pil->lens, pil->columns, pil->seqs, pil->d_store, pil->store_at))) return rc;
+			pil->out->alloc_s = t_alloc_s - a0;
 		}
 		if (ext) {  // (the pieces external_device_bytes counts, in its order; the partition is not larger than the stream)
 			const size_t part_cap = (size_t)std::min<uint64_t>(P.partition_bytes, n_bytes);
@@ -776,6 +803,16 @@ struct DeviceSort {
 		return URMAPX_OK;
 	}
 
+	// the pileup, in core: beside the depth and the statistics, on the same records
+	int pileup_in_core() {
+		if (!pil || ext) return URMAPX_OK;
+		Span span(pil->out->count_s);
+		if (const int rc = urx::pileup::pileup_count(PW, d_rec.p, 0, d_off.p, 0, n, nullptr, pil->R, nullptr)) return rc;
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(nullptr));
+		return URMAPX_OK;
+	}
+
 	// the sorted stream, a slice at a time: into order, deflate, copy back
 	int sorted_stream() {
 		slice_bytes = (size_t)slice_members() * MEMBER;
@@ -831,13 +868,15 @@ struct DeviceSort {
 		const uint8_t *const action = md ? d_action.p : nullptr;
 		for (uint64_t p0 = 0; p0 < n_bytes; p0 += P.partition_bytes) {
 			const uint64_t p1 = p0 + P.partition_bytes < n_bytes ? p0 + P.partition_bytes : n_bytes;
-			// (every record crosses the device in each of these passes: the depth and the statistics are taken in the first one only)
-			const bool count = dep && p0 == 0, tally = sta && p0 == 0;
+			// (every record crosses the device in each of these passes: the depth, the statistics and the pileup are taken in the first one only)
+			const bool count = dep && p0 == 0, tally = sta && p0 == 0, pile = pil && p0 == 0;
 			int r = pass(false, [&](const uint8_t *at, uint64_t base, uint32_t i0, uint32_t i1, hipStream_t s) -> int {
 				hipLaunchKernelGGL(place_kernel, dim3(grid_for(i1 - i0)), dim3(NT), 0, s, at, base, d_off.p, i0, i1, place, action, p0, p1, d_part.p);
 				if (count)
 					if (const int e = urx::depth::depth_count(DW, at, base, d_off.p, i0, i1, action, dep->min_mapq, s)) return e;
-				return tally ? urx::stats::stats_count(SW, at, base, d_off.p, i0, i1, action, s) : URMAPX_OK;
+				if (tally)
+					if (const int e = urx::stats::stats_count(SW, at, base, d_off.p, i0, i1, action, s)) return e;
+				return pile ? urx::pileup::pileup_count(PW, at, base, d_off.p, i0, i1, action, pil->R, s) : URMAPX_OK;
 			});
 			if (r) return r;
 			for (uint64_t s0 = p0; s0 < p1; s0 += slice_bytes) {
@@ -848,7 +887,7 @@ struct DeviceSort {
 		return URMAPX_OK;
 	}
 
-	// the depth's result and the statistics', then the sort's: the members trimmed to their size and handed to finish_result, which owns them from there
+	// the depth's result, the statistics' and the pileup's, then the sort's: the members trimmed to their size and handed to finish_result, which owns them from there
 	int finish() {
 		if (dep)
 			if (const int rc = urx::depth::depth_finish(DW, dep->out)) return rc;
@@ -856,6 +895,8 @@ struct DeviceSort {
 			sta->out->records = n;
 			if (const int rc = urx::stats::stats_finish(SW, sta->names, sta->lens, sta->command, sta->out)) return rc;
 		}
+		if (pil)
+			if (const int rc = urx::pileup::pileup_finish(PW, pil->names, pil->lens, pil->R, pil->command, pil->out)) return rc;
 		if (uint8_t *fit = (uint8_t *)realloc(z.get(), z_bytes ? z_bytes : 1)) {
 			(void)z.release();
 			z.reset(fit);
@@ -880,7 +921,7 @@ uint64_t urmapx_bam_sort_markdup_device_bytes(size_t n_bytes, uint64_t n_records
 
 static int sort_entry(int device, const uint64_t *budget, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
                       size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out, const DepthAsk *dep = nullptr,
-                      const StatsAsk *sta = nullptr) {
+                      const StatsAsk *sta = nullptr, const PileupAsk *pil = nullptr) {
 	if (!out || (n_bytes && !records) || (n_starts && !starts)) return URMAPX_E_ARG;
 	memset(out, 0, sizeof *out);
 	if (md) memset(md, 0, sizeof *md);
@@ -896,7 +937,7 @@ static int sort_entry(int device, const uint64_t *budget, const void *records, s
 			HIP_TRY(hipMemGetInfo(&free_b, &total_b));
 			have = free_b > URMAPX_SORT_HEADROOM ? (uint64_t)free_b - URMAPX_SORT_HEADROOM : 1u;
 		}
-		rc = DeviceSort{device, budget ? &have : nullptr, (const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, dep, sta, out}.run();
+		rc = DeviceSort{device, budget ? &have : nullptr, (const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, dep, sta, pil, out}.run();
 	} catch (const std::bad_alloc &) {
 		rc = URMAPX_E_NOMEM;
 	}
@@ -904,6 +945,7 @@ static int sort_entry(int device, const uint64_t *budget, const void *records, s
 	if (rc) urmapx_bam_sort_free(out);
 	if (rc && dep) urmapx_depth_free(dep->out);
 	if (rc && sta) urmapx_stats_free(sta->out);
+	if (rc && pil) urmapx_pileup_free(pil->out);
 	return rc;
 }
 
@@ -934,14 +976,53 @@ int urmapx_bam_sort_with(int device, uint64_t budget_bytes, const void *records,
                          const uint64_t *starts, size_t n_starts, const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out) {
 	const urmapx_bam_sort_extras none{};
 	const urmapx_bam_sort_extras &E = extras ? *extras : none;
-	if (!E.depth && !E.stats) return sort_entry(device, &budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, E.md, out);
+	const urmapx_bam_sort_extras2 with{E.md, E.dopts, E.names, E.lens, E.depth, E.stats, E.stats_command, nullptr, nullptr, nullptr, nullptr, nullptr};
+	return urmapx_bam_sort_with2(device, budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, &with, out);
+}
+
+int urmapx_bam_sort_with2(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
+                          const uint64_t *starts, size_t n_starts, const urmapx_bam_sort_extras2 *extras, urmapx_bam_sort_result *out) {
+	const urmapx_bam_sort_extras2 none{};
+	const urmapx_bam_sort_extras2 &E = extras ? *extras : none;
+	if (!E.depth && !E.stats && !E.pileup) return sort_entry(device, &budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, E.md, out);
 	if (E.depth) memset(E.depth, 0, sizeof *E.depth);
 	if (E.stats) memset(E.stats, 0, sizeof *E.stats);
+	if (E.pileup) memset(E.pileup, 0, sizeof *E.pileup);
 	DepthAsk dask{E.dopts ? E.dopts->min_mapq : 0u, E.names, E.lens, 0, E.depth};
 	const StatsAsk sask{E.names, E.lens, E.stats_command, E.stats};
 	if (const int rc = urx::depth::check_refs(n_ref, E.names, E.lens, &dask.entries)) return rc;
+	PileupAsk pask{urx::pileup::Rule(), E.names, E.lens, dask.entries - n_ref, E.seqs, nullptr, nullptr, E.pileup_command, E.pileup};
+	// the bases: the caller's, or the index's -- in place where its store is resident on this device, else fetched once to the host
+	std::vector<uint8_t> fetched;
+	std::vector<const uint8_t *> fetched_at;
+	std::vector<uint64_t> store_at;
+	if (E.pileup) {
+		if (const int rc = urx::pileup::rule_of(E.popts, &pask.R)) return rc;
+		if (!E.seqs) {
+			if (!E.index || urmapx_index_seq_count(E.index) != n_ref) return URMAPX_E_ARG;
+			const urx::IndexStore S = urx::index_store(E.index);
+			if (S.d_seq && S.device == device) {
+				store_at.resize((size_t)n_ref + 1, 0);
+				for (uint32_t r = 0; r < n_ref; ++r) {
+					store_at[r] = urmapx_index_seq_offset(E.index, r);
+					if (urmapx_index_seq_length(E.index, r) != E.lens[r] || store_at[r] + E.lens[r] > S.seq_data_size) return URMAPX_E_ARG;
+				}
+				pask.d_store = S.d_seq;
+				pask.store_at = store_at.data();
+			} else {
+				try {
+					if (const int rc = urx::pileup::index_sequences(E.index, n_ref, E.lens, fetched, fetched_at)) return rc;
+				} catch (const std::bad_alloc &) {
+					return URMAPX_E_NOMEM;
+				}
+				pask.seqs = fetched_at.data();
+			}
+		}
+		if (pask.seqs)
+			if (const int rc = urx::pileup::check_input(n_ref, E.names, E.lens, pask.seqs, &pask.columns)) return rc;
+	}
 	return sort_entry(device, &budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, E.md, out, E.depth ? &dask : nullptr,
-	                  E.stats ? &sask : nullptr);
+	                  E.stats ? &sask : nullptr, E.pileup ? &pask : nullptr);
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 //   line_len / block_scan / line_write   a slice of the run list at a time: the length of every line, their starts, the bytes.  A run
 //                        ends where the next one starts if that is on the same reference, else at the reference's end
 #include "depth_dev.h"
+#include "block_scan_dev.h"
 
 #include <algorithm>
 #include <chrono>
@@ -31,6 +32,8 @@
 
 using namespace urx::bamsort;
 using namespace urx::depth;
+using urx::devscan::block_scan_kernel;
+using urx::devscan::BS_NT;
 
 namespace {
 
@@ -38,7 +41,6 @@ using Clock = std::chrono::steady_clock;
 double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::now() - t).count(); }
 
 constexpr uint32_t DNT = urx::depth::NT;
-constexpr uint32_t BS_NT = 1024;  // threads of block_scan_kernel
 
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
 __device__ __forceinline__ uint32_t shfl32(uint32_t v, uint32_t from) { return (uint32_t)__shfl((int)v, (int)from, 64); }
@@ -158,32 +160,7 @@ __global__ __launch_bounds__(DNT) void depth_count_kernel(const uint8_t *rec, ui
 	}
 }
 
-// ---- the scan ----
-// one workgroup: out[i] = in[0] + .. + in[i - 1] for i < m (out may be in), the total to out[m] if with_total
-template <class TO>
-__global__ __launch_bounds__(BS_NT) void block_scan_kernel(const uint32_t *in, TO *out, uint32_t m, int with_total) {
-	__shared__ uint64_t part[BS_NT];
-	const uint32_t t = threadIdx.x, run = (m + BS_NT - 1) / BS_NT;
-	const uint64_t lo = (uint64_t)t * run < m ? (uint64_t)t * run : m, hi = lo + run < m ? lo + run : m;
-	uint64_t sum = 0;
-	for (uint64_t i = lo; i < hi; ++i) sum += in[i];
-	part[t] = sum;
-	__syncthreads();
-	for (uint32_t s = 1; s < BS_NT; s <<= 1) {
-		const uint64_t a = t >= s ? part[t - s] : 0;
-		__syncthreads();
-		part[t] += a;
-		__syncthreads();
-	}
-	uint64_t at = part[t] - sum;
-	for (uint64_t i = lo; i < hi; ++i) {
-		const uint32_t x = in[i];
-		out[i] = (TO)at;
-		at += x;
-	}
-	if (with_total && t == BS_NT - 1) out[m] = (TO)part[t];
-}
-
+// ---- the scan (block_scan_kernel: block_scan_dev.h) ----
 // eight neighbouring counters from g on, those from g1 on as 0 (g is a multiple of eight: the array comes from hipMalloc)
 __device__ __forceinline__ void load8(const uint32_t *d, uint64_t g, uint64_t g1, uint32_t (&v)[SCAN_ITEMS]) {
 	if (g + SCAN_ITEMS <= g1) {

@@ -1103,7 +1103,7 @@ struct Run {
 		ctxs.clear(); texts.clear(); replicas.clear();  // (the destructor's pass finds nothing)
 	}
 	// ---- bam_sort: the kept records (rep.sam_file_bytes of them, in input order) into coordinate order, then samout -- header block with
-	// the @HD line in a member of its own, the sorted stream, the end-of-file member -- and samout.bai; under depth_out the bedGraph file, under stats_out the statistics' ----
+	// the @HD line in a member of its own, the sorted stream, the end-of-file member -- and samout.bai; under depth_out the bedGraph file, under stats_out the statistics', under vcf_out the pileup's ----
 	// What the parts of write_sorted hand on.  Both results are freed on every way out; where the library has freed and zeroed them
 	// already (a call that failed) the frees find null pointers
 	struct Sorted {
@@ -1114,11 +1114,12 @@ struct Run {
 		urmapx_markdup_stats M;
 		urmapx_depth_result D;
 		urmapx_stats_result T;
-		std::vector<const char *> ref_names;  // depth_out, stats_out: the names and lengths of the @SQ lines
+		urmapx_pileup_result V;
+		std::vector<const char *> ref_names;  // depth_out, stats_out, vcf_out: the names and lengths of the @SQ lines
 		std::vector<uint32_t> ref_lens;
-		Sorted() { memset(&S, 0, sizeof S); memset(&M, 0, sizeof M); memset(&D, 0, sizeof D); memset(&T, 0, sizeof T); }
+		Sorted() { memset(&S, 0, sizeof S); memset(&M, 0, sizeof M); memset(&D, 0, sizeof D); memset(&T, 0, sizeof T); memset(&V, 0, sizeof V); }
 		Sorted(const Sorted &) = delete;
-		~Sorted() { urmapx_bam_sort_free(&S); urmapx_depth_free(&D); urmapx_stats_free(&T); }
+		~Sorted() { urmapx_bam_sort_free(&S); urmapx_depth_free(&D); urmapx_stats_free(&T); urmapx_pileup_free(&V); }
 	};
 	static bool host_sort() { return getenv("URMAPX_HOST_TEXT") || getenv("URMAPX_HOST_SORT"); }
 	void write_sorted() {
@@ -1132,11 +1133,12 @@ struct Run {
 		sink.write_through();
 		const double bam_s = write_bam_and_bai(W);
 		const double sorted_s = rep.sort_s = secs(t0, now());
-		double bed_s = 0, stats_file_s = 0;
+		double bed_s = 0, stats_file_s = 0, vcf_file_s = 0;
 		if (opt.depth_out) bed_s = write_depth(W);
 		if (opt.stats_out) stats_file_s = write_stats(W);
-		if (opt.depth_out || opt.stats_out) rep.sort_s = secs(t0, now());
-		report_sorted(W, sorted_s, bam_s, bed_s, stats_file_s);
+		if (opt.vcf_out) vcf_file_s = write_vcf(W);
+		if (opt.depth_out || opt.stats_out || opt.vcf_out) rep.sort_s = secs(t0, now());
+		report_sorted(W, sorted_s, bam_s, bed_s, stats_file_s, vcf_file_s);
 		trace.add("sort", -1, 0, t0);
 	}
 	bool sorted_header(std::string &hdr) {
@@ -1145,9 +1147,9 @@ struct Run {
 		if (!bgzf_members(hdr)) { fail.raise(URMAPX_E_NOMEM, "out of memory"); return false; }
 		return true;
 	}
-	// The sort, on the first device.  Planned -- sort_mem, depth_out or stats_out (both are taken on the way: include/urmapx.h "Depth",
-	// "Stats") or the test knob that forces partitions --: one call, which plans from the budget and streams where it must
-	// (urmapx_bam_sort_with; with neither result that is urmapx_bam_sort_external), and nothing else is tried.  Else in core, and if the records do not fit,
+	// The sort, on the first device.  Planned -- sort_mem, depth_out, stats_out or vcf_out (all three are taken on the way: include/urmapx.h
+	// "Depth", "Stats", "Pileup") or the test knob that forces partitions --: one call, which plans from the budget and streams where it must
+	// (urmapx_bam_sort_with2; with none of the results that is urmapx_bam_sort_external), and nothing else is tried.  Else in core, and if the records do not fit,
 	// planned from the memory that is free.  Where the device is full of lanes, this run's and the pool's go first (the mapping is over)
 	// and the same call is made once more.  Under URMAPX_HOST_TEXT / URMAPX_HOST_SORT the host's sort, once
 	int sort_kept(Sorted &W) {
@@ -1158,18 +1160,21 @@ struct Run {
 		urmapx_depth_result *const depth = opt.depth_out ? &W.D : nullptr;
 		const urmapx_depth_opts dopts{opt.depth_mapq};
 		urmapx_stats_result *const stats = opt.stats_out ? &W.T : nullptr;
-		for (uint32_t r = 0; (depth || stats) && r < W.n_ref; ++r) {
+		urmapx_pileup_result *const pileup = opt.vcf_out ? &W.V : nullptr;
+		const urmapx_pileup_opts popts{opt.vcf_mapq, opt.vcf_baseq, opt.vcf_min_alt, opt.vcf_min_pct};
+		for (uint32_t r = 0; (depth || stats || pileup) && r < W.n_ref; ++r) {
 			W.ref_names.push_back(urmapx_index_label(I, r));
 			W.ref_lens.push_back(urmapx_index_seq_length(I, r));
 		}
-		const urmapx_bam_sort_extras extras{md, &dopts, W.ref_names.data(), W.ref_lens.data(), depth, stats, opt.cmdline};
-		if (host_sort()) return urmapx_bam_sort_with_host(rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), &extras, &W.S);
-		auto planned_sort = [&]() { return urmapx_bam_sort_with(phys(0), opt.sort_mem, rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), &extras, &W.S); };
+		// (the pileup's bases: the index's store, in place where it is resident on the sort's device, else fetched once)
+		const urmapx_bam_sort_extras2 extras{md, &dopts, W.ref_names.data(), W.ref_lens.data(), depth, stats, opt.cmdline, &popts, nullptr, I, pileup, opt.cmdline};
+		if (host_sort()) return urmapx_bam_sort_with2_host(rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), &extras, &W.S);
+		auto planned_sort = [&]() { return urmapx_bam_sort_with2(phys(0), opt.sort_mem, rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), &extras, &W.S); };
 		auto in_core = [&]() {
 			return md ? urmapx_bam_sort_markdup(phys(0), rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), md, &W.S)
 			          : urmapx_bam_sort(phys(0), rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), &W.S);
 		};
-		const bool planned = depth || stats || opt.sort_mem != 0 || getenv("URMAPX_TEST_SORT_PARTITION");
+		const bool planned = depth || stats || pileup || opt.sort_mem != 0 || getenv("URMAPX_TEST_SORT_PARTITION");
 		int rc = planned ? planned_sort() : in_core();
 		if (rc == URMAPX_E_NOMEM) {
 			close();
@@ -1181,7 +1186,14 @@ struct Run {
 	}
 	// why the sort did not run: the device sorts' out-of-memory with the least budget that would do, the depth's references, or the code
 	void refuse_sort(int rc, const Sorted &W) {
-		if (rc == URMAPX_E_NOMEM && !host_sort() && !opt.depth_out && opt.stats_out) {
+		if (rc == URMAPX_E_NOMEM && !host_sort() && opt.vcf_out) {
+			if (W.V.least_budget)
+				fail.raise(rc, "bam_sort with vcf_out: the pileup's counters (16 bytes a reference base), the sort's arrays, its staging buffers and one slice need at least " +
+				                   std::to_string(W.V.least_budget) + " bytes on the device" +
+				                   (opt.sort_mem ? ", " + std::to_string(opt.sort_mem) + " were given (sort_mem)" : std::string(", fewer are free")));
+			else
+				fail.raise(rc, "bam_sort with vcf_out: out of device memory");
+		} else if (rc == URMAPX_E_NOMEM && !host_sort() && !opt.depth_out && opt.stats_out) {
 			if (W.T.least_budget)
 				fail.raise(rc, "bam_sort with stats: the statistics' tables, the sort's arrays, its staging buffers and one slice need at least " +
 				                   std::to_string(W.T.least_budget) + " bytes on the device" +
@@ -1210,6 +1222,8 @@ struct Run {
 			fail.raise(rc, "depth: a reference name that is empty or longer than 255 bytes");
 		else if (rc == URMAPX_E_ARG && opt.stats_out)
 			fail.raise(rc, "stats: a reference name that is empty or longer than 255 bytes");
+		else if (rc == URMAPX_E_ARG && opt.vcf_out)
+			fail.raise(rc, "vcf_out: a reference name that is empty or longer than 255 bytes, or an index without its sequences");
 		else
 			fail.raise(rc, std::string("bam_sort: ") + urmapx_strerror(rc));
 	}
@@ -1270,9 +1284,21 @@ struct Run {
 		rep.stats_duplicated = T.duplicated; rep.stats_insert_median = T.insert_median;
 		return file_s;
 	}
-	// the report's fields of the sort, the marking, the depth and the statistics, and under URMAPX_VERBOSE their lines, which the scripts read:
+	// the VCF file and the report's total -> the file's seconds
+	double write_vcf(const Sorted &W) {
+		const auto ts0 = now();
+		const urmapx_pileup_result &V = W.V;
+		FileSink vsink;
+		if (!vsink.open(opt.vcf_out) || !vsink.write_at(V.text, V.text_bytes, 0, 1) || !vsink.finish(V.text_bytes))
+			fail.raise(URMAPX_E_IO, std::string("Error writing ") + opt.vcf_out);
+		const double file_s = secs(ts0, now());
+		rep.write_s += file_s;
+		rep.pileup_sites = V.sites; rep.pileup_records = V.records; rep.pileup_alt_alleles = V.alt_alleles;
+		return file_s;
+	}
+	// the report's fields of the sort, the marking, the depth, the statistics and the pileup, and under URMAPX_VERBOSE their lines, which the scripts read:
 	// scripts/bam_sort_bench.py, depth_bench.py, bam_sort_external_bench.py, markdup_bench.py, in this order
-	void report_sorted(const Sorted &W, double sorted_s, double bam_s, double bed_s, double stats_file_s) {
+	void report_sorted(const Sorted &W, double sorted_s, double bam_s, double bed_s, double stats_file_s, double vcf_file_s) {
 		const urmapx_bam_sort_result &S = W.S;
 		const urmapx_markdup_stats &M = W.M;
 		const urmapx_depth_result &D = W.D;
@@ -1295,6 +1321,14 @@ struct Run {
 			if (verbose)
 				fprintf(stderr, "stats seconds: total %.4f alloc %.4f count %.4f format %.4f write %.4f; records %llu bytes %llu\n", rep.stats_s, T.alloc_s, T.count_s,
 				        T.format_s, stats_file_s, (unsigned long long)T.records, (unsigned long long)T.text_bytes);
+		}
+		if (opt.vcf_out) {
+			const urmapx_pileup_result &V = W.V;
+			rep.pileup_s = V.alloc_s + V.count_s + V.sites_s + V.format_s + V.copy_s + vcf_file_s;
+			if (verbose)
+				fprintf(stderr, "pileup seconds: total %.4f alloc %.4f count %.4f sites %.4f format %.4f copy %.4f write %.4f; records %llu sites %llu alleles %llu bytes %llu\n",
+				        rep.pileup_s, V.alloc_s, V.count_s, V.sites_s, V.format_s, V.copy_s, vcf_file_s, (unsigned long long)V.records, (unsigned long long)V.sites,
+				        (unsigned long long)V.alt_alleles, (unsigned long long)V.text_bytes);
 		}
 		rep.sort_partitions = S.external ? S.partitions : 0;
 		if (S.external && verbose)
@@ -1322,6 +1356,7 @@ struct Run {
 			remove((std::string(samout) + ".bai").c_str());
 			if (opt.depth_out) remove(opt.depth_out);
 			if (opt.stats_out) remove(opt.stats_out);
+			if (opt.vcf_out) remove(opt.vcf_out);
 		}
 		ftab.reset();  // (inside the run's clock; the lanes are let go outside it)
 		const auto t2 = now();
@@ -2128,6 +2163,17 @@ static int map_files_entry(urmapx_index *I, const urmapx_map_options *opt, const
 	if (opt->stats_out && ((samout && (!strcmp(opt->stats_out, samout) || std::string(opt->stats_out) == std::string(samout) + ".bai")) ||
 	                       (opt->depth_out && !strcmp(opt->stats_out, opt->depth_out)))) {
 		say(err, errcap, "stats_out names the BAM file, its index or the depth file: the statistics need a file of their own");
+		return URMAPX_E_ARG;
+	}
+	if (opt->vcf_out && !opt->bam_sort) { say(err, errcap, "vcf_out needs bam_sort: the bases are piled up while the records are sorted"); return URMAPX_E_ARG; }
+	if (opt->vcf_out && !opt->vcf_out[0]) { say(err, errcap, "vcf_out needs a file name"); return URMAPX_E_ARG; }
+	if (opt->vcf_out && ((samout && (!strcmp(opt->vcf_out, samout) || std::string(opt->vcf_out) == std::string(samout) + ".bai")) ||
+	                     (opt->depth_out && !strcmp(opt->vcf_out, opt->depth_out)) || (opt->stats_out && !strcmp(opt->vcf_out, opt->stats_out)))) {
+		say(err, errcap, "vcf_out names the BAM file, its index, the depth file or the statistics' file: the sites need a file of their own");
+		return URMAPX_E_ARG;
+	}
+	if (opt->vcf_out && (opt->vcf_mapq > 255u || opt->vcf_baseq > 255u || opt->vcf_min_alt == 0u || opt->vcf_min_pct > 100u)) {
+		say(err, errcap, "vcf_out: vcf_mapq and vcf_baseq are 0 .. 255, vcf_min_alt is 1 or more, vcf_min_pct is 0 .. 100");
 		return URMAPX_E_ARG;
 	}
 	const int shards = opt->sam_shards > 1 ? opt->sam_shards : 1;

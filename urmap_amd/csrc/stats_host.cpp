@@ -380,26 +380,8 @@ int urmapx_bam_sort_with_host(const void *records, size_t n_bytes, uint32_t n_re
                               const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out) {
 	const urmapx_bam_sort_extras none{};
 	const urmapx_bam_sort_extras &E = extras ? *extras : none;
-	if (!E.depth && !E.stats) {
-		return E.md ? urmapx_bam_sort_markdup_host(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, E.md, out)
-		            : urmapx_bam_sort_host(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, out);
-	}
-	if (E.depth) memset(E.depth, 0, sizeof *E.depth);
-	if (E.stats) memset(E.stats, 0, sizeof *E.stats);
-	uint64_t entries = 0;
-	int rc = urx::depth::check_refs(n_ref, E.names, E.lens, &entries);
-	if (rc) return rc;
-	// the flags as written: the marking's decisions beside the records as they came (order matters to neither)
-	const urx::bamsort::AfterMark hook = [&](const uint8_t *rec, const std::vector<uint64_t> &offs, const uint8_t *action) -> int {
-		if (offs.size() - 1 >= 0x7FFFFFFFu) return URMAPX_E_ARG;
-		if (E.depth)
-			if (const int r = urx::depth::depth_host(rec, offs, action, n_ref, E.names, E.lens, E.dopts ? E.dopts->min_mapq : 0u, E.depth)) return r;
-		return E.stats ? stats_host(rec, offs, action, n_ref, E.names, E.lens, E.stats_command, E.stats) : URMAPX_OK;
-	};
-	rc = urx::bamsort::sort_host_hooked(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, E.md, out, hook);
-	if (rc && E.depth) urmapx_depth_free(E.depth);
-	if (rc && E.stats) urmapx_stats_free(E.stats);
-	return rc;
+	const urmapx_bam_sort_extras2 with{E.md, E.dopts, E.names, E.lens, E.depth, E.stats, E.stats_command, nullptr, nullptr, nullptr, nullptr, nullptr};
+	return urmapx_bam_sort_with2_host(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, &with, out);
 }
 
 }  // extern "C"

@@ -72,6 +72,9 @@ struct Opts {
 	bool depth_given = false, depth_mapq_given = false;
 	std::string stats;     // -stats FILE: with -sort, a text file of the alignment statistics of the records of the -bamout file
 	bool stats_given = false;
+	std::string vcf;       // -vcfout FILE: with -sort, a sites-only VCF file of the columns where the records of the -bamout file differ from the reference
+	std::string vcf_mapq, vcf_baseq, vcf_min_alt, vcf_min_pct;  // -vcf_mapq N, -vcf_baseq N, -vcf_min_alt N, -vcf_min_pct N: its thresholds
+	bool vcf_given = false, vcf_mapq_given = false, vcf_baseq_given = false, vcf_min_alt_given = false, vcf_min_pct_given = false;
 	std::string tags, rg;  // -tags NM,MD,AS and -rg '@RG\tID:..': optional fields of the records, the read group's header line
 	bool tags_given = false, rg_given = false;
 	bool trunclabels = false, wordlength_given = false;
@@ -141,6 +144,11 @@ static Opts parse(int argc, char **argv) {
 		else if (a == "-depth") { o.depth = val(); o.depth_given = true; }
 		else if (a == "-stats") { o.stats = val(); o.stats_given = true; }
 		else if (a == "-depth_mapq") { o.depth_mapq = val(); o.depth_mapq_given = true; }
+		else if (a == "-vcfout") { o.vcf = val(); o.vcf_given = true; }
+		else if (a == "-vcf_mapq") { o.vcf_mapq = val(); o.vcf_mapq_given = true; }
+		else if (a == "-vcf_baseq") { o.vcf_baseq = val(); o.vcf_baseq_given = true; }
+		else if (a == "-vcf_min_alt") { o.vcf_min_alt = val(); o.vcf_min_alt_given = true; }
+		else if (a == "-vcf_min_pct") { o.vcf_min_pct = val(); o.vcf_min_pct_given = true; }
 		else if (a == "-tags") { o.tags = val(); o.tags_given = true; }
 		else if (a == "-rg") { o.rg = val(); o.rg_given = true; }
 		else if (a == "-quiet") o.quiet = true;
@@ -268,6 +276,31 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 			die("-stats %s: that is the -bamout file, its index or the -depth file; the statistics need a file of their own", o.stats.c_str());
 		if (stat(o.stats.c_str(), &st) == 0 && !S_ISREG(st.st_mode)) die("-stats needs a file name, not a pipe or %s: the file is written at the end of the run", o.stats.c_str());
 	}
+	// -vcfout and its four numbers (defaults: MAPQ 0, base quality 13, 3 reads, 10 per cent)
+	unsigned vcf_num[4] = {0, 13, 3, 10};
+	{
+		const struct { const char *flag; const std::string &text; bool given; unsigned lo, hi; const char *what; } nums[4] = {
+		    {"-vcf_mapq", o.vcf_mapq, o.vcf_mapq_given, 0, 255, "a MAPQ from 0 to 255"},
+		    {"-vcf_baseq", o.vcf_baseq, o.vcf_baseq_given, 0, 255, "a base quality from 0 to 255"},
+		    {"-vcf_min_alt", o.vcf_min_alt, o.vcf_min_alt_given, 1, 0x7FFFFFFFu, "a number of reads from 1 on"},
+		    {"-vcf_min_pct", o.vcf_min_pct, o.vcf_min_pct_given, 0, 100, "a percentage from 0 to 100"}};
+		for (int k = 0; k < 4; ++k) {
+			if (!nums[k].given) continue;
+			if (!o.vcf_given) die("%s needs -vcfout: it is a threshold of the sites that file lists", nums[k].flag);
+			char *end = nullptr;
+			const unsigned long v = strtoul(nums[k].text.c_str(), &end, 10);
+			if (nums[k].text.empty() || *end || nums[k].text[0] == '-' || v < nums[k].lo || v > nums[k].hi) die("%s %s: %s", nums[k].flag, nums[k].text.c_str(), nums[k].what);
+			vcf_num[k] = (unsigned)v;
+		}
+	}
+	if (o.vcf_given) {
+		struct stat st;
+		if (!o.sort) die("-vcfout needs -sort: the bases are piled up while the records of the -bamout file are sorted");
+		if (o.vcf.empty()) die("-vcfout needs a file name");
+		if (o.vcf == o.bamout || o.vcf == o.bamout + ".bai" || (o.depth_given && o.vcf == o.depth) || (o.stats_given && o.vcf == o.stats))
+			die("-vcfout %s: that is the -bamout file, its index, the -depth file or the -stats file; the sites need a file of their own", o.vcf.c_str());
+		if (stat(o.vcf.c_str(), &st) == 0 && !S_ISREG(st.st_mode)) die("-vcfout needs a file name, not a pipe or %s: the file is written at the end of the run", o.vcf.c_str());
+	}
 	if (o.sort) {
 		struct stat st;
 		if (!bam) die("-sort needs -bamout: it sorts the records of a BAM file");
@@ -312,6 +345,8 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 	mo.depth_out = o.depth_given ? o.depth.c_str() : nullptr;
 	mo.depth_mapq = depth_mapq;
 	mo.stats_out = o.stats_given ? o.stats.c_str() : nullptr;
+	mo.vcf_out = o.vcf_given ? o.vcf.c_str() : nullptr;
+	mo.vcf_mapq = vcf_num[0]; mo.vcf_baseq = vcf_num[1]; mo.vcf_min_alt = vcf_num[2]; mo.vcf_min_pct = vcf_num[3];
 	urmapx_map_report rep;
 	memset(&rep, 0, sizeof rep);
 	char err[1024];
@@ -363,6 +398,9 @@ static int cmd_map(const Opts &o, int argc, char **argv) {
 			progress_log(q, "%16.3f  Seconds for the statistics in %s: %llu reads, %llu mapped, %llu properly paired, %llu duplicated, median insert size %llu\n\n", rep.stats_s,
 			             o.stats.c_str(), (unsigned long long)rep.stats_reads, (unsigned long long)rep.stats_mapped, (unsigned long long)rep.stats_properly_paired,
 			             (unsigned long long)rep.stats_duplicated, (unsigned long long)rep.stats_insert_median);
+		if (o.vcf_given)
+			progress_log(q, "%16.3f  Seconds for the pileup in %s: %llu records counted, %llu sites, %llu alternative alleles\n\n", rep.pileup_s, o.vcf.c_str(),
+			             (unsigned long long)rep.pileup_records, (unsigned long long)rep.pileup_sites, (unsigned long long)rep.pileup_alt_alleles);
 		if (o.markdup)
 			progress_log(q, "%16.3f  Seconds to mark duplicates: %llu of %llu pairs, %llu of %llu fragments\n\n", rep.markdup_s, (unsigned long long)rep.pairs_duplicate,
 			             (unsigned long long)rep.pairs_examined, (unsigned long long)rep.fragments_duplicate, (unsigned long long)rep.fragments_examined);
@@ -678,6 +716,10 @@ int main(int argc, char **argv) {
                 "      -depth_mapq N: with -depth, records with a MAPQ below N do not count (0..255; default 0)\n"
                 "      -stats FILE: with -sort, the alignment statistics of the records as written -- counts by flag, MAPQ, read lengths, insert\n"
                 "          sizes, qualities and bases per cycle, GC, indels, reads per reference -- as a text file, counted on the GPU beside the sort\n"
+                "      -vcfout FILE: with -sort, the columns where the records as written show a base other than the reference's, as a sites-only\n"
+                "          VCF 4.2 file with DP and AD (SNV candidates; no indels, no genotypes), piled up on the GPU beside the sort\n"
+                "      -vcf_mapq N, -vcf_baseq N: with -vcfout, the least MAPQ of a record and the least quality of a base that count (0..255; defaults 0, 13)\n"
+                "      -vcf_min_alt N, -vcf_min_pct N: with -vcfout, an alternative allele needs N bases (from 1; default 3) and N per cent of the column's (0..100; default 10)\n"
                 "      -sortmem N[K|M|G]: with -sort, the GPU memory the sort may take; records that do not fit it stream through the GPU in partitions\n"
 	                "      -tags NM,MD,AS: these optional fields behind QUAL of every mapped record (any subset; computed on the GPU), SAM and BAM\n"
 	                "      -rg '@RG\\tID:x\\tSM:y': that line in the header in front of @PG and RG:Z:x on every record\n"
