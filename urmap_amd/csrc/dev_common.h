@@ -463,6 +463,17 @@ __device__ __forceinline__ void glds_dword(const void *gsrc, uint32_t lds_dst) {
 	             : "v"(gsrc), "s"(lds_dst)
 	             : "memory");
 }
+// global_load_lds_dwordx3: the same with 12 bytes per lane, one request per lane where three glds_dword make three.  Lane l's
+// three dwords land at lds_dst + 16*l -- cells of SIXTEEN bytes, 1 KB per instruction -- and the fourth dword of each cell is
+// not written (measured on gfx950 with a 16-byte aligned and a 4-byte aligned lds_dst: profiles/r7/README.md).  gsrc is
+// 4-byte aligned.  Same rule about waits.
+__device__ __forceinline__ void glds_dwordx3(const void *gsrc, uint32_t lds_dst) {
+	unsigned keep;
+	asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx3 %1, off\n\ts_mov_b32 m0, %0"
+	             : "=&s"(keep)
+	             : "v"(gsrc), "s"(lds_dst)
+	             : "memory");
+}
 __device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 template <class T>

@@ -223,6 +223,11 @@ static constexpr int SE_HITW1 = 1;
 // LAYOUT 1 (round 5): the slot entries in LDS come out of DevIndex::slot16 -- pr_lo = the slot's position, pr_hi = tally | row length
 // << 8, pr_sl = the row's second position (rows of two) or its index in DevIndex::rows -- instead of the two dwords around the
 // 5-byte slot and the slot number's low half
+// LAYOUT 2: the same three dwords brought in by ONE 12-byte LDS-DMA per k-mer (a third of the requests).  global_load_lds_dwordx3 puts lane
+// l's dwords at destination + 16 * l and leaves the fourth dword of each 16-byte cell alone (measured: profiles/r7/README.md), so entry e =
+// the dwords 4 * e + 0 / 1 / 2 of an array of 4 * NSEG * 64 dwords -- and the fourth dword of every cell is free: the instances whose row
+// store lies in LDS keep its plane of first positions there (walk_heads, row_entry), which pays for the fourth dword.  The other instances
+// have no such plane to move and stay on LAYOUT 1 (a fourth dword per k-mer would cost them a wave per SIMD).
 // KCH (round 6): the chunks of 64 k-MER START positions the instance holds per strand -- NCH by default (every base but the last W - 1 starts a k-mer);
 // an instance for reads whose QL - W + 1 k-mers fit fewer chunks (150 bases, W = 24: 127 starts = two chunks of a three-chunk read) keeps slot entries,
 // prefix array and chain groups for those only: a third less LDS in them, a third fewer group steps in every unrolled loop over them
@@ -764,12 +769,19 @@ struct SearchWave {
 	// position q covers the same bases as the plus-strand k-mer at nwords-1-q.  pr_lo / pr_hi = the two aligned dwords
 	// around the 5-byte slot, pr_sl = the low half of the slot number (its two low bits say where the slot starts in
 	// them: 5*slot = slot mod 4), pr_hb = bit 32 of the slot numbers of a chunk as one ballot word per [strand][chunk].
+	// The three are consecutive thirds of one array of 3 * NSEG * 64 dwords; LAYOUT 2 has its 16-byte cells in an array of
+	// 4 * NSEG * 64 dwords from pr_lo on (see the top of SearchWave).
 	// A position without a k-mer gathered zeros: tally 0 = TALLY_FREE.
 	uint32_t *pr_lo, *pr_hi, *pr_sl;
 	uint64_t *pr_hb;
 	uint32_t reserved = 0;  // padding (once the LDS address of a prefetch sink): kept with park_for_dp's `clipped` so that the compiled kernels stay what was measured
 	__device__ __forceinline__ void probe_get(int s, int q, uint32_t &tally, uint32_t &pos) const {
 		const int e = s * KCH * 64 + (s ? nwords - 1 - q : q);
+		if constexpr (LAYOUT == 2) {
+			pos = pr_lo[4 * e];
+			tally = pr_lo[4 * e + 1] & 0xFFu;
+			return;
+		}
 		if constexpr (LAYOUT == 1) {
 			pos = pr_lo[e];
 			tally = pr_hi[e] & 0xFFu;
@@ -836,13 +848,17 @@ struct SearchWave {
 				const uint64_t hb = stage_b[2 * g], ok = stage_b[2 * g + 1];
 				const bool v = (ok >> lane) & 1ull;
 				const uint32_t sl = stage_sl[g * 64 + lane];
-				if constexpr (LAYOUT == 1) {
+				if constexpr (LAYOUT >= 1) {
 					// one aligned 16-byte slot of DevIndex::slot16: position, tally | row length, second position or row index
 					const uint64_t slot16 = (uint64_t)sl | (((hb >> lane) & 1ull) << 32);
 					const uint8_t *ap = v ? reinterpret_cast<const uint8_t *>(X.slot16) + 16ull * slot16 : reinterpret_cast<const uint8_t *>(g_zero16);
-					glds_dword(ap, lds_addr(pr_lo + g * 64));
-					glds_dword(ap + 4, lds_addr(pr_hi + g * 64));
-					glds_dword(ap + 8, lds_addr(pr_sl + g * 64));
+					if constexpr (LAYOUT == 2) {
+						glds_dwordx3(ap, lds_addr(pr_lo + g * 4 * 64));  // lane l = entry g * 64 + l: its cell's first three dwords
+					} else {
+						glds_dword(ap, lds_addr(pr_lo + g * 64));
+						glds_dword(ap + 4, lds_addr(pr_hi + g * 64));
+						glds_dword(ap + 8, lds_addr(pr_sl + g * 64));
+					}
 					continue;
 				}
 #ifdef URX_FAULT_SLOT32  // fault injection for the test suite's own check (profiles/r5/fault_slot32.txt): the slot number cut to 32 bits
@@ -870,14 +886,21 @@ struct SearchWave {
 			const int s2 = g / KCH, c = g % KCH;
 			const int p = 64 * c + lane;
 			T[g] = 0; ps[g] = 0; sl[g] = 0;
-			if constexpr (LAYOUT == 1) {
+			if constexpr (LAYOUT >= 1) {
 				// sl carries what rows_fetch needs instead of a slot number: row length | (second position or row index) << 32
 				if (p < nwords) {
 					const int e = s2 * KCH * 64 + (s2 ? nwords - 1 - p : p);
-					const uint32_t hi = pr_hi[e];
-					ps[g] = pr_lo[e];
+					uint32_t hi, d2;
+					if constexpr (LAYOUT == 2) {
+						ps[g] = pr_lo[4 * e]; hi = pr_lo[4 * e + 1]; d2 = pr_lo[4 * e + 2];
+						// the row store's two words (rows_fetch), kept here already -- nothing of the entry stays in registers across probe_gather.
+						// Position 0 of group g, lane l goes to the fourth dword of cell g * 64 + l: the next read's probe overwrites the entries,
+						// not that dword
+						pr_lo[4 * (g * 64 + lane) + 3] = ps[g];
+						rowstore[(size_t)g * 64 + lane] = d2;
+					} else { hi = pr_hi[e]; ps[g] = pr_lo[e]; d2 = pr_sl[e]; }
 					T[g] = hi & 0xFFu;
-					sl[g] = (uint64_t)((hi >> 8) & 0xFFu) | ((uint64_t)pr_sl[e] << 32);
+					sl[g] = (uint64_t)((hi >> 8) & 0xFFu) | ((uint64_t)d2 << 32);
 				}
 				act[g] = (T[g] & TALLY_MY_BIT) != 0 && T[g] != TALLY_BOTH1;
 				continue;
@@ -938,16 +961,17 @@ struct SearchWave {
 		// own (the probe read it with the slot), so a row of two needs nothing but this entry, and phase 4 (rows of length <= 2) reads
 		// no `rows` at all: one dependent round trip and one 64-byte sector less per such row.  rowstore: [g] = the row's index in
 		// `rows` (rows of three and more), [NSEG + g] = position 0, [2 NSEG + g] = position 1.
-		if constexpr (LAYOUT == 1) {
+		if constexpr (LAYOUT >= 1) {
 			// everything came with the probe (DevIndex::slot16): no read at all.  rowstore[g] = second position (rows of two) or the row's
-			// index in `rows`, [NSEG + g] = position 0
+			// index in `rows`, [NSEG + g] = position 0 (LAYOUT 2: walk_heads has stored both)
 #pragma unroll
 			for (int g = 0; g < NSEG; ++g) {
 				rl[g] = act[g] ? (int)(sl[g] & 0xFFu) : 0;
-				if (act[g]) {
-					rowstore[(size_t)g * 64 + lane] = (uint32_t)(sl[g] >> 32);
-					rowstore[(size_t)(NSEG + g) * 64 + lane] = ps[g];
-				}
+				if constexpr (LAYOUT == 1)
+					if (act[g]) {
+						rowstore[(size_t)g * 64 + lane] = (uint32_t)(sl[g] >> 32);
+						rowstore[(size_t)(NSEG + g) * 64 + lane] = ps[g];
+					}
 			}
 			return;
 		}
@@ -981,6 +1005,11 @@ struct SearchWave {
 	// row entry k of the chain of lane l in group seg (ROWS kernels)
 	// short_row: the row has at most two entries (the candidate belongs to phase 4's half of the list)
 	__device__ __forceinline__ uint32_t row_entry(int seg, int k, int l, bool short_row) const {
+		if constexpr (LAYOUT == 2) {
+			if (k == 0) return pr_lo[4 * (seg * 64 + l) + 3];
+			const uint32_t x = rowstore[(size_t)seg * 64 + l];
+			return short_row ? x : X.rows[(size_t)x + (uint32_t)k];
+		}
 		if constexpr (LAYOUT == 1) {
 			if (k == 0) return rowstore[(size_t)(NSEG + seg) * 64 + l];
 			const uint32_t x = rowstore[(size_t)seg * 64 + l];
@@ -1058,13 +1087,15 @@ __global__ __launch_bounds__(64, SEARCH_WAVES_PER_EU(NCH)) void search_se_kernel
 	static_assert(PART == 0 || (!OVF && !DBG && ROWS == 1), "phase 3 is parked by the production first pass only");
 	// stats != nullptr (URMAPX_PHASE_STATS): per-phase shader cycles are accumulated into stats (u64 each, from byte 8)
 	static_assert(KCH == NCH || (ROWS == 2 && PART == 0 && !OVF && !DBG), "fewer k-mer chunks: the production first pass on the slot16 layout");
-	using SW = SearchWave<NCH, OVF, ROWS == 2 ? 1 : 0, KCH>;
+	// the row store in LDS (see KCH above); those instances take a k-mer's slot16 entry with one 12-byte LDS-DMA (SearchWave: LAYOUT 2)
+	constexpr bool RS_LDS = KCH < NCH || (NCH == 2 && ROWS == 2 && PART == 0 && !OVF && !DBG);
+	using SW = SearchWave<NCH, OVF, ROWS == 2 ? (RS_LDS ? 2 : 1) : 0, KCH>;
 	constexpr int NQ_BYTES = ((SW::QMAX + 4 + 255) / 256) * 256;  // the next read's bytes from a 4-byte aligned address on, in 256-byte DMA pieces
 	__shared__ __attribute__((aligned(16))) uint8_t sQ2[2 * SW::QMAX];  // plus strand, then reverse complement
 	uint8_t *const sQp = sQ2, *const sQm = sQ2 + SW::QMAX;
 	__shared__ __attribute__((aligned(16))) uint4 qpl[2 * 2 * NCH];     // both strands as bit planes (dev_common.h): [strand][block of 32]
 	__shared__ __attribute__((aligned(16))) uint8_t nextQ[NQ_BYTES];
-	__shared__ uint32_t pr_lo[SW::NSEG * 64], pr_hi[SW::NSEG * 64], pr_sl[SW::NSEG * 64];
+	__shared__ uint32_t pr[(RS_LDS ? 4 : 3) * SW::NSEG * 64];  // the slot entries (SearchWave::probe_get): three arrays, or (RS_LDS) cells of four dwords
 	__shared__ uint64_t pr_hb[SW::NSEG];
 	__shared__ uint16_t top[URMAPX_MAX_PATH_OPS];
 	__shared__ __attribute__((aligned(8))) uint16_t pre[2 * SW::NSEG * 64 + 2];
@@ -1079,8 +1110,7 @@ __global__ __launch_bounds__(64, SEARCH_WAVES_PER_EU(NCH)) void search_se_kernel
 	// candidate queue (ring): reference position, query position | plus << 14 | second phase << 15
 	__shared__ __attribute__((aligned(8))) uint32_t cq_db[128];
 	__shared__ uint16_t cq_qp[128];
-	constexpr bool RS_LDS = KCH < NCH || (NCH == 2 && ROWS == 2 && PART == 0 && !OVF && !DBG);
-	__shared__ uint32_t rs_lds[RS_LDS ? 2 * SW::NSEG * 64 : 1];  // the row store (rows_fetch, row_entry)
+	__shared__ uint32_t rs_lds[RS_LDS ? SW::NSEG * 64 : 1];  // the row store (rows_fetch, row_entry); RS_LDS: the second positions / row indexes, the first positions lie in pr's cells
 	// between two gather steps both are idle: the next read's slot numbers are staged there on their way to the pr_* arrays
 	static_assert(SW::NSEG * 64 * 4 <= sizeof(pre) && 2 * SW::NSEG * 8 <= sizeof(cq_db), "staging");
 	uint32_t *const stage_sl = reinterpret_cast<uint32_t *>(pre);
@@ -1096,7 +1126,7 @@ __global__ __launch_bounds__(64, SEARCH_WAVES_PER_EU(NCH)) void search_se_kernel
 	S.sQ[0] = sQp; S.sQ[1] = sQm; S.sT = sT;
 	S.ropsL = ropsL; S.ropsR = ropsR; S.cand = cand; S.top = top; S.pre = pre;
 	S.hsp_db = hsp_db; S.hsp_pk = hsp_pk;
-	S.pr_lo = pr_lo; S.pr_hi = pr_hi; S.pr_sl = pr_sl; S.pr_hb = pr_hb;
+	S.pr_lo = pr; S.pr_hi = pr + SW::NSEG * 64; S.pr_sl = pr + 2 * SW::NSEG * 64; S.pr_hb = pr_hb;
 	{
 		uint8_t *sc = scratch + (size_t)blockIdx.x * scratch_stride;
 		if constexpr (RS_LDS) S.rowstore = rs_lds;
@@ -2053,12 +2083,14 @@ hipError_t launch_pack_seq(const uint8_t *d_seq, uint32_t seq_data_size, uint4 *
 // this table can reach on this device (one 64-byte sector per slot, 6 % of the slots straddle two)
 // ------------------------------------------------------------------------------------------------
 // MODE 0: one 8-byte load per slot (what load_slot does); 1: two 4-byte loads per slot; 2: two 4-byte LDS-DMA loads per
-// slot (what the search kernel's probe_gather does); 3: one 12-byte LDS-DMA load per slot; 4: one 16-byte load per slot.
+// slot (what the search kernel's probe_gather does on an index without slot16); 3: one 12-byte LDS-DMA load per slot; 4: one 16-byte
+// load per slot.  5 and 6: the slot16 address shape -- a 16-byte aligned entry, entries 16 bytes apart, over the same table -- as
+// three 4-byte LDS-DMA loads per entry (at +0, +4 and +8), or as one 12-byte LDS-DMA load per entry (probe_gather on slot16).
 // The slot rate of each mode says whether random access is priced per sector or per request.
 template <int MODE>
 __global__ __launch_bounds__(256) void gather_bench_kernel(const uint8_t *__restrict__ blob, uint64_t slot_count,
                                                            uint64_t magic, uint32_t iters, uint32_t *sink) {
-	__shared__ uint32_t dst[MODE == 2 ? 4 * 8 * 2 * 64 : (MODE == 3 ? 4 * 8 * 3 * 64 : 1)];
+	__shared__ uint32_t dst[MODE == 2 ? 4 * 8 * 2 * 64 : (MODE == 5 ? 4 * 8 * 3 * 64 : (MODE == 3 || MODE == 6 ? 4 * 8 * 4 * 64 : 1))];  // (a 12-byte LDS-DMA fills 16-byte cells)
 	uint64_t x = murmur64(((uint64_t)blockIdx.x << 20) + threadIdx.x + 1);
 	uint32_t acc = 0;
 	const int wv = threadIdx.x >> 6;
@@ -2088,23 +2120,22 @@ __global__ __launch_bounds__(256) void gather_bench_kernel(const uint8_t *__rest
 			             "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3]), "+v"(hi[4]), "+v"(hi[5]), "+v"(hi[6]), "+v"(hi[7])::"memory");
 #pragma unroll
 			for (int u = 0; u < 8; ++u) acc += lo[u] ^ hi[u];
-		} else if constexpr (MODE == 2 || MODE == 3) {
+		} else if constexpr (MODE == 2 || MODE == 3 || MODE == 5 || MODE == 6) {
 			constexpr int PER = MODE == 2 ? 2 : 3;
 #pragma unroll
 			for (int u = 0; u < 8; ++u) {
 				x = murmur64(x + 0x9E3779B97F4A7C15ull);
-				const uint8_t *a = blob + ((5ull * mod_slots(x, slot_count, magic)) & ~3ull);
-				if constexpr (MODE == 2) {
+				const uint8_t *a = blob + ((5ull * mod_slots(x, slot_count, magic)) & (MODE >= 5 ? ~15ull : ~3ull));
+				if constexpr (MODE == 2 || MODE == 5) {
 					glds_dword(a, lds_addr(dst + ((wv * 8 + u) * PER + 0) * 64));
 					glds_dword(a + 4, lds_addr(dst + ((wv * 8 + u) * PER + 1) * 64));
+					if constexpr (MODE == 5) glds_dword(a + 8, lds_addr(dst + ((wv * 8 + u) * PER + 2) * 64));
 				} else {
-					unsigned keep;
-					asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx3 %1, off\n\ts_mov_b32 m0, %0"
-					             : "=&s"(keep) : "v"(a), "s"(lds_addr(dst + (wv * 8 + u) * PER * 64)) : "memory");
+					glds_dwordx3(a, lds_addr(dst + (wv * 8 + u) * 4 * 64));
 				}
 			}
 			wait_vm0();
-			acc += dst[(wv * 8 * PER) * 64 + (threadIdx.x & 63) + (i & 7) * 64];
+			acc += dst[(wv * 8 * (MODE == 3 || MODE == 6 ? 4 : PER)) * 64 + (threadIdx.x & 63) + (i & 7) * 64];
 		} else {
 			uint4 v[8];
 #pragma unroll
@@ -2126,6 +2157,8 @@ hipError_t launch_gather_bench(const DevIndex &X, uint32_t blocks, uint32_t iter
 	else if (mode == 2) hipLaunchKernelGGL(gather_bench_kernel<2>, dim3(blocks), dim3(256), 0, s, X.blob, X.slotCount, X.slotMagic, iters, d_sink);
 	else if (mode == 3) hipLaunchKernelGGL(gather_bench_kernel<3>, dim3(blocks), dim3(256), 0, s, X.blob, X.slotCount, X.slotMagic, iters, d_sink);
 	else if (mode == 4) hipLaunchKernelGGL(gather_bench_kernel<4>, dim3(blocks), dim3(256), 0, s, X.blob, X.slotCount, X.slotMagic, iters, d_sink);
+	else if (mode == 5) hipLaunchKernelGGL(gather_bench_kernel<5>, dim3(blocks), dim3(256), 0, s, X.blob, X.slotCount, X.slotMagic, iters, d_sink);
+	else if (mode == 6) hipLaunchKernelGGL(gather_bench_kernel<6>, dim3(blocks), dim3(256), 0, s, X.blob, X.slotCount, X.slotMagic, iters, d_sink);
 	else hipLaunchKernelGGL(gather_bench_kernel<0>, dim3(blocks), dim3(256), 0, s, X.blob, X.slotCount, X.slotMagic, iters, d_sink);
 	return hipGetLastError();
 }
