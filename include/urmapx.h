@@ -441,7 +441,7 @@ typedef struct urmapx_map_options {
 	                     * without bam_sort */
 	const char *depth_out; /* -depth (with bam_sort): a bedGraph file of the per-base depth of the records as the BAM file holds them --
 	                     * under markdup without the duplicates --, taken on first_gpu while the records lie there for the sort (see "Depth"
-	                     * below; urmapx_bam_sort_depth, on the host road urmapx_bam_sort_depth_host).  The BAM file and its index are those
+	                     * below; urmapx_bam_sort_with, on the host road urmapx_bam_sort_with_host).  The BAM file and its index are those
 	                     * of the run without it but for the @PG line.  The depth arrays come off sort_mem (or off what is free) before the
 	                     * sort is planned; URMAPX_E_NOMEM naming the least budget where they do not fit.  The totals go to the report, the
 	                     * table per reference to urmapx_map_depth_summary.  NULL: none.  URMAPX_E_ARG without bam_sort, and for a name
@@ -456,7 +456,7 @@ typedef struct urmapx_map_options {
 	                     * A failed run removes the file with the others */
 	const char *vcf_out;   /* -vcfout (with bam_sort): a sites-only VCF 4.2 file of the columns where the records as the BAM file holds them --
 	                     * under markdup without the marked duplicates -- show a base other than the reference's (see "Pileup" below),
-	                     * counted on first_gpu where the depth is taken (urmapx_bam_sort_with2, on the host road urmapx_bam_sort_with2_host).
+	                     * counted on first_gpu where the depth is taken (urmapx_bam_sort_with, on the host road urmapx_bam_sort_with_host).
 	                     * The reference bases are the index's sequence store, read in place where it is resident on first_gpu and fetched
 	                     * once (urmapx_index_fetch_spans) where it is not.  Its ##urmapCommand line carries cmdline.  The BAM file and its
 	                     * index are those of the run without it but for the @PG line.  The counters (16 bytes a reference base) come off
@@ -882,7 +882,7 @@ int urmapx_bam_sort_external(int device, uint64_t budget_bytes, const void *reco
  * The input is BAM records as above, in any order, n_ref reference names (C strings of 1 .. 255 bytes: the names of the @SQ lines) and
  * their lengths l_ref.  The rule is `samtools depth` without -J, -s and base-quality filters; the result is exact.
  *  1. Eligible: a record with 0 <= refID < n_ref, pos >= 0, (flag & 0x704) == 0 -- not unmapped, secondary, QC-fail or duplicate -- and
- *     MAPQ >= min_mapq.  The flag is the one the record carries; inside urmapx_bam_sort_depth it is the one the record carries in the
+ *     MAPQ >= min_mapq.  The flag is the one the record carries; inside urmapx_bam_sort_with it is the one the record carries in the
  *     sorted stream, so under marking bit 0x400 is the marking's decision, not the incoming bit.  Supplementary records (0x800) count.
  *  2. Covered columns: the CIGAR is walked with a reference cursor c that starts at pos.  M, = and X of length L cover the columns
  *     [c, c + L) that lie in [0, l_ref) and advance c by L; D and N advance c and cover nothing; I, S, H and P do nothing.  Columns
@@ -903,12 +903,12 @@ int urmapx_bam_sort_external(int device, uint64_t budget_bytes, const void *reco
  * of the array at a time, and their lines are made in slices of 65 536 runs (URMAPX_TEST_DEPTH_SLICE=N: of N) that are copied back
  * while the next one is formatted.  urmapx_bam_depth_host (depth_host.cpp, written apart from it: a difference array and a running
  * sum in plain loops) gives the same bytes and numbers.  starts / n_starts: as for the sort.
- * urmapx_bam_sort_depth is urmapx_bam_sort_external with the depth taken while the records are on the device: in core by one launch
- * over the unsorted records once the marking has decided, on the external road on the chunks of the first placing pass, where the
- * marking's decisions lie complete beside the records.  The depth arrays (urmapx_bam_depth_resident_bytes) come off the budget before the
- * sort is planned; a budget that does not hold them is URMAPX_E_NOMEM, and depth->least_budget then names the least budget that does.
- * depth NULL: urmapx_bam_sort_external itself (dopts, names and lens unused).  urmapx_bam_sort_depth_host: the host sort (with marking
- * when md is given) and urmapx_bam_depth_host of its stream.
+ * urmapx_bam_sort_with ("The planned sort with what is taken on the way" below) takes the depth while the records are on the device
+ * for the sort: in core by one launch over the unsorted records once the marking has decided, on the external road on the chunks of
+ * the first placing pass, where the marking's decisions lie complete beside the records.  The depth arrays
+ * (urmapx_bam_depth_resident_bytes) come off the budget before the sort is planned; a budget that does not hold them is
+ * URMAPX_E_NOMEM, and depth->least_budget then names the least budget that does.  urmapx_bam_sort_with_host: the host sort (with
+ * marking when md is given) and urmapx_bam_depth_host of its stream.
  * URMAPX_E_ARG: a name that is empty or longer than 255 bytes, 2^31 records or more; else the sort's codes. */
 typedef struct urmapx_depth_opts {
 	uint32_t min_mapq;
@@ -925,7 +925,7 @@ typedef struct urmapx_depth_result {
 	uint32_t text_slices;    /* device: pieces the text was formatted and copied back in */
 	uint64_t records;        /* records seen, eligible or not */
 	uint64_t stage_chunks;   /* urmapx_bam_depth: staged chunks of its pass over the input */
-	uint64_t least_budget;   /* urmapx_bam_sort_depth under URMAPX_E_NOMEM from the budget: the least budget_bytes that holds the call */
+	uint64_t least_budget;   /* urmapx_bam_sort_with under URMAPX_E_NOMEM from the budget: the least budget_bytes that holds the call */
 	double alloc_s, count_s, scan_s, runs_s, format_s, copy_s;  /* device arrays; staging and depth_count_kernel (host: the CIGAR walk);
 	                          * the scan (host: the running sum and the runs); boundary flags, compaction and the summaries; the lines;
 	                          * the lines back to the host (inside no other part) */
@@ -938,14 +938,8 @@ void urmapx_depth_free(urmapx_depth_result *);
 /* device memory urmapx_bam_depth takes for references of total_columns columns in all and n_records records, with staged chunks of
  * the default size (the sum its allocations follow: depth.h) */
 uint64_t urmapx_bam_depth_device_bytes(uint64_t total_columns, uint32_t n_ref, uint64_t n_records);
-/* what of that urmapx_bam_sort_depth adds to the sort: no staging buffers and no record starts of its own */
+/* what of that the depth adds to urmapx_bam_sort_with: no staging buffers and no record starts of its own */
 uint64_t urmapx_bam_depth_resident_bytes(uint64_t total_columns, uint32_t n_ref);
-int urmapx_bam_sort_depth(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
-                          const uint64_t *starts, size_t n_starts, urmapx_markdup_stats *md, const urmapx_depth_opts *dopts,
-                          const char *const *names, const uint32_t *lens, urmapx_depth_result *depth, urmapx_bam_sort_result *out);
-int urmapx_bam_sort_depth_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
-                               size_t n_starts, urmapx_markdup_stats *md, const urmapx_depth_opts *dopts, const char *const *names,
-                               const uint32_t *lens, urmapx_depth_result *depth, urmapx_bam_sort_result *out);
 
 /* ---- Stats (alignment QC tables of BAM records, as a tab-separated text) ----
  * The input is BAM records as above, in any order, and the n_ref reference names and lengths (as for the depth).  Every counter is 64
@@ -1017,31 +1011,12 @@ int urmapx_bam_stats_host(const void *records, size_t n_bytes, uint32_t n_ref, c
 void urmapx_stats_free(urmapx_stats_result *);
 /* device bytes of the statistics' tables: what they add to the planned sort (the sum the allocation follows: stats.h) */
 uint64_t urmapx_bam_stats_resident_bytes(uint32_t n_ref);
-/* The planned sort with what is taken on the way.  md NULL: no marking.  depth NULL: no depth (dopts unused).  stats NULL: no
- * statistics (stats_command unused).  names and lens: needed with depth or stats.  With neither this is urmapx_bam_sort_external, with
- * depth alone urmapx_bam_sort_depth.  The statistics are taken where the depth is -- in core by one launch over the unsorted records
- * once the marking has decided, on the external road on the chunks of the first placing pass -- and their tables come off the budget
- * with the depth's before the sort is planned; under URMAPX_E_NOMEM from the budget both results' least_budget name the least budget
- * that holds the call.  _host: the host sort (with marking when md is given) and the host versions on its records. */
-typedef struct urmapx_bam_sort_extras {
-	urmapx_markdup_stats *md;
-	const urmapx_depth_opts *dopts;
-	const char *const *names;
-	const uint32_t *lens;
-	urmapx_depth_result *depth;
-	urmapx_stats_result *stats;
-	const char *stats_command;
-} urmapx_bam_sort_extras;
-int urmapx_bam_sort_with(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
-                         const uint64_t *starts, size_t n_starts, const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out);
-int urmapx_bam_sort_with_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
-                              size_t n_starts, const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out);
 
 /* ---- Pileup (SNV candidate sites of BAM records against the reference bases, as a sites-only VCF 4.2 text) ----
  * The input is BAM records as above, in any order, the n_ref reference names and lengths (as for the depth) and the reference bases,
  * lens[r] ASCII letters per reference.  Every rule is exact integer arithmetic and no count depends on the order of the records.
  *  1. Which records count: exactly the depth's (items 1-2 of "Depth").  The record has a reference (0 <= refID < n_ref) and a position
- *     (pos >= 0), none of the flags 0x704 as the file carries them -- inside urmapx_bam_sort_with2 under marking bit 0x400 is the
+ *     (pos >= 0), none of the flags 0x704 as the file carries them -- inside urmapx_bam_sort_with under marking bit 0x400 is the
  *     marking's decision, not the incoming bit (on the external road the action byte stands in) --, and its MAPQ is at least min_mapq
  *     (default 0).  Supplementary records (0x800) count.  A record whose CIGAR, SEQ and QUAL do not lie inside its block_size counts
  *     as a record and adds no base.
@@ -1083,7 +1058,7 @@ typedef struct urmapx_pileup_result {
 	size_t text_bytes;
 	uint64_t sites, alt_alleles, records;  /* lines behind the header; ALT entries over all lines; records that counted (rule 1) */
 	uint64_t stage_chunks;   /* urmapx_bam_pileup: staged chunks of its pass over the input */
-	uint64_t least_budget;   /* urmapx_bam_sort_with2 under URMAPX_E_NOMEM from the budget: the least budget_bytes that holds the call */
+	uint64_t least_budget;   /* urmapx_bam_sort_with under URMAPX_E_NOMEM from the budget: the least budget_bytes that holds the call */
 	double alloc_s, count_s, sites_s, format_s, copy_s;  /* device arrays; staging and pileup_count_kernel (host: the walk); the site
 	                          * kernels (host: the scan of the columns); the text; waiting for the slices' copies */
 } urmapx_pileup_result;
@@ -1099,13 +1074,18 @@ void urmapx_pileup_free(urmapx_pileup_result *);
 uint64_t urmapx_bam_pileup_resident_bytes(uint64_t total_columns, uint32_t n_ref, int seq_resident);
 /* what urmapx_bam_pileup takes: those with the upload, the record starts and two staging buffers */
 uint64_t urmapx_bam_pileup_device_bytes(uint64_t total_columns, uint32_t n_ref, uint64_t n_records);
-/* urmapx_bam_sort_with with the pileup: the seven fields of urmapx_bam_sort_extras in their order, then the pileup's.  pileup NULL: no
- * pileup, and the call is urmapx_bam_sort_with.  The reference bases: seqs (as above), or, with seqs NULL, index: its sequence store,
- * read in place where it is resident on `device`, else fetched once through urmapx_index_fetch_spans and uploaded; its sequence count
- * and lengths must be n_ref and lens (URMAPX_E_ARG).  The pileup is taken where the depth and the statistics are, and its arrays come
- * off the budget with theirs; under URMAPX_E_NOMEM from the budget every result's least_budget names the least budget that holds the
- * call.  _host: the host sort and the host versions on its records. */
-typedef struct urmapx_bam_sort_extras2 {
+
+/* ---- The planned sort with what is taken on the way ----
+ * urmapx_bam_sort_external with the depth, the statistics and the pileup, each or none, taken while the records are on the device: in
+ * core by their launches over the unsorted records once the marking has decided, on the external road on the chunks of the first
+ * placing pass.  md NULL: no marking.  depth NULL: no depth (dopts unused).  stats NULL: no statistics (stats_command unused).  pileup
+ * NULL: no pileup (popts, seqs, index and pileup_command unused).  names and lens: needed with any of the three.  With none this is
+ * urmapx_bam_sort_external.  The pileup's reference bases: seqs (as for urmapx_bam_pileup), or, with seqs NULL, index: its sequence
+ * store, read in place where it is resident on `device`, else fetched once through urmapx_index_fetch_spans and uploaded; its
+ * sequence count and lengths must be n_ref and lens (URMAPX_E_ARG).  The arrays of what is asked for come off the budget before the
+ * sort is planned; under URMAPX_E_NOMEM from the budget the least_budget of every result asked for names the least budget that holds
+ * the call.  _host: the host sort (with marking when md is given) and the host versions on its records. */
+typedef struct urmapx_bam_sort_extras {
 	urmapx_markdup_stats *md;
 	const urmapx_depth_opts *dopts;
 	const char *const *names;
@@ -1118,11 +1098,11 @@ typedef struct urmapx_bam_sort_extras2 {
 	const urmapx_index *index;
 	urmapx_pileup_result *pileup;
 	const char *pileup_command;
-} urmapx_bam_sort_extras2;
-int urmapx_bam_sort_with2(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
-                          const uint64_t *starts, size_t n_starts, const urmapx_bam_sort_extras2 *extras, urmapx_bam_sort_result *out);
-int urmapx_bam_sort_with2_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
-                               size_t n_starts, const urmapx_bam_sort_extras2 *extras, urmapx_bam_sort_result *out);
+} urmapx_bam_sort_extras;
+int urmapx_bam_sort_with(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
+                         const uint64_t *starts, size_t n_starts, const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out);
+int urmapx_bam_sort_with_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
+                              size_t n_starts, const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out);
 
 const char *urmapx_strerror(int code);
 /* "gfx950" etc. of the ctx's device; NULL without a device */

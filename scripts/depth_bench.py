@@ -4,7 +4,7 @@
   The reads (the generator, genome and mapping of scripts/markdup_bench.py) are mapped ONCE in this process to raw BAM records, as a lane
   hands them to -sort.  Then, on these same kept records and in this same process, the planned device sort with marking
   (urmapx_bam_sort_external, what -sort -markdup runs) is called --rounds times without the depth and --rounds times with it
-  (urmapx_bam_sort_depth), taking turns (a drift of the machine falls on both alike), after one warm-up of each.  Without the depth the
+  (urmapx_bam_sort_with), taking turns (a drift of the machine falls on both alike), after one warm-up of each.  Without the depth the
   call runs no line of the depth's code.
       wall_s of both: median, min, max; added_wall_s: with minus without, median of the rounds' differences
       depth_parts_s: alloc, count, scan, runs, format, copy of the depth result, each median, min, max

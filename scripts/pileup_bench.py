@@ -4,14 +4,14 @@
   The reads (the generator, genome and mapping of scripts/markdup_bench.py) are mapped ONCE in this process to raw BAM records, as a lane
   hands them to -sort.  Then, on these same kept records and in this same process, the planned device sort with marking
   (urmapx_bam_sort_external, what -sort -markdup runs) is called --rounds times without the pileup, --rounds times with it
-  (urmapx_bam_sort_with2; the bases are the index's resident sequence store, read in place) and --rounds times with the depth, the
+  (urmapx_bam_sort_with; the bases are the index's resident sequence store, read in place) and --rounds times with the depth, the
   statistics and the pileup together, taking turns (a drift of the machine falls on all alike), after one warm-up of each.  Without
   the pileup the call runs no line of its code.
       wall_s of the first two: median, min, max; added_wall_s: with minus without, median of the rounds' differences
       pileup_parts_s: alloc, count, sites, format, copy of the pileup's result, each median, min, max; in core count_s is the one
           launch of pileup_count_kernel over all records and the wait for it
       increments: with min_baseq 0 and reads without N every covered base of every counted record is one atomic add, and their number
-          is the depth's sum of bases (urmapx_bam_sort_depth on the same records); --rounds more sorts with the pileup at min_baseq 0
+          is the depth's sum of bases (urmapx_bam_sort_with on the same records); --rounds more sorts with the pileup at min_baseq 0
           give increments_per_s and added_bytes_per_s (4 bytes an increment) against their count_s (median).  At the default floor
           of 13 fewer bases count; that count_s is the one in pileup_parts_s
       counter_bytes and sites_bytes_per_s: the counters' 16 bytes a column over sites_s (median)

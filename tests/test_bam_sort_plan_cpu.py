@@ -138,7 +138,7 @@ def test_sort_mem_through_the_pipeline_under_the_sanitizers(san, tmp_path):  # n
     assert rc == 1 and "sort_mem needs bam_sort" in text
 
 
-IN_CORE, MARKING, PLANNED, DEPTH = "urmapx_bam_sort", "urmapx_bam_sort_markdup", "urmapx_bam_sort_external", "urmapx_bam_sort_depth"
+IN_CORE, MARKING, PLANNED, DEPTH = "urmapx_bam_sort", "urmapx_bam_sort_markdup", "urmapx_bam_sort_external", "urmapx_bam_sort_with"
 G = 1 << 30
 # options, the device-sort calls the stand-in refuses, the calls it then sees (entry, budget; None: an in-core entry), does the run end well
 LADDER = [

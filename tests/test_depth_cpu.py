@@ -121,7 +121,7 @@ def duplicated_input():
 
 
 def test_the_host_twin_counts_the_flags_as_written():
-    """urmapx_bam_sort_depth_host under marking = urmapx_bam_depth_host of the inflated sorted, marked stream; the BAM bytes and the
+    """urmapx_bam_sort_with_host with the depth under marking = urmapx_bam_depth_host of the inflated sorted, marked stream; the BAM bytes and the
     index are those of the call without depth"""
     records, names, lens = duplicated_input()
     members, bai, depth, rep = api.bam_sort_host(records, 3, markdup=True, depth=(names, lens), report=True)

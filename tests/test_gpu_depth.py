@@ -1,4 +1,4 @@
-"""GPU: per-base depth on the device (urmapx_bam_depth, urmapx_bam_sort_depth; depth.hip) against the host version (depth_host.cpp) and the
+"""GPU: per-base depth on the device (urmapx_bam_depth, urmapx_bam_sort_with; depth.hip) against the host version (depth_host.cpp) and the
 model of tests/depth_lib.py: text bytes, run count and summaries, at the edges of the kernels' grids, tiles, segments and slices."""
 import ctypes as C
 import os

@@ -1,4 +1,4 @@
-"""GPU: the pileup on the device (urmapx_bam_pileup, urmapx_bam_sort_with2; pileup.hip) against the host version (pileup_host.cpp)
+"""GPU: the pileup on the device (urmapx_bam_pileup, urmapx_bam_sort_with; pileup.hip) against the host version (pileup_host.cpp)
 and the model of tests/pileup_lib.py, byte for byte: at the edges of the persistent grid, of the 64 lanes and the nibbles, of the CIGAR
 sharing, of the references, of the segments and slices of the site search, with counter offsets past 2^32 bytes, beside the sort on
 both its roads, and through urmapx_map_files.  Columns beyond 2^32 are not tested: their counters alone would take 64 GiB."""

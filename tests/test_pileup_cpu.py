@@ -241,16 +241,16 @@ def test_structs_and_the_memory_sum_in_step_with_the_header():
     assert [n for n, _ in api.PileupResult._fields_] == ["text", "text_bytes", "sites", "alt_alleles", "records", "stage_chunks", "least_budget", "alloc_s",
                                                          "count_s", "sites_s", "format_s", "copy_s"]
     assert C.sizeof(api.PileupResult) == 96 and api.PileupResult.alloc_s.offset == 56 and C.sizeof(api.PileupOpts) == 16
-    assert C.sizeof(api.BamSortExtras) == 56 and len(api.BamSortExtras._fields_) == 7
-    assert [n for n, _ in api.BamSortExtras2._fields_] == [n for n, _ in api.BamSortExtras._fields_] + ["popts", "seqs", "index", "pileup", "pileup_command"]
-    assert C.sizeof(api.BamSortExtras2) == 96 and api.BamSortExtras2.popts.offset == 56
+    assert [n for n, _ in api.BamSortExtras._fields_] == ["md", "dopts", "names", "lens", "depth", "stats", "stats_command", "popts", "seqs", "index", "pileup",
+                                                          "pileup_command"]
+    assert C.sizeof(api.BamSortExtras) == 96 and api.BamSortExtras.popts.offset == 56 and api.BamSortExtras.stats_command.offset == 48
     assert C.sizeof(api.MapOptionsPileup) == C.sizeof(api.MapOptionsStats) + 24 and api.MapOptionsPileup.vcf_out.offset == C.sizeof(api.MapOptionsStats)
     assert C.sizeof(api.MapReportPileup) == C.sizeof(api.MapReportStats) + 32 and api.MapReportPileup.pileup_s.offset == C.sizeof(api.MapReportStats)
     header = open(os.path.join(ROOT, "include", "urmapx.h")).read()
     for struct, words in (("urmapx_pileup_result", ("*text;", "text_bytes;", "sites,", "alt_alleles,", "records;", "stage_chunks;", "least_budget;", "alloc_s,", "count_s,",
                                                     "sites_s,", "format_s,", "copy_s;")),
-                          ("urmapx_bam_sort_extras2", ("*md;", "*dopts;", "*names;", "*lens;", "*depth;", "*stats;", "*stats_command;", "*popts;", "*seqs;", "*index;",
-                                                       "*pileup;", "*pileup_command;")),
+                          ("urmapx_bam_sort_extras", ("*md;", "*dopts;", "*names;", "*lens;", "*depth;", "*stats;", "*stats_command;", "*popts;", "*seqs;", "*index;",
+                                                      "*pileup;", "*pileup_command;")),
                           ("urmapx_pileup_opts", ("min_mapq,", "min_baseq,", "min_alt,", "min_pct;"))):
         body = header[header.index("typedef struct " + struct + " {"):header.index("} " + struct + ";")]
         at = [body.index(w) for w in words]

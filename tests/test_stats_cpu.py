@@ -243,14 +243,18 @@ def test_structs_and_the_memory_sum_in_step_with_the_header():
     assert [n for n, _ in api.StatsResult._fields_] == ["text", "text_bytes", "records", "reads", "mapped", "properly_paired", "duplicated", "insert_median",
                                                         "stage_chunks", "least_budget", "alloc_s", "count_s", "format_s"]
     assert C.sizeof(api.StatsResult) == 104 and api.StatsResult.alloc_s.offset == 80
-    assert [n for n, _ in api.BamSortExtras._fields_] == ["md", "dopts", "names", "lens", "depth", "stats", "stats_command"] and C.sizeof(api.BamSortExtras) == 56
+    # the one struct of what the planned sort takes on the way: twelve fields, the statistics' command at 48, the pileup's from 56 on
+    assert [n for n, _ in api.BamSortExtras._fields_] == ["md", "dopts", "names", "lens", "depth", "stats", "stats_command", "popts", "seqs", "index", "pileup",
+                                                          "pileup_command"]
+    assert C.sizeof(api.BamSortExtras) == 96 and api.BamSortExtras.stats_command.offset == 48 and api.BamSortExtras.popts.offset == 56
     header = open(os.path.join(ROOT, "include", "urmapx.h")).read()
     body = header[header.index("typedef struct urmapx_stats_result"):header.index("} urmapx_stats_result;")]
     at = [body.index(w) for w in ("*text;", "text_bytes;", "records,", " reads,", "insert_median;", "stage_chunks;", "least_budget;", "alloc_s,")]
     assert at == sorted(at) and "Stats (alignment QC tables" in header
-    body = header[header.index("typedef struct urmapx_bam_sort_extras"):header.index("} urmapx_bam_sort_extras;")]
-    at = [body.index(w) for w in ("*md;", "*dopts;", "*names;", "*lens;", "*depth;", "*stats;", "*stats_command;")]
-    assert at == sorted(at)
+    body = header[header.index("typedef struct urmapx_bam_sort_extras {"):header.index("} urmapx_bam_sort_extras;")]
+    at = [body.index(w) for w in ("*md;", "*dopts;", "*names;", "*lens;", "*depth;", "*stats;", "*stats_command;", "*popts;", "*seqs;", "*index;", "*pileup;",
+                                  "*pileup_command;")]
+    assert at == sorted(at) and body.count(";") == 12
     # the tables: 64 SN words, MQ, GC, ID, IS, RL, BC, both quality tables, three words a reference and three more
     words = 64 + 256 + 104 + 2 * 257 + 3 * 8001 + 2 * 65536 + 6 * 1025 + 2 * 94 * 1025
     assert api.bam_stats_resident_bytes(0) == 8 * (words + 3) + 4096 and api.bam_stats_resident_bytes(1000) - api.bam_stats_resident_bytes(0) == 24000

@@ -46,11 +46,10 @@ EXPORTS = (
     "urmapx_bam_sort_markdup", "urmapx_bam_sort_markdup_host", "urmapx_bam_sort_markdup_device_bytes",
     "urmapx_bam_sort_plan_for", "urmapx_bam_sort_external",
     "urmapx_bam_depth", "urmapx_bam_depth_host", "urmapx_depth_free", "urmapx_bam_depth_device_bytes", "urmapx_bam_depth_resident_bytes",
-    "urmapx_bam_sort_depth", "urmapx_bam_sort_depth_host", "urmapx_map_depth_summary",
+    "urmapx_map_depth_summary",
     "urmapx_bam_stats", "urmapx_bam_stats_host", "urmapx_stats_free", "urmapx_bam_stats_resident_bytes",
-    "urmapx_bam_sort_with", "urmapx_bam_sort_with_host",
     "urmapx_bam_pileup", "urmapx_bam_pileup_host", "urmapx_pileup_free", "urmapx_bam_pileup_resident_bytes", "urmapx_bam_pileup_device_bytes",
-    "urmapx_bam_sort_with2", "urmapx_bam_sort_with2_host",
+    "urmapx_bam_sort_with", "urmapx_bam_sort_with_host",
     "urmapx_calmd", "urmapx_ref_span", "urmapx_sam_se_tags", "urmapx_sam_pe_tags", "urmapx_bam_se_tags", "urmapx_bam_pe_tags",
     "urmapx_read_group_id", "urmapx_sam_header_rg", "urmapx_bam_header_rg", "urmapx_index_fetch_spans", "urmapx_text_set_tags",
     "urmapx_text_tag_ms", "urmapx_tags_batch",
@@ -192,12 +191,6 @@ class StatsResult(C.Structure):
                 ("least_budget", C.c_uint64), ("alloc_s", C.c_double), ("count_s", C.c_double), ("format_s", C.c_double)]
 
 
-class BamSortExtras(C.Structure):
-    """urmapx_bam_sort_extras: what urmapx_bam_sort_with takes on the way"""
-    _fields_ = [("md", C.POINTER(MarkdupStats)), ("dopts", C.POINTER(DepthOpts)), ("names", C.POINTER(C.c_char_p)), ("lens", C.c_void_p),
-                ("depth", C.POINTER(DepthResult)), ("stats", C.POINTER(StatsResult)), ("stats_command", C.c_char_p)]
-
-
 class PileupOpts(C.Structure):
     _fields_ = [("min_mapq", C.c_uint32), ("min_baseq", C.c_uint32), ("min_alt", C.c_uint32), ("min_pct", C.c_uint32)]
 
@@ -208,10 +201,12 @@ class PileupResult(C.Structure):
                 ("format_s", C.c_double), ("copy_s", C.c_double)]
 
 
-class BamSortExtras2(C.Structure):
-    """urmapx_bam_sort_extras2: BamSortExtras' fields, then the pileup's"""
-    _fields_ = BamSortExtras._fields_ + [("popts", C.POINTER(PileupOpts)), ("seqs", C.POINTER(C.c_char_p)), ("index", C.c_void_p),
-                                         ("pileup", C.POINTER(PileupResult)), ("pileup_command", C.c_char_p)]
+class BamSortExtras(C.Structure):
+    """urmapx_bam_sort_extras: what urmapx_bam_sort_with takes on the way"""
+    _fields_ = [("md", C.POINTER(MarkdupStats)), ("dopts", C.POINTER(DepthOpts)), ("names", C.POINTER(C.c_char_p)), ("lens", C.c_void_p),
+                ("depth", C.POINTER(DepthResult)), ("stats", C.POINTER(StatsResult)), ("stats_command", C.c_char_p),
+                ("popts", C.POINTER(PileupOpts)), ("seqs", C.POINTER(C.c_char_p)), ("index", C.c_void_p), ("pileup", C.POINTER(PileupResult)),
+                ("pileup_command", C.c_char_p)]
 
 
 STATS_FIELDS = ("word_length", "max_ix", "seqdata_size", "slots", "indexed", "not_indexed", "wildcard", "indexed2", "free", "collision",
@@ -872,39 +867,6 @@ def bam_depth_resident_bytes(total_columns, n_ref):
     return int(L.urmapx_bam_depth_resident_bytes(int(total_columns), int(n_ref)))
 
 
-def _bam_sort_depth(fn_name, head, records, n_ref, in_front, report, starts, markdup, depth, depth_mapq):
-    """the planned sort with the depth taken on the way (urmapx_bam_sort_depth, urmapx_bam_sort_depth_host) -> (members, bai, depth
-    result[, report]); the depth result is (text, runs, summaries) and the report holds its fields as depth_*"""
-    src = np.frombuffer(bytes(records), dtype=np.uint8)
-    L = lib()
-    fn = getattr(L, fn_name)
-    fn.argtypes = ([C.c_int, C.c_uint64][:len(head)] + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(MarkdupStats),
-                                                       C.POINTER(DepthOpts), C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(DepthResult), C.POINTER(BamSortResult)])
-    L.urmapx_bam_sort_free.argtypes = [C.POINTER(BamSortResult)]
-    L.urmapx_bam_sort_free.restype = None
-    L.urmapx_depth_free.argtypes = [C.POINTER(DepthResult)]
-    L.urmapx_depth_free.restype = None
-    nm, ln = _depth_refs(n_ref, *depth)
-    st = np.ascontiguousarray(starts if starts is not None else [], dtype=np.uint64)
-    res, md, dres, opts = BamSortResult(), MarkdupStats(), DepthResult(), DepthOpts(int(depth_mapq))
-    rc = fn(*head, src.ctypes.data if len(src) else None, len(src), int(n_ref), int(in_front), st.ctypes.data if len(st) else None, len(st),
-            C.byref(md) if markdup else None, C.byref(opts), nm, ln.ctypes.data if len(ln) else None, C.byref(dres), C.byref(res))
-    if rc != 0:
-        e = UrmapxError(rc, fn_name + (": %d bytes are needed at the least" % dres.least_budget if dres.least_budget else ""))
-        e.least_budget = int(dres.least_budget)
-        raise e
-    try:
-        out = (C.string_at(res.bgzf, res.bgzf_bytes) if res.bgzf_bytes else b"", C.string_at(res.bai, res.bai_bytes), _depth_out(dres, False))
-        rep = {k: getattr(res, k) for k, _ in BamSortResult._fields_ if k not in ("bgzf", "bai")}
-        if markdup:
-            rep.update({k: getattr(md, k) for k, _ in MarkdupStats._fields_})
-        rep.update({"depth_" + k: getattr(dres, k) for k, _ in DepthResult._fields_ if k not in ("text", "refs")})
-    finally:
-        L.urmapx_bam_sort_free(C.byref(res))
-        L.urmapx_depth_free(C.byref(dres))
-    return out + (rep,) if report else out
-
-
 def _bam_stats(fn_name, head, records, n_ref, names, lens, command, report, starts):
     src = np.frombuffer(bytes(records), dtype=np.uint8)
     L = lib()
@@ -944,47 +906,6 @@ def bam_stats_resident_bytes(n_ref):
     L.urmapx_bam_stats_resident_bytes.argtypes = [C.c_uint32]
     L.urmapx_bam_stats_resident_bytes.restype = C.c_uint64
     return int(L.urmapx_bam_stats_resident_bytes(int(n_ref)))
-
-
-def _bam_sort_with(fn_name, head, records, n_ref, in_front, report, starts, markdup, depth, depth_mapq, stats):
-    """the planned sort with the depth and the statistics taken on the way (urmapx_bam_sort_with, urmapx_bam_sort_with_host) ->
-    (members, bai[, depth result], stats text[, report]); the report holds the depth's fields as depth_* and the statistics' as stats_*"""
-    src = np.frombuffer(bytes(records), dtype=np.uint8)
-    L = lib()
-    fn = getattr(L, fn_name)
-    fn.argtypes = ([C.c_int, C.c_uint64][:len(head)] + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(BamSortExtras),
-                                                       C.POINTER(BamSortResult)])
-    for free, kind in (("urmapx_bam_sort_free", BamSortResult), ("urmapx_depth_free", DepthResult), ("urmapx_stats_free", StatsResult)):
-        getattr(L, free).argtypes = [C.POINTER(kind)]
-        getattr(L, free).restype = None
-    nm, ln = _depth_refs(n_ref, *(depth if depth is not None else stats))
-    st = np.ascontiguousarray(starts if starts is not None else [], dtype=np.uint64)
-    res, md, dres, sres, opts = BamSortResult(), MarkdupStats(), DepthResult(), StatsResult(), DepthOpts(int(depth_mapq))
-    ex = BamSortExtras(C.pointer(md) if markdup else None, C.pointer(opts), nm, ln.ctypes.data if len(ln) else None,
-                       C.pointer(dres) if depth is not None else None, C.pointer(sres) if stats is not None else None, None)
-    rc = fn(*head, src.ctypes.data if len(src) else None, len(src), int(n_ref), int(in_front), st.ctypes.data if len(st) else None, len(st),
-            C.byref(ex), C.byref(res))
-    if rc != 0:
-        least = int(sres.least_budget or dres.least_budget)
-        e = UrmapxError(rc, fn_name + (": %d bytes are needed at the least" % least if least else ""))
-        e.least_budget = least
-        raise e
-    try:
-        out = (C.string_at(res.bgzf, res.bgzf_bytes) if res.bgzf_bytes else b"", C.string_at(res.bai, res.bai_bytes))
-        rep = {k: getattr(res, k) for k, _ in BamSortResult._fields_ if k not in ("bgzf", "bai")}
-        if markdup:
-            rep.update({k: getattr(md, k) for k, _ in MarkdupStats._fields_})
-        if depth is not None:
-            out += (_depth_out(dres, False),)
-            rep.update({"depth_" + k: getattr(dres, k) for k, _ in DepthResult._fields_ if k not in ("text", "refs")})
-        if stats is not None:
-            out += (C.string_at(sres.text, sres.text_bytes) if sres.text_bytes else b"",)
-            rep.update({"stats_" + k: getattr(sres, k) for k, _ in StatsResult._fields_ if k != "text"})
-    finally:
-        L.urmapx_bam_sort_free(C.byref(res))
-        L.urmapx_depth_free(C.byref(dres))
-        L.urmapx_stats_free(C.byref(sres))
-    return out + (rep,) if report else out
 
 
 def _pileup_opts(opts):
@@ -1055,28 +976,31 @@ def bam_pileup_device_bytes(total_columns, n_ref, n_records):
     return int(L.urmapx_bam_pileup_device_bytes(int(total_columns), int(n_ref), int(n_records)))
 
 
-def _bam_sort_with2(fn_name, head, records, n_ref, in_front, report, starts, markdup, depth, depth_mapq, stats, pileup):
-    """the planned sort with the depth, the statistics and the pileup taken on the way (urmapx_bam_sort_with2, urmapx_bam_sort_with2_host)
-    -> (members, bai[, depth result][, stats text], VCF text[, report]); the report holds the pileup's fields as pileup_*.  pileup:
+def _bam_sort_with(fn_name, head, records, n_ref, in_front, report, starts, markdup, depth, depth_mapq, stats, pileup):
+    """the planned sort with the depth, the statistics and the pileup, each or none, taken on the way (urmapx_bam_sort_with,
+    urmapx_bam_sort_with_host) -> (members, bai[, depth result][, stats text][, VCF text][, report]); the depth result is (text, runs,
+    summaries), and the report holds the results' fields as depth_*, stats_* and pileup_*.  depth, stats: (names, lens).  pileup:
     (names, lens, seqs, opts); seqs may be an Index, whose sequence store then gives the bases"""
     src = np.frombuffer(bytes(records), dtype=np.uint8)
     L = lib()
     fn = getattr(L, fn_name)
-    fn.argtypes = ([C.c_int, C.c_uint64][:len(head)] + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(BamSortExtras2),
+    fn.argtypes = ([C.c_int, C.c_uint64][:len(head)] + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(BamSortExtras),
                                                        C.POINTER(BamSortResult)])
     for free, kind in (("urmapx_bam_sort_free", BamSortResult), ("urmapx_depth_free", DepthResult), ("urmapx_stats_free", StatsResult),
                        ("urmapx_pileup_free", PileupResult)):
         getattr(L, free).argtypes = [C.POINTER(kind)]
         getattr(L, free).restype = None
-    names, lens, seqs, popts = pileup
-    nm, ln = _depth_refs(n_ref, names, lens)
-    index = seqs.h if isinstance(seqs, Index) else None
-    sq = None if index is not None else _pileup_seqs(n_ref, seqs)
+    nm, ln = _depth_refs(n_ref, *(pileup if pileup is not None else depth if depth is not None else stats)[:2])
+    sq = index = po = None
+    if pileup is not None:
+        index = pileup[2].h if isinstance(pileup[2], Index) else None
+        sq = None if index is not None else _pileup_seqs(n_ref, pileup[2])
+        po = _pileup_opts(pileup[3])
     st = np.ascontiguousarray(starts if starts is not None else [], dtype=np.uint64)
-    res, md, dres, sres, pres, opts, po = BamSortResult(), MarkdupStats(), DepthResult(), StatsResult(), PileupResult(), DepthOpts(int(depth_mapq)), _pileup_opts(popts)
-    ex = BamSortExtras2(C.pointer(md) if markdup else None, C.pointer(opts), nm, ln.ctypes.data if len(ln) else None,
-                        C.pointer(dres) if depth is not None else None, C.pointer(sres) if stats is not None else None, None,
-                        C.pointer(po) if po is not None else None, sq, index, C.pointer(pres), None)
+    res, md, dres, sres, pres, opts = BamSortResult(), MarkdupStats(), DepthResult(), StatsResult(), PileupResult(), DepthOpts(int(depth_mapq))
+    ex = BamSortExtras(C.pointer(md) if markdup else None, C.pointer(opts), nm, ln.ctypes.data if len(ln) else None,
+                       C.pointer(dres) if depth is not None else None, C.pointer(sres) if stats is not None else None, None,
+                       C.pointer(po) if po is not None else None, sq, index, C.pointer(pres) if pileup is not None else None, None)
     rc = fn(*head, src.ctypes.data if len(src) else None, len(src), int(n_ref), int(in_front), st.ctypes.data if len(st) else None, len(st),
             C.byref(ex), C.byref(res))
     if rc != 0:
@@ -1095,8 +1019,9 @@ def _bam_sort_with2(fn_name, head, records, n_ref, in_front, report, starts, mar
         if stats is not None:
             out += (C.string_at(sres.text, sres.text_bytes) if sres.text_bytes else b"",)
             rep.update({"stats_" + k: getattr(sres, k) for k, _ in StatsResult._fields_ if k != "text"})
-        out += (C.string_at(pres.text, pres.text_bytes) if pres.text_bytes else b"",)
-        rep.update({"pileup_" + k: getattr(pres, k) for k, _ in PileupResult._fields_ if k != "text"})
+        if pileup is not None:
+            out += (C.string_at(pres.text, pres.text_bytes) if pres.text_bytes else b"",)
+            rep.update({"pileup_" + k: getattr(pres, k) for k, _ in PileupResult._fields_ if k != "text"})
     finally:
         L.urmapx_bam_sort_free(C.byref(res))
         L.urmapx_depth_free(C.byref(dres))
@@ -1159,34 +1084,24 @@ def bam_sort(records: bytes, n_ref, device=0, bytes_in_front=0, report=False, st
     (urmapx_bam_sort_markdup; markdup.hip), and the report holds the counters and markdup_s.  budget: device bytes the sort may take
     (0: what is free): the call is urmapx_bam_sort_external, which streams the records through the device where they do not fit the
     budget; the report's external, partitions, stage_chunks and stage_s say what it did.  depth=(names, lens) of the n_ref references:
-    the call is urmapx_bam_sort_depth (budget None: 0), the per-base depth of the records as written -- under markdup without the
+    the call is urmapx_bam_sort_with (budget None: 0), the per-base depth of the records as written -- under markdup without the
     duplicates -- is taken while they are on the device, and a third item (text, runs, summaries) comes back, as from bam_depth;
-    depth_mapq: its least MAPQ.  stats=(names, lens): the call is urmapx_bam_sort_with, the alignment statistics of the records as
+    depth_mapq: its least MAPQ.  stats=(names, lens): urmapx_bam_sort_with too, the alignment statistics of the records as
     written are counted where the depth is taken, and their text comes back as one more item behind the depth's (as from bam_stats).
-    pileup=(names, lens, seqs, opts): the call is urmapx_bam_sort_with2, the SNV candidate sites of the records as written are piled up
+    pileup=(names, lens, seqs, opts): urmapx_bam_sort_with too, the SNV candidate sites of the records as written are piled up
     there too, and their VCF text comes back as the last item in front of the report (as from bam_pileup); seqs: a bytes object per
     reference, or an Index, whose sequence store then gives the bases."""
-    if pileup is not None:
-        return _bam_sort_with2("urmapx_bam_sort_with2", (int(device), int(budget or 0)), records, n_ref, bytes_in_front, report, starts, markdup, depth,
-                               depth_mapq, stats, pileup)
-    if stats is not None:
+    if depth is not None or stats is not None or pileup is not None:
         return _bam_sort_with("urmapx_bam_sort_with", (int(device), int(budget or 0)), records, n_ref, bytes_in_front, report, starts, markdup, depth,
-                              depth_mapq, stats)
-    if depth is not None:
-        return _bam_sort_depth("urmapx_bam_sort_depth", (int(device), int(budget or 0)), records, n_ref, bytes_in_front, report, starts, markdup, depth,
-                               depth_mapq)
+                              depth_mapq, stats, pileup)
     return _bam_sort("urmapx_bam_sort", (int(device),), records, n_ref, bytes_in_front, report, starts, markdup, budget)
 
 
 def bam_sort_host(records: bytes, n_ref, bytes_in_front=0, report=False, starts=None, markdup=False, depth=None, depth_mapq=0, stats=None, pileup=None):
     """the same contract on the host, no device (urmapx_bam_sort_host, urmapx_bam_sort_markdup_host): std::stable_sort and zlib inside
-    the BGZF framing.  depth, stats, pileup: as for bam_sort (urmapx_bam_sort_depth_host, urmapx_bam_sort_with_host, urmapx_bam_sort_with2_host)"""
-    if pileup is not None:
-        return _bam_sort_with2("urmapx_bam_sort_with2_host", (), records, n_ref, bytes_in_front, report, starts, markdup, depth, depth_mapq, stats, pileup)
-    if stats is not None:
-        return _bam_sort_with("urmapx_bam_sort_with_host", (), records, n_ref, bytes_in_front, report, starts, markdup, depth, depth_mapq, stats)
-    if depth is not None:
-        return _bam_sort_depth("urmapx_bam_sort_depth_host", (), records, n_ref, bytes_in_front, report, starts, markdup, depth, depth_mapq)
+    the BGZF framing.  depth, stats, pileup: as for bam_sort (urmapx_bam_sort_with_host)"""
+    if depth is not None or stats is not None or pileup is not None:
+        return _bam_sort_with("urmapx_bam_sort_with_host", (), records, n_ref, bytes_in_front, report, starts, markdup, depth, depth_mapq, stats, pileup)
     return _bam_sort("urmapx_bam_sort_host", (), records, n_ref, bytes_in_front, report, starts, markdup)
 
 

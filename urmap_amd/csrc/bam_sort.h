@@ -3,7 +3,6 @@
 // of and the function that writes them down as a .bai file.  Not installed.
 #pragma once
 #include <cstdint>
-#include <functional>
 #include <vector>
 
 #include "../../include/urmapx.h"
@@ -166,12 +165,6 @@ enum : uint8_t { MD_KEEP = 0, MD_SET = 1, MD_CLEAR = 2 };  // what becomes of a 
 // eligible record whose SEQ and QUAL do not lie inside it
 int markdup_host(const uint8_t *rec, const std::vector<uint64_t> &offs, std::vector<uint8_t> &action, urmapx_markdup_stats *md);
 
-// the host sort (urmapx_bam_sort_host, urmapx_bam_sort_markdup_host with md) with a call once the marking has decided: the records as
-// they came, their starts, and what becomes of every record's bit 0x400 (null without marking).  What it returns ends the sort if not 0
-// (urmapx_bam_sort_depth_host takes the depth there)
-using AfterMark = std::function<int(const uint8_t *rec, const std::vector<uint64_t> &offs, const uint8_t *action)>;
-int sort_host_hooked(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts, size_t n_starts,
-                     urmapx_markdup_stats *md, urmapx_bam_sort_result *out, const AfterMark &hook);
 
 }  // namespace bamsort
 }  // namespace urx

@@ -33,6 +33,7 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include <optional>
 
 using namespace urx::bamsort;
 
@@ -391,60 +392,39 @@ uint32_t radix_sort(SortArrays &S, uint32_t n, uint32_t bits, uint32_t *hist) {
 template void scan_launch<uint32_t, uint64_t>(const uint32_t *, uint32_t, uint64_t *, uint64_t *);
 template void scan_launch<uint32_t, uint32_t>(const uint32_t *, uint32_t, uint32_t *, uint64_t *);
 
+int staged_alone(int device, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, const uint64_t *starts, size_t n_starts, Beside &B, uint64_t *stage_chunks,
+                 double *count_s) {
+	std::vector<uint64_t> offs;
+	int rc = urx::depth::scan_for_depth(rec, n_bytes, n_ref, starts, n_starts, offs);
+	if (rc) return rc;
+	const uint32_t n = (uint32_t)(offs.size() - 1);
+	std::vector<uint32_t> cut;
+	uint64_t stage = default_stage_bytes(n_bytes);
+	stage = std::max(stage, cut_chunks(offs.data(), n, stage, false, cut));
+	*stage_chunks = cut.size() - 1;
+
+	HIP_TRY(hipSetDevice(device));
+	Dev<uint64_t> d_off;
+	Dev<uint8_t> d_stage[2];
+	TwoStreams st;
+	// (the pieces the by-products' standalone_bytes count, in their order)
+	if ((rc = B.begin(n)) || (rc = d_off.alloc((size_t)n + 1)) || (rc = d_stage[0].alloc((size_t)stage + 16)) || (rc = d_stage[1].alloc((size_t)stage + 16)) ||
+	    (rc = st.create()))
+		return rc;
+	const auto t = Clock::now();
+	HIP_TRY(hipMemcpy(d_off.p, offs.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+	rc = staged_pass(rec, offs.data(), n, cut, false, stage, d_stage, st, [&](const uint8_t *at, uint64_t base, uint32_t i0, uint32_t i1, hipStream_t s) {
+		return B.count(at, base, d_off.p, i0, i1, nullptr, s);
+	});
+	if (rc) return rc;
+	*count_s = since(t);
+	return B.finish();
+}
+
 }  // namespace bamsort
 }  // namespace urx
 
 namespace {
-
-// the two streams of the external road: a staging buffer's copy and the kernels that read it go to the buffer's own stream, so the
-// kernels of one chunk run while the next chunk is copied
-struct StageStreams {
-	hipStream_t s[2] = {nullptr, nullptr};
-	int create() {
-		for (int b = 0; b < 2; ++b) HIP_TRY(hipStreamCreateWithFlags(&s[b], hipStreamNonBlocking));
-		return URMAPX_OK;
-	}
-	int wait() {
-		for (int b = 0; b < 2; ++b)
-			if (s[b]) HIP_TRY(hipStreamSynchronize(s[b]));
-		return URMAPX_OK;
-	}
-	~StageStreams() {
-		for (int b = 0; b < 2; ++b)
-			if (s[b]) (void)hipStreamDestroy(s[b]);
-	}
-};
-
-// what urmapx_bam_sort_depth adds to the planned sort (include/urmapx.h "Depth"); names and lens are checked (check_refs: entries)
-struct DepthAsk {
-	uint32_t min_mapq;
-	const char *const *names;
-	const uint32_t *lens;
-	uint64_t entries;
-	urmapx_depth_result *out;
-};
-
-// what the statistics add to it (include/urmapx.h "Stats"); names and lens are checked
-struct StatsAsk {
-	const char *const *names;
-	const uint32_t *lens;
-	const char *command;
-	urmapx_stats_result *out;
-};
-
-// what the pileup adds to it (include/urmapx.h "Pileup"); names, lens and the rule are checked.  The bases: seqs on the host, or, with
-// seqs null, d_store on the sort's device with reference r's letters from store_at[r] on
-struct PileupAsk {
-	urx::pileup::Rule R;
-	const char *const *names;
-	const uint32_t *lens;
-	uint64_t columns;
-	const uint8_t *const *seqs;
-	const uint8_t *d_store;
-	const uint64_t *store_at;
-	const char *command;
-	urmapx_pileup_result *out;
-};
 
 // adds the time from where it is made to the end of its scope
 struct Span {
@@ -459,8 +439,8 @@ struct KeyVal { uint64_t *key; uint32_t *val; };  // a key array and the record-
 struct ChunkMarks { uint32_t *flag, *index; };    // per placed record: does a chunk begin here; behind the flags their sums, one more
 
 // One device sort, from the caller's records to the result.  budget == nullptr: the in-core road, whatever it takes (urmapx_bam_sort,
-// urmapx_bam_sort_markdup).  Else the road the plan names for *budget device bytes (urmapx_bam_sort_external), with `dep` for what the
-// depth arrays leave of them (urmapx_bam_sort_depth).  run() lists the stages; a stage returns a code, and the first that is not 0 ends
+// urmapx_bam_sort_markdup).  Else the road the plan names for *budget device bytes (urmapx_bam_sort_external), with `beside` for what
+// their arrays leave of them (urmapx_bam_sort_with).  run() lists the stages; a stage returns a code, and the first that is not 0 ends
 // the run: every member lets go of what it holds.
 struct DeviceSort {
 	// ---- what the caller gave (sort_entry) ----
@@ -473,9 +453,7 @@ struct DeviceSort {
 	const uint64_t *const starts;
 	const size_t n_starts;
 	urmapx_markdup_stats *const md;
-	const DepthAsk *const dep;
-	const StatsAsk *const sta;
-	const PileupAsk *const pil;
+	const std::vector<Beside *> &beside;  // what is taken on the way, in the order depth, statistics, pileup
 	urmapx_bam_sort_result *const out;
 	size_t n_ref1() const { return (size_t)n_ref + 1; }
 	bool look() const { return md != nullptr; }  // the marking compares neighbours: a staged chunk is followed by its successor
@@ -489,7 +467,7 @@ struct DeviceSort {
 	urmapx_bam_sort_plan P{};
 	std::vector<uint32_t> cut;
 	bool ext = false;
-	uint64_t depth_bytes = 0, stats_bytes = 0, pileup_bytes = 0, sort_budget = 0;
+	uint64_t beside_bytes = 0, sort_budget = 0;
 
 	// ---- the device arrays, in the order they are allocated (external_device_bytes counts them in this order) ----
 	// What each holds, stage by stage; "free" means any later stage may take it.
@@ -514,10 +492,7 @@ struct DeviceSort {
 	Dev<uint32_t> d_val[3], d_end, d_hist, d_range, d_ref[4];
 	Dev<Chunk> d_chunks;
 	MarkdupOwn W;
-	urx::depth::DepthOwn DW;
-	urx::stats::StatsOwn SW;
-	urx::pileup::PileupOwn PW;
-	StageStreams st;
+	TwoStreams st;
 	IndexArrays X;
 	// ---- the arrays' later names; each is given in one place ----
 	uint32_t *notes4 = nullptr;  // does record i carry flag 0x4: from keys_kernel to bounds_kernel
@@ -536,8 +511,7 @@ struct DeviceSort {
 	int run() {
 		int rc;
 		if ((rc = scan_chain()) || (rc = choose_road()) || (rc = allocate()) || (rc = upload()) || (rc = sort_by_coordinate()) || (rc = destinations()) ||
-		    (rc = index_arrays()) || (rc = mark_duplicates()) || (rc = depth_in_core()) || (rc = stats_in_core()) ||
-		    (rc = pileup_in_core()) || (rc = sorted_stream()))
+		    (rc = index_arrays()) || (rc = mark_duplicates()) || (rc = beside_in_core()) || (rc = sorted_stream()))
 			return rc;
 		return finish();
 	}
@@ -554,14 +528,11 @@ struct DeviceSort {
 		return URMAPX_OK;
 	}
 
-	// the plan for staged chunks of `stage` bytes; where nothing fits, the least budget is the depth arrays', the statistics' tables',
-	// the pileup's arrays' and the plan's
+	// the plan for staged chunks of `stage` bytes; where nothing fits, the least budget is the by-products' arrays' and the plan's
 	int plan(uint64_t stage) {
 		const int r = plan_with_stage(n_bytes, n, md != nullptr, sort_budget, stage, &P);
-		const uint64_t least = depth_bytes + stats_bytes + pileup_bytes + P.device_bytes;
-		if (r == URMAPX_E_NOMEM && dep) dep->out->least_budget = least;
-		if (r == URMAPX_E_NOMEM && sta) sta->out->least_budget = least;
-		if (r == URMAPX_E_NOMEM && pil) pil->out->least_budget = least;
+		if (r == URMAPX_E_NOMEM)
+			for (Beside *B : beside) *B->least_budget = beside_bytes + P.device_bytes;
 		return r;
 	}
 	// The road.  On the external one the staged chunks, under marking each with the next chunk's first record behind it (first_kernel
@@ -569,22 +540,12 @@ struct DeviceSort {
 	// successor, makes the buffers grow, and the partition is planned again around them
 	int choose_road() {
 		if (budget) {
-			// the depth arrays, the statistics' tables and the pileup's arrays come off the budget before the sort is planned
-			depth_bytes = dep ? urx::depth::resident_bytes(dep->entries, n_ref, urx::depth::text_runs()) : 0u;
-			stats_bytes = sta ? urx::stats::resident_bytes(n_ref) : 0u;
-			pileup_bytes = pil ? urx::pileup::resident_bytes(pil->columns, n_ref, urx::pileup::segment_columns(), urx::pileup::slice_sites(), !pil->seqs) : 0u;
-			const uint64_t own = depth_bytes + stats_bytes + pileup_bytes;
-			sort_budget = *budget > own ? *budget - own : 0u;
+			// the by-products' arrays come off the budget before the sort is planned
+			for (const Beside *B : beside) beside_bytes += B->resident_bytes();
+			sort_budget = *budget > beside_bytes ? *budget - beside_bytes : 0u;
 			if (const int rc = plan(default_stage_bytes(n_bytes))) return rc;
 			if (P.external) {
-				uint64_t need = 0;
-				for (uint64_t i0 = 0; i0 < n;) {
-					const uint64_t i1 = chunk_end(offs.data(), n, i0, P.stage_bytes, look()), seen = look() && i1 < n ? i1 + 1 : i1;
-					cut.push_back((uint32_t)i0);
-					need = std::max(need, offs[seen] - offs[i0]);
-					i0 = i1;
-				}
-				cut.push_back(n);
+				const uint64_t need = cut_chunks(offs.data(), n, P.stage_bytes, look(), cut);
 				if (need > P.stage_bytes)
 					if (const int rc = plan(need)) return rc;
 			}
@@ -599,24 +560,11 @@ struct DeviceSort {
 	int allocate() {
 		int rc;
 		HIP_TRY(hipSetDevice(device));
-		if (dep) {
-			if (n >= 0x7FFFFFFFu) return URMAPX_E_ARG;
-			dep->out->records = n;
+		if (!beside.empty() && n >= 0x7FFFFFFFu) return URMAPX_E_ARG;
+		for (Beside *B : beside) {
 			const double a0 = t_alloc_s;
-			if ((rc = DW.begin(n_ref, dep->names, dep->lens, dep->entries))) return rc;
-			dep->out->alloc_s = t_alloc_s - a0;
-		}
-		if (sta) {
-			if (n >= 0x7FFFFFFFu) return URMAPX_E_ARG;
-			const double a0 = t_alloc_s;
-			if ((rc = SW.begin(n_ref))) return rc;
-			sta->out->alloc_s = t_alloc_s - a0;
-		}
-		if (pil) {
-			if (n >= 0x7FFFFFFFu) return URMAPX_E_ARG;
-			const double a0 = t_alloc_s;
-			if ((rc = PW.begin(n_ref, pil->lens, pil->columns, pil->seqs, pil->d_store, pil->store_at))) return rc;
-			pil->out->alloc_s = t_alloc_s - a0;
+			if ((rc = B->begin(n))) return rc;
+			*B->alloc_s = t_alloc_s - a0;
 		}
 		if (ext) {  // (the pieces external_device_bytes counts, in its order; the partition is not larger than the stream)
 			const size_t part_cap = (size_t)std::min<uint64_t>(P.partition_bytes, n_bytes);
@@ -643,24 +591,11 @@ struct DeviceSort {
 		return URMAPX_OK;
 	}
 
-	// One pass over the input on the external road: chunk c goes to staging buffer c & 1 on that buffer's stream (a plain copy from the
-	// caller's pageable memory: the call returns when the bytes have left it), `launch` queues the chunk's kernels behind it, and the
-	// next chunk's copy runs while they do.  Before a buffer is written again its stream is waited for.
+	// one pass over the input on the external road (staged_pass): its time counts in stage_s
 	template <class Launch>
 	int pass(bool with_successor, Launch &&launch) {
 		const auto t0 = Clock::now();
-		HIP_TRY(hipStreamSynchronize(nullptr));
-		for (size_t c = 0; c + 1 < cut.size(); ++c) {
-			const int b = (int)(c & 1u);
-			const uint32_t i0 = cut[c], i1 = cut[c + 1], seen = with_successor && i1 < n ? i1 + 1u : i1;
-			const uint64_t bytes = offs[seen] - offs[i0];
-			if (bytes > P.stage_bytes) return URMAPX_E_NODEVICE;  // (never: the buffers were sized by these very chunks)
-			HIP_TRY(hipStreamSynchronize(st.s[b]));
-			if (bytes) HIP_TRY(hipMemcpyAsync(d_stage[b].p, rec + offs[i0], (size_t)bytes, hipMemcpyHostToDevice, st.s[b]));
-			if (const int r = launch((const uint8_t *)d_stage[b].p, offs[i0], i0, i1, st.s[b])) return r;
-		}
-		HIP_TRY(hipGetLastError());
-		const int r = st.wait();
+		const int r = staged_pass(rec, offs.data(), n, cut, with_successor, P.stage_bytes, d_stage, st, launch);
 		out->stage_s += since(t0);
 		return r;
 	}
@@ -782,34 +717,17 @@ struct DeviceSort {
 		return markdup_device(A, W, md);
 	}
 
-	// depth, in core: one launch over the records as they came, now that every bit 0x400 is what the file will hold.  (On the external
-	// road the decisions wait in d_action until the records pass again: the first placing pass counts, in partitions)
-	int depth_in_core() {
-		if (!dep || ext) return URMAPX_OK;
-		Span span(dep->out->count_s);
-		if (const int rc = urx::depth::depth_count(DW, d_rec.p, 0, d_off.p, 0, n, nullptr, dep->min_mapq, nullptr)) return rc;
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(nullptr));
-		return URMAPX_OK;
-	}
-
-	// the statistics, in core: beside the depth, on the same records
-	int stats_in_core() {
-		if (!sta || ext) return URMAPX_OK;
-		Span span(sta->out->count_s);
-		if (const int rc = urx::stats::stats_count(SW, d_rec.p, 0, d_off.p, 0, n, nullptr, nullptr)) return rc;
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(nullptr));
-		return URMAPX_OK;
-	}
-
-	// the pileup, in core: beside the depth and the statistics, on the same records
-	int pileup_in_core() {
-		if (!pil || ext) return URMAPX_OK;
-		Span span(pil->out->count_s);
-		if (const int rc = urx::pileup::pileup_count(PW, d_rec.p, 0, d_off.p, 0, n, nullptr, pil->R, nullptr)) return rc;
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(nullptr));
+	// What is taken beside the sort, in core: one by-product after the other, each with its launches over the records as they came,
+	// now that every bit 0x400 is what the file will hold.  (On the external road the decisions wait in d_action until the records pass
+	// again: the first placing pass counts, in partitions)
+	int beside_in_core() {
+		if (ext) return URMAPX_OK;
+		for (Beside *B : beside) {
+			Span span(*B->count_s);
+			if (const int rc = B->count(d_rec.p, 0, d_off.p, 0, n, nullptr, nullptr)) return rc;
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipStreamSynchronize(nullptr));
+		}
 		return URMAPX_OK;
 	}
 
@@ -826,7 +744,7 @@ struct DeviceSort {
 		host_cap = urmapx_bgzf_bound(n_bytes);
 		z.reset((uint8_t *)malloc(host_cap ? host_cap : 1));
 		rc = !z ? URMAPX_E_NOMEM : ext ? partitions() : slices();
-		Z.reset();  // (the compressor's device memory goes before depth_finish asks for its own)
+		Z.reset();  // (the compressor's device memory goes before the by-products' finish() ask for their own)
 		return rc;
 	}
 	// a slice that lies on the device: deflate, copy back
@@ -868,15 +786,13 @@ struct DeviceSort {
 		const uint8_t *const action = md ? d_action.p : nullptr;
 		for (uint64_t p0 = 0; p0 < n_bytes; p0 += P.partition_bytes) {
 			const uint64_t p1 = p0 + P.partition_bytes < n_bytes ? p0 + P.partition_bytes : n_bytes;
-			// (every record crosses the device in each of these passes: the depth, the statistics and the pileup are taken in the first one only)
-			const bool count = dep && p0 == 0, tally = sta && p0 == 0, pile = pil && p0 == 0;
+			// (every record crosses the device in each of these passes: the by-products are taken in the first one only)
 			int r = pass(false, [&](const uint8_t *at, uint64_t base, uint32_t i0, uint32_t i1, hipStream_t s) -> int {
 				hipLaunchKernelGGL(place_kernel, dim3(grid_for(i1 - i0)), dim3(NT), 0, s, at, base, d_off.p, i0, i1, place, action, p0, p1, d_part.p);
-				if (count)
-					if (const int e = urx::depth::depth_count(DW, at, base, d_off.p, i0, i1, action, dep->min_mapq, s)) return e;
-				if (tally)
-					if (const int e = urx::stats::stats_count(SW, at, base, d_off.p, i0, i1, action, s)) return e;
-				return pile ? urx::pileup::pileup_count(PW, at, base, d_off.p, i0, i1, action, pil->R, s) : URMAPX_OK;
+				if (p0 == 0)
+					for (Beside *B : beside)
+						if (const int e = B->count(at, base, d_off.p, i0, i1, action, s)) return e;
+				return URMAPX_OK;
 			});
 			if (r) return r;
 			for (uint64_t s0 = p0; s0 < p1; s0 += slice_bytes) {
@@ -887,16 +803,10 @@ struct DeviceSort {
 		return URMAPX_OK;
 	}
 
-	// the depth's result, the statistics' and the pileup's, then the sort's: the members trimmed to their size and handed to finish_result, which owns them from there
+	// the by-products' results, then the sort's: the members trimmed to their size and handed to finish_result, which owns them from there
 	int finish() {
-		if (dep)
-			if (const int rc = urx::depth::depth_finish(DW, dep->out)) return rc;
-		if (sta) {
-			sta->out->records = n;
-			if (const int rc = urx::stats::stats_finish(SW, sta->names, sta->lens, sta->command, sta->out)) return rc;
-		}
-		if (pil)
-			if (const int rc = urx::pileup::pileup_finish(PW, pil->names, pil->lens, pil->R, pil->command, pil->out)) return rc;
+		for (Beside *B : beside)
+			if (const int rc = B->finish()) return rc;
 		if (uint8_t *fit = (uint8_t *)realloc(z.get(), z_bytes ? z_bytes : 1)) {
 			(void)z.release();
 			z.reset(fit);
@@ -920,8 +830,7 @@ uint64_t urmapx_bam_sort_markdup_device_bytes(size_t n_bytes, uint64_t n_records
 }
 
 static int sort_entry(int device, const uint64_t *budget, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts,
-                      size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out, const DepthAsk *dep = nullptr,
-                      const StatsAsk *sta = nullptr, const PileupAsk *pil = nullptr) {
+                      size_t n_starts, urmapx_markdup_stats *md, urmapx_bam_sort_result *out, const std::vector<Beside *> &beside = {}) {
 	if (!out || (n_bytes && !records) || (n_starts && !starts)) return URMAPX_E_ARG;
 	memset(out, 0, sizeof *out);
 	if (md) memset(md, 0, sizeof *md);
@@ -937,15 +846,14 @@ static int sort_entry(int device, const uint64_t *budget, const void *records, s
 			HIP_TRY(hipMemGetInfo(&free_b, &total_b));
 			have = free_b > URMAPX_SORT_HEADROOM ? (uint64_t)free_b - URMAPX_SORT_HEADROOM : 1u;
 		}
-		rc = DeviceSort{device, budget ? &have : nullptr, (const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, dep, sta, pil, out}.run();
+		rc = DeviceSort{device, budget ? &have : nullptr, (const uint8_t *)records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, beside, out}.run();
 	} catch (const std::bad_alloc &) {
 		rc = URMAPX_E_NOMEM;
 	}
 	out->alloc_s = t_alloc_s;  // (the arrays are freed by now)
 	if (rc) urmapx_bam_sort_free(out);
-	if (rc && dep) urmapx_depth_free(dep->out);
-	if (rc && sta) urmapx_stats_free(sta->out);
-	if (rc && pil) urmapx_pileup_free(pil->out);
+	if (rc)
+		for (Beside *B : beside) B->free_result();
 	return rc;
 }
 
@@ -965,39 +873,26 @@ int urmapx_bam_sort_external(int device, uint64_t budget_bytes, const void *reco
 	return sort_entry(device, &budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out);
 }
 
-int urmapx_bam_sort_depth(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
-                          const uint64_t *starts, size_t n_starts, urmapx_markdup_stats *md, const urmapx_depth_opts *dopts,
-                          const char *const *names, const uint32_t *lens, urmapx_depth_result *depth, urmapx_bam_sort_result *out) {
-	const urmapx_bam_sort_extras extras{md, dopts, names, lens, depth, nullptr, nullptr};
-	return urmapx_bam_sort_with(device, budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, &extras, out);
-}
-
 int urmapx_bam_sort_with(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
                          const uint64_t *starts, size_t n_starts, const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out) {
 	const urmapx_bam_sort_extras none{};
 	const urmapx_bam_sort_extras &E = extras ? *extras : none;
-	const urmapx_bam_sort_extras2 with{E.md, E.dopts, E.names, E.lens, E.depth, E.stats, E.stats_command, nullptr, nullptr, nullptr, nullptr, nullptr};
-	return urmapx_bam_sort_with2(device, budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, &with, out);
-}
-
-int urmapx_bam_sort_with2(int device, uint64_t budget_bytes, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front,
-                          const uint64_t *starts, size_t n_starts, const urmapx_bam_sort_extras2 *extras, urmapx_bam_sort_result *out) {
-	const urmapx_bam_sort_extras2 none{};
-	const urmapx_bam_sort_extras2 &E = extras ? *extras : none;
 	if (!E.depth && !E.stats && !E.pileup) return sort_entry(device, &budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, E.md, out);
 	if (E.depth) memset(E.depth, 0, sizeof *E.depth);
 	if (E.stats) memset(E.stats, 0, sizeof *E.stats);
 	if (E.pileup) memset(E.pileup, 0, sizeof *E.pileup);
-	DepthAsk dask{E.dopts ? E.dopts->min_mapq : 0u, E.names, E.lens, 0, E.depth};
-	const StatsAsk sask{E.names, E.lens, E.stats_command, E.stats};
-	if (const int rc = urx::depth::check_refs(n_ref, E.names, E.lens, &dask.entries)) return rc;
-	PileupAsk pask{urx::pileup::Rule(), E.names, E.lens, dask.entries - n_ref, E.seqs, nullptr, nullptr, E.pileup_command, E.pileup};
+	uint64_t entries = 0, columns = 0;
+	if (const int rc = urx::depth::check_refs(n_ref, E.names, E.lens, &entries)) return rc;
+	columns = entries - n_ref;
+	urx::pileup::Rule R;
+	const uint8_t *const *seqs = E.seqs;
+	const uint8_t *d_store = nullptr;
 	// the bases: the caller's, or the index's -- in place where its store is resident on this device, else fetched once to the host
 	std::vector<uint8_t> fetched;
 	std::vector<const uint8_t *> fetched_at;
 	std::vector<uint64_t> store_at;
 	if (E.pileup) {
-		if (const int rc = urx::pileup::rule_of(E.popts, &pask.R)) return rc;
+		if (const int rc = urx::pileup::rule_of(E.popts, &R)) return rc;
 		if (!E.seqs) {
 			if (!E.index || urmapx_index_seq_count(E.index) != n_ref) return URMAPX_E_ARG;
 			const urx::IndexStore S = urx::index_store(E.index);
@@ -1007,22 +902,33 @@ int urmapx_bam_sort_with2(int device, uint64_t budget_bytes, const void *records
 					store_at[r] = urmapx_index_seq_offset(E.index, r);
 					if (urmapx_index_seq_length(E.index, r) != E.lens[r] || store_at[r] + E.lens[r] > S.seq_data_size) return URMAPX_E_ARG;
 				}
-				pask.d_store = S.d_seq;
-				pask.store_at = store_at.data();
+				d_store = S.d_seq;
 			} else {
 				try {
 					if (const int rc = urx::pileup::index_sequences(E.index, n_ref, E.lens, fetched, fetched_at)) return rc;
 				} catch (const std::bad_alloc &) {
 					return URMAPX_E_NOMEM;
 				}
-				pask.seqs = fetched_at.data();
+				seqs = fetched_at.data();
 			}
 		}
-		if (pask.seqs)
-			if (const int rc = urx::pileup::check_input(n_ref, E.names, E.lens, pask.seqs, &pask.columns)) return rc;
+		if (seqs)
+			if (const int rc = urx::pileup::check_input(n_ref, E.names, E.lens, seqs, &columns)) return rc;
 	}
-	return sort_entry(device, &budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, E.md, out, E.depth ? &dask : nullptr,
-	                  E.stats ? &sask : nullptr, E.pileup ? &pask : nullptr);
+	// what is taken beside the sort: the one place that names them.  Their arrays go when this scope ends, and count in alloc_s
+	int rc;
+	{
+		std::optional<urx::depth::DepthBeside> dep;
+		std::optional<urx::stats::StatsBeside> sta;
+		std::optional<urx::pileup::PileupBeside> pil;
+		std::vector<Beside *> beside;
+		if (E.depth) beside.push_back(&dep.emplace(n_ref, E.names, E.lens, entries, E.dopts ? E.dopts->min_mapq : 0u, E.depth));
+		if (E.stats) beside.push_back(&sta.emplace(n_ref, E.names, E.lens, E.stats_command, E.stats));
+		if (E.pileup) beside.push_back(&pil.emplace(n_ref, R, E.names, E.lens, columns, seqs, d_store, d_store ? store_at.data() : nullptr, E.pileup_command, E.pileup));
+		rc = sort_entry(device, &budget_bytes, records, n_bytes, n_ref, bytes_in_front, starts, n_starts, E.md, out, beside);
+	}
+	if (out) out->alloc_s = t_alloc_s;
+	return rc;
 }
 
 }  // extern "C"

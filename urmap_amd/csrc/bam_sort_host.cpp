@@ -2,11 +2,15 @@
 // device sort of bam_sort.hip: the walk along the block_size chain, the members' table, the .bai writer.  See include/urmapx.h
 // "Sorted BAM output" for the contract and bam_sort.h for the pieces.
 #include "bam_sort.h"
+#include "depth.h"
+#include "pileup.h"
+#include "stats.h"
 
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 
 namespace urx {
@@ -225,6 +229,10 @@ namespace {
 using Clock = std::chrono::steady_clock;
 double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::now() - t).count(); }
 
+// a call once the marking has decided: the records as they came, their starts, and what becomes of every record's bit 0x400 (null
+// without marking).  What it returns ends the sort if not 0 (urmapx_bam_sort_with_host takes the depth, the statistics and the pileup there)
+using AfterMark = std::function<int(const uint8_t *rec, const std::vector<uint64_t> &offs, const uint8_t *action)>;
+
 int sort_host(const uint8_t *rec, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts, size_t n_starts, urmapx_markdup_stats *md,
               urmapx_bam_sort_result *out, const AfterMark *hook) {
 	auto t = Clock::now();
@@ -359,6 +367,50 @@ int urmapx_bam_sort_plan_for(size_t n_bytes, uint64_t n_records, int markdup, ui
 	return plan_with_stage(n_bytes, n_records, markdup != 0, budget_bytes, default_stage_bytes(n_bytes), plan);
 }
 
+int urmapx_bam_sort_with_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts, size_t n_starts,
+                              const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out) {
+	const urmapx_bam_sort_extras none{};
+	const urmapx_bam_sort_extras &E = extras ? *extras : none;
+	if (!E.depth && !E.stats && !E.pileup) {
+		return E.md ? urmapx_bam_sort_markdup_host(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, E.md, out)
+		            : urmapx_bam_sort_host(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, out);
+	}
+	if (E.depth) memset(E.depth, 0, sizeof *E.depth);
+	if (E.stats) memset(E.stats, 0, sizeof *E.stats);
+	if (E.pileup) memset(E.pileup, 0, sizeof *E.pileup);
+	uint64_t columns = 0;
+	urx::pileup::Rule R;
+	int rc = urx::depth::check_refs(n_ref, E.names, E.lens, &columns);
+	if (!rc && E.pileup) rc = urx::pileup::rule_of(E.popts, &R);
+	if (rc) return rc;
+	try {
+		std::vector<uint8_t> store;
+		std::vector<const uint8_t *> ptrs;
+		const uint8_t *const *seqs = E.seqs;
+		if (E.pileup && !seqs) {
+			if ((rc = urx::pileup::index_sequences(E.index, n_ref, E.lens, store, ptrs))) return rc;
+			seqs = ptrs.data();
+		}
+		if (E.pileup && (rc = urx::pileup::check_input(n_ref, E.names, E.lens, seqs, &columns))) return rc;
+		// the flags as written: the marking's decisions beside the records as they came (order matters to none of the three)
+		const AfterMark hook = [&](const uint8_t *rec, const std::vector<uint64_t> &offs, const uint8_t *action) -> int {
+			if (offs.size() - 1 >= 0x7FFFFFFFu) return URMAPX_E_ARG;
+			if (E.depth)
+				if (const int r = urx::depth::depth_host(rec, offs, action, n_ref, E.names, E.lens, E.dopts ? E.dopts->min_mapq : 0u, E.depth)) return r;
+			if (E.stats)
+				if (const int r = urx::stats::stats_host(rec, offs, action, n_ref, E.names, E.lens, E.stats_command, E.stats)) return r;
+			return E.pileup ? urx::pileup::pileup_host(rec, offs, action, n_ref, E.names, E.lens, seqs, R, E.pileup_command, E.pileup) : URMAPX_OK;
+		};
+		rc = sort_host_entry(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, E.md, out, &hook);
+	} catch (const std::bad_alloc &) {
+		rc = URMAPX_E_NOMEM;
+	}
+	if (rc && E.depth) urmapx_depth_free(E.depth);
+	if (rc && E.stats) urmapx_stats_free(E.stats);
+	if (rc && E.pileup) urmapx_pileup_free(E.pileup);
+	return rc;
+}
+
 void urmapx_bam_sort_free(urmapx_bam_sort_result *R) {
 	if (!R) return;
 	free(R->bgzf);
@@ -368,12 +420,3 @@ void urmapx_bam_sort_free(urmapx_bam_sort_result *R) {
 }
 
 }  // extern "C"
-
-namespace urx {
-namespace bamsort {
-int sort_host_hooked(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts, size_t n_starts,
-                     urmapx_markdup_stats *md, urmapx_bam_sort_result *out, const AfterMark &hook) {
-	return sort_host_entry(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, md, out, &hook);
-}
-}  // namespace bamsort
-}  // namespace urx

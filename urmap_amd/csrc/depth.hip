@@ -1,4 +1,4 @@
-// depth.hip -- per-base depth of BAM records on the device (urmapx_bam_depth, and the depth step of urmapx_bam_sort_depth; the rule is
+// depth.hip -- per-base depth of BAM records on the device (urmapx_bam_depth, and the depth step of urmapx_bam_sort_with; the rule is
 // in include/urmapx.h "Depth", the sizes and the memory sum in depth.h, the host version in depth_host.cpp).
 //
 // The counters are one uint32 array in which reference r owns l_ref + 1 entries from base[r] on; all their arithmetic is modulo 2^32,
@@ -371,29 +371,6 @@ __global__ __launch_bounds__(DNT) void line_write_kernel(const uint64_t *list, u
 	}
 }
 
-// page-locked memory of the host
-struct Pinned {
-	uint8_t *p = nullptr;
-	int alloc(size_t n) {
-		const hipError_t e = hipHostMalloc((void **)&p, n ? n : 1, hipHostMallocDefault);
-		if (e != hipSuccess) { p = nullptr; (void)hipGetLastError(); return urx::hip_rc(e); }
-		return URMAPX_OK;
-	}
-	~Pinned() {
-		if (p) (void)hipHostFree(p);
-	}
-};
-struct TwoStreams {
-	hipStream_t s[2] = {nullptr, nullptr};
-	int create() {
-		for (int b = 0; b < 2; ++b) HIP_TRY(hipStreamCreateWithFlags(&s[b], hipStreamNonBlocking));
-		return URMAPX_OK;
-	}
-	~TwoStreams() {
-		for (int b = 0; b < 2; ++b)
-			if (s[b]) (void)hipStreamDestroy(s[b]);
-	}
-};
 // the text as it grows on the host (malloc: the result owns it in the end)
 struct HostText {
 	char *p = nullptr;
@@ -558,58 +535,19 @@ int depth_finish(DepthOwn &W, urmapx_depth_result *out) {
 	return URMAPX_OK;
 }
 
+uint64_t DepthBeside::resident_bytes() const { return urx::depth::resident_bytes(entries, n_ref, text_runs()); }
+int DepthBeside::begin(uint32_t n) {
+	out->records = n;
+	return W.begin(n_ref, names, lens, entries);
+}
+int DepthBeside::count(const uint8_t *at, uint64_t base, const uint64_t *off, uint32_t i0, uint32_t i1, const uint8_t *action, hipStream_t stream) {
+	return depth_count(W, at, base, off, i0, i1, action, min_mapq, stream);
+}
+int DepthBeside::finish() { return depth_finish(W, out); }
+void DepthBeside::free_result() { urmapx_depth_free(out); }
+
 }  // namespace depth
 }  // namespace urx
-
-namespace {
-
-int depth_device(int device, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, const char *const *names, const uint32_t *lens, uint64_t entries,
-                 const uint64_t *starts, size_t n_starts, uint32_t min_mapq, urmapx_depth_result *out) {
-	std::vector<uint64_t> offs;
-	int rc = scan_for_depth(rec, n_bytes, n_ref, starts, n_starts, offs);
-	if (rc) return rc;
-	const uint32_t n = (uint32_t)(offs.size() - 1);
-	out->records = n;
-	// the staged chunks: runs of whole records, one at the least; a record longer than the chunk asked for makes the buffers grow
-	uint64_t stage = default_stage_bytes(n_bytes);
-	std::vector<uint32_t> cut;
-	for (uint64_t i0 = 0; i0 < n;) {
-		const uint64_t i1 = chunk_end(offs.data(), n, i0, stage, false);
-		cut.push_back((uint32_t)i0);
-		i0 = i1;
-	}
-	cut.push_back(n);
-	for (size_t c = 0; c + 1 < cut.size(); ++c) stage = std::max(stage, offs[cut[c + 1]] - offs[cut[c]]);
-	out->stage_chunks = cut.size() - 1;
-
-	HIP_TRY(hipSetDevice(device));
-	DepthOwn W;
-	Dev<uint64_t> d_off;
-	Dev<uint8_t> d_stage[2];
-	TwoStreams st;
-	// (the pieces standalone_bytes counts, in its order)
-	if ((rc = W.begin(n_ref, names, lens, entries)) || (rc = d_off.alloc((size_t)n + 1)) || (rc = d_stage[0].alloc((size_t)stage + 16)) ||
-	    (rc = d_stage[1].alloc((size_t)stage + 16)) || (rc = st.create()))
-		return rc;
-	auto t = Clock::now();
-	HIP_TRY(hipMemcpy(d_off.p, offs.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	// chunk c goes to staging buffer c & 1 on that buffer's stream, its kernel behind it; the next chunk's copy runs meanwhile
-	for (size_t c = 0; c + 1 < cut.size(); ++c) {
-		const int b = (int)(c & 1u);
-		const uint32_t i0 = cut[c], i1 = cut[c + 1];
-		const uint64_t bytes = offs[i1] - offs[i0];
-		HIP_TRY(hipStreamSynchronize(st.s[b]));
-		if (bytes) HIP_TRY(hipMemcpyAsync(d_stage[b].p, rec + offs[i0], (size_t)bytes, hipMemcpyHostToDevice, st.s[b]));
-		if ((rc = depth_count(W, d_stage[b].p, offs[i0], d_off.p, i0, i1, nullptr, min_mapq, st.s[b]))) return rc;
-	}
-	HIP_TRY(hipGetLastError());
-	for (int b = 0; b < 2; ++b) HIP_TRY(hipStreamSynchronize(st.s[b]));
-	out->count_s = since(t);
-	return depth_finish(W, out);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -624,7 +562,8 @@ int urmapx_bam_depth(int device, const void *records, size_t n_bytes, uint32_t n
 	if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) { (void)hipGetLastError(); return URMAPX_E_NODEVICE; }
 	try {
 		t_alloc_s = 0;
-		rc = depth_device(device, (const uint8_t *)records, n_bytes, n_ref, names, lens, entries, starts, n_starts, opts ? opts->min_mapq : 0u, out);
+		DepthBeside B(n_ref, names, lens, entries, opts ? opts->min_mapq : 0u, out);
+		rc = staged_alone(device, (const uint8_t *)records, n_bytes, n_ref, starts, n_starts, B, &out->stage_chunks, &out->count_s);
 	} catch (const std::bad_alloc &) {
 		rc = URMAPX_E_NOMEM;
 	}

@@ -165,11 +165,4 @@ int urmapx_bam_depth_host(const void *records, size_t n_bytes, uint32_t n_ref, c
 	return rc;
 }
 
-int urmapx_bam_sort_depth_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts, size_t n_starts,
-                               urmapx_markdup_stats *md, const urmapx_depth_opts *dopts, const char *const *names, const uint32_t *lens,
-                               urmapx_depth_result *depth, urmapx_bam_sort_result *out) {
-	const urmapx_bam_sort_extras extras{md, dopts, names, lens, depth, nullptr, nullptr};
-	return urmapx_bam_sort_with_host(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, &extras, out);
-}
-
 }  // extern "C"

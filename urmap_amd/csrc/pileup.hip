@@ -1,4 +1,4 @@
-// pileup.hip -- SNV candidate sites of BAM records on the device (urmapx_bam_pileup, and the pileup step of urmapx_bam_sort_with2; the
+// pileup.hip -- SNV candidate sites of BAM records on the device (urmapx_bam_pileup, and the pileup step of urmapx_bam_sort_with; the
 // rule is in include/urmapx.h "Pileup", the site entry, the sizes and the memory sum in pileup.h, the host version and the formatter
 // in pileup_host.cpp).
 //
@@ -188,30 +188,6 @@ __global__ __launch_bounds__(PNT) void site_write_kernel(const uint4 *cnt, const
 	if (site && rank >= w0 && rank < w1) out[rank - w0] = S;
 }
 
-// page-locked memory of the host
-struct Pinned {
-	uint8_t *p = nullptr;
-	int alloc(size_t n) {
-		const hipError_t e = hipHostMalloc((void **)&p, n ? n : 1, hipHostMallocDefault);
-		if (e != hipSuccess) { p = nullptr; (void)hipGetLastError(); return urx::hip_rc(e); }
-		return URMAPX_OK;
-	}
-	~Pinned() {
-		if (p) (void)hipHostFree(p);
-	}
-};
-struct TwoStreams {
-	hipStream_t s[2] = {nullptr, nullptr};
-	int create() {
-		for (int b = 0; b < 2; ++b) HIP_TRY(hipStreamCreateWithFlags(&s[b], hipStreamNonBlocking));
-		return URMAPX_OK;
-	}
-	~TwoStreams() {
-		for (int b = 0; b < 2; ++b)
-			if (s[b]) (void)hipStreamDestroy(s[b]);
-	}
-};
-
 }  // namespace
 
 namespace urx {
@@ -322,57 +298,16 @@ int pileup_finish(PileupOwn &W, const char *const *names, const uint32_t *lens, 
 	return rc;
 }
 
+uint64_t PileupBeside::resident_bytes() const { return urx::pileup::resident_bytes(columns, n_ref, segment_columns(), slice_sites(), !seqs); }
+int PileupBeside::begin(uint32_t) { return W.begin(n_ref, lens, columns, seqs, d_store, store_at); }
+int PileupBeside::count(const uint8_t *at, uint64_t base, const uint64_t *off, uint32_t i0, uint32_t i1, const uint8_t *action, hipStream_t stream) {
+	return pileup_count(W, at, base, off, i0, i1, action, R, stream);
+}
+int PileupBeside::finish() { return pileup_finish(W, names, lens, R, command, out); }
+void PileupBeside::free_result() { urmapx_pileup_free(out); }
+
 }  // namespace pileup
 }  // namespace urx
-
-namespace {
-
-int pileup_device(int device, const uint8_t *rec, size_t n_bytes, uint32_t n_ref, const char *const *names, const uint32_t *lens, const uint8_t *const *seqs,
-                  uint64_t columns, const uint64_t *starts, size_t n_starts, const Rule &R, const char *command, urmapx_pileup_result *out) {
-	std::vector<uint64_t> offs;
-	int rc = urx::depth::scan_for_depth(rec, n_bytes, n_ref, starts, n_starts, offs);
-	if (rc) return rc;
-	const uint32_t n = (uint32_t)(offs.size() - 1);
-	// the staged chunks: runs of whole records, one at the least; a record longer than the chunk asked for makes the buffers grow
-	uint64_t stage = default_stage_bytes(n_bytes);
-	std::vector<uint32_t> cut;
-	for (uint64_t i0 = 0; i0 < n;) {
-		const uint64_t i1 = chunk_end(offs.data(), n, i0, stage, false);
-		cut.push_back((uint32_t)i0);
-		i0 = i1;
-	}
-	cut.push_back(n);
-	for (size_t c = 0; c + 1 < cut.size(); ++c) stage = std::max(stage, offs[cut[c + 1]] - offs[cut[c]]);
-	out->stage_chunks = cut.size() - 1;
-
-	HIP_TRY(hipSetDevice(device));
-	PileupOwn W;
-	Dev<uint64_t> d_off;
-	Dev<uint8_t> d_stage[2];
-	TwoStreams st;
-	// (the pieces standalone_bytes counts, in its order)
-	if ((rc = W.begin(n_ref, lens, columns, seqs, nullptr, nullptr)) || (rc = d_off.alloc((size_t)n + 1)) || (rc = d_stage[0].alloc((size_t)stage + 16)) ||
-	    (rc = d_stage[1].alloc((size_t)stage + 16)) || (rc = st.create()))
-		return rc;
-	const auto t = Clock::now();
-	HIP_TRY(hipMemcpy(d_off.p, offs.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	// chunk c goes to staging buffer c & 1 on that buffer's stream, its kernel behind it; the next chunk's copy runs meanwhile
-	for (size_t c = 0; c + 1 < cut.size(); ++c) {
-		const int b = (int)(c & 1u);
-		const uint32_t i0 = cut[c], i1 = cut[c + 1];
-		const uint64_t bytes = offs[i1] - offs[i0];
-		HIP_TRY(hipStreamSynchronize(st.s[b]));
-		if (bytes) HIP_TRY(hipMemcpyAsync(d_stage[b].p, rec + offs[i0], (size_t)bytes, hipMemcpyHostToDevice, st.s[b]));
-		if ((rc = pileup_count(W, d_stage[b].p, offs[i0], d_off.p, i0, i1, nullptr, R, st.s[b]))) return rc;
-	}
-	HIP_TRY(hipGetLastError());
-	for (int b = 0; b < 2; ++b) HIP_TRY(hipStreamSynchronize(st.s[b]));
-	out->count_s = since(t);
-	return pileup_finish(W, names, lens, R, command, out);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -389,7 +324,8 @@ int urmapx_bam_pileup(int device, const void *records, size_t n_bytes, uint32_t 
 	if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) { (void)hipGetLastError(); return URMAPX_E_NODEVICE; }
 	try {
 		t_alloc_s = 0;
-		rc = pileup_device(device, (const uint8_t *)records, n_bytes, n_ref, names, lens, seqs, columns, starts, n_starts, R, command, out);
+		PileupBeside B(n_ref, R, names, lens, columns, seqs, nullptr, nullptr, command, out);
+		rc = staged_alone(device, (const uint8_t *)records, n_bytes, n_ref, starts, n_starts, B, &out->stage_chunks, &out->count_s);
 	} catch (const std::bad_alloc &) {
 		rc = URMAPX_E_NOMEM;
 	}

@@ -1,5 +1,5 @@
 // pileup_dev.h -- the device side of the pileup (pileup.hip) as its two callers see it: urmapx_bam_pileup, which streams the records
-// through staging buffers of its own, and the device sort (bam_sort.hip, urmapx_bam_sort_with2), which has them on the device anyway.
+// through staging buffers (staged_alone), and the device sort (bam_sort.hip, urmapx_bam_sort_with), which has them on the device anyway.
 // HIP translation units only.  Not installed.
 #pragma once
 #include "bam_sort_dev.h"
@@ -33,6 +33,31 @@ int pileup_count(const PileupOwn &W, const uint8_t *rec, uint64_t base, const ui
 // once every record is counted: the sites, segment by segment and slice by slice, and the text into out (text, text_bytes, sites,
 // alt_alleles, records, sites_s, format_s, copy_s)
 int pileup_finish(PileupOwn &W, const char *const *names, const uint32_t *lens, const Rule &R, const char *command, urmapx_pileup_result *out);
+
+// The pileup as a by-product of the staged pass (include/urmapx.h "Pileup"); names, lens and the rule are checked.  The bases: seqs on
+// the host, or, with seqs null, d_store on the current device with reference r's letters from store_at[r] on
+struct PileupBeside final : bamsort::Beside {
+	const uint32_t n_ref;
+	const Rule R;
+	const char *const *const names;
+	const uint32_t *const lens;
+	const uint64_t columns;
+	const uint8_t *const *const seqs;
+	const uint8_t *const d_store;
+	const uint64_t *const store_at;
+	const char *const command;
+	urmapx_pileup_result *const out;
+	PileupOwn W;
+	PileupBeside(uint32_t n_ref_, const Rule &R_, const char *const *names_, const uint32_t *lens_, uint64_t columns_, const uint8_t *const *seqs_,
+	             const uint8_t *d_store_, const uint64_t *store_at_, const char *command_, urmapx_pileup_result *out_)
+	    : Beside(&out_->least_budget, &out_->alloc_s, &out_->count_s), n_ref(n_ref_), R(R_), names(names_), lens(lens_), columns(columns_), seqs(seqs_),
+	      d_store(d_store_), store_at(store_at_), command(command_), out(out_) {}
+	uint64_t resident_bytes() const override;
+	int begin(uint32_t n) override;
+	int count(const uint8_t *at, uint64_t base, const uint64_t *off, uint32_t i0, uint32_t i1, const uint8_t *action, hipStream_t stream) override;
+	int finish() override;
+	void free_result() override;
+};
 
 }  // namespace pileup
 }  // namespace urx

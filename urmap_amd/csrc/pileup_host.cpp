@@ -220,48 +220,4 @@ int urmapx_bam_pileup_host(const void *records, size_t n_bytes, uint32_t n_ref, 
 	return rc;
 }
 
-int urmapx_bam_sort_with2_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts, size_t n_starts,
-                               const urmapx_bam_sort_extras2 *extras, urmapx_bam_sort_result *out) {
-	const urmapx_bam_sort_extras2 none{};
-	const urmapx_bam_sort_extras2 &E = extras ? *extras : none;
-	if (!E.depth && !E.stats && !E.pileup) {
-		return E.md ? urmapx_bam_sort_markdup_host(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, E.md, out)
-		            : urmapx_bam_sort_host(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, out);
-	}
-	if (E.depth) memset(E.depth, 0, sizeof *E.depth);
-	if (E.stats) memset(E.stats, 0, sizeof *E.stats);
-	if (E.pileup) memset(E.pileup, 0, sizeof *E.pileup);
-	uint64_t columns = 0;
-	Rule R;
-	int rc = urx::depth::check_refs(n_ref, E.names, E.lens, &columns);
-	if (!rc && E.pileup) rc = rule_of(E.popts, &R);
-	if (rc) return rc;
-	try {
-		std::vector<uint8_t> store;
-		std::vector<const uint8_t *> ptrs;
-		const uint8_t *const *seqs = E.seqs;
-		if (E.pileup && !seqs) {
-			if ((rc = index_sequences(E.index, n_ref, E.lens, store, ptrs))) return rc;
-			seqs = ptrs.data();
-		}
-		if (E.pileup && (rc = check_input(n_ref, E.names, E.lens, seqs, &columns))) return rc;
-		// the flags as written: the marking's decisions beside the records as they came (order matters to none of the three)
-		const urx::bamsort::AfterMark hook = [&](const uint8_t *rec, const std::vector<uint64_t> &offs, const uint8_t *action) -> int {
-			if (offs.size() - 1 >= 0x7FFFFFFFu) return URMAPX_E_ARG;
-			if (E.depth)
-				if (const int r = urx::depth::depth_host(rec, offs, action, n_ref, E.names, E.lens, E.dopts ? E.dopts->min_mapq : 0u, E.depth)) return r;
-			if (E.stats)
-				if (const int r = urx::stats::stats_host(rec, offs, action, n_ref, E.names, E.lens, E.stats_command, E.stats)) return r;
-			return E.pileup ? pileup_host(rec, offs, action, n_ref, E.names, E.lens, seqs, R, E.pileup_command, E.pileup) : URMAPX_OK;
-		};
-		rc = urx::bamsort::sort_host_hooked(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, E.md, out, hook);
-	} catch (const std::bad_alloc &) {
-		rc = URMAPX_E_NOMEM;
-	}
-	if (rc && E.depth) urmapx_depth_free(E.depth);
-	if (rc && E.stats) urmapx_stats_free(E.stats);
-	if (rc && E.pileup) urmapx_pileup_free(E.pileup);
-	return rc;
-}
-
 }  // extern "C"

@@ -1149,7 +1149,7 @@ struct Run {
 	}
 	// The sort, on the first device.  Planned -- sort_mem, depth_out, stats_out or vcf_out (all three are taken on the way: include/urmapx.h
 	// "Depth", "Stats", "Pileup") or the test knob that forces partitions --: one call, which plans from the budget and streams where it must
-	// (urmapx_bam_sort_with2; with none of the results that is urmapx_bam_sort_external), and nothing else is tried.  Else in core, and if the records do not fit,
+	// (urmapx_bam_sort_with; with none of the results that is urmapx_bam_sort_external), and nothing else is tried.  Else in core, and if the records do not fit,
 	// planned from the memory that is free.  Where the device is full of lanes, this run's and the pool's go first (the mapping is over)
 	// and the same call is made once more.  Under URMAPX_HOST_TEXT / URMAPX_HOST_SORT the host's sort, once
 	int sort_kept(Sorted &W) {
@@ -1167,9 +1167,9 @@ struct Run {
 			W.ref_lens.push_back(urmapx_index_seq_length(I, r));
 		}
 		// (the pileup's bases: the index's store, in place where it is resident on the sort's device, else fetched once)
-		const urmapx_bam_sort_extras2 extras{md, &dopts, W.ref_names.data(), W.ref_lens.data(), depth, stats, opt.cmdline, &popts, nullptr, I, pileup, opt.cmdline};
-		if (host_sort()) return urmapx_bam_sort_with2_host(rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), &extras, &W.S);
-		auto planned_sort = [&]() { return urmapx_bam_sort_with2(phys(0), opt.sort_mem, rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), &extras, &W.S); };
+		const urmapx_bam_sort_extras extras{md, &dopts, W.ref_names.data(), W.ref_lens.data(), depth, stats, opt.cmdline, &popts, nullptr, I, pileup, opt.cmdline};
+		if (host_sort()) return urmapx_bam_sort_with_host(rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), &extras, &W.S);
+		auto planned_sort = [&]() { return urmapx_bam_sort_with(phys(0), opt.sort_mem, rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), &extras, &W.S); };
 		auto in_core = [&]() {
 			return md ? urmapx_bam_sort_markdup(phys(0), rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), md, &W.S)
 			          : urmapx_bam_sort(phys(0), rec, n_bytes, W.n_ref, in_front, starts.data(), starts.size(), &W.S);

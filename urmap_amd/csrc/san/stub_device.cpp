@@ -423,94 +423,45 @@ int urmapx_bam_sort_external(int, uint64_t budget, const void *records, size_t n
 	if (rc == URMAPX_OK) { out->external = (uint32_t)plan.external; out->partitions = (uint32_t)plan.partitions; }
 	return rc;
 }
-// the depth's stand-ins: the host version (depth_host.cpp); the planned sort with depth keeps the refusal of a budget that does not
-// hold the depth arrays
+// the stand-ins of what is taken beside the sort: the host versions (depth_host.cpp, stats_host.cpp, pileup_host.cpp)
 int urmapx_bam_depth(int, const void *records, size_t n_bytes, uint32_t n_ref, const char *const *names, const uint32_t *lens, const uint64_t *starts,
                      size_t n_starts, const urmapx_depth_opts *opts, urmapx_depth_result *out) {
 	return urmapx_bam_depth_host(records, n_bytes, n_ref, names, lens, starts, n_starts, opts, out);
 }
-int urmapx_bam_sort_depth(int device, uint64_t budget, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts,
-                          size_t n_starts, urmapx_markdup_stats *md, const urmapx_depth_opts *dopts, const char *const *names, const uint32_t *lens,
-                          urmapx_depth_result *depth, urmapx_bam_sort_result *out) {
-	if (!depth) return urmapx_bam_sort_external(device, budget, records, n_bytes, n_ref, in_front, starts, n_starts, md, out);
-	memset(depth, 0, sizeof *depth);
-	if (stub_sort_refuses("urmapx_bam_sort_depth", &budget)) return URMAPX_E_NOMEM;
-	if (budget == 0) budget = ((uint64_t)200 << 30) - URMAPX_SORT_HEADROOM;  // (hipMemGetInfo above)
-	uint64_t columns = 0;
-	for (uint32_t r = 0; r < n_ref && lens; ++r) columns += lens[r];
-	const uint64_t own = urmapx_bam_depth_resident_bytes(columns, n_ref);
-	urmapx_bam_sort_plan plan;
-	if (const int rc = urmapx_bam_sort_plan_for(n_bytes, n_bytes / 200 + 1, md != nullptr, budget > own ? budget - own : 0u, &plan)) {
-		if (rc == URMAPX_E_NOMEM) depth->least_budget = own + plan.device_bytes;
-		return rc;
-	}
-	const int rc = urmapx_bam_sort_depth_host(records, n_bytes, n_ref, in_front, starts, n_starts, md, dopts, names, lens, depth, out);
-	if (rc == URMAPX_OK) { out->external = (uint32_t)plan.external; out->partitions = (uint32_t)plan.partitions; }
-	return rc;
-}
-// the statistics' stand-ins: the host version (stats_host.cpp); the planned sort with them keeps the refusal of a budget that does not
-// hold the depth arrays and the tables
 int urmapx_bam_stats(int, const void *records, size_t n_bytes, uint32_t n_ref, const char *const *names, const uint32_t *lens, const uint64_t *starts,
                      size_t n_starts, const char *command, urmapx_stats_result *out) {
 	return urmapx_bam_stats_host(records, n_bytes, n_ref, names, lens, starts, n_starts, command, out);
 }
-int urmapx_bam_sort_with(int device, uint64_t budget, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts,
-                         size_t n_starts, const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out) {
-	const urmapx_bam_sort_extras none{};
-	const urmapx_bam_sort_extras &E = extras ? *extras : none;
-	if (!E.stats) return urmapx_bam_sort_depth(device, budget, records, n_bytes, n_ref, in_front, starts, n_starts, E.md, E.dopts, E.names, E.lens, E.depth, out);
-	if (E.depth) memset(E.depth, 0, sizeof *E.depth);
-	memset(E.stats, 0, sizeof *E.stats);
-	if (stub_sort_refuses("urmapx_bam_sort_with", &budget)) return URMAPX_E_NOMEM;
-	if (budget == 0) budget = ((uint64_t)200 << 30) - URMAPX_SORT_HEADROOM;  // (hipMemGetInfo above)
-	uint64_t columns = 0;
-	for (uint32_t r = 0; r < n_ref && E.lens; ++r) columns += E.lens[r];
-	const uint64_t own = (E.depth ? urmapx_bam_depth_resident_bytes(columns, n_ref) : 0u) + urmapx_bam_stats_resident_bytes(n_ref);
-	urmapx_bam_sort_plan plan;
-	if (const int rc = urmapx_bam_sort_plan_for(n_bytes, n_bytes / 200 + 1, E.md != nullptr, budget > own ? budget - own : 0u, &plan)) {
-		if (rc == URMAPX_E_NOMEM) {
-			E.stats->least_budget = own + plan.device_bytes;
-			if (E.depth) E.depth->least_budget = own + plan.device_bytes;
-		}
-		return rc;
-	}
-	const int rc = urmapx_bam_sort_with_host(records, n_bytes, n_ref, in_front, starts, n_starts, &E, out);
-	if (rc == URMAPX_OK) { out->external = (uint32_t)plan.external; out->partitions = (uint32_t)plan.partitions; }
-	return rc;
-}
-// the pileup's stand-ins: the host version (pileup_host.cpp); the planned sort with it keeps the refusal of a budget that does not hold
-// the depth arrays, the tables and the pileup's counters (the bases count as uploaded: no store is resident here)
 int urmapx_bam_pileup(int, const void *records, size_t n_bytes, uint32_t n_ref, const char *const *names, const uint32_t *lens, const uint8_t *const *seqs,
                       const uint64_t *starts, size_t n_starts, const urmapx_pileup_opts *opts, const char *command, urmapx_pileup_result *out) {
 	return urmapx_bam_pileup_host(records, n_bytes, n_ref, names, lens, seqs, starts, n_starts, opts, command, out);
 }
-int urmapx_bam_sort_with2(int device, uint64_t budget, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts,
-                          size_t n_starts, const urmapx_bam_sort_extras2 *extras, urmapx_bam_sort_result *out) {
-	const urmapx_bam_sort_extras2 none{};
-	const urmapx_bam_sort_extras2 &E = extras ? *extras : none;
-	if (!E.pileup) {
-		const urmapx_bam_sort_extras old{E.md, E.dopts, E.names, E.lens, E.depth, E.stats, E.stats_command};
-		return urmapx_bam_sort_with(device, budget, records, n_bytes, n_ref, in_front, starts, n_starts, &old, out);
-	}
+// the planned sort with them: it keeps the refusal of a budget that does not hold the arrays of what is asked for (the pileup's bases
+// count as uploaded: no store is resident here)
+int urmapx_bam_sort_with(int device, uint64_t budget, const void *records, size_t n_bytes, uint32_t n_ref, uint64_t in_front, const uint64_t *starts,
+                         size_t n_starts, const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out) {
+	const urmapx_bam_sort_extras none{};
+	const urmapx_bam_sort_extras &E = extras ? *extras : none;
+	if (!E.depth && !E.stats && !E.pileup) return urmapx_bam_sort_external(device, budget, records, n_bytes, n_ref, in_front, starts, n_starts, E.md, out);
 	if (E.depth) memset(E.depth, 0, sizeof *E.depth);
 	if (E.stats) memset(E.stats, 0, sizeof *E.stats);
-	memset(E.pileup, 0, sizeof *E.pileup);
-	if (stub_sort_refuses("urmapx_bam_sort_with2", &budget)) return URMAPX_E_NOMEM;
+	if (E.pileup) memset(E.pileup, 0, sizeof *E.pileup);
+	if (stub_sort_refuses("urmapx_bam_sort_with", &budget)) return URMAPX_E_NOMEM;
 	if (budget == 0) budget = ((uint64_t)200 << 30) - URMAPX_SORT_HEADROOM;  // (hipMemGetInfo above)
 	uint64_t columns = 0;
 	for (uint32_t r = 0; r < n_ref && E.lens; ++r) columns += E.lens[r];
 	const uint64_t own = (E.depth ? urmapx_bam_depth_resident_bytes(columns, n_ref) : 0u) + (E.stats ? urmapx_bam_stats_resident_bytes(n_ref) : 0u) +
-	                     urmapx_bam_pileup_resident_bytes(columns, n_ref, 0);
+	                     (E.pileup ? urmapx_bam_pileup_resident_bytes(columns, n_ref, 0) : 0u);
 	urmapx_bam_sort_plan plan;
 	if (const int rc = urmapx_bam_sort_plan_for(n_bytes, n_bytes / 200 + 1, E.md != nullptr, budget > own ? budget - own : 0u, &plan)) {
 		if (rc == URMAPX_E_NOMEM) {
-			E.pileup->least_budget = own + plan.device_bytes;
-			if (E.stats) E.stats->least_budget = own + plan.device_bytes;
 			if (E.depth) E.depth->least_budget = own + plan.device_bytes;
+			if (E.stats) E.stats->least_budget = own + plan.device_bytes;
+			if (E.pileup) E.pileup->least_budget = own + plan.device_bytes;
 		}
 		return rc;
 	}
-	const int rc = urmapx_bam_sort_with2_host(records, n_bytes, n_ref, in_front, starts, n_starts, &E, out);
+	const int rc = urmapx_bam_sort_with_host(records, n_bytes, n_ref, in_front, starts, n_starts, &E, out);
 	if (rc == URMAPX_OK) { out->external = (uint32_t)plan.external; out->partitions = (uint32_t)plan.partitions; }
 	return rc;
 }

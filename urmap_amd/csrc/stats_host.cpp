@@ -376,12 +376,4 @@ int urmapx_bam_stats_host(const void *records, size_t n_bytes, uint32_t n_ref, c
 	return rc;
 }
 
-int urmapx_bam_sort_with_host(const void *records, size_t n_bytes, uint32_t n_ref, uint64_t bytes_in_front, const uint64_t *starts, size_t n_starts,
-                              const urmapx_bam_sort_extras *extras, urmapx_bam_sort_result *out) {
-	const urmapx_bam_sort_extras none{};
-	const urmapx_bam_sort_extras &E = extras ? *extras : none;
-	const urmapx_bam_sort_extras2 with{E.md, E.dopts, E.names, E.lens, E.depth, E.stats, E.stats_command, nullptr, nullptr, nullptr, nullptr, nullptr};
-	return urmapx_bam_sort_with2_host(records, n_bytes, n_ref, bytes_in_front, starts, n_starts, &with, out);
-}
-
 }  // extern "C"
